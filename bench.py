@@ -14,8 +14,13 @@ Launch for N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.p
 
 The cameras look at the SAME synthetic scene (one rectangle image, independent sensor noise per camera, the same
 keypoints in a camera-specific order), so the sweep's accept branch does real work and "accepted matches" means
-something.  Besides the contract's K timed steps the line carries a sustained leg (>= 1 s of back-to-back steps) and
-the shader clock measured inside the sweep kernel right after it.
+something.
+
+A plain run sets up, settles the clocks, warms up, times the K steps and prints one JSON line (metric, value, unit, ms_per_step,
+higher_is_better, dtype, ...).  --dump-outputs DIR writes what the last timed step computed (descriptors, match indices) as float32
+.npy files; the inputs are seeded, so two builds can be compared output for output.  --full adds everything else to the same line:
+a cold leg, the one-stream loop, a sustained leg (>= 1 s of back-to-back steps) and the shader clock measured inside the sweep kernel
+right after it, the per-kernel breakdown and roofline, the side sections and the CPU baseline.
 """
 import argparse
 import json
@@ -282,8 +287,15 @@ def main():
                          "this machine allows (profiles/r05_step_overlap.txt); the one-stream figure is then reported as `one_stream`.")
     ap.add_argument("--sections", default="", help="comma list: run only these side sections (e.g. policy_path,front_end); default all")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the informational side sections (other formulation, shares, config[2], front end, pose, two-view, host path): "
+                    help="with --full: skip the informational side sections (other formulation, shares, config[2], front end, pose, two-view, host path): "
                          "the rocprofv3 passes use it so that a kernel's average in their summaries is the average of the step's own launches")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the cold leg, the one-stream loop, the sustained leg and in-kernel clock, the per-kernel "
+                         "breakdown and roofline, the side sections and the CPU baseline.  Without it a run sets up, settles, warms up, times the K "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): descriptors.npy (cameras x keypoints x 64, the "
+                         "descriptor bytes) and matches.npy (per query, the index of the accepted train descriptor, -1 if none); rank 0 only at N > 1")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -419,17 +431,19 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # cold leg: W warm-up steps, then 20 timed steps, BEFORE any clock settling -- what a driver that only does `--warmup W` would see
-    # (reported as value_cold / ms_per_step_cold; every rank runs the same steps)
-    cold_steps = 20
-    for _ in range(args.warmup):
-        step_h()
-    fence()
-    tc = time.perf_counter()
-    for _ in range(cold_steps):
-        step_h()
-    fence()
-    dt_cold = time.perf_counter() - tc
+    # cold leg (--full): W warm-up steps, then 20 timed steps, BEFORE any clock settling -- what a driver that only does `--warmup W` would
+    # see (reported as value_cold / ms_per_step_cold; every rank runs the same steps)
+    cold_steps = 20 if args.full else 0
+    dt_cold = 0.0
+    if args.full:
+        for _ in range(args.warmup):
+            step_h()
+        fence()
+        tc = time.perf_counter()
+        for _ in range(cold_steps):
+            step_h()
+        fence()
+        dt_cold = time.perf_counter() - tc
     # clock settling (not part of W or K: the same step, untimed; every rank runs the same count -- a step may hold a collective)
     for i in range(max(args.settle_steps, 0)):
         step_h()
@@ -464,6 +478,15 @@ def main():
     dt = time.perf_counter() - t0
     ctx.profile_enable(False)
     prof = ctx.profile_read()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the descriptor blocks it wrote and the sweep's match indices (the lane that ran it)
+        if pipelined:
+            _, _, a_last, m_last, _ = lanes[(tick[0] - 1) % len(lanes)]
+        else:
+            a_last, m_last = (mine if mc is not None else arena), d_match
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "descriptors.npy"), a_last.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "matches.npy"), m_last[:n_out].cpu().numpy().astype(np.float32))
     one_stream = None
     pipelined_info = None
     if pipelined:
@@ -476,6 +499,7 @@ def main():
             same_lanes = same_lanes and bool(torch.equal(d_match[:n_out], lx[3][:n_out]))
         pipelined_info = {"sweep_us_while_overlapped": pa[0] / max(pa[1], 1) * 1e3, "sweep_launches": pa[1],
                           "lanes_identical_results": same_lanes, "lanes": len(lanes)}
+    if pipelined and args.full:
         # the same K steps on ONE stream (the device drained between a step's kernels): rounds 1-4's headline, and the region the
         # roofline's per-kernel duration comes from -- a kernel's duration says something about the kernel only while it has the machine
         want_h = d_match[:n_out].clone()
@@ -507,7 +531,7 @@ def main():
     # stamped diagnostic sweep launched straight behind it (MI355X guide, DVFS item 6)
     sustained = None
     clock = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         # back-to-back steps run ~20 % faster than the event-bracketed burst the estimate comes from (no launch gaps): 1.3x margin
         n_sus = max(args.steps, int(1.3 * args.sustain_seconds / max(dt / args.steps, 1e-6)) + 1)
         if world > 1:
@@ -534,20 +558,22 @@ def main():
         fence()
         dsus = time.perf_counter() - ts
         sustained = {"seconds": dsus, "steps": n_sus, "ms_per_step": dsus / n_sus * 1e3}
-    # stage breakdown: a separate short pass with every kernel bracketed (not part of `value`)
-    ctx.profile_reset()
-    ctx.profile_enable(True)
-    for _ in range(min(args.steps, 20)):
-        step()
-    fence()
-    ctx.profile_enable(False)
-    prof_all = ctx.profile_read()
-    if graph is not None:
-        prof = prof_all
+    # stage breakdown (--full): a separate short pass with every kernel bracketed (not part of `value`)
+    prof_all = None
+    if args.full:
+        ctx.profile_reset()
+        ctx.profile_enable(True)
+        for _ in range(min(args.steps, 20)):
+            step()
+        fence()
+        ctx.profile_enable(False)
+        prof_all = ctx.profile_read()
+        if graph is not None:
+            prof = prof_all
 
     # the exchange step on its own (every rank takes part; outside the timed region): SURVEY.md 8(e) asks for it separately
     allgather_us = None
-    if world > 1 and args.backend == "nccl":
+    if args.full and world > 1 and args.backend == "nccl":
         fence()
         tg = time.perf_counter()
         for _ in range(20):
@@ -626,76 +652,13 @@ def main():
                 prof["k2nn_sweep_kernel"] = tuple(leg["sweep_prof_rank0"])
 
     if rank == 0:
-        def avg_us(name, src=None):
-            ms, cnt = (src or prof_all)[name]
-            return (ms / cnt * 1e3) if cnt else None
-
-        sweep_us = avg_us("k2nn_sweep_kernel", prof)
-        clatch_us = avg_us("clatch_kernel")
-        launches = prof["k2nn_sweep_kernel"][1]
-        cmp_per_launch = my_cmp * (args.steps if graph is None else min(args.steps, 20)) / max(launches, 1)
-        compulsory_bytes = sum(64 * (j.nq + counts[j.pair[1]]) + 4 * j.nq for j in jobs)
-        roof = None
-        if sweep_us:
-            t = sweep_us * 1e-6
-            # measured HBM traffic of this kernel comes from separate rocprofv3 --pmc passes (profiles/); it is attached
-            # only when the recorded plan (formulation, shape) is the one that just ran, and says where it came from
-            traffic, traffic_source = None, None
-            tpath = os.path.join(ROOT, "profiles", "r06_k2nn_hbm_traffic.json")
-            if os.path.exists(tpath) and world == 1:
-                try:
-                    rec = json.load(open(tpath))
-                    if rec.get("formulation") == formulation and rec.get("nq") == NKP and rec.get("nt") == NKP \
-                            and not os.environ.get("CLC_K2NN_TARGET_BLOCKS") and not os.environ.get("CLC_K2NN_XCD_MAP"):
-                        traffic = rec.get("hbm_bytes_per_launch")
-                        traffic_source = "static: %s (%s)" % (os.path.relpath(tpath, ROOT), rec.get("how", "rocprofv3 --pmc"))
-                except Exception:
-                    traffic = None
-            hbm = {"achieved_GBps": compulsory_bytes / t / 1e9, "peak_GBps": HBM_PEAK_GBS, "frac": compulsory_bytes / t / 1e9 / HBM_PEAK_GBS,
-                   "algorithmic_bytes_per_launch": compulsory_bytes, "swept_GBps": cmp_per_launch * 64 / t / 1e9,
-                   "note": "compulsory bytes 64 (nq + nt) + 4 nq per pair: the sweep is not HBM-bound"}
-            if formulation == "matrix":
-                flops = cmp_per_launch * 512 * 2
-                roof = {"bound": "mfma", "kernel": "k2nn_sweep_mx_kernel", "achieved": flops / t / 1e12, "peak": MFMA_FP4_PEAK_TFLOPS,
-                        "unit": "TFLOP/s", "frac": flops / t / 1e12 / MFMA_FP4_PEAK_TFLOPS, "traffic": traffic,
-                        "traffic_source": traffic_source, "avg_launch_us": sweep_us,
-                        "algorithmic_flop_per_launch": flops,
-                        "peak_note": "dense FP4 (v_mfma_scale_f32_32x32x64_f8f6f4): 256 CU x 4 SIMD x 4096 flop/clk x 2.4 GHz; "
-                                     "1 comparison = 512 exact +-1 multiply-adds (SURVEY 8d counts it as 32 VALU lane-ops)",
-                        "Gcmp_per_s_kernel": cmp_per_launch / t / 1e9, "hbm": hbm,
-                        # SURVEY.md 8(d) as written: 32 VALU lane-ops per comparison against 39.3 T lane-ops/s (the popcount formulation's
-                        # bound).  Above 1 for this kernel because the work left the vector ALU for the matrix pipe: kept so that the
-                        # line can be checked against the survey's own definition; `frac` above is the binding one.
-                        "valu_8d": {"lane_ops_per_comparison": 32, "achieved_Tlaneops": cmp_per_launch * 32 / t / 1e12,
-                                    "peak_Tlaneops": VALU_PEAK_TLANEOPS, "frac": cmp_per_launch * 32 / t / 1e12 / VALU_PEAK_TLANEOPS,
-                                    "note": "exceeds 1: the comparisons run as FP4 multiply-adds on the matrix pipe, not as xor + popcount lane-ops"}}
-            else:
-                laneops = cmp_per_launch * 32 / t / 1e12
-                roof = {"bound": "valu", "kernel": "k2nn_sweep_kernel", "achieved": laneops, "peak": VALU_PEAK_TLANEOPS,
-                        "unit": "Tlaneop/s", "frac": laneops / VALU_PEAK_TLANEOPS, "traffic": traffic, "traffic_source": traffic_source,
-                        "avg_launch_us": sweep_us,
-                        "peak_note": "256 CU x 64 lanes/clk x 2.4 GHz: measured 4-cycle issue of v_bcnt / SGPR-operand ops",
-                        "lane_ops_per_comparison": 32, "Gcmp_per_s_kernel": cmp_per_launch / t / 1e9, "hbm": hbm}
-            if pipelined and roof is not None:
-                roof["measured_in"] = ("the one-stream region of this run (K steps, the sweep bracketed by HIP events on its stream, the kernel alone on the "
-                                       "device); in the headline region the sweep shares the device with the next step's describe launch: "
-                                       "pipelined.sweep_us_while_overlapped")
-            if isinstance(clock, tuple):
-                roof["clock_ghz_in_kernel"] = {"median": clock[0], "min": clock[1], "max": clock[2], "workgroups": clock[3],
-                                               "what": "s_memtime / s_memrealtime inside a stamped diagnostic sweep launched right behind the sustained leg",
-                                               "frac_at_measured_clock": roof["frac"] * CLOCK_GHZ / clock[0] if formulation == "matrix" else None}
-            elif clock is not None:
-                roof["clock_ghz_in_kernel"] = {"error": clock}
-        n_desc_launch = NKP * (1 if args.per_camera_launches else len(cams))
         out = {
             "metric": "Mmatches/s (512-bit Hamming comparisons) at 10k kp/img, describe+match step",
             "value": total_cmp / (dt / args.steps) / 1e6,
             "unit": "Mmatches/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "settle": {"steps": max(args.settle_steps, 0), "what": "untimed steps before the warm-up so that the timed region runs at settled clocks"},
-            "warmup_effective": args.warmup + cold_steps + max(args.settle_steps, 0) + args.warmup,
-            "value_cold": total_cmp / (dt_cold / cold_steps) / 1e6, "ms_per_step_cold": dt_cold / cold_steps * 1e3,
-            "cold_what": "%d timed steps straight behind the first %d warm-up steps of the process, before the settle steps" % (cold_steps, args.warmup),
+            "warmup_effective": (args.warmup if args.full else 0) + cold_steps + max(args.settle_steps, 0) + args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None,
             "dtype": ("fp4 (+-1) x fp4 -> f32 accumulate, exact integers (matrix pipe)" if formulation == "matrix" else "u32 (xor+popcount)")
@@ -706,21 +669,11 @@ def main():
                        "keypoints_per_image": NKP, "pairs": len(multicam.exhaustive_pairs(n_cams)),
                        "comparisons_per_step": total_cmp, "k2nn_formulation": formulation,
                        "scene": "one rectangle scene, per-camera sensor noise sigma 2, same keypoints in camera-specific order"},
-            "sustained": sustained,
-            "sustained_value": (total_cmp / (sustained["ms_per_step"] * 1e-3) / 1e6) if sustained else None,
-            "stages": {"clatch_us_per_launch": clatch_us, "pyramid_us_per_launch": avg_us("pyramid_kernel"),
-                       "k2nn_sweep_us": sweep_us, "k2nn_merge_us": avg_us("k2nn_merge_kernel"),
-                       "cameras_per_describe_launch": 1 if args.per_camera_launches else len(cams),
-                       "Mdesc_per_s_kernel": (n_desc_launch / clatch_us) if clatch_us else None,
-                       "Mdesc_per_s_step": len(cams) * NKP * world / (dt / args.steps) / 1e6},
-            "roofline": roof,
-            "k2nn_device": ctx.k2nn_device_info(),        # XCDs / CUs the sweep planner reads from the device, and where its unequal shares come from
             "launch_mode": ("hipGraph replay" if graph is not None else
                             ("eager launches, consecutive steps dealt to %d LANES in turn (a lane = context + stream + descriptor arena): step i's sweep runs "
                              "beside the next steps' pyramid + CLATCH; every step does all of its work, results identical to the one-stream loop's; "
                              "`one_stream` = the same K steps with the device drained between a step's kernels (rounds 1-4's value)" % len(lanes)) if pipelined
                             else "eager launches, one stream"),
-            "one_stream": one_stream,
             "pipelined": pipelined_info,
             "collective": ("none" if world == 1 else
                            ("clc_mc_gather_enqueue_dev: " + promoted["exchange"] + " (product exchange, promoted after agreeing with the torch step)") if promoted else
@@ -729,26 +682,106 @@ def main():
                             if args.backend == "nccl" else "REHEARSAL: gloo all_gather staged through host memory")),
             "collective_fallback": collective_fallback,
             "torch_exchange": torch_exchange,
-            "allgather_us_rank0": allgather_us,
             "exchange_legs": exchange_legs,
+            "full": args.full,
         }
-        if world > 1:
-            # what an efficiency computed from this line against the N = 1 line can and cannot show (SURVEY.md 8e defines E(G) against
-            # G x the one-pair rate; the work per step is pairs x 10^8 comparisons and pairs = N (N - 1) / 2)
-            pairs_n = len(multicam.exhaustive_pairs(world))
-            out["efficiency_note"] = (
-                "comparisons per step: N=1 holds 1 pair (2 cameras on one GPU) = %.0e; this line holds %d pair(s) = %.0e on %d GPUs. "
-                "value(N)/(N x value(1)) is bounded by pairs/N x (N=1 step time / this step's critical path): at N=2 the work is the SAME "
-                "1e8 comparisons as N=1 split over two GPUs (one camera's describe + half a pair each, + the exchange), so E(2) <= ~0.8 "
-                "by construction (one-GPU projection without exchange: 61 us per step against 2 x 99.5 / 2); from N=4 on the pair count "
-                "(6, 28) outgrows the rank count and E can exceed 1 against the one-pair N=1 line. cold_/sustained figures of this line were "
-                "measured with the torch exchange." % (float(NKP) * NKP, pairs_n, float(pairs_n) * NKP * NKP, world))
-        # Everything below is reported next to the headline line and never takes it down: each section runs guarded, a
+        if not args.full:
+            # the one-stream loop, the breakdown, the roofline and the CPU baseline are --full's: their keys are present and null
+            out.update(roofline=None, cpu_baseline=None)
+        else:
+            def avg_us(name, src=None):
+                ms, cnt = (src or prof_all)[name]
+                return (ms / cnt * 1e3) if cnt else None
+
+            sweep_us = avg_us("k2nn_sweep_kernel", prof)
+            clatch_us = avg_us("clatch_kernel")
+            launches = prof["k2nn_sweep_kernel"][1]
+            cmp_per_launch = my_cmp * (args.steps if graph is None else min(args.steps, 20)) / max(launches, 1)
+            compulsory_bytes = sum(64 * (j.nq + counts[j.pair[1]]) + 4 * j.nq for j in jobs)
+            roof = None
+            if sweep_us:
+                t = sweep_us * 1e-6
+                # measured HBM traffic of this kernel comes from separate rocprofv3 --pmc passes (profiles/); it is attached
+                # only when the recorded plan (formulation, shape) is the one that just ran, and says where it came from
+                traffic, traffic_source = None, None
+                tpath = os.path.join(ROOT, "profiles", "r06_k2nn_hbm_traffic.json")
+                if os.path.exists(tpath) and world == 1:
+                    try:
+                        rec = json.load(open(tpath))
+                        if rec.get("formulation") == formulation and rec.get("nq") == NKP and rec.get("nt") == NKP \
+                                and not os.environ.get("CLC_K2NN_TARGET_BLOCKS") and not os.environ.get("CLC_K2NN_XCD_MAP"):
+                            traffic = rec.get("hbm_bytes_per_launch")
+                            traffic_source = "static: %s (%s)" % (os.path.relpath(tpath, ROOT), rec.get("how", "rocprofv3 --pmc"))
+                    except Exception:
+                        traffic = None
+                hbm = {"achieved_GBps": compulsory_bytes / t / 1e9, "peak_GBps": HBM_PEAK_GBS, "frac": compulsory_bytes / t / 1e9 / HBM_PEAK_GBS,
+                       "algorithmic_bytes_per_launch": compulsory_bytes, "swept_GBps": cmp_per_launch * 64 / t / 1e9,
+                       "note": "compulsory bytes 64 (nq + nt) + 4 nq per pair: the sweep is not HBM-bound"}
+                if formulation == "matrix":
+                    flops = cmp_per_launch * 512 * 2
+                    roof = {"bound": "mfma", "kernel": "k2nn_sweep_mx_kernel", "achieved": flops / t / 1e12, "peak": MFMA_FP4_PEAK_TFLOPS,
+                            "unit": "TFLOP/s", "frac": flops / t / 1e12 / MFMA_FP4_PEAK_TFLOPS, "traffic": traffic,
+                            "traffic_source": traffic_source, "avg_launch_us": sweep_us,
+                            "algorithmic_flop_per_launch": flops,
+                            "peak_note": "dense FP4 (v_mfma_scale_f32_32x32x64_f8f6f4): 256 CU x 4 SIMD x 4096 flop/clk x 2.4 GHz; "
+                                         "1 comparison = 512 exact +-1 multiply-adds (SURVEY 8d counts it as 32 VALU lane-ops)",
+                            "Gcmp_per_s_kernel": cmp_per_launch / t / 1e9, "hbm": hbm,
+                            # SURVEY.md 8(d) as written: 32 VALU lane-ops per comparison against 39.3 T lane-ops/s (the popcount formulation's
+                            # bound).  Above 1 for this kernel because the work left the vector ALU for the matrix pipe: kept so that the
+                            # line can be checked against the survey's own definition; `frac` above is the binding one.
+                            "valu_8d": {"lane_ops_per_comparison": 32, "achieved_Tlaneops": cmp_per_launch * 32 / t / 1e12,
+                                        "peak_Tlaneops": VALU_PEAK_TLANEOPS, "frac": cmp_per_launch * 32 / t / 1e12 / VALU_PEAK_TLANEOPS,
+                                        "note": "exceeds 1: the comparisons run as FP4 multiply-adds on the matrix pipe, not as xor + popcount lane-ops"}}
+                else:
+                    laneops = cmp_per_launch * 32 / t / 1e12
+                    roof = {"bound": "valu", "kernel": "k2nn_sweep_kernel", "achieved": laneops, "peak": VALU_PEAK_TLANEOPS,
+                            "unit": "Tlaneop/s", "frac": laneops / VALU_PEAK_TLANEOPS, "traffic": traffic, "traffic_source": traffic_source,
+                            "avg_launch_us": sweep_us,
+                            "peak_note": "256 CU x 64 lanes/clk x 2.4 GHz: measured 4-cycle issue of v_bcnt / SGPR-operand ops",
+                            "lane_ops_per_comparison": 32, "Gcmp_per_s_kernel": cmp_per_launch / t / 1e9, "hbm": hbm}
+                if pipelined and roof is not None:
+                    roof["measured_in"] = ("the one-stream region of this run (K steps, the sweep bracketed by HIP events on its stream, the kernel alone on the "
+                                           "device); in the headline region the sweep shares the device with the next step's describe launch: "
+                                           "pipelined.sweep_us_while_overlapped")
+                if isinstance(clock, tuple):
+                    roof["clock_ghz_in_kernel"] = {"median": clock[0], "min": clock[1], "max": clock[2], "workgroups": clock[3],
+                                                   "what": "s_memtime / s_memrealtime inside a stamped diagnostic sweep launched right behind the sustained leg",
+                                                   "frac_at_measured_clock": roof["frac"] * CLOCK_GHZ / clock[0] if formulation == "matrix" else None}
+                elif clock is not None:
+                    roof["clock_ghz_in_kernel"] = {"error": clock}
+            n_desc_launch = NKP * (1 if args.per_camera_launches else len(cams))
+            out.update({
+                "value_cold": total_cmp / (dt_cold / cold_steps) / 1e6, "ms_per_step_cold": dt_cold / cold_steps * 1e3,
+                "cold_what": "%d timed steps straight behind the first %d warm-up steps of the process, before the settle steps" % (cold_steps, args.warmup),
+                "sustained": sustained,
+                "sustained_value": (total_cmp / (sustained["ms_per_step"] * 1e-3) / 1e6) if sustained else None,
+                "stages": {"clatch_us_per_launch": clatch_us, "pyramid_us_per_launch": avg_us("pyramid_kernel"),
+                           "k2nn_sweep_us": sweep_us, "k2nn_merge_us": avg_us("k2nn_merge_kernel"),
+                           "cameras_per_describe_launch": 1 if args.per_camera_launches else len(cams),
+                           "Mdesc_per_s_kernel": (n_desc_launch / clatch_us) if clatch_us else None,
+                           "Mdesc_per_s_step": len(cams) * NKP * world / (dt / args.steps) / 1e6},
+                "roofline": roof,
+                "k2nn_device": ctx.k2nn_device_info(),        # XCDs / CUs the sweep planner reads from the device, and where its unequal shares come from
+                "one_stream": one_stream,
+                "allgather_us_rank0": allgather_us,
+            })
+            if world > 1:
+                # what an efficiency computed from this line against the N = 1 line can and cannot show (SURVEY.md 8e defines E(G) against
+                # G x the one-pair rate; the work per step is pairs x 10^8 comparisons and pairs = N (N - 1) / 2)
+                pairs_n = len(multicam.exhaustive_pairs(world))
+                out["efficiency_note"] = (
+                    "comparisons per step: N=1 holds 1 pair (2 cameras on one GPU) = %.0e; this line holds %d pair(s) = %.0e on %d GPUs. "
+                    "value(N)/(N x value(1)) is bounded by pairs/N x (N=1 step time / this step's critical path): at N=2 the work is the SAME "
+                    "1e8 comparisons as N=1 split over two GPUs (one camera's describe + half a pair each, + the exchange), so E(2) <= ~0.8 "
+                    "by construction (one-GPU projection without exchange: 61 us per step against 2 x 99.5 / 2); from N=4 on the pair count "
+                    "(6, 28) outgrows the rank count and E can exceed 1 against the one-pair N=1 line. cold_/sustained figures of this line were "
+                    "measured with the torch exchange." % (float(NKP) * NKP, pairs_n, float(pairs_n) * NKP * NKP, world))
+        # Everything below (--full) is reported next to the headline line and never takes it down: each section runs guarded, a
         # failure is recorded under its own key -- and makes the process exit non-zero AFTER the line is printed.
         only = set(k for k in (args.sections or "").split(",") if k)
 
         def guarded(key, fn):
-            if only and key not in only:
+            if not args.full or (only and key not in only):
                 return
             try:
                 fn()

@@ -27,3 +27,10 @@ def test_under_a_launcher_nothing_is_spawned():
                          capture_output=True, text=True, cwd=ROOT, env=env, timeout=240)
     assert "starting the ranks myself" not in out.stderr
     assert out.returncode != 0 and "WORLD_SIZE=3" in (out.stdout + out.stderr)
+
+
+def test_help_lists_full_and_dump_outputs():
+    # the options are parsed before anything imports torch: `--help` answers without a GPU
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, cwd=ROOT, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert "--full" in out.stdout and "--dump-outputs DIR" in out.stdout

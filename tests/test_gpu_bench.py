@@ -20,11 +20,12 @@ def _last_json(out):
     raise AssertionError("no JSON line in output:\n" + out[-2000:])
 
 
-def test_default_line_has_contract_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3"],
-                         capture_output=True, text=True, cwd=ROOT, timeout=600)
+def test_default_line_has_contract_fields(oracle, tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full",
+                          "--dump-outputs", str(tmp_path / "full")], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
+    _check_dumped_outputs(oracle, tmp_path / "full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -63,8 +64,42 @@ def test_default_line_has_contract_fields():
     assert d["value"] > 10 * c["value"]          # north-star target: >= 10x the host-CPU matcher
 
 
+def _check_dumped_outputs(oracle, d):
+    """--dump-outputs: the last timed step's descriptor blocks (2 cameras x 10k x 64 bytes) and match indices, float32; the indices are
+    the oracle's 2-NN of the two dumped blocks"""
+    import numpy as np
+    desc, m = np.load(str(d / "descriptors.npy")), np.load(str(d / "matches.npy"))
+    assert desc.dtype == np.float32 and desc.shape == (2, 10000, 64) and m.dtype == np.float32 and m.shape == (10000,)
+    assert desc.min() >= 0 and desc.max() <= 255 and np.array_equal(desc, np.round(desc)) and np.array_equal(m, np.round(m))
+    q, t = desc[0].astype(np.uint8), desc[1].astype(np.uint8)
+    assert np.array_equal(m.astype(np.int32), oracle.k2nn(q, t, 40)) and (m >= 0).sum() > 5000
+    return desc, m
+
+
+def test_plain_line_is_lean_and_dumps_what_it_computed(oracle, tmp_path):
+    """A plain run (no --full) sets up, warms up, times exactly K steps and prints the headline line: the contract's fields, none of
+    --full's legs.  --dump-outputs writes what the last timed step computed, the same whatever K and W (seeded inputs)."""
+    import numpy as np
+    runs = []
+    for steps, warmup, sub in ((7, 2, "a"), (4, 1, "b")):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                              "--dump-outputs", str(tmp_path / sub)], capture_output=True, text=True, cwd=ROOT, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = _last_json(out.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+            assert k in d, k
+        assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup and d["n_gpus"] == 1
+        assert d["unit"] == "Mmatches/s" and d["higher_is_better"] is True and "fp4" in d["dtype"]
+        assert d["ms_per_step"] > 0 and abs(d["value"] - 1e8 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * d["value"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["pipelined"]["sweep_launches"] == steps
+        for k in ("value_cold", "sustained", "one_stream", "stages", "front_end", "pose_solve", "host_path", "policy_path"):
+            assert k not in d, k
+        runs.append(_check_dumped_outputs(oracle, tmp_path / sub))
+    assert all(np.array_equal(x, y) for x, y in zip(*runs))
+
+
 def test_one_stream_flag_gives_the_old_headline_loop():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--one-stream", "--headline-only",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--one-stream", "--full", "--headline-only",
                           "--no-cpu-baseline", "--sustain-seconds", "0.3"], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
@@ -98,7 +133,8 @@ def test_gpus_2_typed_directly_starts_its_own_ranks():
     exit code -- and the N = 2 line comes out (rehearsal: two ranks share the one GPU)."""
     env = dict(os.environ, BENCH_FAULT_AFTER="200")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--settle-steps", "6"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--settle-steps", "6",
+                          "--full"],
                          capture_output=True, text=True, cwd=ROOT, env=env, timeout=280)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "starting the ranks myself" in out.stderr
@@ -115,7 +151,7 @@ def test_two_rank_rehearsal_runs():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", BENCH_FAULT_AFTER="200")   # a hung rank dumps its stacks and exits
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1",
-           "--settle-steps", "6", "--backend", "gloo"]
+           "--settle-steps", "6", "--backend", "gloo", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=280)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     _check_two_rank_line(_last_json(out.stdout))
@@ -139,7 +175,7 @@ def test_four_rank_rehearsal_runs():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", BENCH_FAULT_AFTER="200")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", "29537", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "1",
-           "--settle-steps", "6", "--backend", "gloo", "--sustain-seconds", "0.2"]
+           "--settle-steps", "6", "--backend", "gloo", "--sustain-seconds", "0.2", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=280)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     d = _last_json(out.stdout)

@@ -1,8 +1,9 @@
 """CPU tests of the CLATCH / pyramid / feeder oracle against (i) the learned-pattern hash, (ii) a
 lane-level emulation of the reference reduce-transpose, (iii) closed-form cases and (iv) the
-reference's own KFAST.h / FeatureAngle.h compiled into oracle/_ref."""
+reference's own KFAST.h / FeatureAngle.h, whose outputs on the inputs used here are stored in tests/golden/fast9_ref.npz."""
 import hashlib
 import math
+import os
 import struct
 
 import numpy as np
@@ -113,29 +114,26 @@ def test_descriptor_is_not_degenerate(oracle):
     assert len({bytes(r) for r in d}) > 150
 
 
-def test_fast9_and_angle_match_compiled_reference(oracle, ref_feeder):
-    """orc_fast9 / orc_feature_angle == the reference's KFAST<mt,true> / featureAngle compiled from
-    /root/reference (oracle/_ref), including the width = 38 + 16k shift-by-32 quirk."""
-    for (W, H, seed) in [(640, 480, 1000), (214, 161, 5), (179, 134, 6), (257, 193, 7), (215, 60, 8)]:
-        img = synth.rect_image(W, H, seed=seed, noise_sigma=2.0)
-        a = oracle.fast9(img, 40)
-        for mt in (True, False):
-            b = ref_feeder.kfast(img, 40, mt)
-            assert len(a) == len(b) > 0
-            for f in ("x", "y", "score"):
-                assert np.array_equal(a[f], b[f])
-        ao = np.array([oracle.feature_angle(img, int(k["x"]), int(k["y"])) for k in a[:200]])
-        ar = np.array([ref_feeder.feature_angle(img, int(k["x"]), int(k["y"])) for k in a[:200]])
-        assert np.array_equal(ao.view(np.uint32), ar.view(np.uint32))
+# The reference's own KFAST<mt, true> / featureAngle (include/coloc/KFAST.h, FeatureAngle.h), compiled into oracle/_ref/ and run on
+# exactly the inputs below: their outputs are frozen in tests/golden/fast9_ref.npz (tests/golden/make_golden_fast9.py), each input
+# pinned by the sha256 of its bytes, so that these tests need nothing outside the repository.
+REF_CASES = [(640, 480, 1000), (214, 161, 5), (179, 134, 6), (257, 193, 7), (215, 60, 8)]
+EDGE_SIZES = [(38, 40), (22, 30), (54, 33), (70, 17), (134, 50), (64, 16), (65, 17), (129, 48), (198, 64), (1286, 40)]
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fast9_ref.npz")
 
 
-def test_fast9_width_quirk(oracle, ref_feeder):
+def ref_case_image(W, H, seed):
+    return synth.rect_image(W, H, seed=seed, noise_sigma=2.0)
+
+
+def quirk_images():
+    """(W, expect_any, img): a bright block ending at column 195, seen by the row walk at width 215 and not at 214"""
     rng = np.random.default_rng(1)
+    out = []
     for W, expect_any in ((214, False), (215, True)):
         base = np.zeros((60, W), np.int32); base[10:21, 185:196] = 200
-        img = (base + rng.integers(0, 30, size=base.shape) * (base > 0)).astype(np.uint8)
-        a = oracle.fast9(img, 40); b = ref_feeder.kfast(img, 40, False)
-        assert (len(a) > 0) == expect_any and len(a) == len(b)
+        out.append((W, expect_any, (base + rng.integers(0, 30, size=base.shape) * (base > 0)).astype(np.uint8)))
+    return out
 
 
 def edge_image(W, H):
@@ -147,17 +145,58 @@ def edge_image(W, H):
     return img
 
 
-def test_fast9_edge_sizes_match_compiled_reference(oracle, ref_feeder):
-    """The sizes the GPU detector is tested at around its tile seams and at widths 6 (mod 16) (38 = the narrowest image whose row walk
-    lands on cols - 35): the restatement == the compiled reference there too, so the GPU test's oracle is pinned at those sizes."""
-    dropped = 0
-    for (W, H) in [(38, 40), (22, 30), (54, 33), (70, 17), (134, 50), (64, 16), (65, 17), (129, 48), (198, 64), (1286, 40)]:
-        img = edge_image(W, H)
+def digest(img):
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(img).tobytes()).digest(), np.uint8)
+
+
+def golden_ref(key, img):
+    """the compiled reference's stored output for `key`, after checking that `img` is the input it was computed on"""
+    g = np.load(GOLDEN)
+    assert np.array_equal(digest(img), g[key + "_sha256"]), "%s: the input differs from the one the reference ran on" % key
+    return g
+
+
+def same_kps(a, xys):
+    return len(a) == len(xys) and np.array_equal(np.stack([a["x"], a["y"], a["score"].astype(np.int32)], 1).reshape(-1, 3), xys.reshape(-1, 3))
+
+
+def test_fast9_and_angle_match_compiled_reference(oracle):
+    """orc_fast9 / orc_feature_angle == the reference's KFAST<mt,true> / featureAngle (compiled reference outputs stored in
+    tests/golden/fast9_ref.npz), including the width = 38 + 16k shift-by-32 quirk."""
+    for (W, H, seed) in REF_CASES:
+        key = "case_%dx%d_%d" % (W, H, seed)
+        img = ref_case_image(W, H, seed)
+        g = golden_ref(key, img)
         a = oracle.fast9(img, 40)
-        b = ref_feeder.kfast(img, 40, False)
+        for mt in (True, False):
+            b = g[key + "_mt%d_xys" % mt]
+            assert len(a) == len(b) > 0
+            assert same_kps(a, b)
+        ao = np.array([oracle.feature_angle(img, int(k["x"]), int(k["y"])) for k in a[:200]])
+        assert np.array_equal(ao.view(np.uint32), g[key + "_angle"].view(np.uint32))
+
+
+def test_fast9_width_quirk(oracle):
+    for W, expect_any, img in quirk_images():
+        key = "quirk_%d" % W
+        g = golden_ref(key, img)
+        a = oracle.fast9(img, 40)
+        assert (len(a) > 0) == expect_any and len(a) == int(g[key + "_count"])
+
+
+def test_fast9_edge_sizes_match_compiled_reference(oracle):
+    """The sizes the GPU detector is tested at around its tile seams and at widths 6 (mod 16) (38 = the narrowest image whose row walk
+    lands on cols - 35): the restatement == the compiled reference there too (its outputs stored in tests/golden/fast9_ref.npz), so the
+    GPU test's oracle is pinned at those sizes."""
+    dropped = 0
+    for (W, H) in EDGE_SIZES:
+        key = "edge_%dx%d" % (W, H)
+        img = edge_image(W, H)
+        g = golden_ref(key, img)
+        a = oracle.fast9(img, 40)
+        b = g[key + "_xys"]
         assert len(a) == len(b)
-        for f in ("x", "y", "score"):
-            assert np.array_equal(a[f], b[f])
+        assert same_kps(a, b)
         if W % 16 == 6 and W >= 38:
             dropped += int((a["x"] >= W - 35).sum() == 0 or W == 38)
     assert dropped >= 1

@@ -6,7 +6,7 @@ TAG=${1:-r05}
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG; rm -rf $OUT; mkdir -p $OUT
 stats() { local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o bench -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --sustain-seconds 0 --settle-steps 500 --headline-only "$@" > $OUT/${name}_stdout.log 2>&1 || { tail -20 $OUT/${name}_stdout.log; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -o bench -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --sustain-seconds 0 --settle-steps 500 --headline-only "$@" > $OUT/${name}_stdout.log 2>&1 || { tail -20 $OUT/${name}_stdout.log; exit 1; }
   find $OUT/$name -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${name}_kernel_stats.csv
   rm -rf $OUT/$name
   head -6 $OUT/${name}_kernel_stats.csv | cut -c1-200
