@@ -632,8 +632,11 @@ class Context:
         self._chk(self.lib.clc_desc_cache_mode(self.h, {"off": DESC_CACHE_OFF, "verify": DESC_CACHE_VERIFY, "trust": DESC_CACHE_TRUST}[mode]))
 
     def desc_cache_publish(self, h_desc, d_src=None):
-        """The rows of numpy block h_desc (n x 64) are on this device at d_src (None: the context's own descriptor array, what
-        detect_and_describe filled): later host-pointer match calls given this very block skip its upload."""
+        """The rows of numpy block h_desc (n x 64) are on this device at d_src: later host-pointer match calls given this very block
+        skip its upload.  d_src None: the rows of this context's last describing call -- the frame detect_and_describe(_published)
+        staged (h_desc must hold exactly its first n rows, else CLC_ERR_STATE), or what describe / describe_detected_dev(None) /
+        describe_dev into the context's own array left there (at most that many rows, else CLC_ERR_BAD_ARG); after a describe into
+        caller buffers there is nothing to publish (CLC_ERR_STATE)."""
         assert h_desc.dtype == np.uint8 and h_desc.flags["C_CONTIGUOUS"]
         handle = DescHandle()
         self._chk(self.lib.clc_desc_cache_publish(self.h, d_src, _p(h_desc), int(h_desc.shape[0]), C.byref(handle)))

@@ -454,6 +454,8 @@ int clc_detect_dev(clc_ctx* ctx, void* stream)
     if (!ctx) return CLC_ERR_BAD_ARG;
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "detect: context created without detector options");
     if (!ctx->pyramid_valid) return fail(ctx, CLC_ERR_STATE, "detect before pyramid_build");
+    // the counter that said how many rows clc_describe_detected_dev left in d_desc is about to describe another keypoint list
+    if (ctx->rows_at == ROWS_OWN && ctx->own_rows < 0) ctx->rows_at = ROWS_NONE;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     clc_keypoint* kps[1] = { ctx->d_kps };
     uint32_t* cnt[1] = { ctx->d_count };
@@ -466,6 +468,7 @@ int clc_detect_dev(clc_ctx* ctx, void* stream)
 int clc_detect_batch_dev(clc_ctx* ctx, int n_images, const void* const* d_imgs, uint32_t width, uint32_t height, size_t pitch,
                          clc_keypoint* const* d_kps, uint32_t* const* d_counts, void* const* d_desc, void* stream)
 {
+    if (ctx && d_desc) rows_leave(ctx);              // describes into caller buffers
     if (!ctx || n_images < 0 || (n_images > 0 && (!d_imgs || !d_kps || !d_counts)))
         return fail(ctx, CLC_ERR_BAD_ARG, "detect_batch: null argument");
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "detect_batch: context created without detector options");
@@ -529,9 +532,8 @@ int clc_detect(clc_ctx* ctx, clc_keypoint* h_kps, int capacity, int* n_written, 
     return CLC_OK;
 }
 
-int clc_describe_detected_dev(clc_ctx* ctx, void* d_desc, void* stream)
+static int describe_detected(clc_ctx* ctx, void* d_desc, void* stream)
 {
-    if (!ctx) return CLC_ERR_BAD_ARG;
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "describe_detected: context created without detector options");
     if (!ctx->detected) return fail(ctx, CLC_ERR_STATE, "describe_detected before detect");
     if ((uintptr_t)d_desc & 7u) return fail(ctx, CLC_ERR_BAD_ARG, "describe_detected: misaligned device pointer");
@@ -539,6 +541,15 @@ int clc_describe_detected_dev(clc_ctx* ctx, void* d_desc, void* stream)
     CLC_HIP(ctx, launch_clatch_counted(ctx->pd, ctx->d_arena, ctx->d_kps, count_ptr(ctx), (int)ctx->dopts.maxkp,
                                        d_desc ? (uint64_t*)d_desc : ctx->d_desc, pick(ctx, stream), &ctx->prof));
     return CLC_OK;
+}
+
+int clc_describe_detected_dev(clc_ctx* ctx, void* d_desc, void* stream)
+{
+    if (!ctx) return CLC_ERR_BAD_ARG;
+    rows_leave(ctx);
+    const int rc = describe_detected(ctx, d_desc, stream);
+    if (rc == CLC_OK && (!d_desc || d_desc == ctx->d_desc)) { ctx->rows_at = ROWS_OWN; ctx->own_rows = -1; }
+    return rc;
 }
 
 /* ---- the whole front end on host buffers: GPUDetector::detectAndDescribe (GPUDetector.hpp:216-291) as one enqueue sequence ----------
@@ -554,19 +565,24 @@ int clc_detect_and_describe_view(clc_ctx* ctx, const uint8_t* h_img, uint32_t wi
     if (h_desc) *h_desc = nullptr;
     if (n_written) *n_written = 0;
     if (n_found) *n_found = 0;
+    // the last frame's rows stand no more (even if this call fails); its table block, desc_pending, is where this frame goes
+    if (ctx) { ctx->staged_n = -1; ctx->rows_at = ROWS_NONE; }
     if (!ctx || !h_img) return fail(ctx, CLC_ERR_BAD_ARG, "detect_and_describe: bad argument");
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "detect_and_describe: context created without detector options");
     if (width != ctx->dopts.width || height != ctx->dopts.height)
         return fail(ctx, CLC_ERR_BAD_ARG, "detect_and_describe: image size differs from DetectorOptions width/height");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     { const int rc = ensure_stage(ctx); if (rc != CLC_OK) return rc; }
-    ctx->staged_n = -1;
     // where the descriptors go on the device: a block of the descriptor table that nothing published stands on (a published block
     // stays as it is until its publication dies), else the context's own array
     uint8_t* d_rows = nullptr;
     if (ctx->cache_mode != CLC_DESC_CACHE_OFF) {
         if (!ctx->desc_pending) ctx->desc_pending = desc_reserve(ctx, ctx->device, ctx->dopts.maxkp, &d_rows);
         else d_rows = desc_rows(ctx->desc_pending);
+    } else if (ctx->desc_pending) {
+        // an earlier frame's block must not stand for this one (a NULL publish after the mode changes back would take it)
+        desc_abandon(ctx->desc_pending);
+        ctx->desc_pending = nullptr;
     }
     if (!d_rows) d_rows = (uint8_t*)ctx->d_desc;
     const LevelDesc& L0 = ctx->pd.lv[0];
@@ -582,7 +598,7 @@ int clc_detect_and_describe_view(clc_ctx* ctx, const uint8_t* h_img, uint32_t wi
     ctx->pyramid_valid = true;
     int rc = clc_detect_dev(ctx, nullptr);
     if (rc != CLC_OK) return rc;
-    rc = clc_describe_detected_dev(ctx, d_rows, nullptr);
+    rc = describe_detected(ctx, d_rows, nullptr);
     if (rc != CLC_OK) return rc;
     const uint32_t blocks = (ctx->dopts.maxkp * 4u + 255u) / 256u;
     hipLaunchKernelGGL(frontend_mirror_kernel, dim3(blocks ? blocks : 1u), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_kps, (const uint4*)d_rows,
@@ -591,6 +607,7 @@ int clc_detect_and_describe_view(clc_ctx* ctx, const uint8_t* h_img, uint32_t wi
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int n = (int)h_cnt[0];
     ctx->staged_n = n;
+    ctx->rows_at = ROWS_STAGED;
     if (h_kps) *h_kps = (const clc_keypoint*)(hp + ctx->stage_kps);
     if (h_desc) *h_desc = hp + ctx->stage_desc;
     if (n_written) *n_written = n;
@@ -639,12 +656,16 @@ int clc_detect_store_descriptors(clc_ctx* ctx, void* h_dst, int n, clc_desc_hand
 
 int clc_describe_dev(clc_ctx* ctx, const clc_keypoint* d_kps, int n, void* d_desc, void* stream)
 {
+    if (ctx) rows_leave(ctx);
     if (!ctx || n < 0 || (n > 0 && (!d_kps || !d_desc))) return fail(ctx, CLC_ERR_BAD_ARG, "describe: bad argument");
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "describe: context created without detector options");
     if (!ctx->pyramid_valid) return fail(ctx, CLC_ERR_STATE, "describe before pyramid_build");
     if (((uintptr_t)d_desc & 7u) || ((uintptr_t)d_kps & 3u)) return fail(ctx, CLC_ERR_BAD_ARG, "describe: misaligned device pointer");
+    const bool own = d_desc && d_desc == ctx->d_desc;
+    if (own && (uint32_t)n > ctx->dopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "describe: more keypoints than the context's descriptor array holds");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     CLC_HIP(ctx, launch_clatch(ctx->pd, ctx->d_arena, d_kps, n, (uint64_t*)d_desc, pick(ctx, stream), &ctx->prof));
+    if (own) { ctx->rows_at = ROWS_OWN; ctx->own_rows = n; }
     return CLC_OK;
 }
 
@@ -652,6 +673,7 @@ int clc_describe_batch_dev(clc_ctx* ctx, int n_images, const void* const* d_imgs
                            size_t pitch, const clc_keypoint* const* d_kps, const int* counts, void* const* d_desc,
                            void* stream)
 {
+    if (ctx) rows_leave(ctx);                        // describes into caller buffers
     if (!ctx || n_images < 0 || (n_images > 0 && (!d_imgs || !d_kps || !counts || !d_desc)))
         return fail(ctx, CLC_ERR_BAD_ARG, "describe_batch: null argument");
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "describe_batch: context created without detector options");
@@ -686,6 +708,7 @@ int clc_describe_batch_dev(clc_ctx* ctx, int n_images, const void* const* d_imgs
 
 int clc_describe(clc_ctx* ctx, const clc_keypoint* h_kps, int n, uint8_t* h_desc)
 {
+    if (ctx) rows_leave(ctx);
     if (!ctx || n < 0 || (n > 0 && (!h_kps || !h_desc))) return fail(ctx, CLC_ERR_BAD_ARG, "describe: bad argument");
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "describe: context created without detector options");
     if ((uint32_t)n > ctx->dopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "describe: more keypoints than DetectorOptions.maxkp");
@@ -698,6 +721,7 @@ int clc_describe(clc_ctx* ctx, const clc_keypoint* h_kps, int n, uint8_t* h_desc
     CLC_HIP(ctx, launch_clatch(ctx->pd, ctx->d_arena, ctx->d_kps, n, ctx->d_desc, ctx->stream, &ctx->prof));
     CLC_HIP(ctx, hipMemcpyAsync(h_desc, ctx->d_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->rows_at = ROWS_OWN; ctx->own_rows = n;
     return CLC_OK;
 }
 

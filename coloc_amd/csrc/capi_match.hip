@@ -232,6 +232,7 @@ int clc_describe_match_pair_dev(clc_ctx* ctx, const void* const* d_imgs, uint32_
                                 const clc_keypoint* const* d_kps, const int* counts, void* const* d_desc, int threshold,
                                 int32_t* d_match, void* stream)
 {
+    if (ctx) rows_leave(ctx);                        // describes into caller buffers
     if (!ctx || !d_imgs || !d_kps || !counts || !d_desc || !d_imgs[0] || !d_imgs[1] || counts[0] < 0 || counts[1] < 0 ||
         (counts[0] > 0 && (!d_kps[0] || !d_desc[0] || !d_match)) || (counts[1] > 0 && (!d_kps[1] || !d_desc[1])))
         return fail(ctx, CLC_ERR_BAD_ARG, "describe_match_pair: bad argument");

@@ -46,7 +46,12 @@ struct Profiler {
 };
 } // namespace clc
 
-namespace clc { struct DescEntry; }
+namespace clc {
+struct DescEntry;
+// rows_at: STAGED = the frame of the last clc_detect_and_describe* call (pinned block / desc_pending, staged_n rows); OWN = the
+// context's own d_desc (own_rows); NONE = the last describing call wrote a caller buffer or failed, or nothing was described yet
+enum { ROWS_NONE = 0, ROWS_STAGED = 1, ROWS_OWN = 2 };
+}
 
 struct clc_ctx {
     int device = 0;
@@ -105,6 +110,9 @@ struct clc_ctx {
     size_t stage_img = 0, stage_kps = 0, stage_desc = 0, stage_cnt = 0;      // byte offsets inside h_stage
     clc::DescEntry* desc_pending = nullptr;
     int staged_n = -1;            // rows of the last staged frame (-1: none)
+    // where the rows of this context's last describing call lie: what clc_desc_cache_publish(d_src = NULL) publishes
+    int rows_at = clc::ROWS_NONE;
+    int own_rows = 0;             // ROWS_OWN: rows described into d_desc (-1: the detector's {written} counter tells)
     // host-pointer match entries: pinned mirror of the results (so that the host can verify published blocks while the GPU sweeps)
     uint8_t* h_res = nullptr;
     size_t res_cap = 0;
@@ -130,6 +138,10 @@ int ensure_pnp(clc_ctx* ctx, size_t doubles);             // pose scratch
 int ensure_pinned(clc_ctx* ctx, size_t bytes);            // pinned staging of the pose solves
 int ensure_slots(clc_ctx* ctx, int n, hipStream_t st);    // pyramids (+ detector maps) of n cameras
 int ensure_results(clc_ctx* ctx, size_t bytes);           // pinned mirror of match results
+
+// a describing call begins: the rows of the last one no longer stand (staged_n = -1, desc_pending abandoned, rows_at = NONE)
+// (desc_cache.hip)
+void rows_leave(clc_ctx* ctx);
 
 // K2NN: plan + launch a job list on `st` with the context's formulation / shares (capi_match.hip)
 int default_target_blocks(int formulation, const K2nnDevice& dev = K2nnDevice{});

@@ -33,7 +33,7 @@ uint64_t desc_copy_fold(void* dst, const void* src, size_t n);
 // nullptr when every entry is in use (the caller then writes into memory of its own and nothing is published).
 DescEntry* desc_reserve(const clc_ctx* owner, int device, size_t rows, uint8_t** d_rows);
 uint8_t* desc_rows(DescEntry* e);
-void desc_abandon(DescEntry* e);      // a reservation that will not be published after all
+void desc_abandon(DescEntry* e);      // a reservation that will not be published after all (it stays its owner's, unpublished)
 // The n rows of entry e are the rows now stored at host address h.  fold: desc_block_fold of them when has_fold.
 void desc_publish(DescEntry* e, const void* h, int n, uint64_t fold, bool has_fold, clc_desc_handle* out);
 // Device rows of host block (h, n) if a live entry stands for it under `mode`; the entry stays pinned until desc_release.

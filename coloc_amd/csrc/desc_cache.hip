@@ -116,7 +116,14 @@ void desc_abandon(DescEntry* e)
 {
     if (!e) return;
     std::lock_guard<std::mutex> lk(table().mu);
-    e->reserved = false; e->h = nullptr; e->owner = nullptr;
+    e->reserved = false; e->h = nullptr;                 // (the owner stays: the block serves its next reservation, and dies with it)
+}
+
+void rows_leave(clc_ctx* ctx)
+{
+    ctx->rows_at = ROWS_NONE; ctx->own_rows = 0;
+    ctx->staged_n = -1;
+    if (ctx->desc_pending) { desc_abandon(ctx->desc_pending); ctx->desc_pending = nullptr; }
 }
 
 void desc_publish(DescEntry* e, const void* h, const int n, const uint64_t fold, const bool has_fold, clc_desc_handle* out)
@@ -214,28 +221,49 @@ int clc_desc_cache_publish(clc_ctx* ctx, const void* d_src, const void* h_desc, 
     if (ctx->cache_mode == CLC_DESC_CACHE_OFF || n == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     DescEntry* e = nullptr;
+    bool count_on_device = false;         // rows of clc_describe_detected_dev: how many there are is in the detector's counter
     if (!d_src) {
         if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "desc_cache_publish: context created without detector options and no device source given");
-        // the rows of this context's last clc_detect_and_describe* call already lie in a block of the table ...
-        if (ctx->desc_pending && n == ctx->staged_n) e = ctx->desc_pending;
-        else if (ctx->h_stage && ctx->staged_n >= 0 && n <= ctx->staged_n) {
-            // ... unless that block has been published already (the same frame stored at a second address): the rows are still in
-            // the pinned staging block
-            uint8_t* d = nullptr;
-            e = desc_reserve(ctx, ctx->device, (size_t)n, &d);
-            if (!e) return CLC_OK;
-            hipError_t err = hipMemcpyAsync(d, ctx->h_stage + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream);
-            if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
-            if (err != hipSuccess) { desc_abandon(e); return fail(ctx, CLC_ERR_HIP, "desc_cache_publish", err); }
-        } else d_src = ctx->d_desc;           // rows of the device-resident flow (clc_detect_dev + clc_describe_detected_dev)
+        // NULL = the rows of this context's last describing call, and only if the host block holds exactly those rows: the fold
+        // taken below proves only that the host rows do not change AFTER this call, never that the device rows equal them
+        if (ctx->rows_at == ROWS_STAGED) {
+            if (n > ctx->staged_n || memcmp(h_desc, ctx->h_stage + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES) != 0)
+                return fail(ctx, CLC_ERR_STATE, "desc_cache_publish: the host rows are not the rows of the frame this context staged");
+            // the rows already lie in a block of the table ...
+            if (ctx->desc_pending && n == ctx->staged_n) e = ctx->desc_pending;
+            else {
+                // ... unless that block has been published already (the same frame stored at a second address) or was never taken
+                // (mode off at the time, or a table in use): the rows are still in the pinned staging block
+                uint8_t* d = nullptr;
+                e = desc_reserve(ctx, ctx->device, (size_t)n, &d);
+                if (!e) return CLC_OK;
+                hipError_t err = hipMemcpyAsync(d, ctx->h_stage + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream);
+                if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
+                if (err != hipSuccess) { desc_abandon(e); return fail(ctx, CLC_ERR_HIP, "desc_cache_publish", err); }
+            }
+        } else if (ctx->rows_at == ROWS_OWN) {
+            // the device-resident flow (clc_describe_detected_dev / clc_describe_dev into d_desc) or clc_describe
+            if (n > (ctx->own_rows >= 0 ? ctx->own_rows : (int)ctx->dopts.maxkp))
+                return fail(ctx, CLC_ERR_BAD_ARG, "desc_cache_publish: more rows than this context described");
+            d_src = ctx->d_desc;
+            count_on_device = ctx->own_rows < 0;
+        } else
+            return fail(ctx, CLC_ERR_STATE, "desc_cache_publish: no rows of this context to publish (its last describing call wrote a caller buffer or failed)");
     }
     if (!e) {
         uint8_t* d = nullptr;
         e = desc_reserve(ctx, ctx->device, (size_t)n, &d);
         if (!e) return CLC_OK;                                                       // every entry in use: nothing is published
+        uint32_t cnt[2] = { 0, 0 };
         hipError_t err = hipMemcpyAsync(d, d_src, (size_t)n * CLC_DESC_BYTES, hipMemcpyDeviceToDevice, ctx->stream);
+        if (err == hipSuccess && count_on_device) err = hipMemcpyAsync(cnt, ctx->d_count, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
         if (err != hipSuccess) { desc_abandon(e); return fail(ctx, CLC_ERR_HIP, "desc_cache_publish", err); }
+        // (n <= maxkp was checked above, so the copy stayed inside d_desc; rows past the detector's count are not described rows)
+        if (count_on_device && (uint32_t)n > (cnt[0] < ctx->dopts.maxkp ? cnt[0] : ctx->dopts.maxkp)) {
+            desc_abandon(e);
+            return fail(ctx, CLC_ERR_BAD_ARG, "desc_cache_publish: more rows than this context described");
+        }
     }
     // a verifying context folds the block it publishes (the host has just written it); a trusting one does not, and its entries can
     // then only be hit by trusting lookups

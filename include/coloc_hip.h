@@ -21,7 +21,9 @@
  *   - inputs need no padding (the reference needs +8 readable train vectors,
  *     GPUMatcher.hpp:183-186).
  *   - a context is thread-compatible: one host thread at a time; several contexts per
- *     process / device are fine; no hidden process-global state.  A context owns ONE set of device
+ *     process / device are fine.  The one process-wide state is the descriptor table behind
+ *     clc_desc_cache_* (one per device, guarded by a lock; what one context publishes, another's
+ *     host-pointer match calls may read).  A context owns ONE set of device
  *     workspaces (pyramid arena, matcher top-2 rows and arrival counters, pose scratch), so the `_dev`
  *     calls made on one context must be ordered with respect to each other -- same stream, or
  *     streams joined by events; use one context per concurrently running stream.
@@ -244,7 +246,21 @@ int clc_match_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt
  *       place (opt-in: HIPMatcher::trustPublishedRegions(true));
  *   CLC_DESC_CACHE_OFF: every block is uploaded, like the reference (GPUMatcher.hpp:188-196); the front end publishes nothing.
  * A block published by a TRUST context carries no fold and is invisible to VERIFY lookups.  Up to 32 blocks, least recently used
- * replaced; CLC_DESC_CACHE=0|verify|trust in the environment sets the mode contexts start with. */
+ * replaced; CLC_DESC_CACHE=0|verify|trust in the environment sets the mode contexts start with.
+ * The fold proves only that the host rows have not changed SINCE the publication, never that the device rows equal them: publishing
+ * must put the caller's exact rows on the device.  clc_desc_cache_publish(ctx, d_src, h_desc, n, handle):
+ *   d_src != NULL: the caller states that d_src holds the n rows of h_desc.  The copy runs on the context's stream: rows written on
+ *       another stream must be complete, or that stream joined to the context's, before the call;
+ *   d_src == NULL: the rows of this context's LAST describing call, and only those --
+ *     - after clc_detect_and_describe(_view): the staged frame.  n must be <= its row count and the n host rows must equal its first
+ *       n rows (compared), else CLC_ERR_STATE;
+ *     - after clc_describe (n rows), or clc_describe_detected_dev / clc_describe_dev with the context's own array as the target (the
+ *       detected count / the given n): the context's array.  More rows than that is CLC_ERR_BAD_ARG (a clc_detect* since then makes
+ *       the detected count another list's, and leaves nothing to publish);
+ *     - after a describing call into caller buffers (clc_describe_detected_dev / clc_describe_dev with another target,
+ *       clc_detect_batch_dev with d_desc, clc_describe_batch_dev, clc_describe_match_pair_dev) or a failed one: CLC_ERR_STATE.  Such a
+ *       call also ends the staged frame, so clc_detect_store_descriptors then fails with CLC_ERR_STATE too.
+ *   On every error nothing is published and *handle is zeroed.  Mode CLC_DESC_CACHE_OFF publishes nothing and returns CLC_OK. */
 enum { CLC_DESC_CACHE_OFF = 0, CLC_DESC_CACHE_VERIFY = 1, CLC_DESC_CACHE_TRUST = 2 };
 int clc_desc_cache_mode(clc_ctx* ctx, int mode);
 int clc_desc_cache_publish(clc_ctx* ctx, const void* d_src, const void* h_desc, int n, clc_desc_handle* handle /* nullable */);

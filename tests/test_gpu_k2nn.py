@@ -295,14 +295,26 @@ def test_counted_jobs_read_their_sizes_on_the_device(gpu_ctx, oracle):
         assert (got[na:] == -1).all(), (na, nb)
 
 
+def exact_2nn(ctx, oracle, Q, T, thr):
+    """clc_match_2nn with distances: match, best and second must be the oracle's; returns the match indices."""
+    got = ctx.match_2nn(Q, T, thr, want_dist=True)
+    want = oracle.k2nn(Q, T, thr, want_dist=True)
+    for g, w, what in zip(got, want, ("match", "best", "second")):
+        bad = np.nonzero(g != w)[0]
+        assert len(bad) == 0, "%s differs from the oracle at %d queries, first %s" % (what, len(bad), bad[:8].tolist())
+    return got[0]
+
+
 @pytest.mark.parametrize("mode", ["verify", "trust"])
-def test_descriptor_cache_hits_only_on_the_published_block(oracle, mode):
+def test_descriptor_cache_hits_only_the_published_rows(oracle, mode):
     """clc_desc_cache_publish: descriptors the detector left on the device are found by the host-pointer match entry points when
     they are handed the very host block that was published (same address, same count, and -- "verify", the default -- the same fold
     over ALL rows; "trust": the same first / last / 16 sampled rows) -- and only then.
-    Every variant must give the oracle's matches; the hit / miss counters say which path answered."""
+    Every variant must give the oracle's matches and distances; the hit / miss counters say which path answered.  publish(NULL) of
+    an edited block is refused: the device rows are the frame's, not the edited ones."""
+    import torch
     from coloc_amd import Context
-    from coloc_amd.abi import desc_cache_stats
+    from coloc_amd.abi import CLCError, CLC_ERR_STATE, desc_cache_stats
     W, H = 320, 240
     det = Context(device=0, width=W, height=H, maxkp=8000, matcher=False)
     mat = Context(device=0, width=W, height=H, maxkp=8000, detector=False)
@@ -315,25 +327,30 @@ def test_descriptor_cache_hits_only_on_the_published_block(oracle, mode):
     other[:400, 7] ^= 0x21
     want = oracle.k2nn(desc, other, 40)
     h0, m0 = desc_cache_stats()
-    assert np.array_equal(mat.match_2nn(desc, other, 40), want)                 # nothing published yet: both blocks uploaded
+    assert np.array_equal(exact_2nn(mat, oracle, desc, other, 40), want)        # nothing published yet: both blocks uploaded
     h1, m1 = desc_cache_stats()
     assert h1 == h0 and m1 == m0 + 2
     det.desc_cache_publish(desc)                                                # the rows are still in det's device buffer
-    assert np.array_equal(mat.match_2nn(desc, other, 40), want)                 # query block found on the device
+    assert np.array_equal(exact_2nn(mat, oracle, desc, other, 40), want)        # query block found on the device
     h2, m2 = desc_cache_stats()
     assert h2 == h1 + 1 and m2 == m1 + 1
-    assert np.array_equal(mat.match_2nn(other, desc, 40), oracle.k2nn(other, desc, 40))      # ... also as the train block
+    assert np.array_equal(exact_2nn(mat, oracle, other, desc, 40), oracle.k2nn(other, desc, 40))      # ... also as the train block
     assert desc_cache_stats()[0] == h2 + 1
     copy = desc.copy()                                                          # same content, another address: uploaded
-    assert np.array_equal(mat.match_2nn(copy, other, 40), want)
+    assert np.array_equal(exact_2nn(mat, oracle, copy, other, 40), want)
     assert desc_cache_stats()[0] == h2 + 1
-    assert np.array_equal(mat.match_2nn(desc[:-1], other, 40), want[:-1])       # same address, another count: uploaded
+    assert np.array_equal(exact_2nn(mat, oracle, desc[:-1], other, 40), want[:-1])      # same address, another count: uploaded
     assert desc_cache_stats()[0] == h2 + 1
     desc[0, 3] ^= 0xFF                                                          # the host block changes at its first row: the entry is dropped
-    assert np.array_equal(mat.match_2nn(desc, other, 40), oracle.k2nn(desc, other, 40))
+    assert np.array_equal(exact_2nn(mat, oracle, desc, other, 40), oracle.k2nn(desc, other, 40))
     assert desc_cache_stats()[0] == h2 + 1
-    # map matching and the all-pairs entry take published blocks too
-    det.desc_cache_publish(desc)
+    with pytest.raises(CLCError) as refused:                                    # NULL = the frame's rows, which are not these
+        det.desc_cache_publish(desc)
+    assert refused.value.status == CLC_ERR_STATE
+    # map matching and the all-pairs entry take published blocks too (the edited rows, from a device copy of the caller's)
+    d_desc = torch.from_numpy(desc).cuda()
+    torch.cuda.synchronize()                  # the copy runs on torch's stream, the publish copy on the context's non-blocking one
+    det.desc_cache_publish(desc, d_src=d_desc.data_ptr())
     mat.set_map(other)
     assert np.array_equal(mat.match_map(desc, 60), oracle.k2nn(desc, other, 60))
     res = mat.match_pairs([desc, other], [(0, 1), (1, 0)], 40)
@@ -365,8 +382,8 @@ def test_descriptor_cache_block_rewritten_in_the_middle_is_uploaded(oracle):
 
     def check(expect_hit):
         h0, _ = desc_cache_stats()
-        assert np.array_equal(ctx.match_2nn(other, block, 40), oracle.k2nn(other, block, 40))
-        assert np.array_equal(ctx.match_2nn(block, other, 40), oracle.k2nn(block, other, 40))
+        assert np.array_equal(exact_2nn(ctx, oracle, other, block, 40), oracle.k2nn(other, block, 40))
+        assert np.array_equal(exact_2nn(ctx, oracle, block, other, 40), oracle.k2nn(block, other, 40))
         ctx.set_map(other)
         assert np.array_equal(ctx.match_map(block, 60), oracle.k2nn(block, other, 60))
         res = ctx.match_pairs([block, other], [(0, 1), (1, 0)], 40)
