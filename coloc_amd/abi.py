@@ -86,6 +86,8 @@ EXPORTS = [
     "clc_mc_create", "clc_mc_destroy", "clc_mc_last_error_string", "clc_mc_arena", "clc_mc_gather_dev", "clc_mc_match_dev", "clc_mc_virtual_put", "clc_mc_open_peers",
     "clc_mc_gather_enqueue_dev", "clc_mc_match_enqueue_dev", "clc_mc_counts", "clc_mc_set_overlap", "clc_mc_comm_info", "clc_match_jobs_counted_dev",
     "clc_two_view_acransac", "clc_two_view_acransac_batch", "clc_two_view_minimal",
+    "clc_match_ratio_2nn", "clc_match_ratio_2nn_dev", "clc_match_ratio_pairs", "clc_match_map_ratio", "clc_match_map_ratio_dev",
+    "clc_ratio_matches_to_pairs",
 ]
 KERNELS = ["pyramid_kernel", "clatch_kernel", "k2nn_sweep_kernel", "k2nn_merge_kernel", "pnp_residual_kernel",
            "pnp_score_kernel", "detect_kernels"]
@@ -171,6 +173,13 @@ def load_library():
     lib.clc_set_map.argtypes = [vp, vp, ci]
     lib.clc_match_map_dev.argtypes = [vp, vp, ci, ci, vp, vp]
     lib.clc_match_map.argtypes = [vp, vp, ci, ci, vp]
+    cf = C.c_float
+    lib.clc_match_ratio_2nn.argtypes = [vp, vp, ci, vp, ci, cf, vp, vp, vp]
+    lib.clc_match_ratio_2nn_dev.argtypes = [vp, vp, ci, vp, ci, cf, vp, vp]
+    lib.clc_match_ratio_pairs.argtypes = [vp, vp, vp, ci, vp, vp, ci, cf, vp, vp]
+    lib.clc_match_map_ratio.argtypes = [vp, vp, ci, vp, vp, cf, vp, vp]
+    lib.clc_match_map_ratio_dev.argtypes = [vp, vp, ci, cf, vp, vp]
+    lib.clc_ratio_matches_to_pairs.argtypes = [vp, ci, vp, vp, vp, vp]
     lib.clc_pnp_residuals.argtypes = [vp, vp, ci, vp, vp, ci, vp, vp]
     lib.clc_pnp_score.argtypes = [vp, vp, ci, vp, vp, ci, vp, C.c_double, vp, vp]
     lib.clc_detect.argtypes = [vp, vp, ci, C.POINTER(ci), C.POINTER(ci)]
@@ -241,6 +250,32 @@ def cov_intersection(CA, CB, ca, cb):
     if rc != CLC_OK:
         raise CLCError(rc, lib.clc_status_string(rc).decode())
     return om.value, cov.reshape(3, 3), pos
+
+
+def _xy(xy, n):
+    """positions of one descriptor set as (n, 2) float32, or None"""
+    if xy is None:
+        return None
+    xy = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+    if xy.shape[0] != n:
+        raise ValueError("positions: %d rows for a set of %d descriptors" % (xy.shape[0], n))
+    return xy
+
+
+def ratio_matches_to_pairs(match, xy_db=None, xy_q=None):
+    """Host-only clc_ratio_matches_to_pairs: per-query ratio results (database row or -1) -> the de-duplicated, ordered (k, 2) int32
+    list of (i_ = database row, j_ = query row); positions (database rows indexed by match, query rows) select the position pass."""
+    lib = load_library()
+    match = np.ascontiguousarray(match, dtype=np.int32).reshape(-1)
+    if xy_db is not None:
+        xy_db = np.ascontiguousarray(xy_db, dtype=np.float32).reshape(-1, 2)
+    xy_q = _xy(xy_q, match.shape[0])
+    out = np.empty((max(match.shape[0], 1), 2), dtype=np.int32)
+    n = C.c_int(0)
+    rc = lib.clc_ratio_matches_to_pairs(_p(match), match.shape[0], _p(xy_db), _p(xy_q), _p(out), C.byref(n))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_ratio_matches_to_pairs: " + lib.clc_status_string(rc).decode())
+    return out[:n.value].copy()
 
 
 def _two_view_fill(tv, keep, x1, x2, K1, K2, img_wh, max_iteration, seed, precision):
@@ -729,6 +764,51 @@ class Context:
         optr = (C.c_void_p * len(pairs))(*[o.ctypes.data for o in outs])
         self._chk(self.lib.clc_match_pairs(self.h, dptr, counts, len(descs), flat, len(pairs), int(threshold), optr))
         return outs
+
+    # -- distance-ratio rule (CPUMatcher, include/coloc_hip.h): ratio is CPUMatcher's 0.8 by default
+    def match_ratio(self, Q, T, ratio=0.8, want_dist=False):
+        """Per query: the train row or -1 under (float)d1 < ratio^2 (float)d2; same outputs as match_2nn."""
+        Q = np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, 64)
+        T = np.ascontiguousarray(T, dtype=np.uint8).reshape(-1, 64)
+        m = np.full(Q.shape[0], -2, dtype=np.int32)
+        b = np.zeros(Q.shape[0], dtype=np.uint16) if want_dist else None
+        s = np.zeros(Q.shape[0], dtype=np.uint16) if want_dist else None
+        self._chk(self.lib.clc_match_ratio_2nn(self.h, _p(Q), Q.shape[0], _p(T), T.shape[0], float(ratio), _p(m), _p(b), _p(s)))
+        return (m, b, s) if want_dist else m
+
+    def match_ratio_dev(self, d_q, nq, d_t, nt, ratio, d_match, stream=None):
+        self._chk(self.lib.clc_match_ratio_2nn_dev(self.h, d_q, nq, d_t, nt, float(ratio), d_match, stream))
+
+    def match_ratio_pairs(self, descs, pairs, ratio=0.8, xys=None):
+        """CPUMatcher::computeMatchesPair for every listed (first = database, second = queries) pair; xys: per-camera (n, 2) positions
+        or None.  Returns a list of (k, 2) int32 arrays of (i_ = database row, j_ = query row)."""
+        descs = [np.ascontiguousarray(d, dtype=np.uint8).reshape(-1, 64) for d in descs]
+        ncams = len(descs)
+        counts = (C.c_int * ncams)(*[d.shape[0] for d in descs])
+        dptr = (C.c_void_p * ncams)(*[d.ctypes.data for d in descs])
+        xyp = None
+        if xys is not None:
+            xys = [_xy(x, d.shape[0]) for x, d in zip(xys, descs)]
+            xyp = (C.c_void_p * ncams)(*[None if x is None else x.ctypes.data for x in xys])
+        flat = (C.c_int * max(2 * len(pairs), 1))(*[v for p in pairs for v in p])
+        outs = [np.empty((max(descs[b].shape[0] if 0 <= b < ncams else 0, 1), 2), dtype=np.int32) for _, b in pairs]
+        optr = (C.c_void_p * max(len(pairs), 1))(*[o.ctypes.data for o in outs])
+        n = (C.c_int * max(len(pairs), 1))()
+        self._chk(self.lib.clc_match_ratio_pairs(self.h, dptr, counts, ncams, xyp, flat, len(pairs), float(ratio), optr, n))
+        return [o[:n[p]].copy() for p, o in enumerate(outs)]
+
+    def match_map_ratio(self, Q, ratio=0.8, xy_map=None, xy_q=None):
+        """CPUMatcher::matchSceneWithMap: the map of set_map is the database; (k, 2) int32 of (i_ = map row, j_ = query row)."""
+        Q = np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, 64)
+        xy_map = None if xy_map is None else np.ascontiguousarray(xy_map, dtype=np.float32).reshape(-1, 2)
+        xy_q = _xy(xy_q, Q.shape[0])
+        out = np.empty((max(Q.shape[0], 1), 2), dtype=np.int32)
+        n = C.c_int(0)
+        self._chk(self.lib.clc_match_map_ratio(self.h, _p(Q), Q.shape[0], _p(xy_map), _p(xy_q), float(ratio), _p(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def match_map_ratio_dev(self, d_q, nq, ratio, d_match, stream=None):
+        self._chk(self.lib.clc_match_map_ratio_dev(self.h, d_q, nq, float(ratio), d_match, stream))
 
     def set_map(self, desc):
         desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 64)

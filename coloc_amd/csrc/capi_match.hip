@@ -8,10 +8,12 @@
 #include "desc_cache.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <string>
 #include <vector>
 
 using namespace clc;
@@ -202,13 +204,24 @@ int clc_k2nn_clock_check(clc_ctx* ctx, const void* d_q, int nq, const void* d_t,
     return CLC_OK;
 }
 
-int clc_match_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, int threshold,
-                      int32_t* d_match, void* stream)
+} // extern "C"
+
+namespace {
+
+// what the finalize of a sweep accepts (K2nnJobDev.rule / thr / r2)
+struct Rule {
+    uint32_t rule = K2NN_RULE_K2NN;
+    uint32_t thr = 0;
+    float    r2 = 0.f;
+    void apply(K2nnJobDev& jb) const { jb.rule = rule; jb.thr = thr; jb.r2 = r2; }
+};
+Rule k2nn_rule(int threshold) { Rule r; r.thr = (uint32_t)(uint8_t)threshold; return r; }   // CUDAK2NN.cu:46: the kernel parameter is uint8_t
+Rule ratio_rule(float ratio) { Rule r; r.rule = K2NN_RULE_RATIO; r.r2 = ratio * ratio; return r; }
+bool bad_ratio(float ratio) { return !(ratio > 0.f) || !std::isfinite(ratio); }
+
+// one device query set against one device train set, arguments checked: enqueue on `stream`
+int match_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, const Rule& rule, int32_t* d_match, void* stream)
 {
-    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_match)) || (nt > 0 && !d_t))
-        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: bad argument");
-    if (((uintptr_t)d_q & 15u) || ((uintptr_t)d_t & 15u) || ((uintptr_t)d_match & 3u))
-        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: device pointers must be 16-byte aligned");
     if (nq == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<K2nnJobDev> jobs(1);
@@ -218,8 +231,31 @@ int clc_match_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, in
     jobs[0].out = d_match;
     jobs[0].nq = (uint32_t)nq;
     jobs[0].nt = (uint32_t)nt;
-    jobs[0].thr = (uint32_t)(uint8_t)threshold;   // CUDAK2NN.cu:46: the kernel parameter is uint8_t
+    rule.apply(jobs[0]);
     return run_jobs(ctx, jobs, pick(ctx, stream));
+}
+
+} // namespace
+
+extern "C" {
+
+int clc_match_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, int threshold,
+                      int32_t* d_match, void* stream)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_match)) || (nt > 0 && !d_t))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: bad argument");
+    if (((uintptr_t)d_q & 15u) || ((uintptr_t)d_t & 15u) || ((uintptr_t)d_match & 3u))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: device pointers must be 16-byte aligned");
+    return match_dev(ctx, d_q, nq, d_t, nt, k2nn_rule(threshold), d_match, stream);
+}
+
+int clc_match_ratio_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, float ratio, int32_t* d_match, void* stream)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_match)) || (nt > 0 && !d_t) || bad_ratio(ratio))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_2nn: bad argument");
+    if (((uintptr_t)d_q & 15u) || ((uintptr_t)d_t & 15u) || ((uintptr_t)d_match & 3u))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_2nn: device pointers must be 16-byte aligned");
+    return match_dev(ctx, d_q, nq, d_t, nt, ratio_rule(ratio), d_match, stream);
 }
 
 /* ---- describe both cameras of a pair and match them, as ONE step ------------------------------------------------------------
@@ -380,7 +416,7 @@ void release_sets(HostSet* sets, int n_sets)
 }
 
 // one query set against one train set, both resolved; results into the caller's arrays
-int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, int threshold, int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
+int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
 {
     const size_t nq = (size_t)q.n;
     const size_t off_best = nq * sizeof(int32_t), off_second = off_best + nq * sizeof(uint16_t);
@@ -398,7 +434,7 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, int threshold, int32_t* h_m
         jobs[0].second_out = h_second ? ctx->d_second : nullptr;
         jobs[0].nq = (uint32_t)q.n;
         jobs[0].nt = (uint32_t)t.n;
-        jobs[0].thr = (uint32_t)(uint8_t)threshold;
+        rule.apply(jobs[0]);
         rc = run_jobs(ctx, jobs, ctx->stream);
         hipError_t e = hipSuccess;
         if (rc == CLC_OK) e = hipMemcpyAsync(ctx->h_res, ctx->d_match, nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
@@ -419,28 +455,10 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, int threshold, int32_t* h_m
     return CLC_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int clc_match_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt, int threshold,
-                  int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
-{
-    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!h_q || !h_match)) || (nt > 0 && !h_t))
-        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: bad argument");
-    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_2nn: context created without matcher options");
-    if ((uint32_t)nq > ctx->mopts.maxkp || (uint32_t)nt > ctx->mopts.maxkp)
-        return fail(ctx, CLC_ERR_CAPACITY, "match_2nn: more descriptors than MatcherOptions.maxkp");
-    if (nq == 0) return CLC_OK;
-    CLC_HIP(ctx, hipSetDevice(ctx->device));
-    HostSet q, t;
-    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
-    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t;
-    return match_host(ctx, q, t, threshold, h_match, h_best, h_second);
-}
-
-int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, int ncams, const int* pairs,
-                    int npairs, int threshold, int32_t* const* h_match)
+// the listed camera pairs over host descriptor blocks, one launch group: each camera uploaded (or found published) once.  Pair p sweeps
+// queries = camera pairs[2p + q_side] against train = the other camera; h_match[p] receives one int32 per query row.
+int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts, int ncams, const int* pairs, int npairs, int q_side,
+                     const Rule& rule, int32_t* const* h_match)
 {
     if (!ctx || ncams < 0 || npairs < 0 || (ncams > 0 && (!h_desc || !counts)) || (npairs > 0 && (!pairs || !h_match)))
         return fail(ctx, CLC_ERR_BAD_ARG, "match_pairs: bad argument");
@@ -453,7 +471,7 @@ int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, 
     }
     size_t out_rows = 0;
     for (int p = 0; p < npairs; ++p) {
-        const int a = pairs[2 * p], b = pairs[2 * p + 1];
+        const int a = pairs[2 * p + q_side], b = pairs[2 * p + 1 - q_side];
         if (a < 0 || a >= ncams || b < 0 || b >= ncams || (counts[a] > 0 && !h_match[p]))
             return fail(ctx, CLC_ERR_BAD_ARG, "match_pairs: bad pair entry");
         out_rows += (size_t)counts[a];
@@ -484,7 +502,7 @@ int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, 
         std::vector<K2nnJobDev> jobs;
         size_t o = 0;
         for (int p = 0; p < npairs; ++p) {
-            const int a = pairs[2 * p], b = pairs[2 * p + 1];
+            const int a = pairs[2 * p + q_side], b = pairs[2 * p + 1 - q_side];
             out_off[p] = o;
             if (counts[a] == 0) continue;
             K2nnJobDev jb{};
@@ -493,7 +511,7 @@ int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, 
             jb.out = d_out + o;
             jb.nq = (uint32_t)counts[a];
             jb.nt = (uint32_t)counts[b];
-            jb.thr = (uint32_t)(uint8_t)threshold;
+            rule.apply(jb);
             jobs.push_back(jb);
             o += (size_t)counts[a];
         }
@@ -508,10 +526,36 @@ int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, 
         if (good) break;
     }
     for (int p = 0; p < npairs; ++p) {
-        const int a = pairs[2 * p];
+        const int a = pairs[2 * p + q_side];
         if (counts[a] > 0) memcpy(h_match[p], ctx->h_res + out_off[p] * sizeof(int32_t), (size_t)counts[a] * sizeof(int32_t));
     }
     return CLC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int clc_match_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt, int threshold,
+                  int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!h_q || !h_match)) || (nt > 0 && !h_t))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: bad argument");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_2nn: context created without matcher options");
+    if ((uint32_t)nq > ctx->mopts.maxkp || (uint32_t)nt > ctx->mopts.maxkp)
+        return fail(ctx, CLC_ERR_CAPACITY, "match_2nn: more descriptors than MatcherOptions.maxkp");
+    if (nq == 0) return CLC_OK;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    HostSet q, t;
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
+    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t;
+    return match_host(ctx, q, t, k2nn_rule(threshold), h_match, h_best, h_second);
+}
+
+int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, int ncams, const int* pairs,
+                    int npairs, int threshold, int32_t* const* h_match)
+{
+    return match_pairs_host(ctx, h_desc, counts, ncams, pairs, npairs, 0, k2nn_rule(threshold), h_match);
 }
 
 int clc_set_map(clc_ctx* ctx, const void* h_desc, int n)
@@ -537,7 +581,7 @@ int clc_match_map(clc_ctx* ctx, const void* h_q, int nq, int threshold, int32_t*
     HostSet q, t;
     q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
     t.resident = true; t.d = ctx->d_m; t.n = ctx->map_n;      // the map is on the device already (clc_set_map)
-    return match_host(ctx, q, t, threshold, h_match, nullptr, nullptr);
+    return match_host(ctx, q, t, k2nn_rule(threshold), h_match, nullptr, nullptr);
 }
 
 int clc_match_map_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int32_t* d_match, void* stream)
@@ -546,6 +590,154 @@ int clc_match_map_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int3
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_dev: context created without matcher options");
     if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_dev before set_map");
     return clc_match_2nn_dev(ctx, d_q, nq, ctx->d_m, ctx->map_n, threshold, d_match, stream);
+}
+
+/* ---- the distance-ratio rule: CPUMatcher's matches (include/coloc/CPUMatcher.hpp:56-98) ------------------------------------------
+ * The same sweep with the ratio rule in its finalize (k2nn.hip accept()); per-query results are turned into CPUMatcher's IndMatch lists
+ * on the host (clc_ratio_matches_to_pairs): the de-duplication is a sort over the accepted matches, O(k log k), not a device pass. */
+} // extern "C"
+
+namespace {
+
+// clc_ratio_matches_to_pairs; *why: what was wrong when the status is not CLC_OK.  Positions are needed only where there are query rows
+// to order: with nq == 0 either pointer may be NULL.
+int ratio_to_pairs(const int32_t* match, int nq, const float* xy_db, const float* xy_q, int32_t* pairs, int* n, const char** why)
+{
+    *why = "bad argument";
+    if (!n) return CLC_ERR_BAD_ARG;
+    *n = 0;
+    if (nq < 0 || (nq > 0 && (!match || !pairs))) return CLC_ERR_BAD_ARG;
+    if (nq == 0) return CLC_OK;
+    if (!xy_db != !xy_q) { *why = "positions given for one side only"; return CLC_ERR_BAD_ARG; }
+    const bool pos = xy_db != nullptr;
+    struct Row { float x1, y1, x2, y2; int32_t i, j; };
+    std::vector<Row> rows;
+    for (int j = 0; j < nq; ++j) {
+        const int32_t i = match[j];
+        if (i < 0) continue;
+        Row r{ 0.f, 0.f, 0.f, 0.f, i, j };
+        if (pos) {
+            r.x1 = xy_db[2 * (size_t)i]; r.y1 = xy_db[2 * (size_t)i + 1]; r.x2 = xy_q[2 * (size_t)j]; r.y2 = xy_q[2 * (size_t)j + 1];
+            if (std::isnan(r.x1) || std::isnan(r.y1) || std::isnan(r.x2) || std::isnan(r.y2)) { *why = "NaN position"; return CLC_ERR_BAD_ARG; }   // no order
+        }
+        rows.push_back(r);
+    }
+    // (x_I, y_I, x_J, y_J, i_, j_): the order orc_cpumatcher_pair states; without positions the keys are all 0 and it is (i_, j_)
+    std::sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
+        if (a.x1 != b.x1) return a.x1 < b.x1;
+        if (a.y1 != b.y1) return a.y1 < b.y1;
+        if (a.x2 != b.x2) return a.x2 < b.x2;
+        if (a.y2 != b.y2) return a.y2 < b.y2;
+        if (a.i != b.i) return a.i < b.i;
+        return a.j < b.j;
+    });
+    int k = 0;
+    for (size_t a = 0; a < rows.size(); ++a) {
+        if (k > 0) {
+            const Row& p = rows[(size_t)k - 1];
+            if (p.i == rows[a].i && p.j == rows[a].j) continue;                                            // IndMatch::getDeduplicated
+            if (pos && p.x1 == rows[a].x1 && p.y1 == rows[a].y1 && p.x2 == rows[a].x2 && p.y2 == rows[a].y2) continue;   // IndMatchDecorator
+        }
+        rows[(size_t)k++] = rows[a];
+    }
+    for (int a = 0; a < k; ++a) { pairs[2 * a] = rows[(size_t)a].i; pairs[2 * a + 1] = rows[(size_t)a].j; }
+    *n = k;
+    return CLC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int clc_ratio_matches_to_pairs(const int32_t* match, int nq, const float* xy_db, const float* xy_q, int32_t* pairs, int* n)
+{
+    const char* why = nullptr;
+    return ratio_to_pairs(match, nq, xy_db, xy_q, pairs, n, &why);
+}
+
+int clc_match_ratio_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt, float ratio,
+                        int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!h_q || !h_match)) || (nt > 0 && !h_t) || bad_ratio(ratio))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_2nn: bad argument");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_ratio_2nn: context created without matcher options");
+    if ((uint32_t)nq > ctx->mopts.maxkp || (uint32_t)nt > ctx->mopts.maxkp)
+        return fail(ctx, CLC_ERR_CAPACITY, "match_ratio_2nn: more descriptors than MatcherOptions.maxkp");
+    if (nq == 0) return CLC_OK;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    HostSet q, t;
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
+    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t;
+    return match_host(ctx, q, t, ratio_rule(ratio), h_match, h_best, h_second);
+}
+
+int clc_match_ratio_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, int ncams, const float* const* h_xy,
+                          const int* pairs, int npairs, float ratio, int32_t* const* h_pairs_out, int* n_out)
+{
+    if (!ctx || ncams < 0 || npairs < 0 || (ncams > 0 && (!h_desc || !counts)) || (npairs > 0 && (!pairs || !h_pairs_out || !n_out)) ||
+        bad_ratio(ratio))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_pairs: bad argument");
+    for (int p = 0; p < npairs; ++p) n_out[p] = 0;
+    for (int c = 0; c < ncams; ++c)
+        if (counts[c] < 0) return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_pairs: bad camera entry");
+    // CPUMatcher's orientation: database = pairs[p].first, queries = pairs[p].second
+    std::vector<std::vector<int32_t>> m((size_t)npairs);
+    std::vector<int32_t*> mp((size_t)npairs, nullptr);
+    for (int p = 0; p < npairs; ++p) {
+        const int db = pairs[2 * p], qc = pairs[2 * p + 1];
+        if (db < 0 || db >= ncams || qc < 0 || qc >= ncams || (counts[qc] > 0 && !h_pairs_out[p]))
+            return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_pairs: bad pair entry");
+        if (h_xy && ((counts[db] > 0 && !h_xy[db]) || (counts[qc] > 0 && !h_xy[qc])))
+            return fail(ctx, CLC_ERR_BAD_ARG, "match_ratio_pairs: positions given for one side of a pair only");
+        m[(size_t)p].assign((size_t)counts[qc], -1);
+        mp[(size_t)p] = m[(size_t)p].data();
+    }
+    if (npairs == 0) return CLC_OK;
+    int rc = match_pairs_host(ctx, h_desc, counts, ncams, pairs, npairs, 1, ratio_rule(ratio), mp.data());
+    if (rc != CLC_OK) return rc;
+    for (int p = 0; p < npairs; ++p) {
+        // positions are read only for pairs with rows on both sides (a camera without rows may pass NULL): one side empty = no match
+        const int db = pairs[2 * p], qc = pairs[2 * p + 1];
+        const bool pos = h_xy && counts[db] > 0 && counts[qc] > 0;
+        const char* why = nullptr;
+        rc = ratio_to_pairs(mp[(size_t)p], counts[qc], pos ? h_xy[db] : nullptr, pos ? h_xy[qc] : nullptr, h_pairs_out[p], &n_out[p], &why);
+        if (rc != CLC_OK) {
+            for (int k = 0; k < npairs; ++k) n_out[k] = 0;
+            return fail(ctx, rc, (std::string("match_ratio_pairs: ") + why).c_str());
+        }
+    }
+    return CLC_OK;
+}
+
+int clc_match_map_ratio(clc_ctx* ctx, const void* h_q, int nq, const float* xy_map, const float* xy_q, float ratio, int32_t* h_pairs, int* n_out)
+{
+    if (!ctx || nq < 0 || !n_out || (nq > 0 && (!h_q || !h_pairs)) || bad_ratio(ratio))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_map_ratio: bad argument");
+    *n_out = 0;
+    if (nq > 0 && ctx->map_n > 0 && !xy_map != !xy_q) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_ratio: positions given for one side only");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_ratio: context created without matcher options");
+    if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_ratio before set_map");
+    if ((uint32_t)nq > ctx->mopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "match_map_ratio: more descriptors than MatcherOptions.maxkp");
+    if (nq == 0) return CLC_OK;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    HostSet q, t;
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
+    t.resident = true; t.d = ctx->d_m; t.n = ctx->map_n;      // the map is the database (CPUMatcher.hpp:85-89)
+    std::vector<int32_t> m((size_t)nq, -1);
+    int rc = match_host(ctx, q, t, ratio_rule(ratio), m.data(), nullptr, nullptr);
+    if (rc != CLC_OK) return rc;
+    const bool pos = xy_map && xy_q && ctx->map_n > 0;          // an empty map matches nothing and needs no positions
+    const char* why = nullptr;
+    rc = ratio_to_pairs(m.data(), nq, pos ? xy_map : nullptr, pos ? xy_q : nullptr, h_pairs, n_out, &why);
+    return rc == CLC_OK ? CLC_OK : fail(ctx, rc, (std::string("match_map_ratio: ") + why).c_str());
+}
+
+int clc_match_map_ratio_dev(clc_ctx* ctx, const void* d_q, int nq, float ratio, int32_t* d_match, void* stream)
+{
+    if (!ctx || nq < 0 || (nq > 0 && (!d_q || !d_match))) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_ratio_dev: bad argument");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_ratio_dev: context created without matcher options");
+    if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_ratio_dev before set_map");
+    return clc_match_ratio_2nn_dev(ctx, d_q, nq, ctx->d_m, ctx->map_n, ratio, d_match, stream);
 }
 
 } // extern "C"

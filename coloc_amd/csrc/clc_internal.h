@@ -98,7 +98,13 @@ struct K2nnJobDev {
     uint32_t     bias_a, bias_b;
     uint32_t     bias_magic;  // ceil(2^32 / qblocks): workgroup id / qblocks as a multiply-high (exact for ids below 2^16)
     uint32_t     slot_wgs;    // biased plans: workgroup ids per wave slot in the plan's id space (CUs of one XCD, or of the device)
+    // acceptance rule of the finalize (uniform per job; the sweep and the top-2 fold do not depend on it):
+    // K2NN_RULE_K2NN (0, the default of K2nnJobDev{}): second - best > thr (CUDAK2NN.cu:75);
+    // K2NN_RULE_RATIO: a second distance exists and (float)best < r2 * (float)second (OpenMVG DistanceRatioMatch as CPUMatcher calls it)
+    uint32_t     rule;
+    float        r2;          // ratio * ratio, rounded to float once on the host
 };
+enum { K2NN_RULE_K2NN = 0, K2NN_RULE_RATIO = 1 };
 // what the planner needs to know about the device (clc_ctx_create fills it from the HIP device attributes)
 static constexpr uint32_t kK2nnXcds = 8;       // XCDs the sweep kernel's workgroup map is compiled for (every gfx950 part has eight)
 struct K2nnDevice {
@@ -127,6 +133,7 @@ struct K2nnJobList {
     // tile (5..22), train tiles (23..31: k2nn.hip kBias*); bias_magic != 0: per query block, see launch_k2nn
     uint32_t bias_tab[128];
 };
+static_assert(sizeof(K2nnJobList) <= 4096, "K2nnJobList is passed as a kernel argument: it must stay within the 4 KB kernarg segment");
 struct K2nnPlan {
     size_t   partial_elems;// uint2 entries needed
     bool     atomic_merge; // every job fits the 22-bit global train index -> atomic top-2 merge

@@ -125,7 +125,23 @@ __device__ __forceinline__ void sweep_one(const uint32_t (&q)[R][16], const u32x
 #undef K2NN_PAIR
 }
 
+// The acceptance rule (K2nnJobDev.rule) on the folded top-2: distances, or the CUDAK2NN.cu:54 sentinels 100000 / 200000 where fewer
+// than two / one train rows were swept.  K2NN: CUDAK2NN.cu:75.  Ratio: the sentinel second is checked FIRST -- with one train row the
+// 100000 would pass the ratio test -- then (float)d1 < r2 * (float)d2 (oracle/clc_oracle.c orc_k2nn_omp_ex, rule 1; no contraction:
+// the build has -ffp-contract=off).  A compile-time parameter of the sweep kernels, not a runtime branch in them: the rule is uniform
+// per launch (launch_k2nn), and any change to the finalize of k2nn_sweep_mx_kernel moves its register allocation: with a runtime branch
+// here the compiler (ROCm 7, -O3) put 16 v_mov into the K2NN tile loop; with the template the K2NN instantiations keep their tile loop
+// (check: hipcc -S --cuda-device-only on k2nn.hip, the tile block of k2nn_sweep_mx_kernel<false, false, false, false>).
+template <bool RATIO>
+__device__ __forceinline__ bool accept(const K2nnJobDev& job, const int best_i, const int best_v, const int second_v)
+{
+    if (best_i < 0) return false;
+    if (RATIO) return second_v <= 512 && (float)best_v < job.r2 * (float)second_v;
+    return second_v - best_v > (int)job.thr;
+}
+
 // {best_key, second_key} of one query -> the reference's outputs (CUDAK2NN.cu:54 sentinels, :75 acceptance)
+template <bool RATIO>
 __device__ __forceinline__ void emit_result(const K2nnJobDev& job, const uint32_t qi, const uint32_t bkey, const uint32_t skey)
 {
     int best_v = 100000, second_v = 200000, best_i = -1;
@@ -134,12 +150,12 @@ __device__ __forceinline__ void emit_result(const K2nnJobDev& job, const uint32_
         best_i = (int)(bkey & kIdxMask);
         second_v = skey == kEmpty ? 100000 : (int)(skey >> kKeyShift);
     }
-    job.out[qi] = (best_i >= 0 && second_v - best_v > (int)job.thr) ? best_i : -1;
+    job.out[qi] = accept<RATIO>(job, best_i, best_v, second_v) ? best_i : -1;
     if (job.best_out) job.best_out[qi] = (uint16_t)min(best_v, 65535);
     if (job.second_out) job.second_out[qi] = (uint16_t)min(second_v, 65535);
 }
 
-template <int R>
+template <int R, bool RATIO = false>
 __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_kernel(const K2nnJobList jobs,
                                                                   uint2* __restrict__ partial)
 {
@@ -272,7 +288,7 @@ __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_kernel(const K2nnJobLi
             if (qi < job.nq) {          // every PLANNED row gets an answer; rows past a device-side count hold no key -> -1
                 const uint32_t bkey = atomicExch(top + 2u * qi, kEmpty);
                 const uint32_t skey = atomicExch(top + 2u * qi + 1u, kEmpty);
-                emit_result(job, qi, bkey, skey);
+                emit_result<RATIO>(job, qi, bkey, skey);
             }
         }
         return;
@@ -354,7 +370,8 @@ __device__ __forceinline__ uint32_t mx_decode_rel(const uint32_t bits, const uin
 // PROBE: the same code under another symbol, for the launches of the per-device share probe at context creation (capi_match.hip k2nn_probe_bias):
 // a kernel trace of an application then shows ITS sweeps under k2nn_sweep_mx_kernel<false, false, false> and the probe's -- run from cold
 // clocks, under four different share pairs -- under <..., true>, instead of one average over both.
-template <bool STAMP, bool GLOBAL = false, bool PROBE = false>
+// RATIO: the acceptance rule of the launch's jobs (accept()).
+template <bool STAMP, bool GLOBAL = false, bool PROBE = false, bool RATIO = false>
 __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nnJobList jobs, uint2* __restrict__ partial,
                                                                       uint64_t* __restrict__ stamps)
 {
@@ -604,7 +621,7 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
     if (qi < job.nq) {
         const uint32_t bkey = atomicExch(top + 2u * qi, kEmpty);
         const uint32_t skey = atomicExch(top + 2u * qi + 1u, kEmpty);
-        emit_result(job, qi, bkey, skey);
+        emit_result<RATIO>(job, qi, bkey, skey);
     }
 }
 
@@ -615,7 +632,7 @@ __global__ __launch_bounds__(256) void k2nn_nomatch_kernel(const K2nnJobList job
     const K2nnJobDev& job = jobs.j[blockIdx.y];
     const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
     if (job.nt != 0u || qi >= job.nq) return;
-    emit_result(job, qi, kEmpty, kEmpty);
+    emit_result<false>(job, qi, kEmpty, kEmpty);                      // no best row: -1 under either rule
 }
 
 // Fold the per-split partials of one query and threshold.
@@ -685,7 +702,8 @@ __global__ __launch_bounds__(kMergeQ * kMergeGroups) void k2nn_merge_kernel(cons
             a.second_v = min(a.second_v, b.best_v);
         }
     }
-    job.out[qi] = (a.best_i >= 0 && a.second_v - a.best_v > (int)job.thr) ? a.best_i : -1;
+    const bool ok = job.rule == K2NN_RULE_RATIO ? accept<true>(job, a.best_i, a.best_v, a.second_v) : accept<false>(job, a.best_i, a.best_v, a.second_v);
+    job.out[qi] = ok ? a.best_i : -1;
     if (job.best_out) job.best_out[qi] = (uint16_t)min(a.best_v, 65535);
     if (job.second_out) job.second_out[qi] = (uint16_t)min(a.second_v, 65535);
 }
@@ -825,8 +843,11 @@ K2nnPlan k2nn_plan(K2nnJobDev* jobs, int njobs, int target_blocks, bool xcd_map,
 hipError_t launch_k2nn(const K2nnJobDev* jobs, int njobs, uint2* d_partial, hipStream_t stream, Profiler* prof, int formulation,
                        uint64_t* d_stamps, bool probe)
 {
-    for (int base = 0; base < njobs; base += kK2nnJobsPerLaunch) {
-        const int cnt = njobs - base < kK2nnJobsPerLaunch ? njobs - base : kK2nnJobsPerLaunch;
+    for (int base = 0, cnt = 0; base < njobs; base += cnt) {
+        // the jobs of one launch share the acceptance rule (a template parameter of the sweep kernels)
+        cnt = 1;
+        while (cnt < kK2nnJobsPerLaunch && base + cnt < njobs && jobs[base + cnt].rule == jobs[base].rule) ++cnt;
+        const bool ratio = jobs[base].rule == K2NN_RULE_RATIO;
         K2nnJobList list;
         uint32_t grid_x = 0, max_nq = 0, max_nq_empty = 0;
         for (int j = 0; j < cnt; ++j) {
@@ -881,8 +902,16 @@ hipError_t launch_k2nn(const K2nnJobDev* jobs, int njobs, uint2* d_partial, hipS
         if (max_nq == 0) continue;
         if (grid_x > 0) {
             prof_mark(prof, CLC_KERNEL_K2NN_SWEEP, true, stream);
-            if (formulation == K2NN_POPCOUNT)
+            if (formulation == K2NN_POPCOUNT && ratio)
+                hipLaunchKernelGGL((k2nn_sweep_kernel<kR, true>), dim3(grid_x, cnt), dim3(64 * kWaves), 0, stream, list, d_partial);
+            else if (formulation == K2NN_POPCOUNT)
                 hipLaunchKernelGGL(k2nn_sweep_kernel<kR>, dim3(grid_x, cnt), dim3(64 * kWaves), 0, stream, list, d_partial);
+            else if (ratio && cnt == 1 && list.j[0].bias_a != 0u && list.j[0].bias_magic != 0u)     // (ratio jobs: no stamps, no probe)
+                hipLaunchKernelGGL((k2nn_sweep_mx_kernel<false, true, false, true>), dim3(grid_x, cnt), dim3(64 * kMxWaves), 0, stream, list, d_partial,
+                                   (uint64_t*)nullptr);
+            else if (ratio)
+                hipLaunchKernelGGL((k2nn_sweep_mx_kernel<false, false, false, true>), dim3(grid_x, cnt), dim3(64 * kMxWaves), 0, stream, list, d_partial,
+                                   (uint64_t*)nullptr);
             else if (cnt == 1 && list.j[0].bias_a != 0u && list.j[0].bias_magic != 0u && d_stamps)
                 hipLaunchKernelGGL((k2nn_sweep_mx_kernel<true, true>), dim3(grid_x, cnt), dim3(64 * kMxWaves), 0, stream, list, d_partial, d_stamps);
             else if (cnt == 1 && list.j[0].bias_a != 0u && list.j[0].bias_magic != 0u)

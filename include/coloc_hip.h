@@ -42,7 +42,8 @@ extern "C" {
  * clc_pnp_localize_ac_batch / clc_pose_job, one-rank communicators in clc_mc_create).  3: round 5's additions (clc_desc_cache_mode,
  * clc_describe_match_pair_dev, clc_essential_acransac_batch, clc_inter_pose_batch, clc_k2nn_device_info) and round 6's changes
  * (clc_describe_match_pair_dev lost its `chunks` argument, CLC_K2NN_MATRIX_PLAIN is gone, the descriptor hand-over is by ownership:
- * clc_desc_cache_publish returns a handle).  4: the 'F' / 'H' models of the two-view filter (clc_two_view_acransac, _batch, clc_two_view_minimal).
+ * clc_desc_cache_publish returns a handle).  4: the 'F' / 'H' models of the two-view filter (clc_two_view_acransac, _batch, clc_two_view_minimal);
+ * the distance-ratio entries (clc_match_ratio_*, clc_match_map_ratio*, clc_ratio_matches_to_pairs) came later under 4: new entry points only.
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -72,7 +73,7 @@ typedef struct clc_detector_opts {
 
 /* mirrors coloc::MatcherOptions, include/coloc/colocData.hpp:38-42 */
 typedef struct clc_matcher_opts {
-    float    distRatio;     /* unused by the 2-NN difference rule; kept for the CPU comparator */
+    float    distRatio;     /* unused by the 2-NN difference rule and, like CPUMatcher, by the ratio entries (they take ratio) */
     int      thresh;        /* map-tracking threshold (Mopts.thresh = 60, coloc_node.cpp:85)    */
     uint32_t maxkp;
 } clc_matcher_opts;
@@ -338,6 +339,46 @@ int clc_match_map(clc_ctx* ctx, const void* h_q, int nq, int threshold, int32_t*
 /* The same against descriptors that are still on the GPU (clc_describe*_dev output): enqueue only; d_match[i] = map
  * index or -1.  In a streaming loop the frame's descriptors then never leave the device, only the nq x 4 B result does. */
 int clc_match_map_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int32_t* d_match, void* stream);
+
+/* ---- match, distance-ratio rule: replaces CPUMatcher<T> (include/coloc/CPUMatcher.hpp:22-102), the matcher of every non-CUDA build
+ * (coloc.hpp:66-68), whose calls all go through openMVG::matching::DistanceRatioMatch(ratio, BRUTE_FORCE_HAMMING, database, queries).
+ * Rule, per query: the two smallest Hamming distances d1 <= d2 over all database rows (the same exact sweep as the K2NN entries);
+ * accept iff the database holds at least two rows and (float)d1 < r2 * (float)d2 with r2 = ratio * ratio rounded to float.  Ties for the
+ * minimum (d1 == d2) therefore never pass for ratio <= 1; for ratio > 1 they give the lowest database index.  Fewer than two database
+ * rows (nt < 2): no match.  ratio must be finite and > 0 (else CLC_ERR_BAD_ARG); MatcherOptions.distRatio is not read -- CPUMatcher
+ * ignores its options and passes its own constants.
+ * Per-query entries: the same orientation and outputs as clc_match_2nn / clc_match_2nn_dev / clc_match_map_dev (h_match[q] = database
+ * index or -1; h_best / h_second unchanged), the same descriptor-cache resolution of host blocks.
+ * Pair entries: CPUMatcher's IndMatch lists.  IndMatch(i_ = database row, j_ = query row), two int32 per match; per pair then
+ *   - with positions (xy = count x 2 floats per set): exact duplicate pairs dropped, and matches whose (x_I, y_I, x_J, y_J) repeat an
+ *     earlier one dropped; ordered by (x_I, y_I, x_J, y_J, i_, j_);
+ *   - without positions: identical pairs dropped only; ordered by (i_, j_), the order IndMatch::getDeduplicated leaves.
+ *   That order and the position pass are this project's statement of recalled OpenMVG behaviour (OpenMVG is not available to pin it
+ *   against; the CPU oracle orc_cpumatcher_pair states the same).  Positions for one side only: CLC_ERR_BAD_ARG; a NaN position too.
+ *   A set without rows needs no positions (NULL is fine): a pair with an empty side has no match.
+ *   Capacity of a pair list: one match per query row.  De-duplication runs on the host, O(k log k) over the k accepted matches. */
+int clc_match_ratio_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt, float ratio,
+                        int32_t* h_match, uint16_t* h_best, uint16_t* h_second);
+/* Enqueue only, on `stream`; 16-byte aligned descriptor pointers, like clc_match_2nn_dev. */
+int clc_match_ratio_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, float ratio, int32_t* d_match, void* stream);
+/* CPUMatcher::computeMatches / computeMatchesPair (CPUMatcher.hpp:37-76) over host blocks: DATABASE = camera pairs[p].first, QUERIES =
+ * camera pairs[p].second -- the opposite of clc_match_pairs.  Each camera uploaded (or found published) once, all pairs in one launch
+ * group.  h_xy (nullable; else one pointer per camera, counts[c] x 2 floats) selects the position pass
+ * (h_xy[c] may be NULL for a camera with counts[c] == 0).  h_pairs_out[p] receives n_out[p]
+ * (i_, j_) pairs, capacity 2 x counts[pairs[p].second] int32. */
+int clc_match_ratio_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, int ncams, const float* const* h_xy,
+                          const int* pairs /* npairs x {first = database, second = queries} */, int npairs, float ratio,
+                          int32_t* const* h_pairs_out, int* n_out);
+/* CPUMatcher::matchSceneWithMap (CPUMatcher.hpp:78-97): the map of clc_set_map is the database, IndMatch(i_ = map row, j_ = query row).
+ * xy_map (map_n x 2) and xy_q (nq x 2) both given or both NULL (either may be NULL when its set is empty); h_pairs capacity 2 x nq int32. */
+int clc_match_map_ratio(clc_ctx* ctx, const void* h_q, int nq, const float* xy_map, const float* xy_q, float ratio,
+                        int32_t* h_pairs, int* n_out);
+/* Per query against the map, enqueue only: d_match[q] = map row or -1 (no de-duplication). */
+int clc_match_map_ratio_dev(clc_ctx* ctx, const void* d_q, int nq, float ratio, int32_t* d_match, void* stream);
+/* Host arithmetic only (ctx not needed, no GPU): per-query ratio results match[nq] (database row or -1) -> the de-duplicated, ordered
+ * pair list above; xy_db indexed by match[q], xy_q by q (both or neither; either may be NULL when nq == 0).  pairs capacity 2 x nq int32.  The code the two host pair
+ * entries use. */
+int clc_ratio_matches_to_pairs(const int32_t* match, int nq, const float* xy_db, const float* xy_q, int32_t* pairs, int* n);
 
 /* ---- pose scoring: the data-parallel core of SfM_Localizer::Localize (Localizer.hpp:82-93) --- */
 
