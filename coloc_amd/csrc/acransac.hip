@@ -23,7 +23,7 @@
 // The resection path -- and the seven-point / four-point paths, whose solves are as short as a P3P -- runs solve + nfa + the select of
 // the PREVIOUS round as ONE launch per round (acr_round_kernel<E, KIND> below), the
 // five-point path as two (acr_solve5_kernel: select of the previous round + samples + solve; nfa); several solves of one kind can share
-// those launches (blockIdx.y = solve: the *_chains_kernel forms, driven in lockstep by pose_batch.hip).  The host only polls one packed word per round in pinned memory to learn whether
+// those launches (blockIdx.y = solve, a single solve is a chain of one; pose_batch.hip drives batches in lockstep).  The host only polls one packed word per round in pinned memory to learn whether
 // another round is needed: one round to find the first meaningful model, then one per improvement in the reserve.  Results are identical to the
 // sequential oracle: same samples, bit-identical residuals (same operation order, no FMA contraction), a total order on
 // (residual, index), and the same portable log10 in the NFA terms.
@@ -552,22 +552,10 @@ __device__ __forceinline__ void acr_nfa_body(const AcrProblem& pb, const int P /
     ACR_STAMP(9);
 }
 
-// models from memory (the five-point path: fivept_kernel has written them)
+// the nfa launch of a five-point round (models from memory: acr_solve5_kernel has written them), blockIdx.y = chain: the copies of
+// launch parity `par`
 template <int E>
-__global__ __launch_bounds__(1024) void acr_nfa_kernel(const AcrProblem pb, const int P, const double* __restrict__ models,
-                                                       AcrHyp* __restrict__ hyp, uint32_t* __restrict__ sorted_idx,
-                                                       const AcrState* __restrict__ state)
-{
-    extern __shared__ unsigned char acr_lds[];
-    const int slot = blockIdx.x;
-    if (slot >= state->cur_batch * pb.max_models) return;          // the grid covers the largest batch; this round is smaller
-    acr_nfa_body<E>(pb, P, models + (size_t)slot * pb.model_doubles, hyp + slot, sorted_idx + (size_t)slot * pb.n, (int)threadIdx.x,
-                    (int)blockDim.x, reinterpret_cast<uint64_t*>(acr_lds));
-}
-
-// the nfa launch of a two-view round for up to kMaxBatch solves at once (blockIdx.y = chain): the copies of launch parity `par`
-template <int E>
-__global__ __launch_bounds__(1024) void acr_nfa_chains_kernel(const AcrChains chains, const int par, const int P)
+__global__ __launch_bounds__(1024) void acr_nfa_kernel(const AcrChains chains, const int par, const int P)
 {
     extern __shared__ unsigned char acr_lds[];
     constexpr int kSlots = kAcrMaxBatch * 10;
@@ -575,7 +563,7 @@ __global__ __launch_bounds__(1024) void acr_nfa_chains_kernel(const AcrChains ch
     const AcrProblem& pb = ch.pb;
     const int slot = blockIdx.x;
     const AcrState* state = ch.states + par;                         // what this round's keeper has just written: cur_batch = this round's batch
-    if (slot >= state->cur_batch * pb.max_models) return;
+    if (slot >= state->cur_batch * pb.max_models) return;          // the grid covers the largest batch; this round is smaller
     acr_nfa_body<E>(pb, P, ch.models + ((size_t)par * kSlots + slot) * pb.model_doubles, ch.hyps + (size_t)par * kSlots + slot,
                     ch.sorted + ((size_t)par * kSlots + slot) * pb.n, (int)threadIdx.x, (int)blockDim.x, reinterpret_cast<uint64_t*>(acr_lds));
 }
@@ -908,18 +896,7 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
 }
 
 template <int E, int KIND>
-__global__ __launch_bounds__(1024) void acr_round_kernel(AcrState* __restrict__ states /* [2] */, AcrHyp* __restrict__ hyps /* [2][slots] */,
-                                                         const int par, const int P /* = blockDim.x * E */, const AcrProblem pb,
-                                                         uint32_t* __restrict__ sorted /* [2][slots * n] */,
-                                                         double* __restrict__ models /* [2][slots * 12] */,
-                                                         uint32_t* __restrict__ best_inliers, uint32_t* __restrict__ index_set,
-                                                         unsigned long long* __restrict__ h_word, const AcrFinish fin)
-{
-    acr_round_body<E, KIND>(states, hyps, par, P, pb, sorted, models, best_inliers, index_set, h_word, fin);
-}
-// the same round for up to kMaxBatch solves at once: blockIdx.y = chain (same code, same bits: the file is compiled without contraction)
-template <int E, int KIND>
-__global__ __launch_bounds__(1024) void acr_round_chains_kernel(const AcrChains chains, const int par, const int P)
+__global__ __launch_bounds__(1024) void acr_round_kernel(const AcrChains chains, const int par, const int P /* = blockDim.x * E */)   // (blockIdx.y = chain)
 {
     const AcrChain& ch = chains.c[blockIdx.y];
     acr_round_body<E, KIND>(ch.states, ch.hyps, par, P, ch.pb, ch.sorted, ch.models, ch.best_inliers, ch.index_set, ch.h_word, ch.fin);
@@ -1002,114 +979,15 @@ __device__ __forceinline__ void acr_solve5_body(AcrState* __restrict__ states /*
     fpw::models_of_sample(pb.a, pb.b, pb.K1, pb.K2, id[0], id[1], id[2], id[3], id[4], pb.n, models + ((size_t)par * kSlots + (size_t)it * 10) * 18);
 }
 
-__global__ __launch_bounds__(64) void acr_solve5_kernel(AcrState* __restrict__ states /* [2] */, AcrHyp* __restrict__ hyps /* [2][slots] */,
-                                                        const int par, const AcrProblem pb, uint32_t* __restrict__ sorted /* [2][slots * n] */,
-                                                        double* __restrict__ models /* [2][slots * 18] */,
-                                                        uint32_t* __restrict__ best_inliers, uint32_t* __restrict__ index_set,
-                                                        unsigned long long* __restrict__ h_word, const AcrFinish fin)
-{
-    acr_solve5_body(states, hyps, par, pb, sorted, models, best_inliers, index_set, h_word, fin);
-}
-__global__ __launch_bounds__(64) void acr_solve5_chains_kernel(const AcrChains chains, const int par)
+__global__ __launch_bounds__(64) void acr_solve5_kernel(const AcrChains chains, const int par)       // (blockIdx.y = chain)
 {
     const AcrChain& ch = chains.c[blockIdx.y];
     acr_solve5_body(ch.states, ch.hyps, par, ch.pb, ch.sorted, ch.models, ch.best_inliers, ch.index_set, ch.h_word, ch.fin);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-template <int E>
-static hipError_t acr_launch_nfa(const AcrProblem& pb, int B, int P, const double* d_models, AcrHyp* d_hyp, uint32_t* d_sorted,
-                                 const AcrState* d_state, hipStream_t stream)
-{
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)acr_nfa_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAcrMaxLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const int T = P / E;
-    // one word per element for the exchanges that cross waves + (E <= 8) one for the exact residual bits
-    const size_t lds = (T > 64 ? (size_t)P * 8 : 0) + (E <= 8 ? (size_t)P * 8 : 0);
-    hipLaunchKernelGGL(acr_nfa_kernel<E>, dim3(B * pb.max_models), dim3(T), lds, stream, pb, P, d_models, d_hyp, d_sorted, d_state);
-    return hipGetLastError();
-}
-
-template <int E, int KIND>
-static hipError_t acr_launch_round_one(const AcrProblem& pb, int B, int P, int par, AcrState* d_states, AcrHyp* d_hyps, uint32_t* d_sorted,
-                                       double* d_models, uint32_t* d_best_inliers, uint32_t* d_index_set, unsigned long long* h_word,
-                                       const AcrFinish& fin, hipStream_t stream)
-{
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)acr_round_kernel<E, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAcrMaxLds);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    const int T = P / E;
-    const size_t lds = (T > 64 ? (size_t)P * 8 : 0) + (E <= 8 ? (size_t)P * 8 : 0);
-    hipLaunchKernelGGL((acr_round_kernel<E, KIND>), dim3(B * AcrKind<KIND>::M + 1 /* the keeper */), dim3(T), lds, stream, d_states, d_hyps, par, P, pb,
-                       d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin);
-    return hipGetLastError();
-}
-template <int KIND>
-static hipError_t acr_launch_round_kind(const AcrProblem& pb, int B, int P, int par, AcrState* d_states, AcrHyp* d_hyps, uint32_t* d_sorted,
-                                        double* d_models, uint32_t* d_best_inliers, uint32_t* d_index_set, unsigned long long* h_word,
-                                        const AcrFinish& fin, hipStream_t stream)
-{
-    if (P <= 1024) return acr_launch_round_one<1, KIND>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-    if (P == 2048) return acr_launch_round_one<2, KIND>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-    if (P == 4096) return acr_launch_round_one<4, KIND>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-    if (P == 8192) return acr_launch_round_one<8, KIND>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-    return acr_launch_round_one<16, KIND>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-}
-
-hipError_t launch_acr_round_p3p(const AcrProblem& pb, int par, AcrState* d_states, AcrHyp* d_hyps, uint32_t* d_sorted, double* d_models,
-                                uint32_t* d_best_inliers, uint32_t* d_index_set, unsigned long long* h_word, hipStream_t stream,
-                                int batch_bound, uint8_t* d_mask, AcrResult* d_res, uint8_t* h_mask, int32_t* h_inliers, AcrResult* h_res)
-{
-    const int B = batch_bound < 1 ? 1 : (batch_bound > kAcrMaxBatch ? kAcrMaxBatch : batch_bound);
-    int P = 64;
-    while (P < pb.n) P <<= 1;
-    const AcrFinish fin{ d_mask, d_res, h_mask, h_inliers, h_res };
-    // (kind 0: P3P; 2 / 3: the seven-point / four-point models -- one launch per round for all three)
-    if (pb.kind == 2) return acr_launch_round_kind<2>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-    if (pb.kind == 3) return acr_launch_round_kind<3>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-    if (pb.kind != 0) return hipErrorInvalidValue;
-    return acr_launch_round_kind<0>(pb, B, P, par, d_states, d_hyps, d_sorted, d_models, d_best_inliers, d_index_set, h_word, fin, stream);
-}
-
-// the two-view round: acr_solve5_kernel (replay + samples + five-point; the keeper publishes the PREVIOUS round's word) and the nfa
-// launch over this round's models, both on the copies of launch parity `par`
-hipError_t launch_acr_round_5pt(const AcrProblem& pb, int par, AcrState* d_states, AcrHyp* d_hyps, uint32_t* d_sorted, double* d_models,
-                                uint32_t* d_best_inliers, uint32_t* d_index_set, unsigned long long* h_word, hipStream_t stream,
-                                int batch_bound, uint8_t* d_mask, AcrResult* d_res, uint8_t* h_mask, int32_t* h_inliers, AcrResult* h_res)
-{
-    const int B = batch_bound < 1 ? 1 : (batch_bound > kAcrMaxBatch ? kAcrMaxBatch : batch_bound);
-    constexpr int kSlots = kAcrMaxBatch * 10;
-    int P = 64;
-    while (P < pb.n) P <<= 1;
-    const AcrFinish fin{ d_mask, d_res, h_mask, h_inliers, h_res };
-    hipLaunchKernelGGL(acr_solve5_kernel, dim3(B + 1 /* the keeper */), dim3(64), 0, stream, d_states, d_hyps, par, pb, d_sorted, d_models,
-                       d_best_inliers, d_index_set, h_word, fin);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    const double* mo = d_models + (size_t)par * kSlots * 18;
-    AcrHyp* hy = d_hyps + (size_t)par * kSlots;
-    uint32_t* so = d_sorted + (size_t)par * kSlots * pb.n;
-    const AcrState* stp = d_states + par;                 // what this round's keeper has just written: cur_batch = this round's batch
-    if (P <= 1024) e = acr_launch_nfa<1>(pb, B, P, mo, hy, so, stp, stream);
-    else if (P == 2048) e = acr_launch_nfa<2>(pb, B, P, mo, hy, so, stp, stream);
-    else if (P == 4096) e = acr_launch_nfa<4>(pb, B, P, mo, hy, so, stp, stream);
-    else if (P == 8192) e = acr_launch_nfa<8>(pb, B, P, mo, hy, so, stp, stream);
-    else e = acr_launch_nfa<16>(pb, B, P, mo, hy, so, stp, stream);
-    return e;
-}
-
-// ---- the same rounds for several solves in one launch (lockstep; pose_batch.hip drives them) ----------------------------------------------
+// One launch path: a single solve is a chain of one (AcrRun::enqueue_round), a lockstep batch up to kMaxBatch chains of one kind
+// (drive_group, pose_batch.hip).
 template <typename K>
 static hipError_t acr_dyn_lds(K kernel, bool (&attr_set)[64])
 {
@@ -1122,95 +1000,69 @@ static hipError_t acr_dyn_lds(K kernel, bool (&attr_set)[64])
     }
     return hipSuccess;
 }
-static int acr_chains_width(const AcrChains& chains, int n_chains)
-{
-    int P = 64;
-    for (int c = 0; c < n_chains; ++c) while (P < chains.c[c].pb.n) P <<= 1;
-    return P;
-}
+// one word per element for the exchanges that cross waves + (E <= 8) one for the exact residual bits
+template <int E>
+static size_t acr_lds_bytes(const int P) { return (P / E > 64 ? (size_t)P * 8 : 0) + (E <= 8 ? (size_t)P * 8 : 0); }
+
 template <int E, int KIND>
-static hipError_t acr_launch_round_one_chains(const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
+static hipError_t acr_launch_round(const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
 {
     static bool attr_set[64] = {};
-    const hipError_t e = acr_dyn_lds(acr_round_chains_kernel<E, KIND>, attr_set);
+    const hipError_t e = acr_dyn_lds(acr_round_kernel<E, KIND>, attr_set);
     if (e != hipSuccess) return e;
-    const int T = P / E;
-    const size_t lds = (T > 64 ? (size_t)P * 8 : 0) + (E <= 8 ? (size_t)P * 8 : 0);
-    hipLaunchKernelGGL((acr_round_chains_kernel<E, KIND>), dim3(B * AcrKind<KIND>::M + 1 /* the keeper */, n_chains), dim3(T), lds, stream, chains, par, P);
+    hipLaunchKernelGGL((acr_round_kernel<E, KIND>), dim3(B * AcrKind<KIND>::M + 1 /* the keeper */, n_chains), dim3(P / E), acr_lds_bytes<E>(P),
+                       stream, chains, par, P);
     return hipGetLastError();
 }
-template <int KIND>
-static hipError_t acr_launch_round_kind_chains(const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
+// the five-point round: acr_solve5_kernel (replay + samples + five-point; the keeper publishes the PREVIOUS round's word), then the
+// nfa launch over this round's models
+template <int E>
+static hipError_t acr_launch_round5(const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
 {
-    if (P <= 1024) return acr_launch_round_one_chains<1, KIND>(chains, n_chains, B, P, par, stream);
-    if (P == 2048) return acr_launch_round_one_chains<2, KIND>(chains, n_chains, B, P, par, stream);
-    if (P == 4096) return acr_launch_round_one_chains<4, KIND>(chains, n_chains, B, P, par, stream);
-    if (P == 8192) return acr_launch_round_one_chains<8, KIND>(chains, n_chains, B, P, par, stream);
-    return acr_launch_round_one_chains<16, KIND>(chains, n_chains, B, P, par, stream);
-}
-hipError_t launch_acr_round_p3p_chains(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream)
-{
-    if (n_chains < 1 || n_chains > kMaxBatch) return hipErrorInvalidValue;
-    const int B = batch_bound < 1 ? 1 : (batch_bound > kAcrMaxBatch ? kAcrMaxBatch : batch_bound);
-    const int P = acr_chains_width(chains, n_chains);                // every chain sorts at the widest chain's width: the order of its n real elements is the same
-    const int kind = chains.c[0].pb.kind;                            // (a batch is one kind: check_batch / drive_group)
-    for (int c = 1; c < n_chains; ++c) if (chains.c[c].pb.kind != kind) return hipErrorInvalidValue;
-    if (kind == 2) return acr_launch_round_kind_chains<2>(chains, n_chains, B, P, par, stream);
-    if (kind == 3) return acr_launch_round_kind_chains<3>(chains, n_chains, B, P, par, stream);
-    if (kind != 0) return hipErrorInvalidValue;
-    return acr_launch_round_kind_chains<0>(chains, n_chains, B, P, par, stream);
+    hipLaunchKernelGGL(acr_solve5_kernel, dim3(B + 1 /* the keeper */, n_chains), dim3(64), 0, stream, chains, par);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    static bool attr_set[64] = {};
+    e = acr_dyn_lds(acr_nfa_kernel<E>, attr_set);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(acr_nfa_kernel<E>, dim3(B * 10, n_chains), dim3(P / E), acr_lds_bytes<E>(P), stream, chains, par, P);
+    return hipGetLastError();
 }
 template <int E>
-static hipError_t acr_launch_nfa_chains(const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
+static hipError_t acr_launch_kind(const int kind, const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
 {
-    static bool attr_set[64] = {};
-    const hipError_t e = acr_dyn_lds(acr_nfa_chains_kernel<E>, attr_set);
-    if (e != hipSuccess) return e;
-    const int T = P / E;
-    const size_t lds = (T > 64 ? (size_t)P * 8 : 0) + (E <= 8 ? (size_t)P * 8 : 0);
-    hipLaunchKernelGGL(acr_nfa_chains_kernel<E>, dim3(B * 10, n_chains), dim3(T), lds, stream, chains, par, P);
-    return hipGetLastError();
+    if (kind == 0) return acr_launch_round<E, 0>(chains, n_chains, B, P, par, stream);
+    if (kind == 1) return acr_launch_round5<E>(chains, n_chains, B, P, par, stream);
+    if (kind == 2) return acr_launch_round<E, 2>(chains, n_chains, B, P, par, stream);
+    if (kind == 3) return acr_launch_round<E, 3>(chains, n_chains, B, P, par, stream);
+    return hipErrorInvalidValue;
 }
-hipError_t launch_acr_round_5pt_chains(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream)
+hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream)
 {
     if (n_chains < 1 || n_chains > kMaxBatch) return hipErrorInvalidValue;
+    const int kind = chains.c[0].pb.kind;                            // (a batch is one kind: check_batch / drive_group)
+    for (int c = 1; c < n_chains; ++c) if (chains.c[c].pb.kind != kind) return hipErrorInvalidValue;
     const int B = batch_bound < 1 ? 1 : (batch_bound > kAcrMaxBatch ? kAcrMaxBatch : batch_bound);
-    const int P = acr_chains_width(chains, n_chains);
-    hipLaunchKernelGGL(acr_solve5_chains_kernel, dim3(B + 1 /* the keeper */, n_chains), dim3(64), 0, stream, chains, par);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (P <= 1024) return acr_launch_nfa_chains<1>(chains, n_chains, B, P, par, stream);
-    if (P == 2048) return acr_launch_nfa_chains<2>(chains, n_chains, B, P, par, stream);
-    if (P == 4096) return acr_launch_nfa_chains<4>(chains, n_chains, B, P, par, stream);
-    if (P == 8192) return acr_launch_nfa_chains<8>(chains, n_chains, B, P, par, stream);
-    return acr_launch_nfa_chains<16>(chains, n_chains, B, P, par, stream);
+    int P = 64;                                                      // every chain sorts at the widest chain's width: the order of its n real
+    for (int c = 0; c < n_chains; ++c) while (P < chains.c[c].pb.n) P <<= 1;   // elements is the same
+    if (P <= 1024) return acr_launch_kind<1>(kind, chains, n_chains, B, P, par, stream);
+    if (P == 2048) return acr_launch_kind<2>(kind, chains, n_chains, B, P, par, stream);
+    if (P == 4096) return acr_launch_kind<4>(kind, chains, n_chains, B, P, par, stream);
+    if (P == 8192) return acr_launch_kind<8>(kind, chains, n_chains, B, P, par, stream);
+    return acr_launch_kind<16>(kind, chains, n_chains, B, P, par, stream);
 }
 
-// inputs of a solve: pinned host block -> device workspace, by a launch instead of a copy command (a copy command runs on another
-// engine: 6.6 us + 8 us until the first round starts behind it, against ~3 + 3 us for a launch in the same queue)
-__global__ __launch_bounds__(256) void acr_stage_kernel(const double2* __restrict__ src, double2* __restrict__ dst, const int n2)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n2) dst[i] = src[i];
-}
-hipError_t launch_acr_stage(const double* h_pinned, double* d_dst, size_t n_doubles /* even */, hipStream_t stream)
-{
-    const int n2 = (int)(n_doubles / 2);
-    if (n2 <= 0) return hipSuccess;
-    hipLaunchKernelGGL(acr_stage_kernel, dim3((n2 + 255) / 256), dim3(256), 0, stream, (const double2*)h_pinned, (double2*)d_dst, n2);
-    return hipGetLastError();
-}
-
-// the same for the solves of a lockstep batch in ONE launch (blockIdx.y = solve): eight staging launches on the shared stream were 75 us
-// of a batch's 400
+// inputs of the solves: pinned host blocks -> device workspaces, by ONE launch (blockIdx.y = solve) instead of copy commands (a copy
+// command runs on another engine: 6.6 us + 8 us until the first round starts behind it, against ~3 + 3 us for a launch in the same
+// queue; eight staging launches on the shared stream of a lockstep batch were 75 us of its 400)
 struct AcrStageJobs { const double2* src[kMaxBatch]; double2* dst[kMaxBatch]; int n2[kMaxBatch]; };
-__global__ __launch_bounds__(256) void acr_stage_chains_kernel(const AcrStageJobs jobs)
+__global__ __launch_bounds__(256) void acr_stage_kernel(const AcrStageJobs jobs)
 {
     const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (i < jobs.n2[c]) jobs.dst[c][i] = jobs.src[c][i];
 }
-hipError_t launch_acr_stage_chains(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
-                                   hipStream_t stream)
+hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
+                            hipStream_t stream)
 {
     if (n_chains < 1 || n_chains > kMaxBatch) return hipErrorInvalidValue;
     AcrStageJobs jobs{};
@@ -1220,7 +1072,7 @@ hipError_t launch_acr_stage_chains(const double* const* h_pinned, double* const*
         most = jobs.n2[c] > most ? jobs.n2[c] : most;
     }
     if (most <= 0) return hipSuccess;
-    hipLaunchKernelGGL(acr_stage_chains_kernel, dim3((most + 255) / 256, n_chains), dim3(256), 0, stream, jobs);
+    hipLaunchKernelGGL(acr_stage_kernel, dim3((most + 255) / 256, n_chains), dim3(256), 0, stream, jobs);
     return hipGetLastError();
 }
 

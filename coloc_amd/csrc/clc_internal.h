@@ -255,25 +255,17 @@ struct AcrChain {
     AcrFinish fin;
 };
 struct AcrChains { AcrChain c[kMaxBatch]; };
-// one round of n_chains solves: P3P (one launch) / five-point (two launches); batch_bound and the sort width cover the largest chain
-hipError_t launch_acr_round_p3p_chains(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream);
-hipError_t launch_acr_round_5pt_chains(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream);
-// batch_bound: iterations the launch grids cover (>= the batch the device state asks for); d_mask .. h_res: where the round that
-// completes the run leaves mask / inlier list / result record (device copies + pinned host mirrors)
+// One round of n_chains solves of one kind (a single solve: n_chains = 1): ONE launch for kinds 0 / 2 / 3 (replay of the previous round +
+// samples + P3P / seven-point / four-point + residuals / sort / NFA), TWO for kind 1 (replay + samples + five-point; nfa).  The states,
+// slots, sorted lists and models of a chain hold two copies: this launch reads copy par ^ 1 and writes copy par; the initial state goes
+// into copy 1 and the first launch has par 0.  batch_bound (iterations the grids cover, >= the batch the device states ask for) and the
+// sort width cover the largest chain; chain.fin: where the round that completes a run leaves mask / inlier list / result record.
+hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream);
+// the inputs of n_chains solves, pinned host blocks -> device workspaces, in one launch
+hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
+                            hipStream_t stream);
 // the seven-point / four-point models (kind 2: <= 3 per sample, kind 3: 1) of S samples of normalised correspondences: d_out S x M x 9, NaN = no model
 hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_x2, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
-// the resection round (and the rounds of kinds 2 / 3, by pb.kind) as ONE launch (replay of the previous round + solve + nfa; acransac.hip): d_states / d_hyps / d_sorted / d_models
-// hold two copies, this launch reads copy par ^ 1 and writes copy par; the initial state goes into copy 1 and the first launch has par 0
-hipError_t launch_acr_round_p3p(const AcrProblem& pb, int par, AcrState* d_states, AcrHyp* d_hyps, uint32_t* d_sorted, double* d_models,
-                                uint32_t* d_best_inliers, uint32_t* d_index_set, unsigned long long* h_word, hipStream_t stream,
-                                int batch_bound, uint8_t* d_mask, AcrResult* d_res, uint8_t* h_mask, int32_t* h_inliers, AcrResult* h_res);
-// the two-view round as TWO launches (replay of the previous round + samples + five-point solve; nfa), same two-copy scheme
-hipError_t launch_acr_round_5pt(const AcrProblem& pb, int par, AcrState* d_states, AcrHyp* d_hyps, uint32_t* d_sorted, double* d_models,
-                                uint32_t* d_best_inliers, uint32_t* d_index_set, unsigned long long* h_word, hipStream_t stream,
-                                int batch_bound, uint8_t* d_mask, AcrResult* d_res, uint8_t* h_mask, int32_t* h_inliers, AcrResult* h_res);
-hipError_t launch_acr_stage(const double* h_pinned, double* d_dst, size_t n_doubles /* even */, hipStream_t stream);
-hipError_t launch_acr_stage_chains(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
-                                   hipStream_t stream);
 
 } // namespace clc
 #endif

@@ -40,7 +40,9 @@ int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     *h_rec = hp + in_d;
     *ready = (int32_t*)((uint8_t*)*h_rec + pnp_refine_ready_offset());
     __atomic_store_n(*ready, 0, __ATOMIC_RELAXED);
-    CLC_HIP(ctx, launch_acr_stage(hp, ctx->d_pnp, (in_d + 1) & ~(size_t)1, ctx->stream));          // inputs by a launch, not a copy command
+    const double* src = hp;
+    const size_t n_stage = (in_d + 1) & ~(size_t)1;
+    CLC_HIP(ctx, launch_acr_stage(&src, &ctx->d_pnp, &n_stage, 1, ctx->stream));                 // inputs by a launch, not a copy command
     CLC_HIP(ctx, launch_pnp_refine(dRt, dX, dx, nullptr, N, dK, huber_a > 0.0 ? huber_a : 16.0, 50, ctx->d_pnp + in_d, ctx->stream, &ctx->prof, nullptr,
                                    *h_rec));
     return CLC_OK;

@@ -105,20 +105,13 @@ struct AcrRun {
     int drained(const int code) { (void)hipStreamSynchronize(st); phase = DONE; status = code; return code; }
     int stop(const int code) { phase = DONE; status = code; return code; }
 
+    // the solve's next round as a chain of one (launch_acr_round: one launch, or two for the five-point kind); the word of round r
+    // comes out of round r + 1's first launch
     int enqueue_round(const int bnd)
     {
-        const int S = bnd < 1 ? 1 : (bnd > kAcrMaxBatch ? kAcrMaxBatch : bnd);
-        if (kind != 1) {
-            // one launch: replay of the previous round, this round's samples, P3P (seven-point, four-point), residuals / sort / NFA;
-            // the word of round r comes out of launch r + 1
-            CLC_HIP(ctx, launch_acr_round_p3p(pb, launches & 1, d_state, d_hyp, d_sorted, d_models, d_best, d_index, h_word, st, S, d_mask,
-                                              d_res, nullptr, p_inl, h_res));
-        } else {
-            // two launches: replay of the previous round + this round's samples + five-point solve, then nfa; the word of round r
-            // comes out of round r + 1's first launch
-            CLC_HIP(ctx, launch_acr_round_5pt(pb, launches & 1, d_state, d_hyp, d_sorted, d_models, d_best, d_index, h_word, st, S, d_mask,
-                                              d_res, nullptr, p_inl, h_res));
-        }
+        AcrChains one;
+        chain(one.c[0]);
+        CLC_HIP(ctx, launch_acr_round(one, 1, launches & 1, bnd, st));
         ++launches;
         return CLC_OK;
     }
@@ -259,7 +252,7 @@ struct AcrRun {
 
         st = grouped ? group_stream : ctx->stream;
         stage_src = hp; stage_dst = ctx->d_pnp; stage_n = (in_d + 1) & ~(size_t)1;      // (both blocks are sized past in_d + 1)
-        if (!grouped) CLC_HIP(ctx, launch_acr_stage(stage_src, stage_dst, stage_n, st));  // (grouped: one launch for the batch, drive_group)
+        if (!grouped) CLC_HIP(ctx, launch_acr_stage(&stage_src, &stage_dst, &stage_n, 1, st));   // (grouped: one launch for the batch, drive_group)
         if (!grouped) prof_mark(&ctx->prof, CLC_KERNEL_PNP_SCORE, true, st);
         // Rounds are enqueued ONE AHEAD of what the host knows: the solve / nfa / select kernels take the round's batch from the
         // device state (a round enqueued after the run has finished finds nothing to do), so the GPU goes from one round's
@@ -420,7 +413,7 @@ void drive_runs(std::vector<AcrRun>& runs)
 
 // Lockstep form of the same (round 5, the default of the batched entries): the batch's solves -- one kind, contexts on one device -- share
 // their launches.  Round r of every unfinished solve is ONE launch (resection) or two (two-view) with blockIdx.y = solve
-// (launch_acr_round_*_chains), on the first context's stream, enqueued one ahead as for a single solve; the host waits for the round's
+// (launch_acr_round), on the first context's stream, enqueued one ahead as for a single solve; the host waits for the round's
 // words of all unfinished solves and enqueues the next shared launch while any of them needs one.  A finished solve's part of the later
 // launches finds nothing to replay and returns.  Why: eight interleaved poses were ~80 launches from one thread (4-5 us each inside the
 // runtime, and the runtime serialises launching threads), eight two-view filters ~100; in lockstep they are ~10 and ~16.  Same bits per
@@ -447,7 +440,6 @@ void drive_group(std::vector<AcrRun>& runs)
     std::vector<AcrRun*> live;
     for (AcrRun& r : runs) if (r.phase == AcrRun::ROUNDS && r.grouped) live.push_back(&r);
     if (live.empty()) { drive_runs(runs); return; }
-    const int kind = live[0]->kind;
     hipStream_t st = live[0]->group_stream;
     clc_ctx* ctx0 = live[0]->ctx;
     int launches = 0;
@@ -468,7 +460,7 @@ void drive_group(std::vector<AcrRun>& runs)
         const int n = (int)std::min<size_t>(kMaxBatch, live.size() - k);
         const double* src[kMaxBatch]; double* dst[kMaxBatch]; size_t cnt[kMaxBatch];
         for (int i = 0; i < n; ++i) { src[i] = live[k + i]->stage_src; dst[i] = live[k + i]->stage_dst; cnt[i] = live[k + i]->stage_n; }
-        const hipError_t e = launch_acr_stage_chains(src, dst, cnt, n, st);
+        const hipError_t e = launch_acr_stage(src, dst, cnt, n, st);
         if (e != hipSuccess) { fail_all(fail(ctx0, CLC_ERR_HIP, "acransac: shared staging launch", e)); return; }
     }
     // a round's launches carry the solves that are still in their rounds (what the host knows when it enqueues: a solve that finishes in
@@ -478,8 +470,7 @@ void drive_group(std::vector<AcrRun>& runs)
         int n = 0;
         auto flush = [&]() -> bool {
             if (n == 0) return true;
-            const hipError_t e = kind != 1 ? launch_acr_round_p3p_chains(pack, n, launches & 1, bound, st)
-                                           : launch_acr_round_5pt_chains(pack, n, launches & 1, bound, st);
+            const hipError_t e = launch_acr_round(pack, n, launches & 1, bound, st);
             n = 0;
             if (e != hipSuccess) { fail_all(fail(ctx0, CLC_ERR_HIP, "acransac: shared round launch", e)); return false; }
             return true;
@@ -576,12 +567,8 @@ int clc_pnp_localize_ac_batch(clc_ctx* const* ctxs, clc_pose_job* jobs, int n_jo
 {
     if (n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
     if (n_jobs == 0) return CLC_OK;
-    for (int i = 0; i < n_jobs; ++i) {
-        if (!ctxs[i]) return CLC_ERR_BAD_ARG;
-        for (int j = 0; j < i; ++j)
-            if (ctxs[j] == ctxs[i]) return fail(ctxs[i], CLC_ERR_BAD_ARG, "pnp_localize_ac_batch: every job needs a context of its own");
-        if (ctxs[i]->device != ctxs[0]->device) return fail(ctxs[i], CLC_ERR_BAD_ARG, "pnp_localize_ac_batch: the contexts must live on one device");
-    }
+    const int rc0 = check_batch_contexts(ctxs, n_jobs, "pnp_localize_ac_batch: every job needs a context of its own");
+    if (rc0 != CLC_OK) return rc0;
     std::vector<AcrRun> runs((size_t)n_jobs);
     int worst = CLC_OK, live = 0;
     const bool lockstep = acr_lockstep(0, n_jobs);
