@@ -73,13 +73,6 @@ __device__ __forceinline__ void acr_finish_block(const AcrProblem& pb, const Acr
     }
 }
 
-struct AcrHyp {            // per model slot, written by the nfa kernel
-    double nfa;            // min_k NFA(k); +inf for an empty slot
-    double e_k;            // the k-th smallest residual (kernel units)
-    int32_t k;             // minimising k
-    int32_t n_le;          // residuals <= max_threshold (upper-bound mode gate)
-};
-
 // ---- nfa: one workgroup per model slot ---------------------------------------------------------------------------
 __device__ __forceinline__ double acr_err_resection(const double* __restrict__ P, const double* __restrict__ K, const double s,
                                                     const double Xw, const double Yw, const double Zw, const double uo, const double vo)
@@ -986,8 +979,8 @@ __global__ __launch_bounds__(64) void acr_solve5_kernel(const AcrChains chains, 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// One launch path: a single solve is a chain of one (AcrRun::enqueue_round), a lockstep batch up to kMaxBatch chains of one kind
-// (drive_group, pose_batch.hip).
+// One launch path: a round of a group of solves (acr_drive, pose_batch.hip), up to kMaxBatch chains of one kind per launch; a single
+// solve is a chain of one.
 template <typename K>
 static hipError_t acr_dyn_lds(K kernel, bool (&attr_set)[64])
 {
@@ -1040,7 +1033,7 @@ static hipError_t acr_launch_kind(const int kind, const AcrChains& chains, int n
 hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream)
 {
     if (n_chains < 1 || n_chains > kMaxBatch) return hipErrorInvalidValue;
-    const int kind = chains.c[0].pb.kind;                            // (a batch is one kind: check_batch / drive_group)
+    const int kind = chains.c[0].pb.kind;                            // (a group is one kind: a batch entry solves one model)
     for (int c = 1; c < n_chains; ++c) if (chains.c[c].pb.kind != kind) return hipErrorInvalidValue;
     const int B = batch_bound < 1 ? 1 : (batch_bound > kAcrMaxBatch ? kAcrMaxBatch : batch_bound);
     int P = 64;                                                      // every chain sorts at the widest chain's width: the order of its n real
@@ -1075,8 +1068,6 @@ hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst,
     hipLaunchKernelGGL(acr_stage_kernel, dim3((most + 255) / 256, n_chains), dim3(256), 0, stream, jobs);
     return hipGetLastError();
 }
-
-size_t acr_hyp_bytes() { return sizeof(AcrHyp); }
 
 } // namespace clc
 

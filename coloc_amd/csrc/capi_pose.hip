@@ -141,8 +141,8 @@ static int pnp_ransac_impl(clc_ctx* ctx, const double* h_X, const double* h_x, i
     const size_t in_d = (size_t)5 * N + 16 + ((size_t)3 * S + 1) / 2;
     const size_t scr_d = (size_t)48 * S + (size_t)4 * S + ((size_t)4 * S + 1) / 2;
     const bool refine = refine_huber > 0.0;
-    const size_t ref_d = refine ? (pnp_refine_out_bytes() + 7) / 8 : 0;      // refine record rides in front of the mask
-    const size_t res_d = (pnp_result_bytes() + 7) / 8 + ref_d;
+    const size_t ref_d = refine ? (sizeof(RefineOut) + 7) / 8 : 0;      // refine record rides in front of the mask
+    const size_t res_d = (sizeof(PnpResult) + 7) / 8 + ref_d;
     const size_t out_d = res_d + ((size_t)N + 7) / 8;
     int rc = ensure_pnp(ctx, in_d + scr_d + out_d + 8);
     if (rc != CLC_OK) return rc;
@@ -166,7 +166,7 @@ static int pnp_ransac_impl(clc_ctx* ctx, const double* h_X, const double* h_x, i
     memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
     memcpy(hp + (size_t)5 * N, h_K, sizeof(double) * 9);
     memcpy(hp + (size_t)5 * N + 16, h_samples, sizeof(int32_t) * 3 * S);
-    const size_t ref_off = (pnp_result_bytes() + 7) / 8;
+    const size_t ref_off = (sizeof(PnpResult) + 7) / 8;
     PnpHostStage hs;
     hs.src = hp;
     hs.n_doubles = (int)in_d;
@@ -175,18 +175,16 @@ static int pnp_ransac_impl(clc_ctx* ctx, const double* h_X, const double* h_x, i
     CLC_HIP(ctx, launch_pnp_ransac(dX, dx, N, dK, dSamples, S, thr2, dRt, dCount, dCost, dMask, dRes, ctx->stream, &ctx->prof, &hs));
     if (refine)
         CLC_HIP(ctx, launch_pnp_refine(dRes /* PnpResult.Rt */, dX, dx, dMask, N, dK, refine_huber, 50, dRes + ref_off, ctx->stream,
-                                       &ctx->prof, (const int32_t*)((const uint8_t*)dRes + pnp_result_valid_offset()), hout + ref_off));
+                                       &ctx->prof, &((const PnpResult*)dRes)->h, hout + ref_off));
     if (h_all_Rt) CLC_HIP(ctx, hipMemcpyAsync(h_all_Rt, dRt, sizeof(double) * 48 * S, hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    struct { double Rt[12]; double cost; int32_t h; int32_t count; } r;
-    memcpy(&r, hout, sizeof r);
-    if (h_Rt) memcpy(h_Rt, r.Rt, sizeof(double) * 12);
+    const PnpResult& r = *(const PnpResult*)hout;
+    if (h_Rt) memcpy(h_Rt, r.Rt, sizeof r.Rt);
     if (h_mask) memcpy(h_mask, (const uint8_t*)(hout + res_d), (size_t)N);
     if (n_inliers) *n_inliers = r.h >= 0 ? r.count : 0;
     if (cost) *cost = r.cost;
     if (refine) {
-        struct { double Rt[12]; double cov[36]; double cost; double rmse; int32_t iterations; int32_t n_used; } f;
-        memcpy(&f, hout + ref_off, sizeof f);
+        const RefineOut& f = *(const RefineOut*)(hout + ref_off);
         if (h_Rt) memcpy(h_Rt, f.Rt, sizeof f.Rt);
         if (h_cov) memcpy(h_cov, f.cov, sizeof f.cov);
         if (rmse) *rmse = f.rmse;
@@ -221,7 +219,7 @@ static int essential_impl(clc_ctx* ctx, const double* h_x1, const double* h_x2, 
     //                              [ FE 180 S | cost 10 S | count (10 S int32) ] scratch, [ result | mask ] out
     const size_t in_d = (size_t)4 * N + 32 + ((size_t)5 * S + 1) / 2;
     const size_t scr_d = (size_t)180 * S + (size_t)10 * S + ((size_t)10 * S + 1) / 2;
-    const size_t res_d = (epi_result_bytes() + 7) / 8;
+    const size_t res_d = (sizeof(EpiResult) + 7) / 8;
     const size_t out_d = res_d + ((size_t)N + 7) / 8;
     int rc = ensure_pnp(ctx, in_d + scr_d + out_d + 8);
     if (rc != CLC_OK) return rc;
@@ -249,8 +247,7 @@ static int essential_impl(clc_ctx* ctx, const double* h_x1, const double* h_x2, 
     std::vector<double> fe;
     if (h_all_E) { fe.resize((size_t)180 * S); CLC_HIP(ctx, hipMemcpyAsync(fe.data(), dFE, sizeof(double) * 180 * S, hipMemcpyDeviceToHost, ctx->stream)); }
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    struct { double E[9]; double F[9]; double cost; int32_t h; int32_t count; } r;
-    memcpy(&r, hp, sizeof r);
+    const EpiResult& r = *(const EpiResult*)hp;
     if (h_E) memcpy(h_E, r.E, sizeof r.E);
     if (h_F) memcpy(h_F, r.F, sizeof r.F);
     if (h_mask) memcpy(h_mask, (const uint8_t*)(hp + res_d), (size_t)N);
@@ -291,7 +288,7 @@ int clc_pnp_refine(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     // workspace in doubles: [ X 3N | x 2N | K 16 | Rt_in 12 | mask (N bytes) ] in, [ RefineOut ] out
     const size_t mask_d = ((size_t)N + 7) / 8;
     const size_t in_d = (size_t)5 * N + 16 + 12 + mask_d;
-    const size_t out_d = (pnp_refine_out_bytes() + 7) / 8;
+    const size_t out_d = (sizeof(RefineOut) + 7) / 8;
     int rc = ensure_pnp(ctx, in_d + out_d + 8);
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (in_d > out_d ? in_d : out_d) * sizeof(double) + 64);
@@ -312,8 +309,7 @@ int clc_pnp_refine(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     CLC_HIP(ctx, launch_pnp_refine(dRt, dX, dx, h_inlier_mask ? dMask : nullptr, N, dK, huber_a, max_iter, dOut, ctx->stream, &ctx->prof));
     CLC_HIP(ctx, hipMemcpyAsync(hp, dOut, out_d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    struct { double Rt[12]; double cov[36]; double cost; double rmse; int32_t iterations; int32_t n_used; } r;
-    memcpy(&r, hp, sizeof r);
+    const RefineOut& r = *(const RefineOut*)hp;
     if (h_Rt_out) memcpy(h_Rt_out, r.Rt, sizeof r.Rt);
     if (h_cov) memcpy(h_cov, r.cov, sizeof r.cov);
     if (rmse) *rmse = r.rmse;

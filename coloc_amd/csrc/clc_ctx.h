@@ -95,7 +95,7 @@ struct clc_ctx {
     clc::K2nnDevice k2dev{};          // XCDs and CUs of this context's device (the sweep planner's balance arguments)
     int bias_source = 0;         // 0: built-in default, 1: CLC_K2NN_BIAS, 2: timed probe on this device (k2nn_probe_bias)
     float bias_probe_us[4] = {}; // the probe's sweep times per candidate (0: not probed)
-    hipEvent_t ev_group = nullptr;   // drive_group: the tail of a batch's shared launches, for the other contexts' streams to wait on
+    hipEvent_t ev_group = nullptr;   // acr_drive (pose_batch.hip): orders a shared group's stream and the contexts' own streams
     int cache_mode = CLC_DESC_CACHE_VERIFY;   // how this context's host-pointer match entry points treat published blocks (clc_desc_cache_mode)
     // pnp
     uint8_t* d_pairs = nullptr;   // clc_match_pairs arena: descriptors of all cameras, then results

@@ -162,8 +162,33 @@ hipError_t launch_pnp_score(const double* d_Rt, int H, const double* d_X, const 
                             const double* d_K, double thr2, int32_t* d_count, double* d_cost,
                             hipStream_t stream, Profiler* prof = nullptr);
 
+// The records the pose launches leave for the host (device or pinned host memory; the host reads them as they are).
+struct PnpResult {      // launch_pnp_ransac: one packed record so the host needs a single D2H copy
+    double Rt[12];
+    double cost;
+    int32_t h;          // winning hypothesis (< 0: none)
+    int32_t count;
+};
+struct EpiResult {      // launch_essential_ransac: the same for the five-point problems
+    double E[9];
+    double F[9];
+    double cost;
+    int32_t h;
+    int32_t count;
+};
+struct RefineOut {      // launch_pnp_refine
+    double Rt[12];
+    double cov[36];
+    double cost;        // final 1/2 sum rho
+    double rmse;        // sqrt(final_cost / (2 n_used))  (Refiner.hpp:226)
+    int32_t iterations;
+    int32_t n_used;
+    int32_t ready;      // written LAST (system-scope release): a host that cleared it in a pinned record can poll it instead of
+    int32_t pad_;       // synchronising the stream
+};
+
 // P3P hypotheses for S minimal samples (4 slots each) -> score -> select + inlier mask of the winner.
-// d_result receives one packed record {double Rt[12]; double cost; int32 h; int32 count} (pnp_result_bytes()).
+// d_result receives one PnpResult.
 // hs (nullable): the inputs are still in the caller's pinned host buffer [X 3N | x 2N | K 16 | samples]; the first
 // launch reads them from there and stages them into d_X.. itself, the last one mirrors record + mask into pinned host
 // memory -- no copy commands around the launches.
@@ -176,25 +201,20 @@ struct PnpHostStage {
 hipError_t launch_pnp_ransac(const double* d_X, const double* d_x, int N, const double* d_K, const int32_t* d_samples,
                              int S, double thr2, double* d_Rt, int32_t* d_count, double* d_cost, uint8_t* d_mask,
                              void* d_result, hipStream_t stream, Profiler* prof = nullptr, const PnpHostStage* hs = nullptr);
-size_t pnp_result_bytes();
 // five-point problems for S minimal samples (10 slots of {F(9), E(9)} each) -> symmetric-epipolar score -> select + mask.
-// d_result: {double E[9]; double F[9]; double cost; int32 h; int32 count} (epi_result_bytes()).
+// d_result: one EpiResult.
 hipError_t launch_essential_ransac(const double* d_x1, const double* d_x2, int N, const double* d_K1, const double* d_K2,
                                    const int32_t* d_samples, int S, double thr2, double* d_FE, int32_t* d_count, double* d_cost,
                                    uint8_t* d_mask, void* d_result, hipStream_t stream, Profiler* prof = nullptr);
-size_t epi_result_bytes();
 // symmetric epipolar distance of H fundamental matrices: d_err != null -> H x N residuals, else counts / costs
 hipError_t launch_epipolar(const double* d_F, int H, const double* d_x1, const double* d_x2, int N, double thr2, double* d_err,
                            int32_t* d_count, double* d_cost, hipStream_t stream, Profiler* prof = nullptr);
 // Levenberg-Marquardt refinement of one pose over the (masked) correspondences + 6x6 covariance.
-// d_out: {double Rt[12]; double cov[36]; double cost; double rmse; int32 iterations; int32 n_used}
+// d_out: one RefineOut.
 hipError_t launch_pnp_refine(const double* d_Rt_in, const double* d_X, const double* d_x, const uint8_t* d_mask, int N,
                              const double* d_K, double huber_a, int max_iter, void* d_out, hipStream_t stream,
                              Profiler* prof = nullptr, const int32_t* d_valid = nullptr, void* h_out = nullptr);
 // (h_out: pinned host record written INSTEAD of d_out, so that no device-to-host copy command is needed)
-size_t pnp_result_valid_offset();   // byte offset of the int32 "winning hypothesis" (< 0: none) in the ransac result record
-size_t pnp_refine_out_bytes();
-size_t pnp_refine_ready_offset();   // int32 written last by the refinement launch (1), for a host polling a pinned record
 
 // ---- a-contrario RANSAC (acransac.hip) -----------------------------------------------------------------------
 static constexpr int kAcrMaxBatch = 128;           // iterations evaluated per round
@@ -236,17 +256,21 @@ struct AcrResult {
     int32_t valid;         // iteration that produced the model, -1: no meaningful model
     int32_t iterations, rounds;
 };
-struct AcrHyp;
-size_t acr_hyp_bytes();
+struct AcrHyp {            // per model slot, written by the nfa kernel
+    double nfa;            // min_k NFA(k); +inf for an empty slot
+    double e_k;            // the k-th smallest residual (kernel units)
+    int32_t k;             // minimising k
+    int32_t n_le;          // residuals <= max_threshold (upper-bound mode gate)
+};
 // where the round that COMPLETES a run leaves the result (the finish work rides in that round's launch, and the host returns as soon as
 // the polled word says "done" instead of launching a finish kernel behind the round enqueued ahead)
 struct AcrFinish {
     uint8_t* d_mask; AcrResult* d_res;                 // device copies (the refinement reads them)
     uint8_t* h_mask; int32_t* h_inliers; AcrResult* h_res;     // pinned host memory (nullable)
 };
-// Everything the launches of ONE solve work on; up to kMaxBatch solves of one kind share a launch (blockIdx.y = chain): their rounds then
-// advance in lockstep, one launch (resection) or two (two-view) per round for all of them (round 5: the batched entries were bound by the
-// host's launch calls -- 8 poses = ~80 launches from one thread).
+// Everything the launches of ONE solve work on.  The solves of a group (pose_batch.hip: acr_drive) share their launches, up to kMaxBatch
+// chains of one kind per launch (blockIdx.y = chain): their rounds advance in lockstep, one launch (resection) or two (two-view) per round
+// for all of them (round 5: eight poses in chains of their own were ~80 launches from one thread).
 struct AcrChain {
     AcrProblem pb;
     AcrState* states; AcrHyp* hyps; uint32_t* sorted; double* models;      // two copies each, indexed by launch parity

@@ -16,13 +16,13 @@ using namespace clc;
 
 namespace {
 
-// one refinement staged and enqueued on the context's stream, its record going to pinned memory; returns the `ready` word to poll
+// one refinement staged and enqueued on the context's stream, its record going to pinned memory (h_rec: to poll for `ready`)
 int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, const double* h_K, const double* h_Rt_in, double huber_a,
-                   int32_t** ready, double** h_rec)
+                   RefineOut** h_rec)
 {
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t in_d = (size_t)5 * N + 16 + 12;
-    const size_t out_d = (pnp_refine_out_bytes() + 7) / 8;
+    const size_t out_d = (sizeof(RefineOut) + 7) / 8;
     int rc = ensure_pnp(ctx, in_d + out_d + 8);
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (in_d + out_d) * sizeof(double) + 64);
@@ -37,9 +37,8 @@ int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     memset(hp + (size_t)5 * N, 0, sizeof(double) * 16);
     memcpy(hp + (size_t)5 * N, h_K, sizeof(double) * 9);
     memcpy(hp + (size_t)5 * N + 16, h_Rt_in, sizeof(double) * 12);
-    *h_rec = hp + in_d;
-    *ready = (int32_t*)((uint8_t*)*h_rec + pnp_refine_ready_offset());
-    __atomic_store_n(*ready, 0, __ATOMIC_RELAXED);
+    *h_rec = (RefineOut*)(hp + in_d);
+    __atomic_store_n(&(*h_rec)->ready, 0, __ATOMIC_RELAXED);
     const double* src = hp;
     const size_t n_stage = (in_d + 1) & ~(size_t)1;
     CLC_HIP(ctx, launch_acr_stage(&src, &ctx->d_pnp, &n_stage, 1, ctx->stream));                 // inputs by a launch, not a copy command
@@ -113,7 +112,7 @@ int clc_inter_pose_batch(clc_ctx* const* ctxs, clc_inter_pose_job* jobs, int n_j
     std::vector<clc_two_view_job*> tv((size_t)n_jobs);
     for (int i = 0; i < n_jobs; ++i) tv[(size_t)i] = &jobs[i].tv;
     int worst = acr_two_view_batch(ctxs, tv.data(), n_jobs, 1);
-    struct Pending { int job; int32_t* ready; double* rec; };
+    struct Pending { int job; RefineOut* rec; };
     std::vector<Pending> pend;
     std::vector<InterFront> fr((size_t)n_jobs);
     std::vector<std::vector<double>> Xw((size_t)n_jobs);
@@ -147,8 +146,8 @@ int clc_inter_pose_batch(clc_ctx* const* ctxs, clc_inter_pose_job* jobs, int n_j
         }
         jb.stage = inter_scale_pose(jb, f, common, Xw[(size_t)i]);
         if (jb.stage != CLC_INTER_OK) continue;
-        Pending p{ i, nullptr, nullptr };
-        const int rc = refine_enqueue(ctxs[i], Xw[(size_t)i].data(), f.x2f.data(), jb.n_front, jb.tv.K2, jb.Rt, jb.huber_a, &p.ready, &p.rec);
+        Pending p{ i, nullptr };
+        const int rc = refine_enqueue(ctxs[i], Xw[(size_t)i].data(), f.x2f.data(), jb.n_front, jb.tv.K2, jb.Rt, jb.huber_a, &p.rec);
         if (rc != CLC_OK) { jb.tv.status = rc; jb.stage = CLC_INTER_NO_REFINEMENT; if (worst == CLC_OK) worst = rc; continue; }
         pend.push_back(p);
     }
@@ -157,10 +156,10 @@ int clc_inter_pose_batch(clc_ctx* const* ctxs, clc_inter_pose_job* jobs, int n_j
     for (const Pending& p : pend) {
         clc_inter_pose_job& jb = jobs[p.job];
         uint32_t spins = 0;
-        while (__atomic_load_n(p.ready, __ATOMIC_ACQUIRE) == 0) {
+        while (__atomic_load_n(&p.rec->ready, __ATOMIC_ACQUIRE) == 0) {
             if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
                 const hipError_t e = hipStreamSynchronize(ctxs[p.job]->stream);
-                if (e != hipSuccess || __atomic_load_n(p.ready, __ATOMIC_ACQUIRE) == 0) {
+                if (e != hipSuccess || __atomic_load_n(&p.rec->ready, __ATOMIC_ACQUIRE) == 0) {
                     jb.tv.status = fail(ctxs[p.job], CLC_ERR_HIP, "inter_pose_batch: refinement did not complete", e);
                     jb.stage = CLC_INTER_NO_REFINEMENT;
                     if (worst == CLC_OK) worst = jb.tv.status;
@@ -169,8 +168,7 @@ int clc_inter_pose_batch(clc_ctx* const* ctxs, clc_inter_pose_job* jobs, int n_j
             }
         }
         if (jb.stage != CLC_INTER_OK) continue;
-        struct { double Rt[12]; double cov[36]; double cost; double rmse; int32_t iterations; int32_t n_used; } f;
-        memcpy(&f, p.rec, sizeof f);
+        const RefineOut& f = *p.rec;
         memcpy(jb.Rt, f.Rt, sizeof f.Rt);
         memcpy(jb.cov, f.cov, sizeof f.cov);
         jb.rmse = f.rmse;

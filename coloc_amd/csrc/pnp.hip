@@ -112,13 +112,6 @@ __global__ __launch_bounds__(64) void p3p_kernel(const double* __restrict__ X, c
 // best hypothesis: most inliers, then lowest cost, then lowest index -- and its inlier mask, in ONE
 // launch: every workgroup recomputes the (cheap, deterministic) argmax over the <= 64k hypotheses, so no
 // inter-workgroup hand-off is needed; workgroup 0 also publishes {h, count, cost, pose}.
-struct PnpResult {      // one packed record so the host needs a single D2H copy
-    double Rt[12];
-    double cost;
-    int32_t h;
-    int32_t count;
-};
-
 __device__ __forceinline__ bool hyp_better(const int32_t* __restrict__ count, const double* __restrict__ cost, int b, int a)
 {
     return count[b] > count[a] || (count[b] == count[a] && (cost[b] < cost[a] || (cost[b] == cost[a] && b < a)));
@@ -182,17 +175,6 @@ __global__ __launch_bounds__(256) void pnp_select_mask_kernel(const double* __re
 // Levenberg-Marquardt on the same cost with the same parametrisation, one workgroup per pose,
 // every iteration = one pass over the points (residual + 2x6 Jacobian + 27 sums reduced through
 // wave shuffles and LDS) + a 6x6 Cholesky solve by lane 0.
-struct RefineOut {
-    double Rt[12];
-    double cov[36];
-    double cost;        // final 1/2 sum rho
-    double rmse;        // sqrt(final_cost / (2 n_used))  (Refiner.hpp:226)
-    int32_t iterations;
-    int32_t n_used;
-    int32_t ready;      // written LAST (system-scope release): a host that cleared it in a pinned record can poll it instead of
-    int32_t pad_;       // synchronising the stream
-};
-
 __device__ __forceinline__ void rodrigues(const double* w, double* R)
 {
     const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
@@ -545,8 +527,6 @@ hipError_t launch_pnp_refine(const double* d_Rt_in, const double* d_X, const dou
     prof_mark(prof, CLC_KERNEL_PNP_SCORE, false, stream);
     return hipGetLastError();
 }
-size_t pnp_refine_out_bytes() { return sizeof(RefineOut); }
-size_t pnp_refine_ready_offset() { return offsetof(RefineOut, ready); }
 
 hipError_t launch_pnp_ransac(const double* d_X, const double* d_x, int N, const double* d_K, const int32_t* d_samples,
                              int S, double thr2, double* d_Rt /* 48*S */, int32_t* d_count, double* d_cost,
@@ -577,9 +557,6 @@ hipError_t launch_pnp_ransac(const double* d_X, const double* d_x, int N, const 
     prof_mark(prof, CLC_KERNEL_PNP_SCORE, false, stream);
     return hipGetLastError();
 }
-
-size_t pnp_result_bytes() { return sizeof(PnpResult); }
-size_t pnp_result_valid_offset() { return offsetof(PnpResult, h); }
 
 // ---- two-view scoring: symmetric epipolar distance of H fundamental matrices ----------
 // The error model RobustMatcher::filterEssential gives AC-RANSAC (reference include/coloc/RobustMatcher.hpp:161-168,
@@ -633,14 +610,6 @@ __global__ __launch_bounds__(256) void epipolar_score_kernel(const double* __res
 // five-point problem (csrc/fivept.h, <= 10 real solutions) and writes 10 slots of {F = K2^-T E K1^-1 (9), E (9)};
 // unused slots are NaN so that they score worst.  The arrays of the solver live in scratch memory: this kernel is
 // latency-bound by design (256 lanes), the scoring that follows is the data-parallel part.
-struct EpiResult {      // one packed record so the host needs a single D2H copy
-    double E[9];
-    double F[9];
-    double cost;
-    int32_t h;
-    int32_t count;
-};
-
 __global__ __launch_bounds__(64) void fivept_kernel(const double* __restrict__ x1, const double* __restrict__ x2,
                                                     const double* __restrict__ K1, const double* __restrict__ K2,
                                                     const int32_t* __restrict__ samples, const int S, const int N,
@@ -726,7 +695,6 @@ hipError_t launch_essential_ransac(const double* d_x1, const double* d_x2, int N
     prof_mark(prof, CLC_KERNEL_PNP_SCORE, false, stream);
     return hipGetLastError();
 }
-size_t epi_result_bytes() { return sizeof(EpiResult); }
 
 hipError_t launch_epipolar(const double* d_F, int H, const double* d_x1, const double* d_x2, int N, double thr2, double* d_err,
                            int32_t* d_count, double* d_cost, hipStream_t stream, Profiler* prof)

@@ -56,12 +56,9 @@ size_t dbl(size_t bytes) { return (bytes + 7) / 8; }
 // the resection's one-launch rounds with the seven-point / four-point solve in place of P3P, the model is brought back to pixels in finish().
 // h_model: 12 doubles [R|t] (kind 0), {E (9), F (9)} (kind 1), F or H (9, pixels; kinds 2 / 3).
 //
-// One a-contrario solve as a small state machine (round 4): begin() stages the inputs and enqueues the first two rounds, poll() looks at the
-// pinned progress word ONCE -- if the round the host waits for has come out it enqueues the next one (rounds stay enqueued one ahead of
-// what the host knows) or moves on to the refinement, whose record it then polls the same way --, finish() copies the result out.  A
-// single solve spins on poll() exactly as the loop it replaces did; clc_pnp_localize_ac_batch drives SEVERAL solves, each on a context of
-// its own, from one thread: a solve is a chain of short launches with the host in the loop and leaves the GPU idle most of the time, so
-// the chains of independent cameras interleave (BASELINE config[2]: "batched PnP/RANSAC pose").
+// One a-contrario solve as a small state machine (round 4): begin() validates and prepares the inputs and the problem, poll() looks at the
+// pinned progress word ONCE and reports whether the run needs another round -- or moves on to the refinement, whose record it then polls
+// the same way --, finish() copies the result out.  What goes into the stream of the solve's rounds is acr_drive's.
 struct AcrRun {
     // arguments
     clc_ctx* ctx = nullptr;
@@ -79,22 +76,17 @@ struct AcrRun {
     bool refine = false;
     AcrProblem pb{};
     tv::Normalizer norm_t{};          // kinds 2, 3: the conditioning of both point sets
-    hipStream_t st = nullptr;
-    int launches = 0, bound = 0, reserve0 = 0;
+    hipStream_t st = nullptr;         // the stream of the solve's rounds (its group's: acr_drive)
+    int bound = 0, first_bound = 0, reserve0 = 0;
     uint32_t round = 0, spins = 0;
     std::chrono::steady_clock::time_point wait_start;
-    // lockstep batches (drive_group): the solve's rounds ride in launches shared with the other solves of the batch, on group_stream; the
-    // run only watches its word -- `reported` = the round waited for has come out, `more` = it needs another one (bound: its batch bound)
-    bool grouped = false, reported = false, more = false;
-    hipStream_t group_stream = nullptr, refine_st = nullptr;
-    int first_bound = 0;
+    bool reported = false;            // the round waited for has come out and the run needs another one (bound: its batch bound)
     const double* stage_src = nullptr; double* stage_dst = nullptr; size_t stage_n = 0;   // the inputs' way to the device (a launch, not a copy)
-    int batch_cap = kAcrMaxBatch;      // most iterations a round evaluates (CLC_ACR_BATCH_CAP; batches: see acr_batch_cap)
+    int batch_cap = kAcrMaxBatch;      // most iterations a round evaluates (acr_drive)
     unsigned long long* h_word = nullptr;
     AcrResult* h_res = nullptr;
     int32_t* p_inl = nullptr;
-    double* p_ref = nullptr;
-    int32_t* ready = nullptr;
+    RefineOut* p_ref = nullptr;
     double *d_a = nullptr, *d_b = nullptr, *d_K1 = nullptr, *d_K2 = nullptr, *d_models = nullptr, *d_ref = nullptr;
     AcrState* d_state = nullptr; AcrHyp* d_hyp = nullptr;
     uint32_t *d_sorted = nullptr, *d_best = nullptr, *d_index = nullptr;
@@ -105,19 +97,9 @@ struct AcrRun {
     int drained(const int code) { (void)hipStreamSynchronize(st); phase = DONE; status = code; return code; }
     int stop(const int code) { phase = DONE; status = code; return code; }
 
-    // the solve's next round as a chain of one (launch_acr_round: one launch, or two for the five-point kind); the word of round r
-    // comes out of round r + 1's first launch
-    int enqueue_round(const int bnd)
-    {
-        AcrChains one;
-        chain(one.c[0]);
-        CLC_HIP(ctx, launch_acr_round(one, 1, launches & 1, bnd, st));
-        ++launches;
-        return CLC_OK;
-    }
-
-    // validates, stages, enqueues the first two rounds.  Returns a status; phase == DONE afterwards means there is nothing to wait for.
-    int begin()
+    // validates, lays out the workspace and the pinned block, prepares the inputs; enqueues nothing.  cap: most iterations a round
+    // evaluates.  Returns a status; phase == DONE afterwards means there is nothing to wait for.
+    int begin(const int cap)
     {
         static const int k_m[4] = { 3, 5, 7, 4 }, k_M[4] = { 4, 10, 3, 1 }, k_md[4] = { 12, 18, 12, 12 };
         if (kind < 0 || kind > 3) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: unknown model"));
@@ -136,6 +118,7 @@ struct AcrRun {
         if (max_iteration > 500000) return stop(fail(ctx, CLC_ERR_CAPACITY, "acransac: more than 500000 iterations"));
         if (kind >= 1 && (img_w <= 0 || img_h <= 0)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: image size needed for the two-view models"));
         phase = DONE; status = CLC_ERR_HIP;                                     // (what an early CLC_HIP return leaves behind)
+        batch_cap = cap;
         const int rc0 = begin_body(ad);
         if (rc0 != CLC_OK) { phase = DONE; status = rc0; }
         return rc0;
@@ -151,16 +134,14 @@ struct AcrRun {
         const size_t in_d = (size_t)(ad + 2) * N + 32 + 2 * dbl(sizeof(float) * ((size_t)N + 1)) + state_d;
         // a round's launches read what the round before them wrote: two copies of state, models, slots and sorted lists, indexed by
         // launch parity (acransac.hip: acr_round_kernel, acr_solve5_kernel)
-        if (grouped) batch_cap = kind == 1 ? 12 : 8;                   // (a shared launch carries every chain's speculative slots: shorter rounds)
-        if (const char* e = getenv("CLC_ACR_BATCH_CAP")) { const int v = atoi(e); if (v >= 1 && v <= kAcrMaxBatch) batch_cap = v; }
         const int copies = 2;
         const int Ms = kind == 1 ? 10 : 4;                             // slots per iteration between the parity copies (the kernels' stride)
         const size_t models_d = (size_t)copies * kAcrMaxBatch * Ms * md;
-        const size_t hyp_d = dbl(acr_hyp_bytes() * copies * kAcrMaxBatch * Ms);
+        const size_t hyp_d = dbl(sizeof(AcrHyp) * copies * kAcrMaxBatch * Ms);
         const size_t sorted_d = dbl(sizeof(uint32_t) * (size_t)copies * kAcrMaxBatch * Ms * N);
         const size_t idx_d = dbl(sizeof(uint32_t) * (size_t)N);
         const size_t res_d = dbl(sizeof(AcrResult)), mask_d = dbl((size_t)N);
-        const size_t ref_d = refine ? dbl(pnp_refine_out_bytes()) : 0;
+        const size_t ref_d = refine ? dbl(sizeof(RefineOut)) : 0;
         int rc = ensure_pnp(ctx, in_d + models_d + hyp_d + sorted_d + 2 * idx_d + res_d + mask_d + ref_d + 16);
         if (rc != CLC_OK) return rc;
         // pinned: [ inputs | state mirror | sequence word | result | mask | inlier list | refine record ]
@@ -220,7 +201,7 @@ struct AcrRun {
         h_word = (unsigned long long*)(hp + in_d + state_d);
         h_res = (AcrResult*)(hp + in_d + state_d + 1);
         p_inl = (int32_t*)(hp + in_d + state_d + 1 + res_d + mask_d);
-        p_ref = hp + in_d + state_d + 1 + res_d + mask_d + inl_d;
+        p_ref = (RefineOut*)(hp + in_d + state_d + 1 + res_d + mask_d + inl_d);
         __atomic_store_n(h_word, 0ull, __ATOMIC_RELAXED);
 
         pb = AcrProblem{};
@@ -250,36 +231,23 @@ struct AcrRun {
         pb.max_threshold = std::isinf(precision) ? INFINITY : precision * (pb.norm * pb.norm);
         pb.seed = seed;
 
-        st = grouped ? group_stream : ctx->stream;
         stage_src = hp; stage_dst = ctx->d_pnp; stage_n = (in_d + 1) & ~(size_t)1;      // (both blocks are sized past in_d + 1)
-        if (!grouped) CLC_HIP(ctx, launch_acr_stage(&stage_src, &stage_dst, &stage_n, 1, st));   // (grouped: one launch for the batch, drive_group)
-        if (!grouped) prof_mark(&ctx->prof, CLC_KERNEL_PNP_SCORE, true, st);
-        // Rounds are enqueued ONE AHEAD of what the host knows: the solve / nfa / select kernels take the round's batch from the
-        // device state (a round enqueued after the run has finished finds nothing to do), so the GPU goes from one round's
-        // select straight into the next round's solve while the host is still polling (a 10 us bubble per round otherwise).
-        launches = 0;
         // Upper bound of the batch a round can ask for, from what the host knows when it enqueues it (one or two rounds behind the
         // device): while the index set has not switched the batch doubles up to kAcrMaxBatch; afterwards it is what is left of the
         // reserve, remaining = n_iter - iter (+ a margin for the "no inliers: n_iter++" rule, once per round).
         reserve0 = h_init->reserve;
         bound = h_init->n_iter < batch_cap ? h_init->n_iter : batch_cap;
         first_bound = h_init->cur_batch;                               // (a replaying launch takes its first batch as it stands)
-        if (!grouped) {
-            int rc2 = enqueue_round(first_bound);
-            if (rc2 != CLC_OK) return drained(rc2);
-            rc2 = enqueue_round(bound);                                 // speculative: the round after the one being waited for
-            if (rc2 != CLC_OK) return drained(rc2);
-        }                                                               // (grouped: drive_group enqueues the shared launches)
         round = 1;
         spins = 0;
-        reported = false; more = false;
+        reported = false;
         wait_start = std::chrono::steady_clock::now();
         phase = ROUNDS;
         status = CLC_OK;
         return CLC_OK;
     }
 
-    // this solve's part of a shared launch
+    // this solve's part of a round's launch
     void chain(AcrChain& c) const
     {
         c.pb = pb;
@@ -287,15 +255,16 @@ struct AcrRun {
         c.h_word = h_word;
         c.fin = AcrFinish{ d_mask, d_res, nullptr, p_inl, h_res };
     }
-    // the shared launch of the next round is in the stream: wait for that round's word
+    // the next round is in the stream: wait for that round's word
     void advance()
     {
-        ++round; spins = 0; reported = false; more = false;
+        ++round; spins = 0; reported = false;
         wait_start = std::chrono::steady_clock::now();
     }
 
-    // One look at the progress word / the refinement's ready flag.  Returns the status; phase == DONE when the solve has ended.
-    int poll()
+    // One look at the progress word / the refinement's ready flag; enqueues no round.  prof: where the end of the rounds is marked (null:
+    // nowhere).  Returns the status; phase == DONE when the solve has ended.
+    int poll(Profiler* prof)
     {
         if (phase == ROUNDS) {
             // the select kernel publishes one packed word (round number, iterations consumed, iter, n_iter) in pinned memory: poll it
@@ -316,32 +285,24 @@ struct AcrRun {
                 const long left = (long)n_iter_k - iter_k + 4 + (switched ? 0 : reserve0);
                 bound = left > batch_cap ? batch_cap : (int)left;
                 if (round > 0x7000u) return drained(fail(ctx, CLC_ERR_STATE, "acransac: too many rounds"));
-                if (grouped) { reported = true; more = true; return CLC_OK; }      // (drive_group enqueues the batch's next launch)
-                const int rc = enqueue_round(bound);                   // speculative: the round after the one being waited for
-                if (rc != CLC_OK) return drained(rc);
-                ++round;
-                spins = 0;
-                wait_start = std::chrono::steady_clock::now();
+                reported = true;
                 return CLC_OK;
             }
             // done: the completing round has left the result in pinned memory
-            reported = true; more = false;
-            if (!grouped) prof_mark(&ctx->prof, CLC_KERNEL_PNP_SCORE, false, st);
+            prof_mark(prof, CLC_KERNEL_PNP_SCORE, false, st);
             // The result record, mask and inlier list were written by the round that completed the run BEFORE its word (system-scope
             // release / acquire): no finish launch, and without refinement no stream synchronisation either -- the round enqueued ahead is
             // still in the stream, evaluates nothing and touches no host memory; anything enqueued later on this stream is ordered behind it.
             if (!refine) { phase = DONE; return CLC_OK; }
-            // Behind the launch that completed the run, on the same stream (nothing is queued behind that launch any more: the word of
-            // the last round comes out of the last launch).  The refinement writes its record into pinned memory and sets `ready` last;
-            // the host polls that instead of synchronising the stream (~5 us), with the synchronisation as the fallback after 5 ms.
-            // (A grouped run refines on its OWN context's stream: the shared stream still carries the other solves' rounds.  What the
-            // refinement reads was written before the word the host has just seen -- system-scope release / acquire -- so the launch
-            // needs no ordering against the shared stream.)
-            ready = (int32_t*)((uint8_t*)p_ref + pnp_refine_ready_offset());
-            __atomic_store_n(ready, 0, __ATOMIC_RELAXED);
-            refine_st = grouped ? ctx->stream : st;
+            // On the run's own context's stream: behind the launch that completed the run when the rounds ran there (nothing is queued
+            // behind that launch any more: the word of the last round comes out of the last launch); a shared group's stream still carries
+            // the other solves' rounds, and what the refinement reads was written before the word the host has just seen -- system-scope
+            // release / acquire --, so the launch needs no ordering against it.  The refinement writes its record into pinned memory and
+            // sets `ready` last; the host polls that instead of synchronising the stream (~5 us), with the synchronisation as the fallback
+            // after 5 ms.
+            __atomic_store_n(&p_ref->ready, 0, __ATOMIC_RELAXED);
             const hipError_t e = launch_pnp_refine((const double*)d_res /* AcrResult.model = [R|t] */, d_a, d_b, d_mask, N, d_K1, refine_huber, 50,
-                                                   d_ref, refine_st, &ctx->prof, &d_res->valid, p_ref);
+                                                   d_ref, ctx->stream, &ctx->prof, &d_res->valid, p_ref);
             if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "launch_pnp_refine", e));
             spins = 0;
             wait_start = std::chrono::steady_clock::now();
@@ -349,11 +310,11 @@ struct AcrRun {
             return CLC_OK;
         }
         if (phase == REFINE) {
-            if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == 0) {
+            if (__atomic_load_n(&p_ref->ready, __ATOMIC_ACQUIRE) == 0) {
                 if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - wait_start > std::chrono::milliseconds(5)) {
-                    const hipError_t e = hipStreamSynchronize(refine_st);
+                    const hipError_t e = hipStreamSynchronize(ctx->stream);
                     if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "hipStreamSynchronize(refine stream)", e));
-                    if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == 0) return drained(fail(ctx, CLC_ERR_HIP, "acransac: refinement did not complete"));
+                    if (__atomic_load_n(&p_ref->ready, __ATOMIC_ACQUIRE) == 0) return drained(fail(ctx, CLC_ERR_HIP, "acransac: refinement did not complete"));
                 } else return CLC_OK;
             }
             phase = DONE;
@@ -383,41 +344,136 @@ struct AcrRun {
         if (min_nfa) *min_nfa = r.min_nfa;
         if (iterations) *iterations = r.iterations;
         if (rounds) *rounds = r.rounds;
-        if (refine) {
-            struct { double Rt[12]; double cov[36]; double cost; double rmse; int32_t iterations; int32_t n_used; } f;
-            memcpy(&f, p_ref, sizeof f);
-            if (r.n_inliers > 0) {
-                if (h_model) memcpy(h_model, f.Rt, sizeof f.Rt);
-                if (h_cov) memcpy(h_cov, f.cov, sizeof f.cov);
-                if (rmse) *rmse = f.rmse;
-            }
+        if (refine && r.n_inliers > 0) {
+            if (h_model) memcpy(h_model, p_ref->Rt, sizeof p_ref->Rt);
+            if (h_cov) memcpy(h_cov, p_ref->cov, sizeof p_ref->cov);
+            if (rmse) *rmse = p_ref->rmse;
         }
     }
 };
 
-// All runs to their end from ONE host thread: whichever solve's round has come out gets its next one enqueued (a run is a chain of short
-// launches with the host in the loop, so several runs interleave on the device).  Round 5 measured two and three driving threads (the
-// runs dealt out, each thread on its runs' own contexts and streams): eight two-view filters 0.134 -> 0.136 ms per pair, eight poses
-// 0.049 -> 0.052 ms per pose -- the chains' own latency, not the host's launch calls, is what a batch waits for; one thread stays.
-void drive_runs(std::vector<AcrRun>& runs)
-{
-    size_t live = 0;
-    for (AcrRun& r : runs) if (r.phase != AcrRun::DONE) ++live;
-    while (live > 0)
-        for (AcrRun& r : runs) {
-            if (r.phase == AcrRun::DONE) continue;
-            (void)r.poll();
-            if (r.phase == AcrRun::DONE) --live;
-        }
-}
+// A group: runs that share one stream and one sequence of launches -- round r of every run of the group still in its rounds is ONE
+// launch (resection) or two (two-view) with blockIdx.y = run (launch_acr_round).  The group owns everything that goes into its stream:
+// the ordering behind the other contexts' streams, the staging, the rounds, and the ordering of the other contexts' streams behind it.
+struct AcrGroup {
+    bool shared = false;              // a lockstep batch (acr_lockstep): every run of the batch, on the first context's stream
+    bool running = false;
+    std::vector<AcrRun*> live;        // the runs that entered their rounds
+    hipStream_t st = nullptr;
+    int launches = 0;
 
-// Lockstep form of the same (round 5, the default of the batched entries): the batch's solves -- one kind, contexts on one device -- share
-// their launches.  Round r of every unfinished solve is ONE launch (resection) or two (two-view) with blockIdx.y = solve
-// (launch_acr_round), on the first context's stream, enqueued one ahead as for a single solve; the host waits for the round's
-// words of all unfinished solves and enqueues the next shared launch while any of them needs one.  A finished solve's part of the later
-// launches finds nothing to replay and returns.  Why: eight interleaved poses were ~80 launches from one thread (4-5 us each inside the
-// runtime, and the runtime serialises launching threads), eight two-view filters ~100; in lockstep they are ~10 and ~16.  Same bits per
-// solve: a chain's kernels take its batch from its own device state, the grid and the sort width (the largest chain's) only bound them.
+    // CLC_KERNEL_PNP_SCORE brackets the rounds of a run that has the stream to itself
+    Profiler* prof(AcrRun* r) const { return shared ? nullptr : &r->ctx->prof; }
+    void fail_all(const int code)
+    {
+        for (AcrRun* r : live) if (r->phase != AcrRun::DONE) (void)r->drained(code);
+        running = false;
+    }
+
+    // first: the context of the group's first run, whose stream the group runs on
+    void start(clc_ctx* first)
+    {
+        if (live.empty()) return;
+        st = first->stream;
+        running = true;
+        clc_ctx* ctx0 = live[0]->ctx;
+        // A solve's workspace (its context's d_pnp: inputs, both state copies, slots) may still be written by launches that an EARLIER solve
+        // left on that context's OWN stream -- a solve returns when its word says "done", the round enqueued ahead of it is still queued
+        // and its keeper carries the state forward.  This group's staging and rounds have to come behind those.
+        for (AcrRun* r : live) {
+            r->st = st;
+            clc_ctx* c = r->ctx;
+            if (c->stream == st) continue;
+            const bool ok = (c->ev_group || hipEventCreateWithFlags(&c->ev_group, hipEventDisableTiming) == hipSuccess) &&
+                            hipEventRecord(c->ev_group, c->stream) == hipSuccess && hipStreamWaitEvent(st, c->ev_group, 0) == hipSuccess;
+            if (!ok) (void)hipStreamSynchronize(c->stream);
+        }
+        // the inputs of all runs: one staging launch per kMaxBatch of them
+        for (size_t k = 0; k < live.size(); k += kMaxBatch) {
+            const int n = (int)std::min<size_t>(kMaxBatch, live.size() - k);
+            const double* src[kMaxBatch]; double* dst[kMaxBatch]; size_t cnt[kMaxBatch];
+            for (int i = 0; i < n; ++i) { src[i] = live[k + i]->stage_src; dst[i] = live[k + i]->stage_dst; cnt[i] = live[k + i]->stage_n; }
+            const hipError_t e = launch_acr_stage(src, dst, cnt, n, st);
+            if (e != hipSuccess) {
+                fail_all(fail(ctx0, CLC_ERR_HIP, shared ? "acransac: shared staging launch" : "launch_acr_stage(&stage_src, &stage_dst, &stage_n, 1, st)", e));
+                return;
+            }
+        }
+        for (AcrRun* r : live) prof_mark(prof(r), CLC_KERNEL_PNP_SCORE, true, st);
+        int b0 = 1, b1 = 1;
+        for (AcrRun* r : live) { b0 = std::max(b0, r->first_bound); b1 = std::max(b1, r->bound); }
+        if (enqueue(b0)) (void)enqueue(b1);                            // the second: speculative, the round after the one being waited for
+    }
+
+    // The next round of the runs that are still in their rounds (what the host knows when it enqueues: a run that finishes in the round
+    // being waited for rides along once more and finds nothing to replay), kMaxBatch per launch.  Rounds are enqueued ONE AHEAD of what the
+    // host knows: the solve / nfa / select kernels take the round's batch from the device state (a round enqueued after the run has
+    // finished finds nothing to do), so the GPU goes from one round's select straight into the next round's solve while the host is still
+    // polling (a 10 us bubble per round otherwise).  False: the group has failed.
+    bool enqueue(const int bound)
+    {
+        AcrChains pack;
+        int n = 0;
+        auto flush = [&]() -> bool {
+            if (n == 0) return true;
+            const hipError_t e = launch_acr_round(pack, n, launches & 1, bound, st);
+            n = 0;
+            if (e == hipSuccess) return true;
+            fail_all(fail(live[0]->ctx, CLC_ERR_HIP, shared ? "acransac: shared round launch" : "launch_acr_round(one, 1, launches & 1, bnd, st)", e));
+            return false;
+        };
+        for (AcrRun* r : live) {
+            if (r->phase != AcrRun::ROUNDS) continue;
+            r->chain(pack.c[n++]);
+            if (n == kMaxBatch && !flush()) return false;
+        }
+        if (!flush()) return false;
+        ++launches;
+        return true;
+    }
+
+    // One look at every run that is not waiting for the group's next launch (ROUNDS: its word; REFINE: its record); once every run still
+    // in its rounds has reported, the next launch (refinements of finished runs may still be out on their own streams; they do not hold
+    // the rounds up).
+    void step()
+    {
+        bool any_live = false, rounds_waiting = false, any_more = false;
+        int bnd = 1;
+        for (AcrRun* r : live) {
+            if (r->phase == AcrRun::DONE) continue;
+            any_live = true;
+            if (!(r->phase == AcrRun::ROUNDS && r->reported)) (void)r->poll(prof(r));
+            if (r->phase != AcrRun::ROUNDS) continue;
+            if (!r->reported) rounds_waiting = true;
+            else { any_more = true; bnd = std::max(bnd, r->bound); }
+        }
+        if (!any_live) end();
+        else if (any_more && !rounds_waiting && enqueue(bnd))
+            for (AcrRun* r : live) if (r->phase == AcrRun::ROUNDS) r->advance();
+    }
+
+    // The launch enqueued ahead of the last round is still in the group's stream (it finds nothing to replay, but its keepers carry every
+    // chain's state forward inside that chain's workspace): whatever the other contexts enqueue next on THEIR streams -- the staging of
+    // their next solve, a refinement -- has to come behind it.
+    void end()
+    {
+        running = false;
+        if (std::all_of(live.begin(), live.end(), [&](const AcrRun* r) { return r->ctx->stream == st; })) return;
+        clc_ctx* ctx0 = live[0]->ctx;
+        bool ordered = false;
+        if (ctx0->ev_group || hipEventCreateWithFlags(&ctx0->ev_group, hipEventDisableTiming) == hipSuccess) {
+            ordered = hipEventRecord(ctx0->ev_group, st) == hipSuccess;
+            for (AcrRun* r : live)
+                if (ordered && r->ctx->stream != st) ordered = hipStreamWaitEvent(r->ctx->stream, ctx0->ev_group, 0) == hipSuccess;
+        }
+        if (!ordered) (void)hipStreamSynchronize(st);
+    }
+};
+
+// The batch's solves -- one kind, contexts on one device -- share their launches (lockstep, round 5) or run chains of their own.  Why:
+// eight interleaved poses were ~80 launches from one thread (4-5 us each inside the runtime, and the runtime serialises launching threads),
+// eight two-view filters ~100; in lockstep they are ~10 and ~16.  Same bits per solve: a chain's kernels take its batch from its own device
+// state, the grid and the sort width (the largest chain's) only bound them.
 // Measured (MI355X, N = 1 000, 30 % outliers, tools/time_two_view.py; interleaved -> lockstep, one staging launch
 // for the batch, a round's launches carrying only the solves still in their rounds):
 //     two-view filters   2: 0.417 -> 0.439 ms   4: 0.570 -> 0.574   8: 1.08-1.21 -> 0.75-0.80      (rounds of <= 12 / 16 iterations)
@@ -435,88 +491,32 @@ bool acr_lockstep(const int kind, const int n_jobs)
     if (mode == 1) return true;
     return kind == 1 ? n_jobs >= 4 : n_jobs >= 8;      // (kinds 2, 3 run the resection's one-launch rounds: its break-even)
 }
-void drive_group(std::vector<AcrRun>& runs)
+
+// Every run to its end from ONE host thread.  shared: the runs are ONE group on the first run's context's stream (a lockstep batch);
+// otherwise every run is a group of its own on its context's stream (a single solve, an interleaved batch), started -- staged, its first
+// two rounds enqueued -- as soon as it is begun, so that the host prepares the next run's inputs while the device runs this one's rounds.
+// A run is a chain of short launches with the host in the loop and leaves the GPU idle most of the time, so the groups' chains interleave
+// on the device (BASELINE config[2]: "batched PnP/RANSAC pose").  Round 5 measured two and three driving threads (the runs dealt out,
+// each thread on its runs' own contexts and streams): eight two-view filters 0.134 -> 0.136 ms per pair, eight poses 0.049 -> 0.052 ms per
+// pose -- the chains' own latency, not the host's launch calls, is what a batch waits for; one thread stays.
+void acr_drive(AcrRun* runs, const int n, const bool shared)
 {
-    std::vector<AcrRun*> live;
-    for (AcrRun& r : runs) if (r.phase == AcrRun::ROUNDS && r.grouped) live.push_back(&r);
-    if (live.empty()) { drive_runs(runs); return; }
-    hipStream_t st = live[0]->group_stream;
-    clc_ctx* ctx0 = live[0]->ctx;
-    int launches = 0;
-    auto fail_all = [&](const int code) { for (AcrRun* r : live) if (r->phase != AcrRun::DONE) (void)r->drained(code); };
-    if (hipSetDevice(ctx0->device) != hipSuccess) { fail_all(fail(ctx0, CLC_ERR_HIP, "hipSetDevice")); return; }
-    // A solve's workspace (its context's d_pnp: inputs, both state copies, slots) may still be written by launches that an EARLIER solve
-    // left on that context's OWN stream -- a single or interleaved solve returns when its word says "done", the round enqueued ahead of
-    // it is still queued and its keeper carries the state forward.  The shared stream's staging and rounds have to come behind those.
-    for (AcrRun* r : live) {
-        clc_ctx* c = r->ctx;
-        if (c->stream == st) continue;
-        const bool ok = (c->ev_group || hipEventCreateWithFlags(&c->ev_group, hipEventDisableTiming) == hipSuccess) &&
-                        hipEventRecord(c->ev_group, c->stream) == hipSuccess && hipStreamWaitEvent(st, c->ev_group, 0) == hipSuccess;
-        if (!ok) (void)hipStreamSynchronize(c->stream);
+    std::vector<AcrGroup> groups(shared ? 1 : (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        AcrRun& r = runs[i];
+        AcrGroup& g = groups[shared ? 0 : (size_t)i];
+        g.shared = shared;
+        int cap = shared ? (r.kind == 1 ? 12 : 8) : kAcrMaxBatch;      // (a shared launch carries every chain's speculative slots: shorter rounds)
+        if (const char* e = getenv("CLC_ACR_BATCH_CAP")) { const int v = atoi(e); if (v >= 1 && v <= kAcrMaxBatch) cap = v; }
+        (void)r.begin(cap);
+        if (r.phase == AcrRun::ROUNDS) g.live.push_back(&r);
+        if (!shared) g.start(r.ctx);
+        else if (i == n - 1) g.start(runs[0].ctx);
     }
-    // the inputs of all solves: one staging launch per kMaxBatch of them
-    for (size_t k = 0; k < live.size(); k += kMaxBatch) {
-        const int n = (int)std::min<size_t>(kMaxBatch, live.size() - k);
-        const double* src[kMaxBatch]; double* dst[kMaxBatch]; size_t cnt[kMaxBatch];
-        for (int i = 0; i < n; ++i) { src[i] = live[k + i]->stage_src; dst[i] = live[k + i]->stage_dst; cnt[i] = live[k + i]->stage_n; }
-        const hipError_t e = launch_acr_stage(src, dst, cnt, n, st);
-        if (e != hipSuccess) { fail_all(fail(ctx0, CLC_ERR_HIP, "acransac: shared staging launch", e)); return; }
+    for (bool any = true; any;) {
+        any = false;
+        for (AcrGroup& g : groups) if (g.running) { g.step(); any = true; }
     }
-    // a round's launches carry the solves that are still in their rounds (what the host knows when it enqueues: a solve that finishes in
-    // the round being waited for rides along once more and finds nothing to replay), kMaxBatch per launch
-    auto enqueue = [&](const int bound) -> bool {
-        AcrChains pack;
-        int n = 0;
-        auto flush = [&]() -> bool {
-            if (n == 0) return true;
-            const hipError_t e = launch_acr_round(pack, n, launches & 1, bound, st);
-            n = 0;
-            if (e != hipSuccess) { fail_all(fail(ctx0, CLC_ERR_HIP, "acransac: shared round launch", e)); return false; }
-            return true;
-        };
-        for (AcrRun* r : live) {
-            if (r->phase != AcrRun::ROUNDS) continue;
-            r->chain(pack.c[n++]);
-            if (n == kMaxBatch && !flush()) return false;
-        }
-        if (!flush()) return false;
-        ++launches;
-        return true;
-    };
-    int b0 = 1, b1 = 1;
-    for (AcrRun* r : live) { b0 = std::max(b0, r->first_bound); b1 = std::max(b1, r->bound); }
-    if (!enqueue(b0) || !enqueue(b1)) return;                        // the second: speculative, the round after the one being waited for
-    for (;;) {
-        bool any_live = false, rounds_waiting = false, any_more = false;
-        int bnd = 1;
-        for (AcrRun* r : live) {
-            if (r->phase == AcrRun::DONE) continue;
-            any_live = true;
-            if (!(r->phase == AcrRun::ROUNDS && r->reported)) (void)r->poll();   // ROUNDS: one look at the word; REFINE: one look at the record
-            if (r->phase != AcrRun::ROUNDS) continue;
-            if (!r->reported) rounds_waiting = true;                  // (in its rounds and reported = it needs another round)
-            else { any_more = true; bnd = std::max(bnd, r->bound); }
-        }
-        if (!any_live) break;
-        if (any_more && !rounds_waiting) {
-            // every solve still in its rounds has reported the round waited for: the next shared launch (refinements of finished solves
-            // may still be out on their own streams; they do not hold the rounds up)
-            if (!enqueue(bnd)) return;
-            for (AcrRun* r : live) if (r->phase == AcrRun::ROUNDS) r->advance();
-        }
-    }
-    // The launch enqueued ahead of the last round is still in the shared stream (it finds nothing to replay, but its keepers carry every
-    // chain's state forward inside that chain's workspace): whatever the other contexts enqueue next on THEIR streams -- the staging of
-    // their next solve, a refinement -- has to come behind it.  (Work on the shared stream is ordered by the stream.)
-    bool ordered = false;
-    if (ctx0->ev_group || hipEventCreateWithFlags(&ctx0->ev_group, hipEventDisableTiming) == hipSuccess) {
-        ordered = hipEventRecord(ctx0->ev_group, st) == hipSuccess;
-        for (AcrRun* r : live)
-            if (ordered && r->ctx->stream != st) ordered = hipStreamWaitEvent(r->ctx->stream, ctx0->ev_group, 0) == hipSuccess;
-    }
-    if (!ordered) (void)hipStreamSynchronize(st);
-    // (runs of the batch that were not part of the group -- early outs -- are DONE already)
 }
 
 int acr_impl(clc_ctx* ctx, int kind, const double* h_a, const double* h_b, int N, const double* h_K1, const double* h_K2, int img_w,
@@ -529,12 +529,7 @@ int acr_impl(clc_ctx* ctx, int kind, const double* h_a, const double* h_b, int N
     run.max_iteration = max_iteration; run.seed = seed; run.precision = precision; run.refine_huber = refine_huber;
     run.h_model = h_model; run.h_mask = h_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
     run.min_nfa = min_nfa; run.iterations = iterations; run.rounds = rounds; run.h_cov = h_cov; run.rmse = rmse;
-    int rc = run.begin();
-    if (rc != CLC_OK) return rc;
-    while (run.phase != AcrRun::DONE) {
-        rc = run.poll();
-        if (rc != CLC_OK) return rc;
-    }
+    acr_drive(&run, 1, false);
     run.finish();
     return run.status;
 }
@@ -570,12 +565,9 @@ int clc_pnp_localize_ac_batch(clc_ctx* const* ctxs, clc_pose_job* jobs, int n_jo
     const int rc0 = check_batch_contexts(ctxs, n_jobs, "pnp_localize_ac_batch: every job needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
     std::vector<AcrRun> runs((size_t)n_jobs);
-    int worst = CLC_OK, live = 0;
-    const bool lockstep = acr_lockstep(0, n_jobs);
     for (int i = 0; i < n_jobs; ++i) {
         clc_pose_job& jb = jobs[i];
         AcrRun& r = runs[(size_t)i];
-        r.grouped = lockstep; r.group_stream = ctxs[0]->stream;
         if (jb.Rt) memset(jb.Rt, 0, sizeof(double) * 12);
         if (jb.cov) memset(jb.cov, 0, sizeof(double) * 36);
         jb.n_inliers = 0; jb.error_max = 0.0; jb.rmse = 0.0; jb.iterations = 0;
@@ -584,11 +576,9 @@ int clc_pnp_localize_ac_batch(clc_ctx* const* ctxs, clc_pose_job* jobs, int n_jo
         r.refine_huber = jb.refine ? (jb.huber_a > 0.0 ? jb.huber_a : 16.0) : -1.0;
         r.h_model = jb.Rt; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers; r.error_max = &jb.error_max;
         r.iterations = &jb.iterations; r.h_cov = jb.cov; r.rmse = &jb.rmse;
-        jb.status = r.begin();                        // stages this job's inputs (and, on its own, puts its first two rounds into its context's stream)
-        if (r.phase != AcrRun::DONE) ++live;
     }
-    (void)live;
-    if (lockstep) drive_group(runs); else drive_runs(runs);
+    acr_drive(runs.data(), n_jobs, acr_lockstep(0, n_jobs));
+    int worst = CLC_OK;
     for (int i = 0; i < n_jobs; ++i) {
         AcrRun& r = runs[(size_t)i];
         r.finish();
@@ -663,9 +653,8 @@ int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const doub
 
 namespace {
 
-void two_view_begin(AcrRun& r, clc_ctx* ctx, clc_two_view_job& jb, double* EF, const bool lockstep, hipStream_t group_stream, const int kind)
+void two_view_run(AcrRun& r, clc_ctx* ctx, clc_two_view_job& jb, double* EF, const int kind)
 {
-    r.grouped = lockstep; r.group_stream = group_stream;
     if (jb.E) memset(jb.E, 0, sizeof(double) * 9);
     if (jb.F) memset(jb.F, 0, sizeof(double) * 9);
     jb.n_inliers = 0; jb.iterations = 0; jb.error_max = 0.0; jb.min_nfa = INFINITY;
@@ -673,7 +662,6 @@ void two_view_begin(AcrRun& r, clc_ctx* ctx, clc_two_view_job& jb, double* EF, c
     r.max_iteration = jb.max_iteration; r.seed = jb.seed; r.precision = jb.precision; r.refine_huber = -1.0;
     r.h_model = EF; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers; r.error_max = &jb.error_max;
     r.min_nfa = &jb.min_nfa; r.iterations = &jb.iterations;
-    jb.status = r.begin();
 }
 
 
@@ -699,9 +687,8 @@ int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int 
 {
     std::vector<AcrRun> runs((size_t)n_jobs);
     std::vector<double> EF((size_t)18 * n_jobs, 0.0);
-    const bool lockstep = acr_lockstep(kind, n_jobs);
-    for (int i = 0; i < n_jobs; ++i) two_view_begin(runs[(size_t)i], ctxs[i], *jobs[i], &EF[(size_t)18 * i], lockstep, ctxs[0]->stream, kind);
-    if (lockstep) drive_group(runs); else drive_runs(runs);
+    for (int i = 0; i < n_jobs; ++i) two_view_run(runs[(size_t)i], ctxs[i], *jobs[i], &EF[(size_t)18 * i], kind);
+    acr_drive(runs.data(), n_jobs, acr_lockstep(kind, n_jobs));
     int worst = CLC_OK;
     for (int i = 0; i < n_jobs; ++i) {
         AcrRun& r = runs[(size_t)i];
