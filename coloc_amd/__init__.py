@@ -7,7 +7,9 @@ orchestration (torch.distributed is plumbing only).  There is NO CPU fallback: l
 loudly when the HIP library is missing.
 """
 from .abi import (CLCError, Context, DetectorOptions, MatcherOptions, KP_DTYPE, lib_path, load_library,  # noqa: F401
-                  keypoints_to_features, cov_intersection, ratio_matches_to_pairs, MultiCam, mc_plan)
+                  keypoints_to_features, cov_intersection, ratio_matches_to_pairs, MultiCam, mc_plan,
+                  SELECT_FIRST, SELECT_STRONGEST)
 
 __all__ = ["CLCError", "Context", "DetectorOptions", "MatcherOptions", "KP_DTYPE", "lib_path",
-           "load_library", "keypoints_to_features", "cov_intersection", "ratio_matches_to_pairs", "MultiCam", "mc_plan"]
+           "load_library", "keypoints_to_features", "cov_intersection", "ratio_matches_to_pairs", "MultiCam", "mc_plan",
+           "SELECT_FIRST", "SELECT_STRONGEST"]

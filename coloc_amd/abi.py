@@ -87,8 +87,10 @@ EXPORTS = [
     "clc_mc_gather_enqueue_dev", "clc_mc_match_enqueue_dev", "clc_mc_counts", "clc_mc_set_overlap", "clc_mc_comm_info", "clc_match_jobs_counted_dev",
     "clc_two_view_acransac", "clc_two_view_acransac_batch", "clc_two_view_minimal",
     "clc_match_ratio_2nn", "clc_match_ratio_2nn_dev", "clc_match_ratio_pairs", "clc_match_map_ratio", "clc_match_map_ratio_dev",
-    "clc_ratio_matches_to_pairs",
+    "clc_ratio_matches_to_pairs", "clc_detect_set_selection", "clc_detect_selection",
 ]
+# clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
+SELECT_FIRST, SELECT_STRONGEST = 0, 1
 KERNELS = ["pyramid_kernel", "clatch_kernel", "k2nn_sweep_kernel", "k2nn_merge_kernel", "pnp_residual_kernel",
            "pnp_score_kernel", "detect_kernels"]
 
@@ -184,6 +186,8 @@ def load_library():
     lib.clc_pnp_score.argtypes = [vp, vp, ci, vp, vp, ci, vp, C.c_double, vp, vp]
     lib.clc_detect.argtypes = [vp, vp, ci, C.POINTER(ci), C.POINTER(ci)]
     lib.clc_detect_dev.argtypes = [vp, vp]
+    lib.clc_detect_set_selection.argtypes = [vp, ci]
+    lib.clc_detect_selection.argtypes = [vp]
     lib.clc_detect_buffers.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.clc_describe_detected_dev.argtypes = [vp, vp, vp]
     lib.clc_detect_and_describe.argtypes = [vp, vp, u32, u32, vp, vp, ci, C.POINTER(ci), C.POINTER(ci)]
@@ -607,6 +611,15 @@ class Context:
         n, found = C.c_int(), C.c_int()
         self._chk(self.lib.clc_detect(self.h, _p(kps), cap, C.byref(n), C.byref(found)))
         return kps[:n.value], found.value
+
+    def set_keypoint_selection(self, mode):
+        """clc_detect_set_selection: SELECT_FIRST (default: the first maxkp keypoints in level-major order) or SELECT_STRONGEST (the
+        maxkp highest corner scores, ties by that order, output still in that order) for every later detect call of this context."""
+        self._chk(self.lib.clc_detect_set_selection(self.h, int(mode)))
+
+    @property
+    def keypoint_selection(self):
+        return self.lib.clc_detect_selection(self.h)
 
     def detect_dev(self, stream=None):
         self._chk(self.lib.clc_detect_dev(self.h, stream))

@@ -291,6 +291,11 @@ int clc_ctx_create(int device_id, const clc_detector_opts* dopts, const clc_matc
         ctx->n_tiles = detect_total_tiles(ctx->pd);
         CREATE_HIP(hipMalloc((void**)&ctx->d_kpmask, (size_t)ctx->n_tiles * 16 * sizeof(uint64_t)));
         CREATE_HIP(hipMalloc((void**)&ctx->d_tcount, (size_t)ctx->n_tiles * sizeof(uint32_t)));
+        {   // the selection workspace is small (a few KB per camera): sized for a full batch here, so that no detect call ever allocates
+            const size_t sel_bytes = (size_t)CLC_MAX_BATCH * detect_select_words(ctx->pd) * sizeof(uint32_t);
+            CREATE_HIP(hipMalloc((void**)&ctx->d_select, sel_bytes));
+            CREATE_HIP(hipMemsetAsync(ctx->d_select, 0, sel_bytes, ctx->stream));
+        }
         CREATE_HIP(hipMalloc((void**)&ctx->d_count, 4 * sizeof(uint32_t)));
         CREATE_HIP(hipMemsetAsync(ctx->d_count, 0, 4 * sizeof(uint32_t), ctx->stream));
     }
@@ -326,7 +331,7 @@ int clc_ctx_destroy(clc_ctx* ctx)
     if (!ctx) return CLC_ERR_BAD_ARG;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    void* bufs[] = { ctx->d_arena, ctx->d_kps, ctx->d_desc, ctx->d_score, ctx->d_kpmask, ctx->d_tcount, ctx->d_count, ctx->d_q, ctx->d_t, ctx->d_m, ctx->d_match,
+    void* bufs[] = { ctx->d_arena, ctx->d_kps, ctx->d_desc, ctx->d_score, ctx->d_kpmask, ctx->d_tcount, ctx->d_select, ctx->d_count, ctx->d_q, ctx->d_t, ctx->d_m, ctx->d_match,
                      ctx->d_best, ctx->d_second, ctx->d_partial, ctx->d_pnp, ctx->d_pairs };
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -448,6 +453,18 @@ int clc_pyramid_download(clc_ctx* ctx, int level, uint8_t* h_out)
 /* ---- detect -------------------------------------------------------------------------------- */
 
 static uint32_t* count_ptr(clc_ctx* ctx) { return ctx->d_count; }
+static uint32_t* select_ptr(clc_ctx* ctx) { return ctx->selection == CLC_SELECT_STRONGEST ? ctx->d_select : nullptr; }
+
+int clc_detect_set_selection(clc_ctx* ctx, int mode)
+{
+    if (!ctx) return CLC_ERR_BAD_ARG;
+    if (mode != CLC_SELECT_FIRST && mode != CLC_SELECT_STRONGEST) return fail(ctx, CLC_ERR_BAD_ARG, "detect_set_selection: unknown mode");
+    if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "detect_set_selection: context created without detector options");
+    ctx->selection = mode;
+    return CLC_OK;
+}
+
+int clc_detect_selection(const clc_ctx* ctx) { return ctx ? ctx->selection : -1; }
 
 int clc_detect_dev(clc_ctx* ctx, void* stream)
 {
@@ -460,7 +477,7 @@ int clc_detect_dev(clc_ctx* ctx, void* stream)
     clc_keypoint* kps[1] = { ctx->d_kps };
     uint32_t* cnt[1] = { ctx->d_count };
     CLC_HIP(ctx, launch_detect(ctx->pd, ctx->d_arena, ctx->arena_bytes, 1, ctx->d_score, ctx->d_kpmask, ctx->d_tcount, ctx->dopts.thresh,
-                               ctx->dopts.maxkp, kps, cnt, pick(ctx, stream), &ctx->prof));
+                               ctx->dopts.maxkp, kps, cnt, pick(ctx, stream), &ctx->prof, select_ptr(ctx), &ctx->select_dirty));
     ctx->detected = true;
     return CLC_OK;
 }
@@ -499,7 +516,7 @@ int clc_detect_batch_dev(clc_ctx* ctx, int n_images, const void* const* d_imgs, 
     ctx->pyramid_valid = true;
     ctx->detected = false;               // the context's own keypoint list is not the one this call fills
     CLC_HIP(ctx, launch_detect(ctx->pd, ctx->d_arena, ctx->arena_bytes, n_images, ctx->d_score, ctx->d_kpmask, ctx->d_tcount,
-                               ctx->dopts.thresh, ctx->dopts.maxkp, d_kps, d_counts, st, &ctx->prof));
+                               ctx->dopts.thresh, ctx->dopts.maxkp, d_kps, d_counts, st, &ctx->prof, select_ptr(ctx), &ctx->select_dirty));
     if (d_desc)
         CLC_HIP(ctx, launch_clatch_counted_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, batch, cnts, n_images, st, &ctx->prof));
     return CLC_OK;

@@ -75,6 +75,9 @@ struct clc_ctx {
     uint32_t* d_tcount = nullptr;    // [slot][tile] keypoints of a tile
     uint32_t* d_count = nullptr;     // {written, found} of the context's own keypoint list
     uint32_t n_tiles = 0;
+    int selection = CLC_SELECT_FIRST;   // which keypoints a frame with more than maxkp keeps (clc_detect_set_selection)
+    uint32_t* d_select = nullptr;    // [CLC_MAX_BATCH][detect_select_words] score histograms, cutoffs, band counts of CLC_SELECT_STRONGEST
+    bool select_dirty = false;       // a selecting detect call failed between its launches: the histograms may not be zero
     bool detected = false;
     // match
     uint8_t* d_q = nullptr;

@@ -50,12 +50,16 @@ hipError_t launch_clatch_batch(const PyramidDesc& pd, const uint8_t* arena, size
                                int n_img, hipStream_t stream, Profiler* prof = nullptr);
 
 // ---- detector (FAST-9 + NMS + orientation) ---------------------------------------------------
-// Two launches for the pyramids of n_img cameras (pyramid b at arena + b * slot_stride, score map b at score + b * slot_stride):
+// Two launches (three when selecting) for the pyramids of n_img cameras (pyramid b at arena + b * slot_stride, score map b at score + b * slot_stride):
 // d_mask: n_img x detect_total_tiles() x 16 keypoint-mask words, d_tcount: n_img x detect_total_tiles() tile counts (both rewritten
 // by every call: nothing to clear); d_count[b][0] = keypoints written to d_kps[b] (<= maxkp), d_count[b][1] = found.
+// d_select != nullptr: CLC_SELECT_STRONGEST, three launches.  d_select = kMaxBatch x detect_select_words() words, zero before the first
+// call (every complete call leaves the score histograms in it zeroed again); *select_dirty = a call did not get to enqueue all its
+// launches -- the next one clears the workspace first (a stream operation, no synchronisation).
 hipError_t launch_detect(const PyramidDesc& pd, const uint8_t* arena, size_t slot_stride, int n_img, uint8_t* score, uint64_t* d_mask,
                          uint32_t* d_tcount, uint32_t threshold, uint32_t maxkp, clc_keypoint* const* d_kps, uint32_t* const* d_count,
-                         hipStream_t stream, Profiler* prof = nullptr);
+                         hipStream_t stream, Profiler* prof = nullptr, uint32_t* d_select = nullptr, bool* select_dirty = nullptr);
+uint32_t detect_select_words(const PyramidDesc& pd);
 uint32_t detect_total_tiles(const PyramidDesc& pd);
 // CLATCH with the keypoint count read from device memory (no host round trip after detect)
 hipError_t launch_clatch_counted(const PyramidDesc& pd, const uint8_t* arena, const clc_keypoint* d_kps,

@@ -39,6 +39,14 @@
 //   (Round 5 built the two as ONE launch -- the last tile of a band to arrive emits the band, prefix from per-band arrival words --
 //   and measured it at 24.6 us per frame against 13.3 for the two launches: every step of publish -> arrive -> poll crosses the XCDs
 //   at 1.5-7 us under the load of 1 000 workgroups doing the same; profiles/r05_detect_notes.txt, r05_detect_fused_emit.patch.)
+//
+// Keypoint selection (clc_detect_set_selection): which keypoints a frame with more than maxkp keeps.  CLC_SELECT_FIRST -- the two launches
+// above, the first maxkp in (level, y, x) order.  CLC_SELECT_STRONGEST -- the maxkp highest scores, ties in that order, in THREE launches and
+// no host synchronisation: A<true> also adds its keypoints' scores to a 256-bin histogram per camera (LDS first, one device-scope add per
+// non-empty bin); detect_count_kernel (one workgroup per band) derives the cutoff score and the number of ties kept from the histogram
+// and counts its band's keypoints above / at the cutoff; B<true> sums those pairs in front of its band, ranks its keypoints by two ballots
+// per 256 and writes the selected ones at their rank.  The default path instantiates <false>: no histogram, no third launch.
+// profiles/detect_selection_notes.txt: 21.8 us per 640 x 480 frame against 13.3.
 #include "clc_internal.h"
 
 namespace clc {
@@ -61,7 +69,12 @@ struct DetectArgs {
     uint32_t slot_stride;                     // bytes between the pyramids / score maps of consecutive cameras
     clc_keypoint* kps[kMaxBatch];
     uint32_t* count[kMaxBatch];               // {written, found}
+    uint32_t* sel;                            // CLC_SELECT_STRONGEST: per camera [ 256 score bins | cutoff, ties, -, - | {above, tied} per band ]
+    uint32_t sel_stride;                      // words between the selection workspaces of consecutive cameras
 };
+
+// selection workspace of one camera (words)
+static constexpr uint32_t kSelCut = 256u, kSelBands = 260u;
 
 __device__ __forceinline__ int level_of(const uint32_t* begin, int levels, uint32_t idx)
 {
@@ -120,14 +133,52 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lan
 
 static constexpr uint32_t kEmitList = 2048u;              // keypoints listed per pass (a 640-wide band holds ~35)
 
+// keypoints lie in [3, w - 4] x [3, h - 4] (KFAST.h:431,455): the clamp is the identity on them -- it only keeps a mask that did
+// not come from detect_tile_kernel from reading outside the level.  e = an s_list entry: column | row inside the band << 12.
+__device__ __forceinline__ int kp_x(const LevelDesc& L, uint32_t e) { return min(max((int)(e & 0xFFFu), 3), (int)L.w - 4); }
+__device__ __forceinline__ int kp_y(const LevelDesc& L, uint32_t ty, uint32_t e) { return min(max((int)(ty * (uint32_t)kTileH + (e >> 12)), 3), (int)L.h - 4); }
+
+// one keypoint, orientation included (FeatureAngle.h:179-246: rows of 3,5,7,7,7,5,3 pixels)
+__device__ __forceinline__ void write_keypoint(const LevelDesc& L, int lv, uint32_t ty, uint32_t e, const uint8_t* __restrict__ img,
+                                               const uint8_t* __restrict__ score, clc_keypoint* __restrict__ out)
+{
+    const int x = kp_x(L, e), y = kp_y(L, ty, e);
+    int xs = 0, ys = 0;
+#pragma unroll
+    for (int rr = -3; rr <= 3; ++rr) {
+        const int hw = (rr == -3 || rr == 3) ? 1 : ((rr == -2 || rr == 2) ? 2 : 3);
+        const uint8_t* q8 = img + (size_t)(y + rr) * L.pitch + x;
+#pragma unroll
+        for (int cc = -3; cc <= 3; ++cc) {
+            if (cc < -hw || cc > hw) continue;
+            const int v = q8[cc];
+            xs += cc * v;
+            ys += rr * v;
+        }
+    }
+    clc_keypoint kp;
+    kp.x = x; kp.y = y;
+    kp.score = score[(size_t)y * L.pitch + x];
+    kp.angle = fast_atan2((float)(int16_t)ys, (float)(int16_t)xs);
+    kp.scale = (uint8_t)lv;
+    *out = kp;
+}
+
 // The keypoints of one 16-row band, in (y, x) order, to their final slots carry, carry + 1, ..: scan of the band's mask words (row-major over
-// the band's tiles), orientation per keypoint (FeatureAngle.h:179-246: rows of 3,5,7,7,7,5,3 pixels).  All 256 threads of a workgroup.
+// the band's tiles), orientation per keypoint.  All 256 threads of a workgroup.
 // first_word: the caller's early load of this thread's first mask word (its latency then overlaps whatever the caller did in between).
+// kSel (CLC_SELECT_STRONGEST): a keypoint is written only if its score lies above `cutoff`, or equals it and fewer than `ties` such
+// keypoints stand in front of it; its slot is its rank among the written ones.  above / tied = the keypoints of either kind in front of
+// the band (detect_count_kernel).  The list is then taken 256 keypoints at a time by ALL threads: the ranks come from two ballots per
+// wave and the waves' counts in s_sel (two sets: one barrier per step).
+template <bool kSel>
 __device__ __forceinline__ uint32_t emit_band(const DetectArgs& a, const LevelDesc& L, int lv, uint32_t ty, uint32_t ntx, uint32_t carry,
                                           const uint64_t* __restrict__ mask /* of the band's first tile */, uint64_t first_word,
                                           const uint8_t* __restrict__ img, const uint8_t* __restrict__ score, clc_keypoint* __restrict__ kps,
-                                          uint32_t* s_part, uint16_t* s_list)
+                                          uint32_t* s_part, uint16_t* s_list, uint32_t cutoff = 0u, uint32_t ties = 0u, uint32_t above = 0u,
+                                          uint32_t tied = 0u, uint32_t* s_sel = nullptr)
 {
+    [[maybe_unused]] uint32_t step = 0;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nwords = (uint32_t)kTileH * ntx;
     for (uint32_t w0 = 0; w0 < nwords; w0 += 256u) {
@@ -155,32 +206,32 @@ __device__ __forceinline__ uint32_t emit_band(const DetectArgs& a, const LevelDe
             }
             __syncthreads();
             const uint32_t n_here = min(total - base, kEmitList);
-            for (uint32_t q = tid; q < n_here; q += 256u) {
-                const uint32_t slot = carry + base + q;
-                if (slot >= a.maxkp) break;
-                const uint32_t e = s_list[q];
-                // keypoints lie in [3, w - 4] x [3, h - 4] (KFAST.h:431,455): the clamp is the identity on them -- it only keeps a mask that did
-                // not come from detect_tile_kernel from reading outside the level
-                const int x = min(max((int)(e & 0xFFFu), 3), (int)L.w - 4), y = min(max((int)(ty * kTileH + (e >> 12)), 3), (int)L.h - 4);
-                int xs = 0, ys = 0;
-#pragma unroll
-                for (int rr = -3; rr <= 3; ++rr) {
-                    const int hw = (rr == -3 || rr == 3) ? 1 : ((rr == -2 || rr == 2) ? 2 : 3);
-                    const uint8_t* q8 = img + (size_t)(y + rr) * L.pitch + x;
-#pragma unroll
-                    for (int cc = -3; cc <= 3; ++cc) {
-                        if (cc < -hw || cc > hw) continue;
-                        const int v = q8[cc];
-                        xs += cc * v;
-                        ys += rr * v;
-                    }
+            if constexpr (!kSel) {
+                for (uint32_t q = tid; q < n_here; q += 256u) {
+                    const uint32_t slot = carry + base + q;
+                    if (slot >= a.maxkp) break;
+                    write_keypoint(L, lv, ty, s_list[q], img, score, kps + slot);
                 }
-                clc_keypoint kp;
-                kp.x = x; kp.y = y;
-                kp.score = score[(size_t)y * L.pitch + x];
-                kp.angle = fast_atan2((float)(int16_t)ys, (float)(int16_t)xs);
-                kp.scale = (uint8_t)lv;
-                kps[slot] = kp;
+            } else {
+                for (uint32_t q0 = 0; q0 < n_here; q0 += 256u, ++step) {
+                    const uint32_t q = q0 + tid;
+                    const bool live = q < n_here;
+                    const uint32_t e = live ? s_list[q] : 0u;
+                    const uint32_t sc = live ? score[(size_t)kp_y(L, ty, e) * L.pitch + kp_x(L, e)] : 0u;
+                    const bool is_above = live && sc > cutoff, is_tied = live && sc == cutoff;
+                    const uint64_t b_above = __ballot(is_above), b_tied = __ballot(is_tied);
+                    uint32_t* part = s_sel + 8u * (step & 1u);
+                    if (lane == 0u) { part[wave] = (uint32_t)__popcll(b_above); part[4u + wave] = (uint32_t)__popcll(b_tied); }
+                    __syncthreads();
+                    const uint64_t below = (1ull << lane) - 1ull;
+                    uint32_t n_above = above + (uint32_t)__popcll(b_above & below), n_tied = tied + (uint32_t)__popcll(b_tied & below);
+                    for (uint32_t w = 0; w < wave; ++w) { n_above += part[w]; n_tied += part[4u + w]; }
+                    above += part[0] + part[1] + part[2] + part[3];
+                    tied += part[4] + part[5] + part[6] + part[7];
+                    const uint32_t slot = n_above + min(n_tied, ties);
+                    // (slot < maxkp whenever the histogram is that of these masks; the test keeps any other state inside the buffer)
+                    if ((is_above || (is_tied && n_tied < ties)) && slot < a.maxkp) write_keypoint(L, lv, ty, e, img, score, kps + slot);
+                }
             }
             __syncthreads();
         }
@@ -189,6 +240,9 @@ __device__ __forceinline__ uint32_t emit_band(const DetectArgs& a, const LevelDe
     return carry;                                             // = the keypoints in front of the next band (the same in every thread)
 }
 
+// kSel: the scores of the tile's keypoints also go into the camera's 256-bin histogram (LDS first, then one device-scope add per
+// non-empty bin); the bins are zero when the launch starts (launch_detect) and detect_emit_kernel<true> zeroes them again.
+template <bool kSel>
 __global__ __launch_bounds__(256) void detect_tile_kernel(const DetectArgs a, const uint8_t* __restrict__ arena_base,
                                                           uint8_t* __restrict__ score_base, uint64_t* __restrict__ mask_base,
                                                           uint32_t* __restrict__ tcount_base)
@@ -202,6 +256,7 @@ __global__ __launch_bounds__(256) void detect_tile_kernel(const DetectArgs a, co
     __shared__ uint32_t s_mask[kTileH][2];
     __shared__ uint32_t s_drop[kScRows];
     __shared__ uint32_t s_nkp;
+    __shared__ uint32_t s_hist[kSel ? 256 : 1];
 
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t cam = blockIdx.y;
@@ -239,6 +294,7 @@ __global__ __launch_bounds__(256) void detect_tile_kernel(const DetectArgs a, co
     for (uint32_t i = tid; i < (uint32_t)(kScRows * kScStride / 4); i += 256u) reinterpret_cast<uint32_t*>(s_sc)[i] = 0u;
     if (tid < (uint32_t)kTileH * 2u) s_mask[tid >> 1][tid & 1u] = 0u;
     if (tid == 0) s_nkp = 0u;
+    if constexpr (kSel) s_hist[tid] = 0u;
 
     // ---- KFAST.h:245 replay: does the walk of row gy land on cols - 35?  (levels of width 6 mod 16, tiles at the right end)
     // The answer (s_drop) is only needed when the scores go into the suppression: rows of at most 256 columns -- every level of a 640-wide
@@ -431,6 +487,7 @@ __global__ __launch_bounds__(256) void detect_tile_kernel(const DetectArgs a, co
                     const int xl = 4 * d + k;                                   // column inside the tile
                     atomicOr(&s_mask[r - 1][xl >> 5], 1u << (xl & 31));
                     atomicAdd(&s_nkp, 1u);
+                    if constexpr (kSel) atomicAdd(&s_hist[sc], 1u);
                     gscore[(size_t)(y0 + r - 1) * pitch + x0 + xl] = (uint8_t)sc;
                 }
             }
@@ -440,10 +497,73 @@ __global__ __launch_bounds__(256) void detect_tile_kernel(const DetectArgs a, co
     if (tid < (uint32_t)kTileH)
         mask_base[((size_t)cam * a.n_tiles + tile) * kTileH + tid] = (uint64_t)s_mask[tid][0] | ((uint64_t)s_mask[tid][1] << 32);
     if (tid == 0) tcount_base[(size_t)cam * a.n_tiles + tile] = s_nkp;
+    if constexpr (kSel) {
+        const uint32_t h = s_hist[tid];
+        if (h != 0u) atomicAdd(a.sel + (size_t)cam * a.sel_stride + tid, h);
+    }
+}
+
+// CLC_SELECT_STRONGEST, between the two launches: one workgroup per 16-row band.  Every workgroup turns the camera's histogram into the
+// cutoff -- the largest score c with #{score >= c} >= maxkp -- and the number of keypoints AT the cutoff that are kept (maxkp - #{score > c});
+// a camera that found no more than maxkp gets cutoff 0 (every score lies above it).  It then counts its band's keypoints above and at the
+// cutoff: their sums over the bands in front are the ranks detect_emit_kernel<true> starts from.
+__global__ __launch_bounds__(256) void detect_count_kernel(const DetectArgs a, const uint8_t* __restrict__ score_base,
+                                                           const uint64_t* __restrict__ mask_base)
+{
+    __shared__ uint32_t s_part[4];
+    __shared__ uint32_t s_cut[2];
+    __shared__ uint32_t s_cnt[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t cam = blockIdx.y, band = blockIdx.x;
+    uint32_t* __restrict__ sel = a.sel + (size_t)cam * a.sel_stride;
+    const int lv = level_of(a.band_begin, a.pd.levels, band);
+    const LevelDesc L = a.pd.lv[lv];
+    const uint32_t ty = band - a.band_begin[lv], ntx = a.tiles_x[lv];
+    const uint64_t* __restrict__ mask = mask_base + ((size_t)cam * a.n_tiles + a.tile_begin[lv] + ty * ntx) * kTileH;
+    const uint8_t* __restrict__ score = score_base + (size_t)cam * a.slot_stride + L.offset;
+
+    // thread t holds bin 255 - t: the inclusive scan over the threads is #{score >= 255 - t}
+    const uint32_t bin = 255u - tid;
+    const uint32_t h = sel[bin];
+    uint32_t ge = wave_inclusive_scan(h, lane);
+    if (lane == 63u) s_part[wave] = ge;
+    if (tid < 2u) s_cnt[tid] = 0u;
+    __syncthreads();
+    for (uint32_t w = 0; w < wave; ++w) ge += s_part[w];
+    const uint32_t found = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    // exactly one bin has #{score >= bin} >= maxkp > #{score > bin} when found > maxkp (maxkp >= 1: clc_ctx_create)
+    if (found <= a.maxkp) { if (tid == 0u) { s_cut[0] = 0u; s_cut[1] = 0u; } }
+    else if (ge >= a.maxkp && ge - h < a.maxkp) { s_cut[0] = bin; s_cut[1] = a.maxkp - (ge - h); }
+    __syncthreads();
+    const uint32_t cutoff = s_cut[0];
+
+    uint32_t n_above = 0, n_tied = 0;
+    const uint32_t nwords = (uint32_t)kTileH * ntx;
+    for (uint32_t i = tid; i < nwords; i += 256u) {
+        const uint32_t r = i / ntx, tx = i - r * ntx;
+        uint64_t m = mask[(size_t)tx * kTileH + r];
+        if (cutoff == 0u) { n_above += (uint32_t)__popcll(m); continue; }       // nothing is cut: no score is read
+        while (m != 0ull) {
+            const uint32_t e = (tx * kTileW + (uint32_t)__builtin_ctzll(m)) | (r << 12);
+            m &= m - 1ull;
+            const uint32_t sc = score[(size_t)kp_y(L, ty, e) * L.pitch + kp_x(L, e)];
+            n_above += sc > cutoff ? 1u : 0u;
+            n_tied += sc == cutoff ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { n_above += (uint32_t)__shfl_xor((int)n_above, o); n_tied += (uint32_t)__shfl_xor((int)n_tied, o); }
+    if (lane == 0u) { atomicAdd(&s_cnt[0], n_above); atomicAdd(&s_cnt[1], n_tied); }
+    __syncthreads();
+    if (tid < 2u) sel[kSelBands + 2u * band + tid] = s_cnt[tid];
+    if (band == 0u && tid < 2u) sel[kSelCut + tid] = s_cut[tid];
 }
 
 // One workgroup per 16-row band; the keypoints in front of the band = the sum of the tile counts in front of it (level-major order;
 // <= 13 KB -- no scan launch, no atomics, nothing to re-arm).
+// kSel: the band starts from the keypoints above / at the cutoff in front of it (detect_count_kernel) instead of all of them, and its
+// first workgroup of a camera leaves the histogram zeroed: nothing reads it behind detect_count_kernel.
+template <bool kSel>
 __global__ __launch_bounds__(256) void detect_emit_kernel(const DetectArgs a, const uint8_t* __restrict__ arena_base,
                                                           const uint8_t* __restrict__ score_base, const uint64_t* __restrict__ mask_base,
                                                           const uint32_t* __restrict__ tcount_base)
@@ -468,13 +588,39 @@ __global__ __launch_bounds__(256) void detect_emit_kernel(const DetectArgs a, co
     if (lane == 0) s_part[4 + wave] = s;
     __syncthreads();
     const uint32_t carry = s_part[4] + s_part[5] + s_part[6] + s_part[7];
-    const uint32_t end = emit_band(a, L, lv, ty, ntx, carry, mask, first_word, arena_base + (size_t)cam * a.slot_stride + L.offset,
-                                   score_base + (size_t)cam * a.slot_stride + L.offset, a.kps[cam], s_part, s_list);
+    uint32_t end;
+    if constexpr (!kSel) {
+        end = emit_band<false>(a, L, lv, ty, ntx, carry, mask, first_word, arena_base + (size_t)cam * a.slot_stride + L.offset,
+                               score_base + (size_t)cam * a.slot_stride + L.offset, a.kps[cam], s_part, s_list);
+    } else {
+        __shared__ uint32_t s_sel[16];
+        uint32_t* __restrict__ sel = a.sel + (size_t)cam * a.sel_stride;
+        uint32_t above = 0, tied = 0;
+        for (uint32_t i = tid; i < band; i += 256u) { above += sel[kSelBands + 2u * i]; tied += sel[kSelBands + 2u * i + 1u]; }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { above += (uint32_t)__shfl_xor((int)above, o); tied += (uint32_t)__shfl_xor((int)tied, o); }
+        if (lane == 0) { s_sel[wave] = above; s_sel[4 + wave] = tied; }
+        __syncthreads();
+        above = s_sel[0] + s_sel[1] + s_sel[2] + s_sel[3];
+        tied = s_sel[4] + s_sel[5] + s_sel[6] + s_sel[7];
+        const uint32_t cutoff = sel[kSelCut], ties = sel[kSelCut + 1];
+        __syncthreads();                                         // (s_sel is emit_band's from here)
+        if (band == 0u) sel[tid] = 0u;
+        end = emit_band<true>(a, L, lv, ty, ntx, carry, mask, first_word, arena_base + (size_t)cam * a.slot_stride + L.offset,
+                              score_base + (size_t)cam * a.slot_stride + L.offset, a.kps[cam], s_part, s_list, cutoff, ties, above, tied, s_sel);
+    }
     // the last band of the camera knows the total
     if (tid == 0 && band + 1 == a.n_bands) {
-        a.count[cam][0] = min(end, a.maxkp);   // keypoints written (level-major order, truncated at capacity)
+        a.count[cam][0] = min(end, a.maxkp);   // keypoints written (CLC_SELECT_FIRST: level-major order, truncated at capacity)
         a.count[cam][1] = end;                 // keypoints found
     }
+}
+
+uint32_t detect_select_words(const PyramidDesc& pd)
+{
+    uint32_t bands = 0;
+    for (int i = 0; i < pd.levels; ++i) bands += (pd.lv[i].h + kTileH - 1) / kTileH;
+    return kSelBands + 2u * bands;
 }
 
 uint32_t detect_total_tiles(const PyramidDesc& pd)
@@ -486,7 +632,7 @@ uint32_t detect_total_tiles(const PyramidDesc& pd)
 
 hipError_t launch_detect(const PyramidDesc& pd, const uint8_t* arena, size_t slot_stride, int n_img, uint8_t* score, uint64_t* d_mask,
                          uint32_t* d_tcount, uint32_t threshold, uint32_t maxkp, clc_keypoint* const* d_kps, uint32_t* const* d_count,
-                         hipStream_t stream, Profiler* prof)
+                         hipStream_t stream, Profiler* prof, uint32_t* d_select, bool* select_dirty)
 {
     if (n_img <= 0) return hipSuccess;
     if (n_img > kMaxBatch || slot_stride > 0xFFFFFFFFull) return hipErrorInvalidValue;
@@ -512,13 +658,34 @@ hipError_t launch_detect(const PyramidDesc& pd, const uint8_t* arena, size_t slo
     a.n_tiles = tiles;
     a.n_bands = bands;
     for (int b = 0; b < kMaxBatch; ++b) { a.kps[b] = b < n_img ? d_kps[b] : nullptr; a.count[b] = b < n_img ? d_count[b] : nullptr; }
+    a.sel = d_select;
+    a.sel_stride = detect_select_words(pd);
     if (tiles == 0) return hipSuccess;
+    if (!d_select) {
+        prof_mark(prof, CLC_KERNEL_DETECT, true, stream);
+        hipLaunchKernelGGL(detect_tile_kernel<false>, dim3(tiles, (uint32_t)n_img), dim3(256), 0, stream, a, arena, score, d_mask, d_tcount);
+        hipLaunchKernelGGL(detect_emit_kernel<false>, dim3(bands, (uint32_t)n_img), dim3(256), 0, stream, a, arena, (const uint8_t*)score,
+                           (const uint64_t*)d_mask, (const uint32_t*)d_tcount);
+        prof_mark(prof, CLC_KERNEL_DETECT, false, stream);
+        return hipGetLastError();
+    }
+    // CLC_SELECT_STRONGEST: three launches.  The histograms are zero between calls: the last launch leaves them so.  `select_dirty` is
+    // the host's record that a call did not get as far as enqueueing that launch; only then are they cleared here.
+    if (!select_dirty) return hipErrorInvalidValue;
+    if (*select_dirty) {
+        const hipError_t e = hipMemsetAsync(d_select, 0, (size_t)kMaxBatch * a.sel_stride * sizeof(uint32_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    *select_dirty = true;
     prof_mark(prof, CLC_KERNEL_DETECT, true, stream);
-    hipLaunchKernelGGL(detect_tile_kernel, dim3(tiles, (uint32_t)n_img), dim3(256), 0, stream, a, arena, score, d_mask, d_tcount);
-    hipLaunchKernelGGL(detect_emit_kernel, dim3(bands, (uint32_t)n_img), dim3(256), 0, stream, a, arena, (const uint8_t*)score,
+    hipLaunchKernelGGL(detect_tile_kernel<true>, dim3(tiles, (uint32_t)n_img), dim3(256), 0, stream, a, arena, score, d_mask, d_tcount);
+    hipLaunchKernelGGL(detect_count_kernel, dim3(bands, (uint32_t)n_img), dim3(256), 0, stream, a, (const uint8_t*)score, (const uint64_t*)d_mask);
+    hipLaunchKernelGGL(detect_emit_kernel<true>, dim3(bands, (uint32_t)n_img), dim3(256), 0, stream, a, arena, (const uint8_t*)score,
                        (const uint64_t*)d_mask, (const uint32_t*)d_tcount);
     prof_mark(prof, CLC_KERNEL_DETECT, false, stream);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) *select_dirty = false;
+    return e;
 }
 
 } // namespace clc

@@ -124,6 +124,15 @@ public:
     // same rows; the only reader in the reference is InterfaceROS::processImagePair (InterfaceROS.hpp:30,37), whose call does not match
     // GPUMatcher::setTrainingImage's signature.  mirrorRawOutputs(true) fills it as the reference does; `kps` is always filled.
     void mirrorRawOutputs(bool on) { mirrorDesc_ = on; }
+    // What a frame with more than opts.maxkp corners keeps.  The reference has no rule to copy: it writes past its maxkp-sized
+    // buffers (GPUDetector.hpp:135,281).  Off (the default): the first maxkp in level-major order, so an overflowing frame loses its
+    // coarse levels.  keepStrongest(true): the maxkp highest corner scores, ties by that order, still listed in that order
+    // (CLC_SELECT_STRONGEST, include/coloc_hip.h); one more detector launch, no synchronisation.  keypointsFound() is the uncapped
+    // count either way.
+    void keepStrongest(bool on)
+    {
+        if (ctx_) (void)clc_detect_set_selection(ctx_, on ? CLC_SELECT_STRONGEST : CLC_SELECT_FIRST);
+    }
     // the handle of the block published by the last detect call (host == nullptr: nothing was published)
     const clc_desc_handle& lastPublished() const { return published_; }
 

@@ -43,7 +43,8 @@ extern "C" {
  * clc_describe_match_pair_dev, clc_essential_acransac_batch, clc_inter_pose_batch, clc_k2nn_device_info) and round 6's changes
  * (clc_describe_match_pair_dev lost its `chunks` argument, CLC_K2NN_MATRIX_PLAIN is gone, the descriptor hand-over is by ownership:
  * clc_desc_cache_publish returns a handle).  4: the 'F' / 'H' models of the two-view filter (clc_two_view_acransac, _batch, clc_two_view_minimal);
- * the distance-ratio entries (clc_match_ratio_*, clc_match_map_ratio*, clc_ratio_matches_to_pairs) came later under 4: new entry points only.
+ * the distance-ratio entries (clc_match_ratio_*, clc_match_map_ratio*, clc_ratio_matches_to_pairs) came later under 4: new entry points only;
+ * so did the keypoint selection rule (clc_detect_set_selection, clc_detect_selection).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -170,8 +171,22 @@ int clc_pyramid_download(clc_ctx* ctx, int level, uint8_t* h_out);
  * (GPUDetector.hpp:262-277; KFAST.h:502-540; FeatureAngle.h:197-246) -- on the GPU, all levels.
  * Keypoints come out in the reference's order: level-major, then (y, x) ascending, with level-local
  * integer coordinates, corner score, orientation and level.  FAST threshold = opts.thresh.
- * At most DetectorOptions.maxkp keypoints are kept (the first ones in that order; the reference
- * overflows its buffers instead, GPUDetector.hpp:135,281); *n_found reports how many there were. */
+ * At most DetectorOptions.maxkp keypoints are kept; *n_found reports how many there were.  WHICH ones are kept when a frame has
+ * more is this library's choice, not the reference's: the reference writes past its maxkp-sized buffers instead
+ * (GPUDetector.hpp:135,281).  The context's selection rule (clc_detect_set_selection) decides:
+ *   CLC_SELECT_FIRST (the default): the first maxkp in that order -- a frame that overflows loses its coarse levels.
+ *   CLC_SELECT_STRONGEST: the maxkp with the highest corner scores, still in that order.  With c the largest score such that at
+ *     least maxkp keypoints score >= c, every keypoint scoring above c is kept, and of those scoring exactly c the first
+ *     maxkp - #{score > c} in that order; in numpy, D[sort(argsort(-score, kind="stable")[:maxkp])] of the uncapped list D.
+ *     The result does not depend on scheduling; a frame with no more than maxkp keypoints comes out as under CLC_SELECT_FIRST.
+ * Either way {written, found} = {min(found, maxkp), found}, and the fields of a kept keypoint are those it has in the uncapped list. */
+enum { CLC_SELECT_FIRST = 0, CLC_SELECT_STRONGEST = 1 };
+/* The rule of every later detect call of the context (clc_detect, clc_detect_dev, clc_detect_and_describe, clc_detect_and_describe_view,
+ * clc_detect_batch_dev -- there every camera gets its own cutoff).  CLC_SELECT_STRONGEST costs one more launch between the detector's two
+ * and no synchronisation.  CLC_ERR_BAD_ARG for an unknown mode or a NULL context, CLC_ERR_STATE for a context without detector options. */
+int clc_detect_set_selection(clc_ctx* ctx, int mode);
+/* The context's current rule; negative for a NULL context. */
+int clc_detect_selection(const clc_ctx* ctx);
 int clc_detect(clc_ctx* ctx, clc_keypoint* h_kps, int capacity, int* n_written, int* n_found);
 /* Device-resident: keypoints stay in the context (clc_detect_buffers), nothing is copied back. */
 int clc_detect_dev(clc_ctx* ctx, void* stream);
@@ -198,7 +213,8 @@ int clc_detect_and_describe_view(clc_ctx* ctx, const uint8_t* h_img, uint32_t wi
 int clc_detect_store_descriptors(clc_ctx* ctx, void* h_dst, int n, clc_desc_handle* handle /* nullable */);
 
 /* The device-resident front end for the frames of n_images <= CLC_MAX_BATCH cameras at once (GPUDetector::detectAndDescribe,
- * GPUDetector.hpp:216-291, once per drone in ColoC::processImages, coloc.hpp:150-163): ONE pyramid launch, TWO detector launches
+ * GPUDetector.hpp:216-291, once per drone in ColoC::processImages, coloc.hpp:150-163): ONE pyramid launch, TWO detector launches (three
+ * under CLC_SELECT_STRONGEST)
  * and -- when d_desc is not NULL -- ONE CLATCH launch for all of them, nothing synchronised, nothing copied back.  d_imgs[b]: u8
  * width x height device image (pitch bytes per row, the DetectorOptions size); d_kps[b]: room for DetectorOptions.maxkp keypoints;
  * d_counts[b]: uint32[2] on the device, {written, found}; d_desc[b]: maxkp x 64 B (rows past the count are left alone).  Same
