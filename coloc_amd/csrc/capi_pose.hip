@@ -129,6 +129,7 @@ static int pnp_ransac_impl(clc_ctx* ctx, const double* h_X, const double* h_x, i
                            double* rmse = nullptr)
 {
     if (!ctx || N < 0 || S < 0 || !h_K || (N > 0 && (!h_X || !h_x))) return fail(ctx, CLC_ERR_BAD_ARG, "pnp_ransac: bad argument");
+    if (!pose_K_ok(h_K)) return fail(ctx, CLC_ERR_BAD_ARG, "pnp_ransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }");
     if (n_inliers) *n_inliers = 0;
     if (N < 3 || S == 0) { if (h_mask && N > 0) memset(h_mask, 0, (size_t)N); return CLC_OK; }
     if (S > 16384) return fail(ctx, CLC_ERR_CAPACITY, "pnp_ransac: more than 16384 samples per call");
@@ -282,6 +283,7 @@ int clc_pnp_refine(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
 {
     if (!ctx || N < 0 || !h_K || !h_Rt_in || (N > 0 && (!h_X || !h_x))) return fail(ctx, CLC_ERR_BAD_ARG, "pnp_refine: bad argument");
     if (N < 3) return fail(ctx, CLC_ERR_BAD_ARG, "pnp_refine: needs at least 3 correspondences");
+    if (!pose_K_ok(h_K)) return fail(ctx, CLC_ERR_BAD_ARG, "pnp_refine: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }");
     if (!(huber_a > 0.0)) huber_a = 16.0;          // ceres::HuberLoss(Square(4.0)), Refiner.hpp:122
     if (max_iter <= 0) max_iter = 50;
     CLC_HIP(ctx, hipSetDevice(ctx->device));

@@ -127,6 +127,11 @@ namespace clc {
 // records the failure text on the context (clc_last_error_string) and returns `code`
 int fail(clc_ctx* ctx, int code, const char* what, hipError_t e = hipSuccess);
 
+// The pose entry points (P3P, a-contrario pose, refinement) read K as { fx, skew, cx; 0, fy, cy; 0, 0, 1 }: the minimal solver and the
+// refinement use K[0], K[1], K[2], K[4], K[5] only, while the residual kernels apply all nine entries.  A K that is anything else (a
+// scaled K, K[3] != 0) would give the two halves of one solve different cameras, so it is refused (include/coloc_hip.h, clc_pnp_refine).
+inline bool pose_K_ok(const double* K) { return K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0; }
+
 #define CLC_HIP(ctx, call)                                                      \
     do {                                                                        \
         hipError_t e__ = (call);                                                \

@@ -16,6 +16,7 @@
 // relative tolerance on `cost` in the tests.
 #include "clc_internal.h"
 #include "p3p.h"
+#include "so3.h"
 #include "fivept_wave.h"
 
 namespace clc {
@@ -175,135 +176,7 @@ __global__ __launch_bounds__(256) void pnp_select_mask_kernel(const double* __re
 // Levenberg-Marquardt on the same cost with the same parametrisation, one workgroup per pose,
 // every iteration = one pass over the points (residual + 2x6 Jacobian + 27 sums reduced through
 // wave shuffles and LDS) + a 6x6 Cholesky solve by lane 0.
-__device__ __forceinline__ void rodrigues(const double* w, double* R)
-{
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    if (th2 < 1e-24) {
-        R[0] = 1; R[1] = -w[2]; R[2] = w[1]; R[3] = w[2]; R[4] = 1; R[5] = -w[0]; R[6] = -w[1]; R[7] = w[0]; R[8] = 1;
-        return;
-    }
-    const double th = sqrt(th2), ith = 1.0 / th;
-    double s, c;
-    sincos(th, &s, &c);                 // one shared range reduction
-    const double k0 = w[0] * ith, k1 = w[1] * ith, k2 = w[2] * ith, v = 1.0 - c;
-    R[0] = c + k0 * k0 * v;      R[1] = k0 * k1 * v - k2 * s; R[2] = k0 * k2 * v + k1 * s;
-    R[3] = k1 * k0 * v + k2 * s; R[4] = c + k1 * k1 * v;      R[5] = k1 * k2 * v - k0 * s;
-    R[6] = k2 * k0 * v - k1 * s; R[7] = k2 * k1 * v + k0 * s; R[8] = c + k2 * k2 * v;
-}
-
-// angle-axis of a rotation matrix (row-major)
-__device__ __forceinline__ void log_so3(const double* R, double* w)
-{
-    const double tr = R[0] + R[4] + R[8];
-    double c = 0.5 * (tr - 1.0);
-    c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);
-    const double th = acos(c);
-    const double ax = R[7] - R[5], ay = R[2] - R[6], az = R[3] - R[1];
-    if (th < 1e-9) { w[0] = 0.5 * ax; w[1] = 0.5 * ay; w[2] = 0.5 * az; return; }
-    if (M_PI - th < 1e-6) {
-        // near pi: take the axis from the diagonal
-        const double xx = 0.5 * (R[0] + 1.0), yy = 0.5 * (R[4] + 1.0), zz = 0.5 * (R[8] + 1.0);
-        double x = sqrt(xx > 0 ? xx : 0), y = sqrt(yy > 0 ? yy : 0), z = sqrt(zz > 0 ? zz : 0);
-        if (ax < 0) x = -x; if (ay < 0) y = -y; if (az < 0) z = -z;
-        w[0] = th * x; w[1] = th * y; w[2] = th * z;
-        return;
-    }
-    const double f = th / (2.0 * sin(th));
-    w[0] = f * ax; w[1] = f * ay; w[2] = f * az;
-}
-
-// dR/dw_k (Gallego & Yezzi 2015): (w_k [w]x + [w x (I - R) e_k]x) R / |w|^2 ; generators at w -> 0
-__device__ __forceinline__ void d_rodrigues(const double* w, const double* R, double (*dR)[9])
-{
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    for (int k = 0; k < 3; ++k) {
-        double A[9];
-        if (th2 < 1e-16) {
-            for (int i = 0; i < 9; ++i) A[i] = 0.0;
-            if (k == 0) { A[5] = -1; A[7] = 1; } else if (k == 1) { A[2] = 1; A[6] = -1; } else { A[1] = -1; A[3] = 1; }
-            for (int i = 0; i < 9; ++i) dR[k][i] = A[i];
-            continue;
-        }
-        // u = w x ((I - R) e_k)
-        const double m0 = (k == 0 ? 1.0 : 0.0) - R[0 + k], m1 = (k == 1 ? 1.0 : 0.0) - R[3 + k], m2 = (k == 2 ? 1.0 : 0.0) - R[6 + k];
-        const double u0 = w[1] * m2 - w[2] * m1, u1 = w[2] * m0 - w[0] * m2, u2 = w[0] * m1 - w[1] * m0;
-        const double b0 = w[k] * w[0] + u0, b1 = w[k] * w[1] + u1, b2 = w[k] * w[2] + u2;   // w_k w + u
-        // A = [b]x / th2
-        A[0] = 0; A[1] = -b2; A[2] = b1; A[3] = b2; A[4] = 0; A[5] = -b0; A[6] = -b1; A[7] = b0; A[8] = 0;
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                dR[k][3 * i + j] = (A[3 * i] * R[j] + A[3 * i + 1] * R[3 + j] + A[3 * i + 2] * R[6 + j]) / th2;
-    }
-}
-
-// One entry of the same derivative: element e (0..8) of dR/dw_k, for 27 lanes working in parallel.
-__device__ __forceinline__ double d_rodrigues_entry(const double* w, const double* R, const int k, const int e)
-{
-    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
-    if (th2 < 1e-16) {
-        const int pos = k == 0 ? 7 : (k == 1 ? 2 : 3), neg = k == 0 ? 5 : (k == 1 ? 6 : 1);
-        return e == pos ? 1.0 : (e == neg ? -1.0 : 0.0);
-    }
-    const double m0 = (k == 0 ? 1.0 : 0.0) - R[0 + k], m1 = (k == 1 ? 1.0 : 0.0) - R[3 + k], m2 = (k == 2 ? 1.0 : 0.0) - R[6 + k];
-    const double u0 = w[1] * m2 - w[2] * m1, u1 = w[2] * m0 - w[0] * m2, u2 = w[0] * m1 - w[1] * m0;
-    const double b0 = w[k] * w[0] + u0, b1 = w[k] * w[1] + u1, b2 = w[k] * w[2] + u2;
-    const double A[9] = { 0, -b2, b1, b2, 0, -b0, -b1, b0, 0 };
-    const int i = e / 3, j = e - 3 * i;
-    return (A[3 * i] * R[j] + A[3 * i + 1] * R[3 + j] + A[3 * i + 2] * R[6 + j]) / th2;
-}
-
-// index of entry (i, j), j >= i, in the packed upper triangle the normal-equation sums are kept in (row-major: 00 01 .. 05 11 ..)
-__device__ __forceinline__ constexpr int packed6(const int i, const int j) { return i <= j ? i * 6 - i * (i - 1) / 2 + (j - i) : j * 6 - j * (j - 1) / 2 + (i - j); }
-
-// Cholesky solve of the damped 6x6 system (A + lambda diag(A)) d = g, A given as its PACKED upper triangle (21 values, read
-// where they lie -- LDS: a 6 x 6 register copy costs 72 VGPRs in the one lane that runs this); returns false if not SPD
-__device__ __forceinline__ bool solve6(const double* Ap, const double* g, double lambda, double* d)
-{
-    // fully unrolled (compile-time indices) so that L, y stay in registers instead of scratch
-    double L[36], Linv[6];    // Linv[i] = 1 / L[i][i]: six divisions instead of twenty-seven
-    bool spd = true;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            const double aij = Ap[packed6(i, j)];
-            double sum = aij + (i == j ? lambda * (aij > 1e-12 ? aij : 1e-12) : 0.0);
-#pragma unroll
-            for (int k = 0; k < j; ++k) sum -= L[6 * i + k] * L[6 * j + k];
-            if (i == j) { spd = spd && (sum > 0.0); L[6 * i + i] = sqrt(sum > 0.0 ? sum : 1.0); Linv[i] = 1.0 / L[6 * i + i]; }
-            else L[6 * i + j] = sum * Linv[j];
-        }
-    }
-    if (!spd) return false;
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double sum = g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) sum -= L[6 * i + k] * y[k];
-        y[i] = sum * Linv[i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double sum = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) sum -= L[6 * k + i] * d[k];
-        d[i] = sum * Linv[i];
-    }
-    return true;
-}
-
-// column c of A^-1 (A SPD, packed upper triangle): called by six lanes in parallel, one column each
-__device__ __forceinline__ bool invert6_column(const double* A, int c, double* inv)
-{
-    double e[6], col[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) e[r] = r == c ? 1.0 : 0.0;
-    if (!solve6(A, e, 0.0, col)) return false;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) inv[6 * r + c] = col[r];
-    return true;
-}
+// rodrigues / log_so3 / d_rodrigues_entry / solve6 / invert6_column: so3.h (host + device, so that the tests run them on the CPU too)
 
 static constexpr int kRefineSums = 29;   // 21 (upper JtWJ) + 6 (JtWr) + 1 (cost) + 1 (points used)
 static constexpr int kRefineThreads = 512;

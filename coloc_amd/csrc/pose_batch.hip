@@ -107,6 +107,7 @@ struct AcrRun {
         const int ad = kind == 0 ? 3 : 2;
         if (!ctx || N < 0 || max_iteration < 0 || (kind <= 1 && !h_K1) || (kind == 1 && !h_K2) || (N > 0 && (!h_a || !h_b)))
             return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: bad argument"));
+        if (kind == 0 && !pose_K_ok(h_K1)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }"));
         if (n_inliers) *n_inliers = 0;
         if (error_max) *error_max = 0.0;
         if (min_nfa) *min_nfa = INFINITY;

@@ -449,7 +449,9 @@ int clc_pnp_ransac(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
  * Outputs (all nullable): h_Rt_out 12 doubles, h_cov 36 doubles = (J^T W J)^-1 in the [angle-axis | t]
  * parametrisation (row-major), *rmse = sqrt(final_cost / (2 n_used)) (Refiner.hpp:226), *iterations.
  * huber_a <= 0 selects the reference's 16.  Ceres is absent here, so results are defined by this
- * cost, not by Ceres' iterates (unpinned). */
+ * cost, not by Ceres' iterates (unpinned).
+ * h_K, here and in clc_pnp_ransac / clc_pnp_localize / clc_pnp_p3p / clc_pnp_acransac / clc_pnp_localize_ac(_batch), must be
+ * { fx, skew, cx; 0, fy, cy; 0, 0, 1 } exactly: any other K (a scaled one, K[3] != 0) is CLC_ERR_BAD_ARG. */
 int clc_pnp_refine(clc_ctx* ctx, const double* h_X, const double* h_x, int N, const double* h_K,
                    const uint8_t* h_inlier_mask, const double* h_Rt_in, double huber_a, int max_iter,
                    double* h_Rt_out, double* h_cov, double* rmse, int* iterations);

@@ -90,13 +90,16 @@ def test_ransac_is_deterministic_and_matches_scored_hypotheses(gpu_ctx, oracle):
     assert m1.sum() == cnt[order[0]] and np.array_equal(m1, err[order[0]] < 9.0)
 
 
-def test_ransac_degenerate_inputs(gpu_ctx):
+def test_ransac_degenerate_inputs(gpu_ctx, oracle):
     sc = synth.pnp_scene(50, seed=1)
     Rt, mask, _ = gpu_ctx.pnp_ransac(sc["X"][:2], sc["x"][:2], sc["K"])
     assert Rt is None and not mask.any()
     X = np.zeros((10, 3)); X[:, 2] = 5.0                      # all points identical: no triad
-    Rt, mask, _ = gpu_ctx.pnp_ransac(X, np.full((10, 2), 100.0), sc["K"])
+    xd = np.full((10, 2), 100.0)
+    Rt, mask, _ = gpu_ctx.pnp_ransac(X, xd, sc["K"])
     assert Rt is None or np.isfinite(Rt).all()
+    if Rt is not None:                                        # a returned pose is the pose its inlier mask belongs to
+        assert mask.sum() == oracle.pnp_score(oracle.pnp_residuals(Rt, X, xd, sc["K"]), 16.0)[0][0]
 
 
 # ---- refinement: numpy restatement of the same cost as the test-side checker ----------
