@@ -49,6 +49,21 @@ class PoseJob(C.Structure):
                 ("n_inliers", C.c_int), ("iterations", C.c_int), ("status", C.c_int), ("error_max", C.c_double), ("rmse", C.c_double)]
 
 
+class CameraK3(C.Structure):
+    """clc_camera_k3 (include/coloc_hip.h): Pinhole_Intrinsic_Radial_K3"""
+    _fields_ = [("focal", C.c_double), ("ppx", C.c_double), ("ppy", C.c_double), ("k1", C.c_double), ("k2", C.c_double), ("k3", C.c_double)]
+
+
+class TrackJob(C.Structure):
+    """clc_track_job (include/coloc_hip.h)"""
+    _fields_ = [("d_match", C.c_void_p), ("nq", C.c_int), ("d_count", C.c_void_p), ("d_kps", C.c_void_p), ("d_feat", C.c_void_p),
+                ("feat_stride", C.c_int), ("cam", CameraK3), ("after_stream", C.c_void_p), ("max_iteration", C.c_int), ("seed", C.c_uint64),
+                ("precision", C.c_double), ("refine", C.c_int), ("huber_a", C.c_double),
+                ("Rt", C.c_void_p), ("cov", C.c_void_p), ("track_query", C.c_void_p), ("track_map", C.c_void_p), ("inliers", C.c_void_p),
+                ("inlier_mask", C.c_void_p), ("n_tracks", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int), ("status", C.c_int),
+                ("error_max", C.c_double), ("rmse", C.c_double)]
+
+
 ABI_VERSION = 4          # CLC_ABI_VERSION of include/coloc_hip.h
 DESC_CACHE_OFF, DESC_CACHE_VERIFY, DESC_CACHE_TRUST = 0, 1, 2
 
@@ -88,6 +103,7 @@ EXPORTS = [
     "clc_two_view_acransac", "clc_two_view_acransac_batch", "clc_two_view_minimal",
     "clc_match_ratio_2nn", "clc_match_ratio_2nn_dev", "clc_match_ratio_pairs", "clc_match_map_ratio", "clc_match_map_ratio_dev",
     "clc_ratio_matches_to_pairs", "clc_detect_set_selection", "clc_detect_selection",
+    "clc_set_map_points", "clc_track_build_dev", "clc_track_localize_dev", "clc_track_localize_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -233,6 +249,10 @@ def load_library():
     lib.clc_k2nn_queries_per_block.argtypes = [vp]
     lib.clc_k2nn_plan_query.argtypes = [vp, ci, ci, vp]
     lib.clc_k2nn_device_info.argtypes = [vp, vp, vp]
+    lib.clc_set_map_points.argtypes = [vp, vp, ci]
+    lib.clc_track_build_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.clc_track_localize_dev.argtypes = [vp, vp]
+    lib.clc_track_localize_batch_dev.argtypes = [vp, vp, ci]
     _lib = lib
     return lib
 
@@ -498,6 +518,47 @@ def pnp_localize_batch(ctxs, problems, max_iteration=256, seeds=None, precision=
                         mask=mask[:X.shape[0]].astype(bool), inliers=inl[:j.n_inliers].copy(), error_max=j.error_max, rmse=j.rmse,
                         iterations=j.iterations))
     return out
+
+
+def _track_fill(j, keep, d_match, nq, cam, d_kps=None, d_feat=None, feat_stride=4, d_count=None, after_stream=None, max_iteration=256,
+                seed=1, precision=float("inf"), refine=True, huber_a=16.0, outputs=True):
+    """fills a TrackJob; cam = (focal, ppx, ppy, k1, k2, k3); device pointers as integers"""
+    j.d_match, j.nq, j.d_count, j.d_kps, j.d_feat, j.feat_stride = d_match, int(nq), d_count, d_kps, d_feat, int(feat_stride)
+    j.cam = CameraK3(*[float(v) for v in cam])
+    j.after_stream = after_stream
+    j.max_iteration, j.seed, j.precision, j.refine, j.huber_a = int(max_iteration), int(seed), float(precision), (1 if refine else 0), float(huber_a)
+    if not outputs:
+        return None
+    n = max(int(nq), 1)
+    Rt, cov = np.zeros(12), np.zeros(36)
+    tq, tm, inl, mask = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+    keep.append((Rt, cov, tq, tm, inl, mask))
+    j.Rt, j.cov, j.track_query, j.track_map, j.inliers, j.inlier_mask = (a.ctypes.data for a in (Rt, cov, tq, tm, inl, mask))
+    return Rt, cov, tq, tm, inl, mask
+
+
+def _track_result(j, Rt, cov, tq, tm, inl, mask):
+    found = j.n_inliers > 0
+    nt = max(min(j.n_tracks, len(tq)), 0)
+    return dict(Rt=Rt.reshape(3, 4).copy() if found else None, cov=cov.reshape(6, 6).copy() if (found and j.refine) else None,
+                n_tracks=j.n_tracks, track_query=tq[:nt].copy(), track_map=tm[:nt].copy(), inliers=inl[:j.n_inliers].copy(),
+                mask=mask[:nt].astype(bool), error_max=j.error_max, rmse=j.rmse, iterations=j.iterations, status=j.status)
+
+
+def track_localize_batch_dev(ctxs, jobs):
+    """clc_track_localize_batch_dev: jobs = [dict(d_match=, nq=, cam=, d_kps= | d_feat=, ...), ...] (the keywords of
+    Context.track_localize_dev), job i on ctxs[i], the map points from ctxs[0].  Returns a list of result dicts."""
+    lib = load_library()
+    n = len(jobs)
+    assert len(ctxs) == n
+    arr = (TrackJob * n)()
+    keep = []
+    outs = [_track_fill(arr[i], keep, **jobs[i]) for i in range(n)]
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_track_localize_batch_dev(hs, arr, n)
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_track_localize_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    return [_track_result(arr[i], *outs[i]) for i in range(n)]
 
 
 def desc_handle_live(handle):
@@ -826,6 +887,28 @@ class Context:
     def set_map(self, desc):
         desc = np.ascontiguousarray(desc, dtype=np.uint8).reshape(-1, 64)
         self._chk(self.lib.clc_set_map(self.h, _p(desc), desc.shape[0]))
+
+    def set_map_points(self, X):
+        """clc_set_map_points: (n, 3) float64, row i = the landmark of map descriptor row i; an empty array clears"""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        self._chk(self.lib.clc_set_map_points(self.h, _p(X) if X.shape[0] else None, X.shape[0]))
+
+    def track_build_dev(self, d_X, d_x, d_query, d_map, d_n, stream=None, **job):
+        """clc_track_build_dev: the track kernel alone, enqueue only; job keywords as track_localize_dev (d_match, nq, cam, d_kps | d_feat,
+        feat_stride, d_count); outputs are device pointers with room for nq tracks"""
+        j = TrackJob()
+        _track_fill(j, None, outputs=False, **job)
+        self._chk(self.lib.clc_track_build_dev(self.h, C.byref(j), d_X, d_x, d_query, d_map, d_n, stream))
+
+    def track_localize_dev(self, **job):
+        """clc_track_localize_dev: setupTracks + localizeImage from device memory.  Keywords: d_match, nq, cam = (focal, ppx, ppy, k1, k2, k3),
+        d_kps or d_feat (+ feat_stride), d_count, after_stream, max_iteration, seed, precision, refine, huber_a.  Returns a dict: Rt, cov,
+        n_tracks, track_query, track_map, inliers (into the track list), mask, error_max, rmse, iterations."""
+        j = TrackJob()
+        keep = []
+        out = _track_fill(j, keep, **job)
+        self._chk(self.lib.clc_track_localize_dev(self.h, C.byref(j)))
+        return _track_result(j, *out)
 
     def match_map_dev(self, d_q, nq, threshold, d_match, stream=None):
         self._chk(self.lib.clc_match_map_dev(self.h, d_q, nq, int(threshold), d_match, stream))

@@ -1048,20 +1048,32 @@ hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int 
 // inputs of the solves: pinned host blocks -> device workspaces, by ONE launch (blockIdx.y = solve) instead of copy commands (a copy
 // command runs on another engine: 6.6 us + 8 us until the first round starts behind it, against ~3 + 3 us for a launch in the same
 // queue; eight staging launches on the shared stream of a lockstep batch were 75 us of its 400)
-struct AcrStageJobs { const double2* src[kMaxBatch]; double2* dst[kMaxBatch]; int n2[kMaxBatch]; };
+struct AcrStageJobs {
+    const double2* src[kMaxBatch]; double2* dst[kMaxBatch]; int n2[kMaxBatch];
+    const double* dev_a[kMaxBatch]; const double* dev_b[kMaxBatch]; int n_corr[kMaxBatch];     // (dev_a null: everything from src)
+};
 __global__ __launch_bounds__(256) void acr_stage_kernel(const AcrStageJobs jobs)
 {
     const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    if (i < jobs.n2[c]) jobs.dst[c][i] = jobs.src[c][i];
+    if (i >= jobs.n2[c]) return;
+    const double* da = jobs.dev_a[c];
+    if (!da) { jobs.dst[c][i] = jobs.src[c][i]; return; }
+    // a | b of a resection = the track kernel's X (3 n) | x (2 n) in device memory; 5 n may be odd, so this part goes double by double
+    const int na = 3 * jobs.n_corr[c], nab = 5 * jobs.n_corr[c];
+    const double* db = jobs.dev_b[c];
+    const double* src = (const double*)jobs.src[c];
+    double* dst = (double*)jobs.dst[c];
+    for (int e = 2 * i; e < 2 * i + 2; ++e) dst[e] = e < na ? da[e] : (e < nab ? db[e - na] : src[e]);
 }
 hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
-                            hipStream_t stream)
+                            hipStream_t stream, const double* const* d_a, const double* const* d_b, const int* n_corr)
 {
     if (n_chains < 1 || n_chains > kMaxBatch) return hipErrorInvalidValue;
     AcrStageJobs jobs{};
     int most = 0;
     for (int c = 0; c < n_chains; ++c) {
         jobs.src[c] = (const double2*)h_pinned[c]; jobs.dst[c] = (double2*)d_dst[c]; jobs.n2[c] = (int)(n_doubles[c] / 2);
+        if (d_a && d_b && n_corr && d_a[c] && d_b[c]) { jobs.dev_a[c] = d_a[c]; jobs.dev_b[c] = d_b[c]; jobs.n_corr[c] = n_corr[c]; }
         most = jobs.n2[c] > most ? jobs.n2[c] : most;
     }
     if (most <= 0) return hipSuccess;

@@ -107,6 +107,13 @@ struct clc_ctx {
     size_t pnp_cap = 0;   // doubles
     void* h_pin = nullptr;        // pinned staging for the pose solve
     size_t pin_cap = 0;
+    // 2D-3D tracks (track.hip)
+    double* d_map_X = nullptr;    // clc_set_map_points: the landmark of map descriptor row i, 3 doubles each
+    int map_X_n = -1, map_X_cap = 0;      // (-1: none set)
+    uint8_t* d_trk = nullptr;     // [ X 3 cap | x 2 cap | query cap | map cap | n ]: the tracks of this context's job (clc_track_localize*_dev)
+    uint8_t* h_trk = nullptr;     // pinned: [ count word (64 B) | query cap | map cap ]
+    size_t trk_cap = 0;           // tracks
+    hipEvent_t ev_track = nullptr;   // orders the track launch behind job.after_stream, and the contexts' streams behind the launch
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     uint8_t* h_stage = nullptr;

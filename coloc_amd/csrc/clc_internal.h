@@ -290,8 +290,32 @@ struct AcrChains { AcrChain c[kMaxBatch]; };
 // sort width cover the largest chain; chain.fin: where the round that completes a run leaves mask / inlier list / result record.
 hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream);
 // the inputs of n_chains solves, pinned host blocks -> device workspaces, in one launch
+// d_a / d_b / n_corr (all three or none; entries nullable): chain c's first 3 n_corr[c] + 2 n_corr[c] doubles -- the resection's a | b --
+// come from the DEVICE blocks d_a[c] (3 n) and d_b[c] (2 n) instead of the pinned block (the track kernel's output, track.hip); everything
+// behind them still comes from the pinned block
 hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
-                            hipStream_t stream);
+                            hipStream_t stream, const double* const* d_a = nullptr, const double* const* d_b = nullptr,
+                            const int* n_corr = nullptr);
+
+// ---- 2D-3D tracks (track.hip): Localizer::setupTracks on the device ---------------------------------------------------------------
+struct TrackJobDev {
+    const int32_t* match; const uint32_t* count; const clc_keypoint* kps; const float* feat;     // in (count nullable; kps or feat)
+    double* X; double* x; int32_t* query; int32_t* map; int32_t* n;                             // out, device (cap tracks; n nullable)
+    uint32_t* h_n; int32_t* h_query; int32_t* h_map;                                            // out, pinned host mirrors (nullable)
+    int nq, feat_stride, cap;
+    double focal, ppx, ppy, k1, k2, k3;
+};
+struct TrackJobs {
+    TrackJobDev j[kMaxBatch];
+    const double* map_X; int map_n;
+    float scale[CLC_MAX_LEVELS];      // (float) pow((double) 1.2f, level), from the host: clc_keypoints_to_features' values
+};
+// ONE launch for n_jobs <= kMaxBatch cameras (blockIdx.y = job); scale[] is filled in here
+hipError_t launch_track_build(TrackJobs& jobs, int n_jobs, hipStream_t stream);
+// validates a job's inputs against the context that holds the map points and fills the kernel's view of them (outputs are the caller's)
+int track_job_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, const char* who);
+// the context's own track block (device: X | x | query | map | n; pinned: word | query | map) for `cap` tracks
+int ensure_track(clc_ctx* ctx, size_t cap);
 // the seven-point / four-point models (kind 2: <= 3 per sample, kind 3: 1) of S samples of normalised correspondences: d_out S x M x 9, NaN = no model
 hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_x2, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
 

@@ -64,6 +64,7 @@ struct AcrRun {
     clc_ctx* ctx = nullptr;
     int kind = 0, N = 0, img_w = 0, img_h = 0, max_iteration = 0;
     const double *h_a = nullptr, *h_b = nullptr, *h_K1 = nullptr, *h_K2 = nullptr;
+    const double *dev_a = nullptr, *dev_b = nullptr;    // kind 0 from device memory (track.hip): a | b are staged from these blocks, h_a / h_b unused
     uint64_t seed = 0;
     double precision = 0.0, refine_huber = -1.0;
     double* h_model = nullptr; uint8_t* h_mask = nullptr; int32_t* h_inliers = nullptr;
@@ -105,7 +106,8 @@ struct AcrRun {
         if (kind < 0 || kind > 3) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: unknown model"));
         m = k_m[kind]; M = k_M[kind]; md = k_md[kind];
         const int ad = kind == 0 ? 3 : 2;
-        if (!ctx || N < 0 || max_iteration < 0 || (kind <= 1 && !h_K1) || (kind == 1 && !h_K2) || (N > 0 && (!h_a || !h_b)))
+        if (!ctx || N < 0 || max_iteration < 0 || (kind <= 1 && !h_K1) || (kind == 1 && !h_K2) || (N > 0 && !(dev_a && dev_b) && (!h_a || !h_b)) ||
+            ((dev_a || dev_b) && (kind != 0 || !dev_a || !dev_b)))
             return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: bad argument"));
         if (kind == 0 && !pose_K_ok(h_K1)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }"));
         if (n_inliers) *n_inliers = 0;
@@ -175,7 +177,7 @@ struct AcrRun {
                 q1[2 * i] = h_a[2 * i] * norm_t.d + norm_t.tx; q1[2 * i + 1] = h_a[2 * i + 1] * norm_t.d + norm_t.ty;
                 q2[2 * i] = h_b[2 * i] * norm_t.d + norm_t.tx; q2[2 * i + 1] = h_b[2 * i + 1] * norm_t.d + norm_t.ty;
             }
-        } else {
+        } else if (!dev_a) {
             memcpy(hp, h_a, sizeof(double) * ad * N);
             memcpy(hp + (size_t)ad * N, h_b, sizeof(double) * 2 * N);
         }
@@ -393,8 +395,13 @@ struct AcrGroup {
         for (size_t k = 0; k < live.size(); k += kMaxBatch) {
             const int n = (int)std::min<size_t>(kMaxBatch, live.size() - k);
             const double* src[kMaxBatch]; double* dst[kMaxBatch]; size_t cnt[kMaxBatch];
-            for (int i = 0; i < n; ++i) { src[i] = live[k + i]->stage_src; dst[i] = live[k + i]->stage_dst; cnt[i] = live[k + i]->stage_n; }
-            const hipError_t e = launch_acr_stage(src, dst, cnt, n, st);
+            const double* da[kMaxBatch]; const double* db[kMaxBatch]; int nc[kMaxBatch];      // (runs that start from device tracks)
+            for (int i = 0; i < n; ++i) {
+                const AcrRun* r = live[k + i];
+                src[i] = r->stage_src; dst[i] = r->stage_dst; cnt[i] = r->stage_n;
+                da[i] = r->dev_a; db[i] = r->dev_b; nc[i] = r->N;
+            }
+            const hipError_t e = launch_acr_stage(src, dst, cnt, n, st, da, db, nc);
             if (e != hipSuccess) {
                 fail_all(fail(ctx0, CLC_ERR_HIP, shared ? "acransac: shared staging launch" : "launch_acr_stage(&stage_src, &stage_dst, &stage_n, 1, st)", e));
                 return;
@@ -727,6 +734,146 @@ int clc_two_view_acransac_batch(clc_ctx* const* ctxs, int model, clc_two_view_jo
     std::vector<clc_two_view_job*> ptr((size_t)n_jobs);
     for (int i = 0; i < n_jobs; ++i) ptr[(size_t)i] = &jobs[i];
     return acr_two_view_batch(ctxs, ptr.data(), n_jobs, kind);
+}
+
+} // extern "C"
+
+// ---- Localizer::localizeImage from device tracks (include/coloc_hip.h: clc_track_localize*_dev) ----------------------------------------
+// The track kernel (track.hip) writes each job's correspondences into its context's track block and the count N into a pinned word; the
+// host waits for that one number -- AcrRun::begin_body lays the workspace out by N and builds the N-dependent NFA tables --, then the
+// runs go through acr_drive like every other solve.  The staging launch reads TWO sources per run: a | b from the track block, K, the
+// tables and the initial state from the pinned block (launch_acr_stage); no gather launch of its own, and nothing sized by N sits in
+// front of the count.
+namespace {
+
+// the track block of a context (ensure_track): [ X 3 cap | x 2 cap | query cap | map cap | n ]
+struct TrackBlock {
+    double *X, *x; int32_t *query, *map, *n; uint32_t* h_n; int32_t *h_query, *h_map;
+    explicit TrackBlock(const clc_ctx* c)
+    {
+        const size_t cap = c->trk_cap;
+        X = (double*)c->d_trk; x = X + 3 * cap; query = (int32_t*)(x + 2 * cap); map = query + cap; n = map + cap;
+        h_n = (uint32_t*)c->h_trk; h_query = (int32_t*)(c->h_trk + 64); h_map = h_query + cap;
+    }
+};
+
+int track_localize(clc_ctx* const* ctxs, clc_track_job* jobs, const int n_jobs)
+{
+    clc_ctx* c0 = ctxs[0];
+    for (int i = 0; i < n_jobs; ++i) {
+        clc_track_job& jb = jobs[i];
+        if (jb.Rt) memset(jb.Rt, 0, sizeof(double) * 12);
+        if (jb.cov) memset(jb.cov, 0, sizeof(double) * 36);
+        jb.n_tracks = 0; jb.n_inliers = 0; jb.iterations = 0; jb.status = CLC_OK; jb.error_max = 0.0; jb.rmse = 0.0;
+    }
+    CLC_HIP(c0, hipSetDevice(c0->device));
+    hipStream_t st = c0->stream;
+    std::vector<TrackJobDev> dev((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        int rc = track_job_inputs(c0, jobs[i], dev[(size_t)i], "track_localize: bad argument");
+        if (rc == CLC_OK && jobs[i].max_iteration < 0) rc = fail(c0, CLC_ERR_BAD_ARG, "track_localize: negative max_iteration");
+        if (rc == CLC_OK) rc = ensure_track(ctxs[i], (size_t)std::min(jobs[i].nq, kAcrMaxN));
+        if (rc != CLC_OK) {
+            if (ctxs[i] != c0) (void)fail(ctxs[i], rc, clc_last_error_string(c0));
+            jobs[i].status = rc;
+            return rc;
+        }
+    }
+    // behind whatever produced the inputs: an event on the producer's stream, no host synchronisation
+    for (int i = 0; i < n_jobs; ++i) {
+        hipStream_t prod = (hipStream_t)jobs[i].after_stream;
+        if (!prod || prod == st) continue;
+        clc_ctx* c = ctxs[i];
+        const bool ok = (c->ev_track || hipEventCreateWithFlags(&c->ev_track, hipEventDisableTiming) == hipSuccess) &&
+                        hipEventRecord(c->ev_track, prod) == hipSuccess && hipStreamWaitEvent(st, c->ev_track, 0) == hipSuccess;
+        if (!ok) CLC_HIP(c, hipStreamSynchronize(prod));
+    }
+    // the tracks of all jobs: one launch per kMaxBatch of them
+    for (int k = 0; k < n_jobs; k += kMaxBatch) {
+        const int n = std::min(kMaxBatch, n_jobs - k);
+        TrackJobs pack{};
+        pack.map_X = c0->d_map_X; pack.map_n = c0->map_X_n;
+        for (int i = 0; i < n; ++i) {
+            const TrackBlock tb(ctxs[k + i]);
+            TrackJobDev& d = dev[(size_t)(k + i)];
+            d.X = tb.X; d.x = tb.x; d.query = tb.query; d.map = tb.map; d.n = tb.n;
+            d.h_n = tb.h_n;
+            d.h_query = jobs[k + i].track_query ? tb.h_query : nullptr;
+            d.h_map = jobs[k + i].track_map ? tb.h_map : nullptr;
+            d.cap = std::min(jobs[k + i].nq, kAcrMaxN);
+            __atomic_store_n(tb.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
+            pack.j[i] = d;
+        }
+        CLC_HIP(c0, launch_track_build(pack, n, st));
+    }
+    const bool shared = acr_lockstep(0, n_jobs);
+    if (!shared && n_jobs > 1) {
+        // every other run stages from its track block on its context's OWN stream: behind the track launch
+        bool ordered = (c0->ev_track || hipEventCreateWithFlags(&c0->ev_track, hipEventDisableTiming) == hipSuccess) &&
+                       hipEventRecord(c0->ev_track, st) == hipSuccess;
+        for (int i = 1; i < n_jobs && ordered; ++i) ordered = hipStreamWaitEvent(ctxs[i]->stream, c0->ev_track, 0) == hipSuccess;
+        if (!ordered) CLC_HIP(c0, hipStreamSynchronize(st));
+    }
+    // the one number the host needs: poll the pinned words, the stream synchronisation as the fallback (which also surfaces errors)
+    std::vector<AcrRun> runs((size_t)n_jobs);
+    std::vector<double> Ks((size_t)9 * n_jobs, 0.0);
+    const auto t0 = std::chrono::steady_clock::now();
+    bool synced = false;
+    for (int i = 0; i < n_jobs; ++i) {
+        const TrackBlock tb(ctxs[i]);
+        uint32_t w = __atomic_load_n(tb.h_n, __ATOMIC_ACQUIRE);
+        for (uint32_t spins = 0; w == 0xFFFFFFFFu; w = __atomic_load_n(tb.h_n, __ATOMIC_ACQUIRE)) {
+            if (synced) return fail(c0, CLC_ERR_HIP, "track_localize: the track launch left no count");
+            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+                CLC_HIP(c0, hipStreamSynchronize(st));
+                synced = true;
+            }
+        }
+        clc_track_job& jb = jobs[i];
+        jb.n_tracks = (int)w;
+        double* K = &Ks[(size_t)9 * i];
+        K[0] = jb.cam.focal; K[2] = jb.cam.ppx; K[4] = jb.cam.focal; K[5] = jb.cam.ppy; K[8] = 1.0;      // Pinhole_Intrinsic_Radial_K3::K()
+        AcrRun& r = runs[(size_t)i];
+        r.ctx = ctxs[i]; r.kind = 0; r.N = jb.n_tracks; r.dev_a = tb.X; r.dev_b = tb.x; r.h_K1 = K;
+        r.max_iteration = jb.max_iteration; r.seed = jb.seed; r.precision = jb.precision;
+        r.refine_huber = jb.refine ? (jb.huber_a > 0.0 ? jb.huber_a : 16.0) : -1.0;
+        r.h_model = jb.Rt; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers; r.error_max = &jb.error_max;
+        r.iterations = &jb.iterations; r.h_cov = jb.cov; r.rmse = &jb.rmse;
+    }
+    acr_drive(runs.data(), n_jobs, shared);
+    int worst = CLC_OK;
+    for (int i = 0; i < n_jobs; ++i) {
+        AcrRun& r = runs[(size_t)i];
+        clc_track_job& jb = jobs[i];
+        r.finish();
+        jb.status = r.status;
+        // trackedFeatures: the kernel wrote the pinned mirrors before the count came out
+        const TrackBlock tb(ctxs[i]);
+        const size_t nt = (size_t)std::min(jb.n_tracks, std::min(jb.nq, kAcrMaxN));
+        if (jb.track_query && nt) memcpy(jb.track_query, tb.h_query, sizeof(int32_t) * nt);
+        if (jb.track_map && nt) memcpy(jb.track_map, tb.h_map, sizeof(int32_t) * nt);
+        if (r.status != CLC_OK && worst == CLC_OK) worst = r.status;
+    }
+    return worst;
+}
+
+} // namespace
+
+extern "C" {
+
+int clc_track_localize_batch_dev(clc_ctx* const* ctxs, clc_track_job* jobs, int n_jobs)
+{
+    if (n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
+    if (n_jobs == 0) return CLC_OK;
+    const int rc0 = check_batch_contexts(ctxs, n_jobs, "track_localize_batch: every job needs a context of its own");
+    if (rc0 != CLC_OK) return rc0;
+    return track_localize(ctxs, jobs, n_jobs);
+}
+
+int clc_track_localize_dev(clc_ctx* ctx, clc_track_job* job)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "track_localize: null context / job");
+    return track_localize(&ctx, job, 1);
 }
 
 } // extern "C"

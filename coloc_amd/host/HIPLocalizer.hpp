@@ -14,6 +14,8 @@
 //        PoseRefiner::refinePose (Ceres, Huber(4^2), pose only) + 6x6 covariance  ->  clc_pnp_refine;
 //        rmse = mean pixel distance between the observations and the reprojected inliers (the value the reference
 //        leaves in rmse after cv::projectPoints with zero distortion and fy = fx, :141-170)
+// Additions (no counterpart in the reference): localizeImages (several cameras at once), and setMapPoints + localizeImageDev --
+//   localizeImage from tracks built on the device, setupTracks not running on the host at all (clc_track_localize_dev).
 // Functions return EXIT_SUCCESS / EXIT_FAILURE through bool, i.e. FALSE MEANS SUCCESS (coloc.hpp:241,338), except
 // refine(), which like the reference returns the refiner's own status (true = refined).
 // Second call site of the same solve: Reconstructor::resectionCamera (Reconstructor.hpp:282-307) calls
@@ -96,6 +98,79 @@ public:
         std::cout << "Localization successful" << std::endl;
         inliers = matching_data.vec_inliers;
         if (!refined) std::cerr << "Refining pose for image failed." << std::endl;
+        return EXIT_SUCCESS;
+    }
+
+    // The landmarks of the map's descriptor rows, in mapRegionIdx order, onto the device (clc_set_map_points): call it where the map is
+    // handed to the matcher (GPUMatcher::setMapData, coloc.hpp:196-198, 456-458).  false = success.
+    bool setMapPoints(colocData& data)
+    {
+        std::vector<double> X(3 * data.mapRegionIdx.size());
+        for (size_t i = 0; i < data.mapRegionIdx.size(); ++i) {
+            const auto& P = data.scene.GetLandmarks().at(data.mapRegionIdx[i]).X;
+            for (int r = 0; r < 3; ++r) X[3 * i + r] = P[r];
+        }
+        const int rc = ctx_ ? clc_set_map_points(ctx_, X.data(), static_cast<int>(data.mapRegionIdx.size())) : CLC_ERR_STATE;
+        if (rc != CLC_OK) std::cerr << "HIPLocalizer: clc_set_map_points: " << clc_status_string(rc) << std::endl;
+        return rc == CLC_OK ? EXIT_SUCCESS : EXIT_FAILURE;
+    }
+
+    // localizeImage from tracks built ON THE DEVICE (clc_track_localize_dev): d_match is what clc_match_map_dev left on the GPU for this
+    // frame (nq planned rows, d_count the detector's count pair or NULL), the 2-D side the detector's d_kps or a device block of feature
+    // positions (d_feat, feat_stride floats per row); after_stream = the stream that produced them (NULL: the localizer's own, or done).
+    // setupTracks does not run and nothing but the track count crosses to the host before the solve.  Leaves pose, covariance, rmse,
+    // trackedFeatures (IndMatch(map, query), matchFeaturesWithMap's order) and inliers exactly as setupTracks + localizeImage leave
+    // them for the same frame, and advances `seed` the same way.  rmse is the reference's mean pixel distance of the reprojected inliers
+    // (Localizer.hpp:141-170), evaluated on the host from the inliers' landmarks and feature positions in `data` (the only tracks the
+    // host touches).
+    bool localizeImageDev(int& idx, openMVG::geometry::Pose3& pose, colocData& data, Cov6& covariance, float& rmse,
+                          openMVG::matching::IndMatches& trackedFeatures, std::vector<uint32_t>& inliers, const int32_t* d_match, int nq,
+                          const uint32_t* d_count, const clc_keypoint* d_kps, const float* d_feat = nullptr, int feat_stride = 4,
+                          void* after_stream = nullptr)
+    {
+        openMVG::cameras::Pinhole_Intrinsic_Radial_K3 cam = camera(idx);
+        const uint64_t seed_value = seed++;
+        trackedFeatures.clear();
+        if (!ctx_ || nq <= 0) { std::cout << "Localization unsuccessful" << std::endl; return EXIT_FAILURE; }
+        std::vector<int32_t> tq(static_cast<size_t>(nq)), tm(static_cast<size_t>(nq)), inl(static_cast<size_t>(nq));
+        double Rt[12], cov[36];
+        clc_track_job jb{};
+        jb.d_match = d_match; jb.nq = nq; jb.d_count = d_count; jb.d_kps = d_kps; jb.d_feat = d_feat; jb.feat_stride = feat_stride;
+        jb.cam = clc_camera_k3{ cam.focal(), cam.principal_point()[0], cam.principal_point()[1], (*dist)[idx](0), (*dist)[idx](1), (*dist)[idx](2) };
+        jb.after_stream = after_stream;
+        jb.max_iteration = 256; jb.seed = seed_value; jb.precision = std::numeric_limits<double>::infinity();
+        jb.refine = 1; jb.huber_a = 16.0;
+        jb.Rt = Rt; jb.cov = cov; jb.track_query = tq.data(); jb.track_map = tm.data(); jb.inliers = inl.data();
+        const int rc = clc_track_localize_dev(ctx_, &jb);
+        if (rc != CLC_OK) {
+            std::cerr << "HIPLocalizer: clc_track_localize_dev: " << clc_last_error_string(ctx_) << std::endl;
+            std::cout << "Localization unsuccessful" << std::endl;
+            return EXIT_FAILURE;
+        }
+        for (int i = 0; i < jb.n_tracks; ++i)
+            trackedFeatures.emplace_back(static_cast<openMVG::IndexT>(tm[static_cast<size_t>(i)]), static_cast<openMVG::IndexT>(tq[static_cast<size_t>(i)]));
+        if (!(jb.n_inliers > 2.5 * 3)) { std::cout << "Localization unsuccessful" << std::endl; return EXIT_FAILURE; }
+        pose = pose_from_Rt(Rt);
+        for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) covariance(i, j) = cov[6 * i + j];
+        // the inliers' correspondences, as setupTracks fills them: all mean_reprojection reads
+        openMVG::sfm::Image_Localizer_Match_Data md;
+        md.pt3D.resize(3, static_cast<size_t>(jb.n_tracks));
+        md.pt2D.resize(2, static_cast<size_t>(jb.n_tracks));
+        md.vec_inliers.assign(inl.begin(), inl.begin() + jb.n_inliers);
+        const auto& regions = *data.regions.at(idx).get();
+        for (uint32_t c : md.vec_inliers) {
+            const auto& X = data.scene.GetLandmarks().at(data.mapRegionIdx[trackedFeatures[c].i_]).X;
+            for (int r = 0; r < 3; ++r) md.pt3D(r, c) = X[r];
+            const auto p = regions.GetRegionPosition(trackedFeatures[c].j_);
+            const openMVG::Vec2 px = cam.get_ud_pixel(openMVG::Vec2(static_cast<double>(p[0]), static_cast<double>(p[1])));
+            md.pt2D(0, c) = px[0];
+            md.pt2D(1, c) = px[1];
+        }
+        double Kd[9];
+        intrinsics(cam, Kd);
+        rmse = mean_reprojection(pose, Kd, md);
+        std::cout << "Localization successful" << std::endl;
+        inliers = md.vec_inliers;
         return EXIT_SUCCESS;
     }
 

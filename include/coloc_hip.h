@@ -44,7 +44,8 @@ extern "C" {
  * (clc_describe_match_pair_dev lost its `chunks` argument, CLC_K2NN_MATRIX_PLAIN is gone, the descriptor hand-over is by ownership:
  * clc_desc_cache_publish returns a handle).  4: the 'F' / 'H' models of the two-view filter (clc_two_view_acransac, _batch, clc_two_view_minimal);
  * the distance-ratio entries (clc_match_ratio_*, clc_match_map_ratio*, clc_ratio_matches_to_pairs) came later under 4: new entry points only;
- * so did the keypoint selection rule (clc_detect_set_selection, clc_detect_selection).
+ * so did the keypoint selection rule (clc_detect_set_selection, clc_detect_selection) and the device-side 2D-3D tracks
+ * (clc_set_map_points, clc_track_build_dev, clc_track_localize_dev, clc_track_localize_batch_dev).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -693,6 +694,85 @@ typedef struct clc_inter_pose_job {
     int            n_map_matches; /* the reference's chain: global map points matched to the temporary map (before the depth-ratio screen) */
 } clc_inter_pose_job;
 int clc_inter_pose_batch(clc_ctx* const* ctxs, clc_inter_pose_job* jobs, int n_jobs);
+
+/* ---- 2D-3D tracks on the device: replaces Localizer::setupTracks (include/coloc/Localizer.hpp:59-75) ---------------------
+ * The one stage of ColoC::intraPoseEstimator (coloc.hpp:201-272: matchSceneWithMap -> setupTracks -> Localize -> refine) that ran
+ * on the host.  With it the frame stays on the device from the image to the pose: clc_match_map_dev leaves d_match[nq] on the GPU,
+ * the track kernel turns it -- with the detector's keypoints and the map's 3-D points -- into the solve's correspondences, and the
+ * a-contrario solve starts from them.  (Later under ABI 4: new entry points only.)
+ *
+ * clc_set_map_points: h_X n x 3 doubles, row i = the landmark of map descriptor row i -- scene.GetLandmarks().at(mapRegionIdx[i]).X
+ * (Localizer.hpp:66), the order of clc_inter_pose_job.map_X.  Uploaded once per map, beside clc_set_map (GPUMatcher::setMapData,
+ * coloc.hpp:196-198, 456-458); synchronous.  Works on a context without detector / matcher options.  n == 0: no map points any more.
+ *
+ * A track job, per camera.  All inputs are DEVICE memory:
+ *   d_match[nq]   query q -> map row or -1, as clc_match_map_dev writes it; an index outside [0, number of map points) counts as
+ *                 "no match" (the rule of clc_inter_pose_job.map_n);
+ *   d_count       nullable: the detector's {written, found} pair (clc_detect_buffers); rows q >= d_count[0] are ignored, as
+ *                 clc_match_jobs_counted_dev treats them.  nq is then the PLANNED size (at most the keypoint capacity);
+ *   the 2-D side  EITHER d_kps, the detector's level-local keypoints (levels 0 .. 7) -- the feature position is scale * (float)x,
+ *                 scale * (float)y in float with scale = (float)pow((double)1.2f, level), clc_keypoints_to_features' values
+ *                 (GPUDetector.hpp:172-179) -- OR d_feat, float positions already scaled, row q at d_feat + q * feat_stride (a
+ *                 Features() block: feat_stride = 4).  Exactly one of the two;
+ *   cam           Pinhole_Intrinsic_Radial_K3: the position, widened to double, goes through get_ud_pixel (ima2cam, the r2 == 0
+ *                 shortcut, both 1.05 bracket loops, bisection to 1e-10, cam2ima) in fp64 in the host's operation order, so the
+ *                 result has the host's bits.  (A bracket the host's bisection would never leave ends after 4096 steps here.)
+ * The tracks are the accepted queries in ASCENDING q -- the order matchFeaturesWithMap emits (GPUMatcher.hpp:263-266) and
+ * setupTracks walks; the a-contrario sampler is a function of (seed, iteration, index set), so the order is part of the result.
+ *
+ * clc_track_build_dev: the kernel alone, enqueue only on `stream` (capturable like the other _dev entries); reads the inputs and
+ * cam of *job, writes d_X (3 N), d_x (2 N), d_query / d_map (N int32: the reference's trackedFeatures j_ / i_) and *d_n = N.  The
+ * output buffers hold job->nq tracks each; all but d_X and d_x are nullable.
+ *
+ * clc_track_localize_dev: tracks + Localizer::localizeImage (Localizer.hpp:77-108) for one camera, from device memory: the track
+ * launch, then the a-contrario solve of clc_pnp_acransac (refine == 0) / clc_pnp_localize_ac (refine != 0) with
+ * K = { focal, 0, ppx; 0, focal, ppy; 0, 0, 1 } (Pinhole_Intrinsic_Radial_K3::K()), same result bit for bit as those entries give
+ * for the host-gathered copy of the same tracks.  The host waits for ONE number, the track count N (a pinned word the kernel
+ * writes; the a-contrario tables depend on it); matches, keypoints, map points and correspondences are never copied in either
+ * direction.  Host outputs (nullable): Rt 12, cov 36 (refine), track_query / track_map / inliers / inlier_mask with room for nq
+ * entries (inliers index the track list, ascending residual order).  N <= 3: CLC_OK, n_inliers = 0; N > 16384: CLC_ERR_CAPACITY;
+ * no map points, or fewer map points than the context's map rows (clc_set_map): CLC_ERR_STATE; both or neither of d_kps / d_feat:
+ * CLC_ERR_BAD_ARG.
+ * ORDERING.  A context's stream is NON-BLOCKING: it does not wait for work on the NULL stream or any other stream.  A caller that
+ * produced d_match / d_kps on another stream (torch's current stream, say) passes it as after_stream: the call records an event
+ * there and makes its own stream wait for it -- no host synchronisation.  after_stream == NULL means "already ordered": the inputs
+ * were produced on the context's own stream (clc_stream) or are complete.
+ *
+ * clc_track_localize_batch_dev: n jobs, job i on ctxs[i] (a context of its own each, one device, as clc_pnp_localize_ac_batch);
+ * the map points are ctxs[0]'s.  ONE track launch for the batch on ctxs[0]'s stream, then the solves interleaved or in lockstep
+ * exactly as clc_pnp_localize_ac_batch runs them; every job's result is the single call's.  jobs[i].status per job; returns the
+ * first failure. */
+typedef struct clc_camera_k3 { double focal, ppx, ppy, k1, k2, k3; } clc_camera_k3;
+typedef struct clc_track_job {
+    /* in */
+    const int32_t*      d_match;
+    int                 nq;
+    const uint32_t*     d_count;      /* nullable */
+    const clc_keypoint* d_kps;        /* or */
+    const float*        d_feat;
+    int                 feat_stride;  /* floats per row of d_feat */
+    clc_camera_k3       cam;
+    void*               after_stream; /* nullable: the stream that produced d_match / d_kps */
+    int                 max_iteration;
+    uint64_t            seed;
+    double              precision;    /* +inf: a-contrario threshold */
+    int                 refine;
+    double              huber_a;      /* <= 0: 16 */
+    /* out (pointers nullable, host memory) */
+    double*             Rt;
+    double*             cov;
+    int32_t*            track_query;
+    int32_t*            track_map;
+    int32_t*            inliers;
+    uint8_t*            inlier_mask;
+    int                 n_tracks, n_inliers, iterations, status;
+    double              error_max, rmse;
+} clc_track_job;
+int clc_set_map_points(clc_ctx* ctx, const double* h_X, int n);
+int clc_track_localize_dev(clc_ctx* ctx, clc_track_job* job);
+int clc_track_localize_batch_dev(clc_ctx* const* ctxs, clc_track_job* jobs, int n_jobs);
+int clc_track_build_dev(clc_ctx* ctx, const clc_track_job* job, double* d_X, double* d_x, int32_t* d_query, int32_t* d_map,
+                        int32_t* d_n, void* stream);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
