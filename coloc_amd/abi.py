@@ -64,6 +64,19 @@ class TrackJob(C.Structure):
                 ("error_max", C.c_double), ("rmse", C.c_double)]
 
 
+class PairJob(C.Structure):
+    """clc_pair_job (include/coloc_hip.h)"""
+    _fields_ = [("d_match", C.c_void_p), ("nq", C.c_int), ("nt", C.c_int), ("d_count_a", C.c_void_p), ("d_count_b", C.c_void_p),
+                ("d_kps_a", C.c_void_p), ("d_feat_a", C.c_void_p), ("feat_stride_a", C.c_int),
+                ("d_kps_b", C.c_void_p), ("d_feat_b", C.c_void_p), ("feat_stride_b", C.c_int),
+                ("cam_a", CameraK3), ("cam_b", CameraK3), ("after_stream", C.c_void_p),
+                ("img_w", C.c_int), ("img_h", C.c_int), ("max_iteration", C.c_int), ("seed", C.c_uint64), ("precision", C.c_double),
+                ("M", C.c_void_p), ("F", C.c_void_p), ("pair_q", C.c_void_p), ("pair_t", C.c_void_p), ("x1", C.c_void_p), ("x2", C.c_void_p),
+                ("inliers", C.c_void_p), ("inlier_mask", C.c_void_p),
+                ("n_pairs", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int), ("status", C.c_int),
+                ("error_max", C.c_double), ("min_nfa", C.c_double)]
+
+
 ABI_VERSION = 4          # CLC_ABI_VERSION of include/coloc_hip.h
 DESC_CACHE_OFF, DESC_CACHE_VERIFY, DESC_CACHE_TRUST = 0, 1, 2
 
@@ -104,6 +117,7 @@ EXPORTS = [
     "clc_match_ratio_2nn", "clc_match_ratio_2nn_dev", "clc_match_ratio_pairs", "clc_match_map_ratio", "clc_match_map_ratio_dev",
     "clc_ratio_matches_to_pairs", "clc_detect_set_selection", "clc_detect_selection",
     "clc_set_map_points", "clc_track_build_dev", "clc_track_localize_dev", "clc_track_localize_batch_dev",
+    "clc_pair_build_dev", "clc_pair_filter_dev", "clc_pair_filter_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -253,6 +267,9 @@ def load_library():
     lib.clc_track_build_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.clc_track_localize_dev.argtypes = [vp, vp]
     lib.clc_track_localize_batch_dev.argtypes = [vp, vp, ci]
+    lib.clc_pair_build_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.clc_pair_filter_dev.argtypes = [vp, ci, vp]
+    lib.clc_pair_filter_batch_dev.argtypes = [vp, ci, vp, ci]
     _lib = lib
     return lib
 
@@ -559,6 +576,50 @@ def track_localize_batch_dev(ctxs, jobs):
     if rc != CLC_OK:
         raise CLCError(rc, "clc_track_localize_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
     return [_track_result(arr[i], *outs[i]) for i in range(n)]
+
+
+def _pair_fill(j, keep, d_match, nq, nt, cam_a, cam_b, d_kps_a=None, d_feat_a=None, feat_stride_a=4, d_kps_b=None, d_feat_b=None,
+               feat_stride_b=4, d_count_a=None, d_count_b=None, after_stream=None, img_wh=(0, 0), max_iteration=256, seed=1,
+               precision=float("inf"), outputs=True):
+    """fills a PairJob; cam_* = (focal, ppx, ppy, k1, k2, k3); device pointers as integers"""
+    j.d_match, j.nq, j.nt, j.d_count_a, j.d_count_b = d_match, int(nq), int(nt), d_count_a, d_count_b
+    j.d_kps_a, j.d_feat_a, j.feat_stride_a = d_kps_a, d_feat_a, int(feat_stride_a)
+    j.d_kps_b, j.d_feat_b, j.feat_stride_b = d_kps_b, d_feat_b, int(feat_stride_b)
+    j.cam_a, j.cam_b = CameraK3(*[float(v) for v in cam_a]), CameraK3(*[float(v) for v in cam_b])
+    j.after_stream = after_stream
+    j.img_w, j.img_h, j.max_iteration, j.seed, j.precision = int(img_wh[0]), int(img_wh[1]), int(max_iteration), int(seed), float(precision)
+    if not outputs:
+        return None
+    n = max(int(nq), 1)
+    M, F, x1, x2 = np.zeros(9), np.zeros(9), np.zeros((n, 2)), np.zeros((n, 2))
+    pq, pt, inl, mask = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+    keep.append((M, F, pq, pt, x1, x2, inl, mask))
+    j.M, j.F, j.pair_q, j.pair_t, j.x1, j.x2, j.inliers, j.inlier_mask = (a.ctypes.data for a in (M, F, pq, pt, x1, x2, inl, mask))
+    return M, F, pq, pt, x1, x2, inl, mask
+
+
+def _pair_result(j, M, F, pq, pt, x1, x2, inl, mask):
+    found = j.n_inliers > 0
+    n = max(min(j.n_pairs, len(pq)), 0)
+    return dict(M=M.reshape(3, 3).copy() if found else None, F=F.reshape(3, 3).copy() if found else None, n_pairs=j.n_pairs,
+                pair_q=pq[:n].copy(), pair_t=pt[:n].copy(), x1=x1[:n].copy(), x2=x2[:n].copy(), inliers=inl[:j.n_inliers].copy(),
+                mask=mask[:n].astype(bool), error_max=j.error_max, min_nfa=j.min_nfa, iterations=j.iterations, status=j.status)
+
+
+def pair_filter_batch_dev(ctxs, model, jobs):
+    """clc_pair_filter_batch_dev: model 'E' | 'F' | 'H'; jobs = [dict(d_match=, nq=, nt=, cam_a=, cam_b=, d_kps_a= | d_feat_a=, ...), ...]
+    (the keywords of Context.pair_filter_dev), job i on ctxs[i].  Returns a list of result dicts."""
+    lib = load_library()
+    n = len(jobs)
+    assert len(ctxs) == n
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **jobs[i]) for i in range(n)]
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_pair_filter_batch_dev(hs, ord(model), arr, n)
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_pair_filter_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    return [_pair_result(arr[i], *outs[i]) for i in range(n)]
 
 
 def desc_handle_live(handle):
@@ -909,6 +970,24 @@ class Context:
         out = _track_fill(j, keep, **job)
         self._chk(self.lib.clc_track_localize_dev(self.h, C.byref(j)))
         return _track_result(j, *out)
+
+    def pair_build_dev(self, d_x1, d_x2, d_pair_q, d_pair_t, d_n, stream=None, **job):
+        """clc_pair_build_dev: the pair kernel alone, enqueue only; job keywords as pair_filter_dev (d_match, nq, nt, cam_a, cam_b,
+        d_kps_* | d_feat_*, feat_stride_*, d_count_*); outputs are device pointers with room for nq pairs"""
+        j = PairJob()
+        _pair_fill(j, None, outputs=False, **job)
+        self._chk(self.lib.clc_pair_build_dev(self.h, C.byref(j), d_x1, d_x2, d_pair_q, d_pair_t, d_n, stream))
+
+    def pair_filter_dev(self, model, **job):
+        """clc_pair_filter_dev: computeRelativePose's gather + the a-contrario filter of model 'E' | 'F' | 'H' from device memory.  Keywords:
+        d_match, nq, nt, cam_a / cam_b = (focal, ppx, ppy, k1, k2, k3), d_kps_a or d_feat_a (+ feat_stride_a), the same for b, d_count_a,
+        d_count_b, after_stream, img_wh, max_iteration, seed, precision.  Returns a dict: M (E, F or H in pixels), F, n_pairs, pair_q, pair_t,
+        x1, x2 (undistorted pixels), inliers (into the pair list), mask, error_max, min_nfa, iterations."""
+        j = PairJob()
+        keep = []
+        out = _pair_fill(j, keep, **job)
+        self._chk(self.lib.clc_pair_filter_dev(self.h, ord(model), C.byref(j)))
+        return _pair_result(j, *out)
 
     def match_map_dev(self, d_q, nq, threshold, d_match, stream=None):
         self._chk(self.lib.clc_match_map_dev(self.h, d_q, nq, int(threshold), d_match, stream))

@@ -1051,6 +1051,8 @@ hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int 
 struct AcrStageJobs {
     const double2* src[kMaxBatch]; double2* dst[kMaxBatch]; int n2[kMaxBatch];
     const double* dev_a[kMaxBatch]; const double* dev_b[kMaxBatch]; int n_corr[kMaxBatch];     // (dev_a null: everything from src)
+    int a_width[kMaxBatch];                                                                     // doubles per correspondence of a: 3 (X) or 2 (x1)
+    double cond[kMaxBatch][3];                                                                  // { d, tx, ty }; d == 0: the points as they are
 };
 __global__ __launch_bounds__(256) void acr_stage_kernel(const AcrStageJobs jobs)
 {
@@ -1058,22 +1060,36 @@ __global__ __launch_bounds__(256) void acr_stage_kernel(const AcrStageJobs jobs)
     if (i >= jobs.n2[c]) return;
     const double* da = jobs.dev_a[c];
     if (!da) { jobs.dst[c][i] = jobs.src[c][i]; return; }
-    // a | b of a resection = the track kernel's X (3 n) | x (2 n) in device memory; 5 n may be odd, so this part goes double by double
-    const int na = 3 * jobs.n_corr[c], nab = 5 * jobs.n_corr[c];
+    // a | b of a resection = the track kernel's X (3 n) | x (2 n) in device memory; 5 n may be odd, so this part goes double by double.
+    // a | b of a two-view solve = the pair kernel's x1 (2 n) | x2 (2 n): x at the even, y at the odd places of both.
+    const int na = jobs.a_width[c] * jobs.n_corr[c], nab = na + 2 * jobs.n_corr[c];
     const double* db = jobs.dev_b[c];
     const double* src = (const double*)jobs.src[c];
     double* dst = (double*)jobs.dst[c];
-    for (int e = 2 * i; e < 2 * i + 2; ++e) dst[e] = e < na ? da[e] : (e < nab ? db[e - na] : src[e]);
+    const double d = jobs.cond[c][0];
+    for (int e = 2 * i; e < 2 * i + 2; ++e) {
+        if (e >= nab) { dst[e] = src[e]; continue; }
+        const double v = e < na ? da[e] : db[e - na];
+        // ACKernelAdaptor's NormalizePoints as AcrRun::begin_body applies it to host points: x * d + tx, y * d + ty (one multiplication,
+        // one addition, no contraction: the host's bits)
+        dst[e] = d != 0.0 ? v * d + jobs.cond[c][1 + (e & 1)] : v;
+    }
 }
 hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
-                            hipStream_t stream, const double* const* d_a, const double* const* d_b, const int* n_corr)
+                            hipStream_t stream, const double* const* d_a, const double* const* d_b, const int* n_corr, const int* a_width,
+                            const double (*cond)[3])
 {
     if (n_chains < 1 || n_chains > kMaxBatch) return hipErrorInvalidValue;
     AcrStageJobs jobs{};
     int most = 0;
     for (int c = 0; c < n_chains; ++c) {
         jobs.src[c] = (const double2*)h_pinned[c]; jobs.dst[c] = (double2*)d_dst[c]; jobs.n2[c] = (int)(n_doubles[c] / 2);
-        if (d_a && d_b && n_corr && d_a[c] && d_b[c]) { jobs.dev_a[c] = d_a[c]; jobs.dev_b[c] = d_b[c]; jobs.n_corr[c] = n_corr[c]; }
+        if (d_a && d_b && n_corr && d_a[c] && d_b[c]) {
+            jobs.dev_a[c] = d_a[c]; jobs.dev_b[c] = d_b[c]; jobs.n_corr[c] = n_corr[c];
+            jobs.a_width[c] = a_width ? a_width[c] : 3;
+            if (jobs.a_width[c] != 2 && jobs.a_width[c] != 3) return hipErrorInvalidValue;
+            if (cond && jobs.a_width[c] == 2) for (int k = 0; k < 3; ++k) jobs.cond[c][k] = cond[c][k];
+        }
         most = jobs.n2[c] > most ? jobs.n2[c] : most;
     }
     if (most <= 0) return hipSuccess;

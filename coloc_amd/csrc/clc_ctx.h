@@ -113,7 +113,11 @@ struct clc_ctx {
     uint8_t* d_trk = nullptr;     // [ X 3 cap | x 2 cap | query cap | map cap | n ]: the tracks of this context's job (clc_track_localize*_dev)
     uint8_t* h_trk = nullptr;     // pinned: [ count word (64 B) | query cap | map cap ]
     size_t trk_cap = 0;           // tracks
-    hipEvent_t ev_track = nullptr;   // orders the track launch behind job.after_stream, and the contexts' streams behind the launch
+    hipEvent_t ev_track = nullptr;   // orders the track / pair launch behind job.after_stream, and the contexts' streams behind the launch
+    // two-view correspondences (pair.hip)
+    uint8_t* d_pair = nullptr;    // [ x1 2 cap | x2 2 cap | q cap | t cap | n ]: the pairs of this context's job (clc_pair_filter*_dev)
+    uint8_t* h_pair = nullptr;    // pinned: [ count word (64 B) | x1 2 cap | x2 2 cap | q cap | t cap ]
+    size_t pair_cap = 0;          // pairs
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     uint8_t* h_stage = nullptr;

@@ -64,7 +64,9 @@ struct AcrRun {
     clc_ctx* ctx = nullptr;
     int kind = 0, N = 0, img_w = 0, img_h = 0, max_iteration = 0;
     const double *h_a = nullptr, *h_b = nullptr, *h_K1 = nullptr, *h_K2 = nullptr;
-    const double *dev_a = nullptr, *dev_b = nullptr;    // kind 0 from device memory (track.hip): a | b are staged from these blocks, h_a / h_b unused
+    // a | b from device memory: X | x of the track block (kind 0, track.hip) or x1 | x2 in pixels of the pair block (kinds 1-3, pair.hip);
+    // they are staged from these blocks -- kinds 2 / 3 conditioned by the staging launch --, h_a / h_b unused
+    const double *dev_a = nullptr, *dev_b = nullptr;
     uint64_t seed = 0;
     double precision = 0.0, refine_huber = -1.0;
     double* h_model = nullptr; uint8_t* h_mask = nullptr; int32_t* h_inliers = nullptr;
@@ -107,7 +109,7 @@ struct AcrRun {
         m = k_m[kind]; M = k_M[kind]; md = k_md[kind];
         const int ad = kind == 0 ? 3 : 2;
         if (!ctx || N < 0 || max_iteration < 0 || (kind <= 1 && !h_K1) || (kind == 1 && !h_K2) || (N > 0 && !(dev_a && dev_b) && (!h_a || !h_b)) ||
-            ((dev_a || dev_b) && (kind != 0 || !dev_a || !dev_b)))
+            ((dev_a || dev_b) && (!dev_a || !dev_b)))
             return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: bad argument"));
         if (kind == 0 && !pose_K_ok(h_K1)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }"));
         if (n_inliers) *n_inliers = 0;
@@ -170,10 +172,11 @@ struct AcrRun {
         double* hp = (double*)ctx->h_pin;
         if (kind >= 2) {
             // ACKernelAdaptor: NormalizePoints(x, &x_, &N_, w, h) for both point sets (x_n = d x + t, oracle/clc_oracle_twoview.c orc_tv_normalize)
+            // (points from device memory: the staging launch applies the same two operations, launch_acr_stage's cond)
             norm_t = tv::normalizer(img_w, img_h);
             double* q1 = hp;
             double* q2 = hp + (size_t)2 * N;
-            for (int i = 0; i < N; ++i) {
+            for (int i = 0; i < N && !dev_a; ++i) {
                 q1[2 * i] = h_a[2 * i] * norm_t.d + norm_t.tx; q1[2 * i + 1] = h_a[2 * i + 1] * norm_t.d + norm_t.ty;
                 q2[2 * i] = h_b[2 * i] * norm_t.d + norm_t.tx; q2[2 * i + 1] = h_b[2 * i + 1] * norm_t.d + norm_t.ty;
             }
@@ -395,13 +398,17 @@ struct AcrGroup {
         for (size_t k = 0; k < live.size(); k += kMaxBatch) {
             const int n = (int)std::min<size_t>(kMaxBatch, live.size() - k);
             const double* src[kMaxBatch]; double* dst[kMaxBatch]; size_t cnt[kMaxBatch];
-            const double* da[kMaxBatch]; const double* db[kMaxBatch]; int nc[kMaxBatch];      // (runs that start from device tracks)
+            const double* da[kMaxBatch]; const double* db[kMaxBatch]; int nc[kMaxBatch];      // (runs that start from device tracks / pairs)
+            int aw[kMaxBatch]; double cond[kMaxBatch][3];
             for (int i = 0; i < n; ++i) {
                 const AcrRun* r = live[k + i];
                 src[i] = r->stage_src; dst[i] = r->stage_dst; cnt[i] = r->stage_n;
                 da[i] = r->dev_a; db[i] = r->dev_b; nc[i] = r->N;
+                aw[i] = r->kind == 0 ? 3 : 2;
+                const bool cnd = r->kind >= 2 && r->dev_a;
+                cond[i][0] = cnd ? r->norm_t.d : 0.0; cond[i][1] = cnd ? r->norm_t.tx : 0.0; cond[i][2] = cnd ? r->norm_t.ty : 0.0;
             }
-            const hipError_t e = launch_acr_stage(src, dst, cnt, n, st, da, db, nc);
+            const hipError_t e = launch_acr_stage(src, dst, cnt, n, st, da, db, nc, aw, cond);
             if (e != hipSuccess) {
                 fail_all(fail(ctx0, CLC_ERR_HIP, shared ? "acransac: shared staging launch" : "launch_acr_stage(&stage_src, &stage_dst, &stage_n, 1, st)", e));
                 return;
@@ -874,6 +881,159 @@ int clc_track_localize_dev(clc_ctx* ctx, clc_track_job* job)
 {
     if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "track_localize: null context / job");
     return track_localize(&ctx, job, 1);
+}
+
+} // extern "C"
+
+// ---- RobustMatcher::computeRelativePose from device matches (include/coloc_hip.h: clc_pair_filter*_dev) ---------------------------------
+// The track path's twin.  The pair kernel (pair.hip) writes each job's correspondences, in PIXELS, into its context's pair block and the
+// count N into a pinned word; the host waits for that one number, then the runs go through acr_drive like every other two-view solve.
+// The staging launch reads x1 | x2 from the pair block -- and conditions them for 'F' / 'H' on the way, where it costs no launch and
+// leaves the block's pinned mirrors in pixels for the pose from E --, K1 / K2, the tables and the initial state from the pinned block.
+namespace {
+
+// the pair block of a context (ensure_pair): device [ x1 2 cap | x2 2 cap | q cap | t cap | n ], pinned [ word (64 B) | x1 | x2 | q | t ]
+struct PairBlock {
+    double *x1, *x2; int32_t *q, *t, *n; uint32_t* h_n; double *h_x1, *h_x2; int32_t *h_q, *h_t;
+    explicit PairBlock(const clc_ctx* c)
+    {
+        const size_t cap = c->pair_cap;
+        x1 = (double*)c->d_pair; x2 = x1 + 2 * cap; q = (int32_t*)(x2 + 2 * cap); t = q + cap; n = t + cap;
+        h_n = (uint32_t*)c->h_pair; h_x1 = (double*)(c->h_pair + 64); h_x2 = h_x1 + 2 * cap; h_q = (int32_t*)(h_x2 + 2 * cap); h_t = h_q + cap;
+    }
+};
+
+int pair_filter(clc_ctx* const* ctxs, const int kind, clc_pair_job* jobs, const int n_jobs)
+{
+    clc_ctx* c0 = ctxs[0];
+    for (int i = 0; i < n_jobs; ++i) {
+        clc_pair_job& jb = jobs[i];
+        if (jb.M) memset(jb.M, 0, sizeof(double) * 9);
+        if (jb.F) memset(jb.F, 0, sizeof(double) * 9);
+        jb.n_pairs = 0; jb.n_inliers = 0; jb.iterations = 0; jb.status = CLC_OK; jb.error_max = 0.0; jb.min_nfa = INFINITY;
+    }
+    CLC_HIP(c0, hipSetDevice(c0->device));
+    hipStream_t st = c0->stream;
+    std::vector<PairJobDev> dev((size_t)n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        int rc = pair_job_inputs(c0, jobs[i], dev[(size_t)i], "pair_filter: bad argument");
+        if (rc == CLC_OK && jobs[i].max_iteration < 0) rc = fail(c0, CLC_ERR_BAD_ARG, "pair_filter: negative max_iteration");
+        if (rc == CLC_OK) rc = ensure_pair(ctxs[i], (size_t)std::min(jobs[i].nq, kAcrMaxN));
+        if (rc != CLC_OK) {
+            if (ctxs[i] != c0) (void)fail(ctxs[i], rc, clc_last_error_string(c0));
+            jobs[i].status = rc;
+            return rc;
+        }
+    }
+    // behind whatever produced the inputs: an event on the producer's stream, no host synchronisation
+    for (int i = 0; i < n_jobs; ++i) {
+        hipStream_t prod = (hipStream_t)jobs[i].after_stream;
+        if (!prod || prod == st) continue;
+        clc_ctx* c = ctxs[i];
+        const bool ok = (c->ev_track || hipEventCreateWithFlags(&c->ev_track, hipEventDisableTiming) == hipSuccess) &&
+                        hipEventRecord(c->ev_track, prod) == hipSuccess && hipStreamWaitEvent(st, c->ev_track, 0) == hipSuccess;
+        if (!ok) CLC_HIP(c, hipStreamSynchronize(prod));
+    }
+    // the correspondences of all jobs: one launch per kMaxBatch of them
+    for (int k = 0; k < n_jobs; k += kMaxBatch) {
+        const int n = std::min(kMaxBatch, n_jobs - k);
+        PairJobs pack{};
+        for (int i = 0; i < n; ++i) {
+            const PairBlock pb(ctxs[k + i]);
+            const clc_pair_job& jb = jobs[k + i];
+            PairJobDev& d = dev[(size_t)(k + i)];
+            d.x1 = pb.x1; d.x2 = pb.x2; d.pair_q = pb.q; d.pair_t = pb.t; d.n = pb.n;
+            d.h_n = pb.h_n;
+            d.h_q = jb.pair_q ? pb.h_q : nullptr;
+            d.h_t = jb.pair_t ? pb.h_t : nullptr;
+            d.h_x1 = jb.x1 ? pb.h_x1 : nullptr;
+            d.h_x2 = jb.x2 ? pb.h_x2 : nullptr;
+            d.cap = std::min(jb.nq, kAcrMaxN);
+            __atomic_store_n(pb.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
+            pack.j[i] = d;
+        }
+        CLC_HIP(c0, launch_pair_build(pack, n, st));
+    }
+    const bool shared = acr_lockstep(kind, n_jobs);
+    if (!shared && n_jobs > 1) {
+        // every other run stages from its pair block on its context's OWN stream: behind the pair launch
+        bool ordered = (c0->ev_track || hipEventCreateWithFlags(&c0->ev_track, hipEventDisableTiming) == hipSuccess) &&
+                       hipEventRecord(c0->ev_track, st) == hipSuccess;
+        for (int i = 1; i < n_jobs && ordered; ++i) ordered = hipStreamWaitEvent(ctxs[i]->stream, c0->ev_track, 0) == hipSuccess;
+        if (!ordered) CLC_HIP(c0, hipStreamSynchronize(st));
+    }
+    // the one number the host needs: poll the pinned words, the stream synchronisation as the fallback (which also surfaces errors)
+    std::vector<AcrRun> runs((size_t)n_jobs);
+    std::vector<double> Ks((size_t)18 * n_jobs, 0.0), EF((size_t)18 * n_jobs, 0.0);
+    const auto t0 = std::chrono::steady_clock::now();
+    bool synced = false;
+    for (int i = 0; i < n_jobs; ++i) {
+        const PairBlock pb(ctxs[i]);
+        uint32_t w = __atomic_load_n(pb.h_n, __ATOMIC_ACQUIRE);
+        for (uint32_t spins = 0; w == 0xFFFFFFFFu; w = __atomic_load_n(pb.h_n, __ATOMIC_ACQUIRE)) {
+            if (synced) return fail(c0, CLC_ERR_HIP, "pair_filter: the pair launch left no count");
+            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
+                CLC_HIP(c0, hipStreamSynchronize(st));
+                synced = true;
+            }
+        }
+        clc_pair_job& jb = jobs[i];
+        jb.n_pairs = (int)w;
+        double* K = &Ks[(size_t)18 * i];                                  // Pinhole_Intrinsic_Radial_K3::K() of the two cameras
+        K[0] = jb.cam_a.focal; K[2] = jb.cam_a.ppx; K[4] = jb.cam_a.focal; K[5] = jb.cam_a.ppy; K[8] = 1.0;
+        K[9] = jb.cam_b.focal; K[11] = jb.cam_b.ppx; K[13] = jb.cam_b.focal; K[14] = jb.cam_b.ppy; K[17] = 1.0;
+        AcrRun& r = runs[(size_t)i];
+        r.ctx = ctxs[i]; r.kind = kind; r.N = jb.n_pairs; r.dev_a = pb.x1; r.dev_b = pb.x2;
+        if (kind == 1) { r.h_K1 = K; r.h_K2 = K + 9; }
+        r.img_w = jb.img_w; r.img_h = jb.img_h;
+        r.max_iteration = jb.max_iteration; r.seed = jb.seed; r.precision = jb.precision; r.refine_huber = -1.0;
+        r.h_model = &EF[(size_t)18 * i]; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers;
+        r.error_max = &jb.error_max; r.min_nfa = &jb.min_nfa; r.iterations = &jb.iterations;
+    }
+    acr_drive(runs.data(), n_jobs, shared);
+    int worst = CLC_OK;
+    for (int i = 0; i < n_jobs; ++i) {
+        AcrRun& r = runs[(size_t)i];
+        clc_pair_job& jb = jobs[i];
+        r.finish();
+        jb.status = r.status;
+        // kind 1: the slots hold { E, F }; kinds 2 / 3: the model matrix, F = it ('F') or zeros ('H') -- as clc_two_view_acransac
+        const double* ef = &EF[(size_t)18 * i];
+        if (jb.M) memcpy(jb.M, ef, sizeof(double) * 9);
+        if (jb.F && kind != 3) memcpy(jb.F, kind == 1 ? ef + 9 : ef, sizeof(double) * 9);
+        // the kernel wrote the pinned mirrors before the count came out
+        const PairBlock pb(ctxs[i]);
+        const size_t np = (size_t)std::min(jb.n_pairs, std::min(jb.nq, kAcrMaxN));
+        if (jb.pair_q && np) memcpy(jb.pair_q, pb.h_q, sizeof(int32_t) * np);
+        if (jb.pair_t && np) memcpy(jb.pair_t, pb.h_t, sizeof(int32_t) * np);
+        if (jb.x1 && np) memcpy(jb.x1, pb.h_x1, sizeof(double) * 2 * np);
+        if (jb.x2 && np) memcpy(jb.x2, pb.h_x2, sizeof(double) * 2 * np);
+        if (r.status != CLC_OK && worst == CLC_OK) worst = r.status;
+    }
+    return worst;
+}
+
+} // namespace
+
+extern "C" {
+
+int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* jobs, int n_jobs)
+{
+    const int kind = two_view_kind(model);
+    if (n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
+    if (n_jobs == 0) return kind < 0 ? CLC_ERR_BAD_ARG : CLC_OK;
+    const int rc0 = check_batch_contexts(ctxs, n_jobs, "pair_filter_batch: every job needs a context of its own");
+    if (rc0 != CLC_OK) return rc0;
+    if (kind < 0) return fail(ctxs[0], CLC_ERR_BAD_ARG, "pair_filter_batch: model must be 'E', 'F' or 'H'");
+    return pair_filter(ctxs, kind, jobs, n_jobs);
+}
+
+int clc_pair_filter_dev(clc_ctx* ctx, int model, clc_pair_job* job)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: null context / job");
+    const int kind = two_view_kind(model);
+    if (kind < 0) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: model must be 'E', 'F' or 'H'");
+    return pair_filter(&ctx, kind, job, 1);
 }
 
 } // extern "C"

@@ -7,6 +7,7 @@
 // matter of one ballot per wave and one 16-entry LDS scan per 1 024 queries.  The undistortion's loops are data-dependent and diverge;
 // at this size that does not matter.
 #include "clc_ctx.h"
+#include "ud_pixel.h"
 
 #include <cmath>
 #include <cstring>
@@ -16,28 +17,6 @@ namespace clc {
 namespace {
 
 constexpr int kTrackThreads = 1024;
-
-// Pinhole_Intrinsic_Radial_K3 (coloc_hip_geometry.hpp:97-135; OpenMVG's Pinhole_Intrinsic_Radial_K3): + - x / sqrt only, in the host's
-// order, and the library is built with -ffp-contract=off: the host's bits
-__device__ __forceinline__ double track_disto(const double r2, const double k1, const double k2, const double k3)
-{
-    const double t = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-    return r2 * t * t;
-}
-__device__ double track_radius_solve(const double r2, const double k1, const double k2, const double k3)
-{
-    double lowerbound = r2, upbound = r2;
-    while (track_disto(lowerbound, k1, k2, k3) > r2) lowerbound /= 1.05;
-    while (track_disto(upbound, k1, k2, k3) < r2) upbound *= 1.05;
-    // (the step cap: a bracket whose width cannot fall below 1e-10 -- coefficients far outside any lens, a keypoint 10^5 focal lengths
-    // out -- spins for ever on the host; a workgroup must not.  A bracket of finite doubles halves to below 1e-10 in < 1 100 steps.)
-    for (int it = 0; it < 4096 && 1e-10 < upbound - lowerbound; ++it) {
-        const double mid = .5 * (lowerbound + upbound);
-        if (track_disto(mid, k1, k2, k3) > r2) upbound = mid;
-        else lowerbound = mid;
-    }
-    return .5 * (lowerbound + upbound);
-}
 
 __global__ __launch_bounds__(kTrackThreads) void track_build_kernel(const TrackJobs jobs)
 {
@@ -66,23 +45,9 @@ __global__ __launch_bounds__(kTrackThreads) void track_build_kernel(const TrackJ
         const uint32_t i = off + before;
         if (ok && i < (uint32_t)jb.cap) {
             float fx, fy;
-            if (jb.kps) {
-                // clc_keypoints_to_features: scale * (float)x in float
-                const clc_keypoint kp = jb.kps[q];
-                const float scale = jobs.scale[kp.scale < CLC_MAX_LEVELS ? kp.scale : CLC_MAX_LEVELS - 1];
-                fx = scale * (float)kp.x;
-                fy = scale * (float)kp.y;
-            } else {
-                const float* f = jb.feat + (size_t)q * (size_t)jb.feat_stride;
-                fx = f[0];
-                fy = f[1];
-            }
-            // get_ud_pixel: ima2cam, radius by bisection, cam2ima
-            const double c0 = ((double)fx - jb.ppx) / jb.focal, c1 = ((double)fy - jb.ppy) / jb.focal;
-            const double r2 = c0 * c0 + c1 * c1;
-            const double radius = (r2 == 0.0) ? 1.0 : sqrt(track_radius_solve(r2, jb.k1, jb.k2, jb.k3) / r2);
-            jb.x[2 * (size_t)i] = jb.focal * (radius * c0) + jb.ppx;
-            jb.x[2 * (size_t)i + 1] = jb.focal * (radius * c1) + jb.ppy;
+            feature_position(jb.kps, jb.feat, jb.feat_stride, q, jobs.scale, &fx, &fy);
+            // get_ud_pixel: ima2cam, radius by bisection, cam2ima (ud_pixel.h, shared with pair.hip)
+            ud_pixel(fx, fy, UdCamera{ jb.focal, jb.ppx, jb.ppy, jb.k1, jb.k2, jb.k3 }, jb.x + 2 * (size_t)i);
             const double* X = jobs.map_X + 3 * (size_t)m;
             jb.X[3 * (size_t)i] = X[0]; jb.X[3 * (size_t)i + 1] = X[1]; jb.X[3 * (size_t)i + 2] = X[2];
             if (jb.query) jb.query[i] = (int32_t)q;

@@ -9,6 +9,8 @@
 //   bool computeRelativePose(relativePose, pair, regions, putativeMatches)                            :372-424
 //   bool filterMatchesPair(pair, regions, putativeMatches, geometricMatches, relativePoses)           :426-453  (coloc.hpp:296)
 //   void filterMatches(regions, putativeMatches, geometricMatches, relativePoses)                     :455-483  (coloc.hpp:167, 412)
+//   bool computeRelativePoseDev / filterMatchesPairDev(pair, d_match, ...)   the same two members from the matcher's DEVICE output:
+//        gather, undistortion and filter through clc_pair_filter_dev, no host round trip
 //        host arithmetic, restated from OpenMVG's published multiview code (motion_from_essential.hpp): the four
 //        (R, t) candidates of E = U diag(1,1,0) V^T (R = U W V^T or U W^T V^T, t = +-u3), every inlier triangulated
 //        (DLT on the bearing vectors) under each candidate, the candidate with most points in front of both cameras
@@ -37,7 +39,7 @@
 #include "coloc_hip.h"
 #include "coloc_hip_geometry.hpp"
 
-static_assert(CLC_ABI_VERSION >= 4, "this policy header uses entry points of ABI version 4 (clc_two_view_acransac)");
+static_assert(CLC_ABI_VERSION >= 4, "this policy header uses entry points of ABI version 4 (clc_two_view_acransac, clc_pair_filter_dev)");
 
 namespace coloc {
 namespace hipgeom {
@@ -511,6 +513,105 @@ public:
         for (size_t ic = 0; ic < relativePose.vec_inliers.size(); ++ic) kept.push_back(pairMatches[relativePose.vec_inliers[ic]]);
         if (!kept.empty()) geometricMatches[currentPair] = kept;
         relativePoses[currentPair] = relativePose;
+        return status;
+    }
+
+    // The pair's two cameras as the device holds them: camera A = pair.first (the QUERY side of d_match), camera B = pair.second (the
+    // TRAIN side); per camera the detector's keypoints OR a block of float positions (clc_pair_job), and its nullable count words.
+    struct PairSideDev { const clc_keypoint* d_kps; const float* d_feat; int feat_stride; const uint32_t* d_count; };
+
+    // computeRelativePose (:372-424) from DEVICE matches: the counterpart of HIPLocalizer::localizeImageDev.  d_match[nq] is the pair's
+    // match array as the matcher left it on the GPU (query row of camera A -> row of camera B, nt rows, or -1), `after_stream` the stream
+    // that produced it and the keypoints (nullptr: already ordered).  The gather, both undistortions and the a-contrario filter of
+    // params->model run through clc_pair_filter_dev: nothing but the pair count and the result crosses to the host.  Fills relativePose
+    // with what computeRelativePose fills for the same matches -- inliers, model matrix, found_residual_precision and, for 'E' / 'H',
+    // the relative pose (its bearing vectors come from the undistorted pixels the kernel mirrors into pinned memory) --, takes the
+    // member's seed++ and has its failure rules.  pairMatches (nullable) receives the putative matches in computeMatches' order.
+    bool computeRelativePoseDev(openMVG::sfm::RelativePose_Info& relativePose, openMVG::Pair current_pair, const int32_t* d_match, int nq, int nt,
+                                const PairSideDev& a, const PairSideDev& b, void* after_stream,
+                                std::vector<openMVG::matching::IndMatch>* pairMatches = nullptr)
+    {
+        last_status_ = kOk;
+        if (pairMatches) pairMatches->clear();
+        const char model = params->model;
+        if (model != 'E' && model != 'F' && model != 'H') return not_on_gpu_path(model, "RobustMatcher.hpp:399-405 knows 'E', 'F', 'H'");
+        auto failed = [&]() { last_status_ = kEstimateFailed; std::cerr << "Unable to estimate relative pose." << std::endl; return static_cast<bool>(EXIT_FAILURE); };
+        if (!ctx_ || nq < 0) return failed();
+        const auto& Ka = params->K[current_pair.first];
+        const auto& Kb = params->K[current_pair.second];
+        const auto& da = params->dist[current_pair.first];
+        const auto& db = params->dist[current_pair.second];
+        const openMVG::cameras::Pinhole_Intrinsic_Radial_K3 camL(params->imageSize.first, params->imageSize.second, Ka(0, 0), Ka(0, 2), Ka(1, 2), da[0],
+                                                                 da[1], da[2]),
+            camR(params->imageSize.first, params->imageSize.second, Kb(0, 0), Kb(0, 2), Kb(1, 2), db[0], db[1], db[2]);
+        const size_t room = static_cast<size_t>(nq > 0 ? nq : 1);
+        std::vector<int32_t> pq(room), pt(room), inl(room);
+        std::vector<double> x1(2 * room), x2(2 * room);
+        double M[9] = {};
+        clc_pair_job jb{};
+        jb.d_match = d_match; jb.nq = nq; jb.nt = nt; jb.d_count_a = a.d_count; jb.d_count_b = b.d_count;
+        jb.d_kps_a = a.d_kps; jb.d_feat_a = a.d_feat; jb.feat_stride_a = a.feat_stride;
+        jb.d_kps_b = b.d_kps; jb.d_feat_b = b.d_feat; jb.feat_stride_b = b.feat_stride;
+        jb.cam_a = clc_camera_k3{ Ka(0, 0), Ka(0, 2), Ka(1, 2), da[0], da[1], da[2] };
+        jb.cam_b = clc_camera_k3{ Kb(0, 0), Kb(0, 2), Kb(1, 2), db[0], db[1], db[2] };
+        jb.after_stream = after_stream;
+        jb.img_w = static_cast<int>(params->imageSize.first); jb.img_h = static_cast<int>(params->imageSize.second);
+        jb.max_iteration = iterationCount; jb.seed = seed++;
+        // filterHomography hands ACRANSAC +inf whatever relativePose_info says (:204); the other two its initial_residual_tolerance
+        jb.precision = model == 'H' ? std::numeric_limits<double>::infinity() : relativePose.initial_residual_tolerance;
+        jb.M = M; jb.pair_q = pq.data(); jb.pair_t = pt.data(); jb.inliers = inl.data();
+        const bool want_pose = model != 'F';
+        if (want_pose) { jb.x1 = x1.data(); jb.x2 = x2.data(); }
+        const int rc = clc_pair_filter_dev(ctx_, model, &jb);
+        if (rc != CLC_OK) {
+            std::cerr << "HIPRobustMatcher: clc_pair_filter_dev: " << clc_last_error_string(ctx_) << std::endl;
+            return failed();
+        }
+        const size_t n = static_cast<size_t>(jb.n_pairs);
+        if (pairMatches)
+            for (size_t k = 0; k < n; ++k)
+                pairMatches->emplace_back(static_cast<openMVG::IndexT>(pq[k]), static_cast<openMVG::IndexT>(pt[k]));
+        relativePose.vec_inliers.assign(inl.begin(), inl.begin() + jb.n_inliers);
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) relativePose.essential_matrix(i, j) = M[3 * i + j];
+        if (model == 'F') {
+            relativePose.found_residual_precision = 5.0;
+            return relativePose.vec_inliers.size() < 2.5 * 7 ? failed() : static_cast<bool>(EXIT_SUCCESS);
+        }
+        if (model == 'E') relativePose.found_residual_precision = jb.error_max;
+        if (relativePose.vec_inliers.size() < 2.5 * (model == 'E' ? 5 : 4)) return failed();
+        if (model == 'H') relativePose.found_residual_precision = jb.error_max;
+        // bearing vectors of the undistorted pixels, as filterEssential / filterHomography ask the intrinsics for them
+        openMVG::Mat xL(2, n), xR(2, n);
+        for (size_t k = 0; k < n; ++k) { xL(0, k) = x1[2 * k]; xL(1, k) = x1[2 * k + 1]; xR(0, k) = x2[2 * k]; xR(1, k) = x2[2 * k + 1]; }
+        const openMVG::Mat3X b1 = camL(xL), b2 = camR(xR);
+        if (model == 'E') {
+            openMVG::geometry::Pose3 relative_pose;
+            if (!hipgeom::RelativePoseFromEssential(b1, b2, relativePose.essential_matrix, relativePose.vec_inliers, &relative_pose)) return failed();
+            relativePose.relativePose = relative_pose;
+        } else {
+            std::vector<openMVG::geometry::Pose3> motions;
+            decomposeHomography(relativePose.essential_matrix, motions);
+            openMVG::geometry::Pose3 final_pose;
+            (void)performChiralityTest(b1, b2, relativePose.essential_matrix, relativePose.vec_inliers, motions, &final_pose);
+            relativePose.relativePose = final_pose;
+        }
+        return EXIT_SUCCESS;
+    }
+
+    // filterMatchesPair (:426-453) from device matches: geometricMatches[pair] and relativePoses[pair] as the host member leaves them
+    // for the same matches; putativeMatches[pair] (nullable map) receives the pair's putative matches, which the host member is handed
+    bool filterMatchesPairDev(openMVG::Pair currentPair, const int32_t* d_match, int nq, int nt, const PairSideDev& a, const PairSideDev& b,
+                              void* after_stream, openMVG::matching::PairWiseMatches& geometricMatches, InterPoseMap& relativePoses,
+                              openMVG::matching::PairWiseMatches* putativeMatches = nullptr)
+    {
+        std::vector<openMVG::matching::IndMatch> pairMatches;
+        openMVG::sfm::RelativePose_Info relativePose;
+        const bool status = computeRelativePoseDev(relativePose, currentPair, d_match, nq, nt, a, b, after_stream, &pairMatches);
+        std::vector<openMVG::matching::IndMatch> kept;
+        for (size_t ic = 0; ic < relativePose.vec_inliers.size(); ++ic) kept.push_back(pairMatches[relativePose.vec_inliers[ic]]);
+        if (!kept.empty()) geometricMatches[currentPair] = kept;
+        relativePoses[currentPair] = relativePose;
+        if (putativeMatches) (*putativeMatches)[currentPair] = pairMatches;
         return status;
     }
 

@@ -45,7 +45,8 @@ extern "C" {
  * clc_desc_cache_publish returns a handle).  4: the 'F' / 'H' models of the two-view filter (clc_two_view_acransac, _batch, clc_two_view_minimal);
  * the distance-ratio entries (clc_match_ratio_*, clc_match_map_ratio*, clc_ratio_matches_to_pairs) came later under 4: new entry points only;
  * so did the keypoint selection rule (clc_detect_set_selection, clc_detect_selection) and the device-side 2D-3D tracks
- * (clc_set_map_points, clc_track_build_dev, clc_track_localize_dev, clc_track_localize_batch_dev).
+ * (clc_set_map_points, clc_track_build_dev, clc_track_localize_dev, clc_track_localize_batch_dev) and two-view correspondences
+ * (clc_pair_build_dev, clc_pair_filter_dev, clc_pair_filter_batch_dev).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -773,6 +774,78 @@ int clc_track_localize_dev(clc_ctx* ctx, clc_track_job* job);
 int clc_track_localize_batch_dev(clc_ctx* const* ctxs, clc_track_job* jobs, int n_jobs);
 int clc_track_build_dev(clc_ctx* ctx, const clc_track_job* job, double* d_X, double* d_x, int32_t* d_query, int32_t* d_map,
                         int32_t* d_n, void* stream);
+
+/* ---- two-view correspondences on the device: replaces the gather of RobustMatcher::computeRelativePose (RobustMatcher.hpp:372-424,
+ * the loop at :393-398) -----------------------------------------------------------------------------------------------------------
+ * The twin of the track entries for the pair filter (filterMatches in initMap / updateMap, filterMatchesPair in interPoseEstimator,
+ * coloc.hpp:296): the pair's d_match stays on the GPU, the pair kernel turns it -- with the two cameras' keypoints -- into the
+ * undistorted correspondences x1 / x2, and the a-contrario solve of clc_two_view_acransac starts from them.  (Later under ABI 4: new
+ * entry points only.)
+ *
+ * A pair job.  Camera A = pair.first (the QUERY side of the match), camera B = pair.second (the TRAIN side).  All inputs are DEVICE
+ * memory:
+ *   d_match[nq]   query row of camera A -> train row of camera B, or -1, as clc_match_2nn_dev / clc_match_jobs_*_dev /
+ *                 clc_match_ratio_2nn_dev write it;
+ *   nt            rows of camera B; d_count_a / d_count_b nullable: the detectors' {written, found} words (clc_detect_buffers).  Rows
+ *                 q >= d_count_a[0] are ignored; a train index outside [0, min(nt, d_count_b[0])) counts as "no match" (the rule of
+ *                 clc_track_job);
+ *   the 2-D side  for each camera independently EITHER d_kps_* (level-local keypoints, position = scale * (float)x in float, the
+ *                 values of clc_keypoints_to_features) OR d_feat_* + feat_stride_* (float positions already scaled), as clc_track_job;
+ *   cam_a, cam_b  Pinhole_Intrinsic_Radial_K3 of the two cameras: both positions go through get_ud_pixel in fp64 in the host's
+ *                 operation order (the host's bits).
+ * The correspondences are the accepted queries in ASCENDING q -- the order GPUMatcher::computeMatches emits IndMatch(i, h_matches[i])
+ * (GPUMatcher.hpp:215-220); the a-contrario sampler is a function of the index set, so the order is part of the result.
+ *
+ * clc_pair_build_dev: the kernel alone, enqueue only on `stream` (capturable like the other _dev entries); writes d_x1 / d_x2 (2 N
+ * doubles each, undistorted PIXELS), d_pair_q / d_pair_t (N int32: the rows of camera A / B) and *d_n = N.  The output buffers hold
+ * job->nq pairs each; all but d_x1 and d_x2 are nullable.
+ *
+ * clc_pair_filter_dev: the pair launch, then the solve of clc_two_view_acransac under model 'E', 'F' or 'H' (both images img_w x img_h)
+ * from device memory, same result bit for bit as that entry gives for the host-gathered copy of the same correspondences; for 'E',
+ * K1 / K2 = { focal, 0, ppx; 0, focal, ppy; 0, 0, 1 } of cam_a / cam_b.  The conditioning of 'F' / 'H' (x * d + tx, y * d + ty) is
+ * applied by the staging launch on the device.  The host waits for ONE number, the pair count N; matches, keypoints and
+ * correspondences are never copied in either direction (no copy command is issued).  Host outputs (nullable): M 9 (E, F or H in
+ * pixels), F 9 (zeros for 'H'), pair_q / pair_t / inliers / inlier_mask with room for nq entries, x1 / x2 with room for 2 nq doubles
+ * (the undistorted pixels, from pinned mirrors the kernel writes).  N <= sample size (5, 7, 4): CLC_OK, n_inliers = 0;
+ * N > 16384: CLC_ERR_CAPACITY; both or neither of d_kps / d_feat for a camera, a misaligned pointer, a non-positive focal, an unknown
+ * model: CLC_ERR_BAD_ARG.  after_stream: as clc_track_job.
+ *
+ * clc_pair_filter_batch_dev: n jobs of ONE model, job i on ctxs[i] (a context of its own each, one device).  ONE pair launch for the
+ * batch on ctxs[0]'s stream, then the solves interleaved or in lockstep exactly as clc_two_view_acransac_batch runs them; every job's
+ * result is the single call's.  jobs[i].status per job; returns the first failure. */
+typedef struct clc_pair_job {
+    /* in */
+    const int32_t*      d_match;
+    int                 nq, nt;
+    const uint32_t*     d_count_a;      /* nullable */
+    const uint32_t*     d_count_b;      /* nullable */
+    const clc_keypoint* d_kps_a;        /* or */
+    const float*        d_feat_a;
+    int                 feat_stride_a;  /* floats per row of d_feat_a */
+    const clc_keypoint* d_kps_b;        /* or */
+    const float*        d_feat_b;
+    int                 feat_stride_b;
+    clc_camera_k3       cam_a, cam_b;
+    void*               after_stream;   /* nullable: the stream that produced d_match / the keypoints */
+    int                 img_w, img_h, max_iteration;
+    uint64_t            seed;
+    double              precision;      /* +inf: a-contrario threshold */
+    /* out (pointers nullable, host memory) */
+    double*             M;
+    double*             F;
+    int32_t*            pair_q;
+    int32_t*            pair_t;
+    double*             x1;
+    double*             x2;
+    int32_t*            inliers;
+    uint8_t*            inlier_mask;
+    int                 n_pairs, n_inliers, iterations, status;
+    double              error_max, min_nfa;
+} clc_pair_job;
+int clc_pair_filter_dev(clc_ctx* ctx, int model, clc_pair_job* job);
+int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* jobs, int n_jobs);
+int clc_pair_build_dev(clc_ctx* ctx, const clc_pair_job* job, double* d_x1, double* d_x2, int32_t* d_pair_q, int32_t* d_pair_t,
+                       int32_t* d_n, void* stream);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
