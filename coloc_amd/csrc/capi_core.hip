@@ -332,11 +332,11 @@ int clc_ctx_destroy(clc_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     void* bufs[] = { ctx->d_arena, ctx->d_kps, ctx->d_desc, ctx->d_score, ctx->d_kpmask, ctx->d_tcount, ctx->d_select, ctx->d_count, ctx->d_q, ctx->d_t, ctx->d_m, ctx->d_match,
-                     ctx->d_best, ctx->d_second, ctx->d_partial, ctx->d_pnp, ctx->d_pairs, ctx->d_map_X, ctx->d_trk, ctx->d_pair };
+                     ctx->d_best, ctx->d_second, ctx->d_partial, ctx->d_pnp, ctx->d_pairs, ctx->d_map_X, ctx->trk.d, ctx->pair.d };
     for (void* b : bufs)
         if (b) (void)hipFree(b);
-    if (ctx->h_trk) (void)hipHostFree(ctx->h_trk);
-    if (ctx->h_pair) (void)hipHostFree(ctx->h_pair);
+    if (ctx->trk.h) (void)hipHostFree(ctx->trk.h);
+    if (ctx->pair.h) (void)hipHostFree(ctx->pair.h);
     if (ctx->ev_track) (void)hipEventDestroy(ctx->ev_track);
     desc_drop_owner(ctx);                  // freeGPUMemory: what this context published dies with it
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);

@@ -53,6 +53,31 @@ struct DescEntry;
 enum { ROWS_NONE = 0, ROWS_STAGED = 1, ROWS_OWN = 2 };
 }
 
+namespace clc {
+// A context's block of gathered correspondences, device and pinned, for `cap` of them (ensure_gather):
+//   device [ a (a_width cap doubles) | b (2 cap) | q cap | t cap | n ]     tracks: X | x | query | map, pairs: x1 | x2 | q | t
+//   pinned [ count word (64 B, 0xFF.. = not out yet) | a | b (where the points are mirrored: pairs) | q | t ]
+struct GatherBlock { uint8_t* d = nullptr; uint8_t* h = nullptr; size_t cap = 0; };
+struct GatherLayout {
+    int a_width; bool mirror_points;
+    size_t d_row() const { return (size_t)(a_width + 2) * sizeof(double) + 2 * sizeof(int32_t); }
+    size_t h_row() const { return (mirror_points ? (size_t)(a_width + 2) * sizeof(double) : 0) + 2 * sizeof(int32_t); }
+};
+constexpr GatherLayout kTrackLayout{ 3, false }, kPairLayout{ 2, true };
+// the block as its arrays (h_a / h_b: null where the points are not mirrored)
+struct GatherView {
+    double *a, *b; int32_t *q, *t, *n; uint32_t* h_n; double *h_a = nullptr, *h_b = nullptr; int32_t *h_q, *h_t;
+    GatherView(const GatherBlock& g, const GatherLayout& lay)
+    {
+        a = (double*)g.d; b = a + lay.a_width * g.cap; q = (int32_t*)(b + 2 * g.cap); t = q + g.cap; n = t + g.cap;
+        h_n = (uint32_t*)g.h;
+        double* hp = (double*)(g.h + 64);
+        if (lay.mirror_points) { h_a = hp; h_b = hp + lay.a_width * g.cap; hp = h_b + 2 * g.cap; }
+        h_q = (int32_t*)hp; h_t = h_q + g.cap;
+    }
+};
+}
+
 struct clc_ctx {
     int device = 0;
     std::vector<float> acr_lg;   // (float) log10(k), k = 0 .. : the a-contrario tables are sums over it
@@ -107,17 +132,11 @@ struct clc_ctx {
     size_t pnp_cap = 0;   // doubles
     void* h_pin = nullptr;        // pinned staging for the pose solve
     size_t pin_cap = 0;
-    // 2D-3D tracks (track.hip)
+    // 2D-3D tracks and two-view correspondences (gather.hip)
     double* d_map_X = nullptr;    // clc_set_map_points: the landmark of map descriptor row i, 3 doubles each
     int map_X_n = -1, map_X_cap = 0;      // (-1: none set)
-    uint8_t* d_trk = nullptr;     // [ X 3 cap | x 2 cap | query cap | map cap | n ]: the tracks of this context's job (clc_track_localize*_dev)
-    uint8_t* h_trk = nullptr;     // pinned: [ count word (64 B) | query cap | map cap ]
-    size_t trk_cap = 0;           // tracks
+    clc::GatherBlock trk, pair;   // the tracks (clc_track_localize*_dev) / the pairs (clc_pair_filter*_dev) of this context's job
     hipEvent_t ev_track = nullptr;   // orders the track / pair launch behind job.after_stream, and the contexts' streams behind the launch
-    // two-view correspondences (pair.hip)
-    uint8_t* d_pair = nullptr;    // [ x1 2 cap | x2 2 cap | q cap | t cap | n ]: the pairs of this context's job (clc_pair_filter*_dev)
-    uint8_t* h_pair = nullptr;    // pinned: [ count word (64 B) | x1 2 cap | x2 2 cap | q cap | t cap ]
-    size_t pair_cap = 0;          // pairs
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     uint8_t* h_stage = nullptr;
@@ -157,6 +176,7 @@ int ensure_pnp(clc_ctx* ctx, size_t doubles);             // pose scratch
 int ensure_pinned(clc_ctx* ctx, size_t bytes);            // pinned staging of the pose solves
 int ensure_slots(clc_ctx* ctx, int n, hipStream_t st);    // pyramids (+ detector maps) of n cameras
 int ensure_results(clc_ctx* ctx, size_t bytes);           // pinned mirror of match results
+int ensure_gather(clc_ctx* ctx, GatherBlock& g, size_t cap, const GatherLayout& lay);      // a gather block (gather.hip)
 
 // a describing call begins: the rows of the last one no longer stand (staged_n = -1, desc_pending abandoned, rows_at = NONE)
 // (desc_cache.hip)

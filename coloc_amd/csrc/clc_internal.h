@@ -291,56 +291,53 @@ struct AcrChains { AcrChain c[kMaxBatch]; };
 hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream);
 // the inputs of n_chains solves, pinned host blocks -> device workspaces, in one launch
 // d_a / d_b / n_corr (all three or none; entries nullable): chain c's first a_width[c] n_corr[c] + 2 n_corr[c] doubles -- the solve's
-// a | b -- come from the DEVICE blocks d_a[c] and d_b[c] instead of the pinned block (the track kernel's X | x, track.hip: a_width 3, the
-// default; the pair kernel's x1 | x2, pair.hip: a_width 2); everything behind them still comes from the pinned block.  cond (nullable;
+// a | b -- come from the DEVICE blocks d_a[c] and d_b[c] instead of the pinned block (gather.hip; the track kernel's X | x: a_width 3, the
+// default; the pair kernel's x1 | x2: a_width 2); everything behind them still comes from the pinned block.  cond (nullable;
 // cond[c] = { d, tx, ty }, d == 0: none): the two-view 'F' / 'H' conditioning x * d + tx, y * d + ty of the device points on their way in
 hipError_t launch_acr_stage(const double* const* h_pinned, double* const* d_dst, const size_t* n_doubles /* even */, int n_chains,
                             hipStream_t stream, const double* const* d_a = nullptr, const double* const* d_b = nullptr,
                             const int* n_corr = nullptr, const int* a_width = nullptr, const double (*cond)[3] = nullptr);
 
-// ---- 2D-3D tracks (track.hip): Localizer::setupTracks on the device ---------------------------------------------------------------
-struct TrackJobDev {
-    const int32_t* match; const uint32_t* count; const clc_keypoint* kps; const float* feat;     // in (count nullable; kps or feat)
-    double* X; double* x; int32_t* query; int32_t* map; int32_t* n;                             // out, device (cap tracks; n nullable)
-    uint32_t* h_n; int32_t* h_query; int32_t* h_map;                                            // out, pinned host mirrors (nullable)
-    int nq, feat_stride, cap;
-    double focal, ppx, ppy, k1, k2, k3;
+// ---- the gathers (gather.hip): Localizer::setupTracks and the loop of RobustMatcher::computeRelativePose (RobustMatcher.hpp:393-398) ----
+// on the device.  ONE ordered compaction; a track writes x | X, a pair x1 | x2.
+struct UdCamera { double focal, ppx, ppy, k1, k2, k3; };              // Pinhole_Intrinsic_Radial_K3 (ud_pixel.h)
+// one 2-D side: rows of detector keypoints or of float feature positions (exactly one), and the camera that undistorts them
+struct GatherSide {
+    const uint32_t* count;                                              // nullable: the rows really there (a detector's counter)
+    const clc_keypoint* kps; const float* feat; int feat_stride;
+    UdCamera cam;
+};
+// what the compaction itself reads and writes
+struct GatherJob {
+    const int32_t* match; GatherSide a;                                 // in: row of side a (the query) -> train row, or -1
+    int nq, cap;                                                        // queries; most correspondences written
+    int32_t* n; uint32_t* h_n;                                          // out: the count, device and pinned (both nullable)
+};
+struct TrackJobDev : GatherJob {
+    double* X; double* x; int32_t* query; int32_t* map;                 // out, device (cap tracks; query / map nullable)
+    int32_t* h_query; int32_t* h_map;                                   // out, pinned host mirrors (nullable)
+};
+struct PairJobDev : GatherJob {
+    GatherSide b; int nt;                                               // in: the train side, camera B
+    double* x1; double* x2; int32_t* pair_q; int32_t* pair_t;           // out, device (cap pairs; pair_q / pair_t nullable)
+    int32_t* h_q; int32_t* h_t; double* h_x1; double* h_x2;             // out, pinned host mirrors (nullable)
 };
 struct TrackJobs {
     TrackJobDev j[kMaxBatch];
     const double* map_X; int map_n;
     float scale[CLC_MAX_LEVELS];      // (float) pow((double) 1.2f, level), from the host: clc_keypoints_to_features' values
 };
-// ONE launch for n_jobs <= kMaxBatch cameras (blockIdx.y = job); scale[] is filled in here
-hipError_t launch_track_build(TrackJobs& jobs, int n_jobs, hipStream_t stream);
-// validates a job's inputs against the context that holds the map points and fills the kernel's view of them (outputs are the caller's)
-int track_job_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, const char* who);
-// the context's own track block (device: X | x | query | map | n; pinned: word | query | map) for `cap` tracks
-int ensure_track(clc_ctx* ctx, size_t cap);
-
-// ---- two-view correspondences (pair.hip): RobustMatcher::computeRelativePose's gather (RobustMatcher.hpp:393-398) on the device ----
-struct PairSideDev {
-    const uint32_t* count; const clc_keypoint* kps; const float* feat;      // in (count nullable; kps or feat)
-    int feat_stride;
-    double focal, ppx, ppy, k1, k2, k3;
-};
-struct PairJobDev {
-    const int32_t* match;                                                   // in: query row of camera A -> train row of camera B, or -1
-    PairSideDev a, b;
-    double* x1; double* x2; int32_t* pair_q; int32_t* pair_t; int32_t* n;   // out, device (cap pairs; all but x1 / x2 nullable)
-    uint32_t* h_n; int32_t* h_q; int32_t* h_t; double* h_x1; double* h_x2;  // out, pinned host mirrors (nullable)
-    int nq, nt, cap;
-};
 struct PairJobs {
     PairJobDev j[kMaxBatch];
     float scale[CLC_MAX_LEVELS];      // as TrackJobs::scale
 };
-// ONE launch for n_jobs <= kMaxBatch pairs (blockIdx.y = job); scale[] is filled in here
-hipError_t launch_pair_build(PairJobs& jobs, int n_jobs, hipStream_t stream);
-// validates a job's inputs and fills the kernel's view of them (outputs are the caller's)
-int pair_job_inputs(clc_ctx* ctx, const clc_pair_job& job, PairJobDev& out, const char* who);
-// the context's own pair block (device: x1 | x2 | q | t | n; pinned: word | x1 | x2 | q | t) for `cap` pairs
-int ensure_pair(clc_ctx* ctx, size_t cap);
+// ONE launch for n_jobs <= kMaxBatch cameras / pairs (blockIdx.y = job); scale[] is filled in here
+hipError_t launch_gather(TrackJobs& jobs, int n_jobs, hipStream_t stream);
+hipError_t launch_gather(PairJobs& jobs, int n_jobs, hipStream_t stream);
+// validates a job's inputs (a track's against the context that holds the map points) and fills the kernel's view of them; the outputs
+// and cap are the caller's.  who: the text of a refused nq / nt / d_match
+int gather_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, const char* who);
+int gather_inputs(clc_ctx* ctx, const clc_pair_job& job, PairJobDev& out, const char* who);
 // the seven-point / four-point models (kind 2: <= 3 per sample, kind 3: 1) of S samples of normalised correspondences: d_out S x M x 9, NaN = no model
 hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_x2, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
 

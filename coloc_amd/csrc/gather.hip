@@ -1,0 +1,247 @@
+// gather.hip -- the two gathers that turn a matcher's d_match into the correspondences an a-contrario solve starts from, on the device,
+// without the frame or the pair going through the host (pose_batch.hip: clc_track_localize*_dev, clc_pair_filter*_dev):
+//   tracks  Localizer::setupTracks (reference include/coloc/Localizer.hpp:59-75): the detector's keypoints (or a block of feature
+//           positions) and the map's 3-D points -> undistorted x | X
+//   pairs   the gather of RobustMatcher::computeRelativePose (RobustMatcher.hpp:372-424, the loop at :393-398): the two cameras' keypoints
+//           (or feature positions) -> undistorted x1 | x2.  The points leave in PIXELS: the 'F' / 'H' conditioning is the staging launch's
+//           (acransac.hip: acr_stage_kernel), so the block and its pinned mirrors serve all three models.
+// Both are ONE ordered compaction (gather below) that differs only in what an accepted query writes.
+//
+// One launch for a batch of jobs, blockIdx.y = job, ONE workgroup per job: nq <= maxkp is 5-10 k (the solve takes at most 16 384
+// correspondences), a few KB in and a few tens of KB out -- the launch is latency-bound, and one workgroup keeps the ordered compaction a
+// matter of one ballot per wave and one 16-entry LDS scan per 1 024 queries.  The undistortion's loops are data-dependent and diverge;
+// at this size that does not matter.
+#include "clc_ctx.h"
+#include "ud_pixel.h"
+
+#include <cmath>
+#include <cstring>
+
+namespace clc {
+
+namespace {
+
+constexpr int kGatherThreads = 1024;
+
+// get_ud_pixel of row `row` of one 2-D side: the feature position, then ima2cam, radius by bisection, cam2ima (ud_pixel.h)
+__device__ __forceinline__ void side_pixel(const GatherSide& s, const uint32_t row, const float* scale, double* out)
+{
+    float fx, fy;
+    feature_position(s.kps, s.feat, s.feat_stride, row, scale, &fx, &fy);
+    ud_pixel(fx, fy, s.cam, out);
+}
+
+// What differs between the gathers: the train rows a match may name (the same in every thread) and what accepted query q -> train row m
+// writes as correspondence i.
+__device__ __forceinline__ int32_t train_rows(const TrackJobs& jobs, const TrackJobDev&) { return jobs.map_n; }
+__device__ __forceinline__ void emit(const TrackJobs& jobs, const TrackJobDev& jb, const uint32_t q, const int32_t m, const size_t i)
+{
+    side_pixel(jb.a, q, jobs.scale, jb.x + 2 * i);
+    const double* X = jobs.map_X + 3 * (size_t)m;
+    jb.X[3 * i] = X[0]; jb.X[3 * i + 1] = X[1]; jb.X[3 * i + 2] = X[2];
+    if (jb.query) jb.query[i] = (int32_t)q;
+    if (jb.map) jb.map[i] = m;
+    if (jb.h_query) jb.h_query[i] = (int32_t)q;
+    if (jb.h_map) jb.h_map[i] = m;
+}
+
+__device__ __forceinline__ int32_t train_rows(const PairJobs&, const PairJobDev& jb)
+{
+    int32_t nt = jb.nt > 0 ? jb.nt : 0;
+    if (jb.b.count) { const uint32_t c = jb.b.count[0]; nt = c < (uint32_t)nt ? (int32_t)c : nt; }
+    return nt;
+}
+__device__ __forceinline__ void emit(const PairJobs& jobs, const PairJobDev& jb, const uint32_t q, const int32_t m, const size_t i)
+{
+    double u1[2], u2[2];
+    side_pixel(jb.a, q, jobs.scale, u1);
+    side_pixel(jb.b, (uint32_t)m, jobs.scale, u2);
+    jb.x1[2 * i] = u1[0]; jb.x1[2 * i + 1] = u1[1];
+    jb.x2[2 * i] = u2[0]; jb.x2[2 * i + 1] = u2[1];
+    if (jb.pair_q) jb.pair_q[i] = (int32_t)q;
+    if (jb.pair_t) jb.pair_t[i] = m;
+    if (jb.h_q) jb.h_q[i] = (int32_t)q;
+    if (jb.h_t) jb.h_t[i] = m;
+    if (jb.h_x1) { jb.h_x1[2 * i] = u1[0]; jb.h_x1[2 * i + 1] = u1[1]; }
+    if (jb.h_x2) { jb.h_x2[2 * i] = u2[0]; jb.h_x2[2 * i + 1] = u2[1]; }
+}
+
+// The compaction, the ONE place that fixes the two rules the solves rest on: correspondence i is the i-th accepted query in ascending
+// query order (the sampler draws by position), and the count comes out last, behind a system-scope fence (the host reads the pinned
+// mirrors on the strength of that word).
+template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
+{
+    const auto& jb = jobs.j[blockIdx.y];
+    __shared__ uint32_t s_wave[kGatherThreads / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t nq = jb.nq > 0 ? (uint32_t)jb.nq : 0u;
+    if (jb.a.count) { const uint32_t c = jb.a.count[0]; nq = c < nq ? c : nq; }
+    const int32_t nt = train_rows(jobs, jb);
+    uint32_t base = 0;                                   // correspondences of the queries before this pass (the same in every thread)
+    for (uint32_t q0 = 0; q0 < nq; q0 += kGatherThreads) {
+        const uint32_t q = q0 + tid;
+        const int32_t m = q < nq ? jb.match[q] : -1;
+        const bool ok = m >= 0 && m < nt;
+        // ordered compaction: accepted lanes below this one in the wave (ballot + mbcnt), accepted queries of the waves before it (LDS)
+        const uint64_t b = __ballot(ok);
+        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
+        __syncthreads();
+        uint32_t off = base, total = 0;
+        for (uint32_t w = 0; w < kGatherThreads / 64; ++w) {
+            const uint32_t c = s_wave[w];
+            off += w < wave ? c : 0u;
+            total += c;
+        }
+        __syncthreads();                                 // (s_wave is written again in the next pass)
+        const uint32_t i = off + before;
+        if (ok && i < (uint32_t)jb.cap) emit(jobs, jb, q, m, (size_t)i);
+        base += total;
+    }
+    // the count comes out last: every wave's stores (device blocks and pinned mirrors) are complete and visible system-wide before the
+    // word the host polls changes
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+        if (jb.n) *jb.n = (int32_t)base;
+        if (jb.h_n) __hip_atomic_store(jb.h_n, base, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+// two instantiations, two kernels: each carries only its own emit
+__global__ __launch_bounds__(kGatherThreads) void track_build_kernel(const TrackJobs jobs) { gather(jobs); }
+__global__ __launch_bounds__(kGatherThreads) void pair_build_kernel(const PairJobs jobs) { gather(jobs); }
+
+template <class Jobs> hipError_t launch(void (*kernel)(const Jobs), Jobs& jobs, const int n_jobs, hipStream_t stream)
+{
+    if (n_jobs < 1 || n_jobs > kMaxBatch) return hipErrorInvalidValue;
+    // GPUDetector.hpp:173 through clc_keypoints_to_features: pow(float, integer) evaluated in double, rounded to float -- on the host
+    for (int l = 0; l < CLC_MAX_LEVELS; ++l) jobs.scale[l] = (float)std::pow((double)1.2f, (double)l);
+    hipLaunchKernelGGL(kernel, dim3(1, n_jobs), dim3(kGatherThreads), 0, stream, jobs);
+    return hipGetLastError();
+}
+
+// one 2-D side, validated ONCE for the track's camera and both cameras of a pair, into the kernel's view of it.  who: "track" / "pair"
+int gather_side(clc_ctx* ctx, const char* who, const uint32_t* count, const clc_keypoint* kps, const float* feat, const int stride,
+                const clc_camera_k3& cam, GatherSide& out)
+{
+    const auto bad = [&](const char* what) { return fail(ctx, CLC_ERR_BAD_ARG, (std::string(who) + what).c_str()); };
+    if ((kps != nullptr) == (feat != nullptr)) return bad(": exactly one of d_kps / d_feat per camera");
+    if (feat && stride < 2) return bad(": feat_stride < 2");
+    if (((uintptr_t)kps & 3u) || ((uintptr_t)feat & 3u) || ((uintptr_t)count & 3u)) return bad(": misaligned device pointer");
+    if (!(cam.focal > 0.0)) return bad(": focal must be positive");
+    out = GatherSide{ count, kps, feat, stride, UdCamera{ cam.focal, cam.ppx, cam.ppy, cam.k1, cam.k2, cam.k3 } };
+    return CLC_OK;
+}
+
+} // namespace
+
+hipError_t launch_gather(TrackJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(track_build_kernel, jobs, n_jobs, stream); }
+hipError_t launch_gather(PairJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(pair_build_kernel, jobs, n_jobs, stream); }
+
+int gather_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, const char* who)
+{
+    out = TrackJobDev{};
+    if (job.nq < 0 || (job.nq > 0 && !job.d_match)) return fail(ctx_map, CLC_ERR_BAD_ARG, who);
+    if ((uintptr_t)job.d_match & 3u) return fail(ctx_map, CLC_ERR_BAD_ARG, "track: misaligned device pointer");
+    const int rc = gather_side(ctx_map, "track", job.d_count, job.d_kps, job.d_feat, job.feat_stride, job.cam, out.a);
+    if (rc != CLC_OK) return rc;
+    out.match = job.d_match; out.nq = job.nq;
+    if (ctx_map->map_X_n < 0) return fail(ctx_map, CLC_ERR_STATE, "track before set_map_points");
+    if (ctx_map->map_n >= 0 && ctx_map->map_X_n < ctx_map->map_n)
+        return fail(ctx_map, CLC_ERR_STATE, "track: fewer map points (set_map_points) than map descriptors (set_map)");
+    return CLC_OK;
+}
+
+int gather_inputs(clc_ctx* ctx, const clc_pair_job& job, PairJobDev& out, const char* who)
+{
+    out = PairJobDev{};
+    if (job.nq < 0 || job.nt < 0 || (job.nq > 0 && !job.d_match)) return fail(ctx, CLC_ERR_BAD_ARG, who);
+    if ((uintptr_t)job.d_match & 3u) return fail(ctx, CLC_ERR_BAD_ARG, "pair: misaligned device pointer");
+    int rc = gather_side(ctx, "pair", job.d_count_a, job.d_kps_a, job.d_feat_a, job.feat_stride_a, job.cam_a, out.a);
+    if (rc == CLC_OK) rc = gather_side(ctx, "pair", job.d_count_b, job.d_kps_b, job.d_feat_b, job.feat_stride_b, job.cam_b, out.b);
+    out.match = job.d_match; out.nq = job.nq; out.nt = job.nt;
+    return rc;
+}
+
+int ensure_gather(clc_ctx* ctx, GatherBlock& g, size_t cap, const GatherLayout& lay)
+{
+    cap = (cap + 63) & ~(size_t)63;
+    if (cap < 64) cap = 64;
+    if (cap <= g.cap && g.d && g.h) return CLC_OK;
+    // (nothing of an earlier call is in flight: a solve returns after its staging launch has consumed the block)
+    if (g.d) { (void)hipFree(g.d); g.d = nullptr; }
+    if (g.h) { (void)hipHostFree(g.h); g.h = nullptr; }
+    g.cap = 0;
+    CLC_HIP(ctx, hipMalloc((void**)&g.d, cap * lay.d_row() + 64));
+    CLC_HIP(ctx, hipHostMalloc((void**)&g.h, 64 + cap * lay.h_row(), hipHostMallocDefault));
+    memset(g.h, 0xFF, 64);
+    g.cap = cap;
+    return CLC_OK;
+}
+
+} // namespace clc
+
+using namespace clc;
+
+extern "C" {
+
+int clc_set_map_points(clc_ctx* ctx, const double* h_X, int n)
+{
+    if (!ctx || n < 0 || (n > 0 && !h_X)) return fail(ctx, CLC_ERR_BAD_ARG, "set_map_points: bad argument");
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    if (n == 0) { ctx->map_X_n = -1; return CLC_OK; }
+    if (n > ctx->map_X_cap) {
+        CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->d_map_X) { (void)hipFree(ctx->d_map_X); ctx->d_map_X = nullptr; }
+        ctx->map_X_cap = 0; ctx->map_X_n = -1;
+        CLC_HIP(ctx, hipMalloc((void**)&ctx->d_map_X, (size_t)n * 3 * sizeof(double)));
+        ctx->map_X_cap = n;
+    }
+    ctx->map_X_n = -1;
+    CLC_HIP(ctx, hipMemcpyAsync(ctx->d_map_X, h_X, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->map_X_n = n;
+    return CLC_OK;
+}
+
+int clc_track_build_dev(clc_ctx* ctx, const clc_track_job* job, double* d_X, double* d_x, int32_t* d_query, int32_t* d_map, int32_t* d_n,
+                        void* stream)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "track_build: null context / job");
+    TrackJobs jobs{};
+    TrackJobDev& jb = jobs.j[0];
+    const int rc = gather_inputs(ctx, *job, jb, "track_build: bad argument");
+    if (rc != CLC_OK) return rc;
+    if (job->nq > 0 && (!d_X || !d_x)) return fail(ctx, CLC_ERR_BAD_ARG, "track_build: null output");
+    if (((uintptr_t)d_X & 7u) || ((uintptr_t)d_x & 7u) || ((uintptr_t)d_query & 3u) || ((uintptr_t)d_map & 3u) || ((uintptr_t)d_n & 3u))
+        return fail(ctx, CLC_ERR_BAD_ARG, "track_build: misaligned device pointer");
+    if (job->nq == 0 && !d_n) return CLC_OK;
+    jb.X = d_X; jb.x = d_x; jb.query = d_query; jb.map = d_map; jb.n = d_n;
+    jb.cap = job->nq;
+    jobs.map_X = ctx->d_map_X; jobs.map_n = ctx->map_X_n;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    CLC_HIP(ctx, launch_gather(jobs, 1, pick(ctx, stream)));
+    return CLC_OK;
+}
+
+int clc_pair_build_dev(clc_ctx* ctx, const clc_pair_job* job, double* d_x1, double* d_x2, int32_t* d_pair_q, int32_t* d_pair_t, int32_t* d_n,
+                       void* stream)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "pair_build: null context / job");
+    PairJobs jobs{};
+    PairJobDev& jb = jobs.j[0];
+    const int rc = gather_inputs(ctx, *job, jb, "pair_build: bad argument");
+    if (rc != CLC_OK) return rc;
+    if (job->nq > 0 && (!d_x1 || !d_x2)) return fail(ctx, CLC_ERR_BAD_ARG, "pair_build: null output");
+    if (((uintptr_t)d_x1 & 7u) || ((uintptr_t)d_x2 & 7u) || ((uintptr_t)d_pair_q & 3u) || ((uintptr_t)d_pair_t & 3u) || ((uintptr_t)d_n & 3u))
+        return fail(ctx, CLC_ERR_BAD_ARG, "pair_build: misaligned device pointer");
+    if (job->nq == 0 && !d_n) return CLC_OK;
+    jb.x1 = d_x1; jb.x2 = d_x2; jb.pair_q = d_pair_q; jb.pair_t = d_pair_t; jb.n = d_n;
+    jb.cap = job->nq;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    CLC_HIP(ctx, launch_gather(jobs, 1, pick(ctx, stream)));
+    return CLC_OK;
+}
+
+} // extern "C"

@@ -50,6 +50,17 @@ void acr_tables(int n, int m, float* logc_n, float* logc_k, std::vector<float>& 
 
 size_t dbl(size_t bytes) { return (bytes + 7) / 8; }
 
+// Every consumer stream behind what `producer` holds now: ONE event (ev: its owner's, created on first use) recorded on the producer and
+// waited for by the consumers, no host synchronisation; where an event call fails the host waits for the producer instead, and what that
+// synchronisation reports is returned.
+hipError_t order_behind(hipEvent_t& ev, hipStream_t producer, const hipStream_t* consumers, const size_t n)
+{
+    bool ok = (ev || hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) && hipEventRecord(ev, producer) == hipSuccess;
+    for (size_t i = 0; i < n && ok; ++i)
+        if (consumers[i] != producer) ok = hipStreamWaitEvent(consumers[i], ev, 0) == hipSuccess;
+    return ok ? hipSuccess : hipStreamSynchronize(producer);
+}
+
 // kind 0: a = X (3 N), b = x (2 N), K1 = intrinsics; kind 1: a = x1, b = x2 (2 N each), K1 / K2, image 2 of img_w x img_h;
 // kinds 2 / 3 (round 6: RobustMatcher's 'F' / 'H' models, RobustMatcher.hpp:128-151, :188-239): a = x1, b = x2 in pixels, both images
 // img_w x img_h -- the points are conditioned by the image size on their way into the pinned block (ACKernelAdaptor), the rounds are
@@ -64,7 +75,7 @@ struct AcrRun {
     clc_ctx* ctx = nullptr;
     int kind = 0, N = 0, img_w = 0, img_h = 0, max_iteration = 0;
     const double *h_a = nullptr, *h_b = nullptr, *h_K1 = nullptr, *h_K2 = nullptr;
-    // a | b from device memory: X | x of the track block (kind 0, track.hip) or x1 | x2 in pixels of the pair block (kinds 1-3, pair.hip);
+    // a | b from device memory: X | x of the track block (kind 0) or x1 | x2 in pixels of the pair block (kinds 1-3) of gather.hip;
     // they are staged from these blocks -- kinds 2 / 3 conditioned by the staging launch --, h_a / h_b unused
     const double *dev_a = nullptr, *dev_b = nullptr;
     uint64_t seed = 0;
@@ -389,10 +400,7 @@ struct AcrGroup {
         for (AcrRun* r : live) {
             r->st = st;
             clc_ctx* c = r->ctx;
-            if (c->stream == st) continue;
-            const bool ok = (c->ev_group || hipEventCreateWithFlags(&c->ev_group, hipEventDisableTiming) == hipSuccess) &&
-                            hipEventRecord(c->ev_group, c->stream) == hipSuccess && hipStreamWaitEvent(st, c->ev_group, 0) == hipSuccess;
-            if (!ok) (void)hipStreamSynchronize(c->stream);
+            if (c->stream != st) (void)order_behind(c->ev_group, c->stream, &st, 1);
         }
         // the inputs of all runs: one staging launch per kMaxBatch of them
         for (size_t k = 0; k < live.size(); k += kMaxBatch) {
@@ -474,14 +482,9 @@ struct AcrGroup {
     {
         running = false;
         if (std::all_of(live.begin(), live.end(), [&](const AcrRun* r) { return r->ctx->stream == st; })) return;
-        clc_ctx* ctx0 = live[0]->ctx;
-        bool ordered = false;
-        if (ctx0->ev_group || hipEventCreateWithFlags(&ctx0->ev_group, hipEventDisableTiming) == hipSuccess) {
-            ordered = hipEventRecord(ctx0->ev_group, st) == hipSuccess;
-            for (AcrRun* r : live)
-                if (ordered && r->ctx->stream != st) ordered = hipStreamWaitEvent(r->ctx->stream, ctx0->ev_group, 0) == hipSuccess;
-        }
-        if (!ordered) (void)hipStreamSynchronize(st);
+        std::vector<hipStream_t> own;
+        for (const AcrRun* r : live) own.push_back(r->ctx->stream);
+        (void)order_behind(live[0]->ctx->ev_group, st, own.data(), own.size());
     }
 };
 
@@ -534,19 +537,25 @@ void acr_drive(AcrRun* runs, const int n, const bool shared)
     }
 }
 
-int acr_impl(clc_ctx* ctx, int kind, const double* h_a, const double* h_b, int N, const double* h_K1, const double* h_K2, int img_w,
-             int img_h, int max_iteration, uint64_t seed, double precision, double refine_huber, double* h_model, uint8_t* h_mask,
-             int32_t* h_inliers, int* n_inliers, double* error_max, double* min_nfa, int* iterations, int* rounds, double* h_cov,
-             double* rmse)
+// a single solve whose arguments are in `run`
+int solve_one(AcrRun& run)
 {
-    AcrRun run;
-    run.ctx = ctx; run.kind = kind; run.h_a = h_a; run.h_b = h_b; run.N = N; run.h_K1 = h_K1; run.h_K2 = h_K2; run.img_w = img_w; run.img_h = img_h;
-    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision; run.refine_huber = refine_huber;
-    run.h_model = h_model; run.h_mask = h_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
-    run.min_nfa = min_nfa; run.iterations = iterations; run.rounds = rounds; run.h_cov = h_cov; run.rmse = rmse;
     acr_drive(&run, 1, false);
     run.finish();
     return run.status;
+}
+
+// The end of a batch: every run's result into its caller's buffers, then per_job(i, status of run i) for what the entry point adds (the
+// job's status, its copies); returns the first failure.
+template <class F> int finish_all(std::vector<AcrRun>& runs, F&& per_job)
+{
+    int first = CLC_OK;
+    for (size_t i = 0; i < runs.size(); ++i) {
+        runs[i].finish();
+        per_job(i, runs[i].status);
+        if (runs[i].status != CLC_OK && first == CLC_OK) first = runs[i].status;
+    }
+    return first;
 }
 
 } // namespace
@@ -558,8 +567,12 @@ int clc_pnp_acransac(clc_ctx* ctx, const double* h_X, const double* h_x, int N, 
                      double* min_nfa, int* iterations)
 {
     if (h_Rt) memset(h_Rt, 0, sizeof(double) * 12);
-    return acr_impl(ctx, 0, h_X, h_x, N, h_K, nullptr, 0, 0, max_iteration, seed, precision, -1.0, h_Rt, h_inlier_mask, h_inliers, n_inliers,
-                    error_max, min_nfa, iterations, nullptr, nullptr, nullptr);
+    AcrRun run;
+    run.ctx = ctx; run.kind = 0; run.h_a = h_X; run.h_b = h_x; run.N = N; run.h_K1 = h_K;
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
+    run.h_model = h_Rt; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
+    run.min_nfa = min_nfa; run.iterations = iterations;
+    return solve_one(run);
 }
 
 int clc_pnp_localize_ac(clc_ctx* ctx, const double* h_X, const double* h_x, int N, const double* h_K, int max_iteration, uint64_t seed,
@@ -569,8 +582,12 @@ int clc_pnp_localize_ac(clc_ctx* ctx, const double* h_X, const double* h_x, int 
     if (h_Rt) memset(h_Rt, 0, sizeof(double) * 12);
     if (h_cov) memset(h_cov, 0, sizeof(double) * 36);
     if (rmse) *rmse = 0.0;
-    return acr_impl(ctx, 0, h_X, h_x, N, h_K, nullptr, 0, 0, max_iteration, seed, precision, huber_a > 0.0 ? huber_a : 16.0, h_Rt,
-                    h_inlier_mask, h_inliers, n_inliers, error_max, nullptr, nullptr, nullptr, h_cov, rmse);
+    AcrRun run;
+    run.ctx = ctx; run.kind = 0; run.h_a = h_X; run.h_b = h_x; run.N = N; run.h_K1 = h_K;
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision; run.refine_huber = huber_a > 0.0 ? huber_a : 16.0;
+    run.h_model = h_Rt; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
+    run.h_cov = h_cov; run.rmse = rmse;
+    return solve_one(run);
 }
 
 int clc_pnp_localize_ac_batch(clc_ctx* const* ctxs, clc_pose_job* jobs, int n_jobs)
@@ -593,26 +610,15 @@ int clc_pnp_localize_ac_batch(clc_ctx* const* ctxs, clc_pose_job* jobs, int n_jo
         r.iterations = &jb.iterations; r.h_cov = jb.cov; r.rmse = &jb.rmse;
     }
     acr_drive(runs.data(), n_jobs, acr_lockstep(0, n_jobs));
-    int worst = CLC_OK;
-    for (int i = 0; i < n_jobs; ++i) {
-        AcrRun& r = runs[(size_t)i];
-        r.finish();
-        jobs[i].status = r.status;
-        if (r.status != CLC_OK && worst == CLC_OK) worst = r.status;
-    }
-    return worst;
+    return finish_all(runs, [&](const size_t i, const int status) { jobs[i].status = status; });
 }
 
 int clc_essential_acransac(clc_ctx* ctx, const double* h_x1, const double* h_x2, int N, const double* h_K1, const double* h_K2,
                            int img_w, int img_h, int max_iteration, uint64_t seed, double precision, double* h_E, double* h_F,
                            uint8_t* h_inlier_mask, int32_t* h_inliers, int* n_inliers, double* error_max, double* min_nfa, int* iterations)
 {
-    double EF[18] = {};
-    const int rc = acr_impl(ctx, 1, h_x1, h_x2, N, h_K1, h_K2, img_w, img_h, max_iteration, seed, precision, -1.0, EF, h_inlier_mask,
-                            h_inliers, n_inliers, error_max, min_nfa, iterations, nullptr, nullptr, nullptr);
-    if (h_E) memcpy(h_E, EF, sizeof(double) * 9);
-    if (h_F) memcpy(h_F, EF + 9, sizeof(double) * 9);
-    return rc;
+    return clc_two_view_acransac(ctx, CLC_MODEL_ESSENTIAL, h_x1, h_x2, N, h_K1, h_K2, img_w, img_h, max_iteration, seed, precision, h_E, h_F,
+                                 h_inlier_mask, h_inliers, n_inliers, error_max, min_nfa, iterations);
 }
 
 // RobustMatcher's model letter -> the solve kind (colocParams::model, RobustMatcher.hpp:399-405)
@@ -624,14 +630,17 @@ int clc_two_view_acransac(clc_ctx* ctx, int model, const double* h_x1, const dou
 {
     const int kind = two_view_kind(model);
     if (kind < 0) return fail(ctx, CLC_ERR_BAD_ARG, "two_view_acransac: model must be 'E', 'F' or 'H'");
-    if (kind == 1)
-        return clc_essential_acransac(ctx, h_x1, h_x2, N, h_K1, h_K2, img_w, img_h, max_iteration, seed, precision, h_M, h_F, h_inlier_mask,
-                                      h_inliers, n_inliers, error_max, min_nfa, iterations);
-    double M9[9] = {};
-    const int rc = acr_impl(ctx, kind, h_x1, h_x2, N, nullptr, nullptr, img_w, img_h, max_iteration, seed, precision, -1.0, M9, h_inlier_mask,
-                            h_inliers, n_inliers, error_max, min_nfa, iterations, nullptr, nullptr, nullptr);
-    if (h_M) memcpy(h_M, M9, sizeof M9);
-    if (h_F) { if (kind == 2) memcpy(h_F, M9, sizeof M9); else memset(h_F, 0, sizeof M9); }
+    // the model as the solve leaves it: { E, F } (kind 1), F or H (kinds 2 / 3: F = the model for 'F', zeros for 'H')
+    double EF[18] = {};
+    AcrRun run;
+    run.ctx = ctx; run.kind = kind; run.h_a = h_x1; run.h_b = h_x2; run.N = N; run.img_w = img_w; run.img_h = img_h;
+    if (kind == 1) { run.h_K1 = h_K1; run.h_K2 = h_K2; }
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
+    run.h_model = EF; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
+    run.min_nfa = min_nfa; run.iterations = iterations;
+    const int rc = solve_one(run);
+    if (h_M) memcpy(h_M, EF, sizeof(double) * 9);
+    if (h_F) memcpy(h_F, kind == 2 ? EF : EF + 9, sizeof(double) * 9);
     return rc;
 }
 
@@ -704,16 +713,11 @@ int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int 
     std::vector<double> EF((size_t)18 * n_jobs, 0.0);
     for (int i = 0; i < n_jobs; ++i) two_view_run(runs[(size_t)i], ctxs[i], *jobs[i], &EF[(size_t)18 * i], kind);
     acr_drive(runs.data(), n_jobs, acr_lockstep(kind, n_jobs));
-    int worst = CLC_OK;
-    for (int i = 0; i < n_jobs; ++i) {
-        AcrRun& r = runs[(size_t)i];
-        r.finish();
-        jobs[i]->status = r.status;
-        if (jobs[i]->E) memcpy(jobs[i]->E, &EF[(size_t)18 * i], sizeof(double) * 9);
-        if (jobs[i]->F) memcpy(jobs[i]->F, &EF[(size_t)18 * i + (kind == 1 ? 9 : (kind == 2 ? 0 : 9))], sizeof(double) * 9);
-        if (r.status != CLC_OK && worst == CLC_OK) worst = r.status;
-    }
-    return worst;
+    return finish_all(runs, [&](const size_t i, const int status) {
+        jobs[i]->status = status;
+        if (jobs[i]->E) memcpy(jobs[i]->E, &EF[18 * i], sizeof(double) * 9);
+        if (jobs[i]->F) memcpy(jobs[i]->F, &EF[18 * i + (kind == 2 ? 0 : 9)], sizeof(double) * 9);
+    });
 }
 
 } // namespace clc
@@ -745,41 +749,104 @@ int clc_two_view_acransac_batch(clc_ctx* const* ctxs, int model, clc_two_view_jo
 
 } // extern "C"
 
-// ---- Localizer::localizeImage from device tracks (include/coloc_hip.h: clc_track_localize*_dev) ----------------------------------------
-// The track kernel (track.hip) writes each job's correspondences into its context's track block and the count N into a pinned word; the
-// host waits for that one number -- AcrRun::begin_body lays the workspace out by N and builds the N-dependent NFA tables --, then the
-// runs go through acr_drive like every other solve.  The staging launch reads TWO sources per run: a | b from the track block, K, the
-// tables and the initial state from the pinned block (launch_acr_stage); no gather launch of its own, and nothing sized by N sits in
-// front of the count.
+// ---- the solves that start from device matches (include/coloc_hip.h: clc_track_localize*_dev, clc_pair_filter*_dev) -------------------
+// Localizer::localizeImage from device tracks, RobustMatcher::computeRelativePose from device pairs.  The gather kernel (gather.hip) writes
+// each job's correspondences into its context's block -- the pairs in PIXELS -- and the count N into a pinned word; the host waits for
+// that one number -- AcrRun::begin_body lays the workspace out by N and builds the N-dependent NFA tables --, then the runs go through
+// acr_drive like every other solve.  The staging launch reads TWO sources per run: a | b from the block -- conditioned for 'F' / 'H' on
+// the way, where it costs no launch and leaves the block's pinned mirrors in pixels for the pose from E --, K, the tables and the initial
+// state from the pinned block (launch_acr_stage); no gather launch of its own, and nothing sized by N sits in front of the count.
 namespace {
 
-// the track block of a context (ensure_track): [ X 3 cap | x 2 cap | query cap | map cap | n ]
-struct TrackBlock {
-    double *X, *x; int32_t *query, *map, *n; uint32_t* h_n; int32_t *h_query, *h_map;
-    explicit TrackBlock(const clc_ctx* c)
+// What differs between the two paths, for gather_solve: the job, its block, the outputs it asks the kernel for, its solve and its results.
+// K / model: 18 doubles each of the driver's, alive until the job's results are out.
+struct TrackPath {
+    using Job = clc_track_job; using Dev = TrackJobDev; using Jobs = TrackJobs;
+    static constexpr const char* who = "track_localize";
+    static constexpr GatherLayout layout = kTrackLayout;
+    static GatherBlock& block(clc_ctx* c) { return c->trk; }
+    static int& count(Job& jb) { return jb.n_tracks; }
+    static void reset(Job& jb)
     {
-        const size_t cap = c->trk_cap;
-        X = (double*)c->d_trk; x = X + 3 * cap; query = (int32_t*)(x + 2 * cap); map = query + cap; n = map + cap;
-        h_n = (uint32_t*)c->h_trk; h_query = (int32_t*)(c->h_trk + 64); h_map = h_query + cap;
-    }
-};
-
-int track_localize(clc_ctx* const* ctxs, clc_track_job* jobs, const int n_jobs)
-{
-    clc_ctx* c0 = ctxs[0];
-    for (int i = 0; i < n_jobs; ++i) {
-        clc_track_job& jb = jobs[i];
         if (jb.Rt) memset(jb.Rt, 0, sizeof(double) * 12);
         if (jb.cov) memset(jb.cov, 0, sizeof(double) * 36);
         jb.n_tracks = 0; jb.n_inliers = 0; jb.iterations = 0; jb.status = CLC_OK; jb.error_max = 0.0; jb.rmse = 0.0;
     }
+    static void pack(Jobs& p, const clc_ctx* c0) { p.map_X = c0->d_map_X; p.map_n = c0->map_X_n; }
+    static void outputs(Dev& d, const GatherView& v, const Job& jb)
+    {
+        d.X = v.a; d.x = v.b; d.query = v.q; d.map = v.t;
+        d.h_query = jb.track_query ? v.h_q : nullptr;
+        d.h_map = jb.track_map ? v.h_t : nullptr;
+    }
+    static void solve(AcrRun& r, Job& jb, int, double* K, double*)
+    {
+        K[0] = jb.cam.focal; K[2] = jb.cam.ppx; K[4] = jb.cam.focal; K[5] = jb.cam.ppy; K[8] = 1.0;      // Pinhole_Intrinsic_Radial_K3::K()
+        r.h_K1 = K;
+        r.refine_huber = jb.refine ? (jb.huber_a > 0.0 ? jb.huber_a : 16.0) : -1.0;
+        r.h_model = jb.Rt; r.h_cov = jb.cov; r.rmse = &jb.rmse;
+    }
+    // trackedFeatures
+    static void results(Job& jb, const GatherView& v, const size_t n, int, const double*)
+    {
+        if (jb.track_query && n) memcpy(jb.track_query, v.h_q, sizeof(int32_t) * n);
+        if (jb.track_map && n) memcpy(jb.track_map, v.h_t, sizeof(int32_t) * n);
+    }
+};
+
+struct PairPath {
+    using Job = clc_pair_job; using Dev = PairJobDev; using Jobs = PairJobs;
+    static constexpr const char* who = "pair_filter";
+    static constexpr GatherLayout layout = kPairLayout;
+    static GatherBlock& block(clc_ctx* c) { return c->pair; }
+    static int& count(Job& jb) { return jb.n_pairs; }
+    static void reset(Job& jb)
+    {
+        if (jb.M) memset(jb.M, 0, sizeof(double) * 9);
+        if (jb.F) memset(jb.F, 0, sizeof(double) * 9);
+        jb.n_pairs = 0; jb.n_inliers = 0; jb.iterations = 0; jb.status = CLC_OK; jb.error_max = 0.0; jb.min_nfa = INFINITY;
+    }
+    static void pack(Jobs&, const clc_ctx*) {}
+    static void outputs(Dev& d, const GatherView& v, const Job& jb)
+    {
+        d.x1 = v.a; d.x2 = v.b; d.pair_q = v.q; d.pair_t = v.t;
+        d.h_q = jb.pair_q ? v.h_q : nullptr;
+        d.h_t = jb.pair_t ? v.h_t : nullptr;
+        d.h_x1 = jb.x1 ? v.h_a : nullptr;
+        d.h_x2 = jb.x2 ? v.h_b : nullptr;
+    }
+    static void solve(AcrRun& r, Job& jb, const int kind, double* K, double* model)
+    {
+        K[0] = jb.cam_a.focal; K[2] = jb.cam_a.ppx; K[4] = jb.cam_a.focal; K[5] = jb.cam_a.ppy; K[8] = 1.0;      // Pinhole_Intrinsic_Radial_K3::K()
+        K[9] = jb.cam_b.focal; K[11] = jb.cam_b.ppx; K[13] = jb.cam_b.focal; K[14] = jb.cam_b.ppy; K[17] = 1.0;  // of the two cameras
+        if (kind == 1) { r.h_K1 = K; r.h_K2 = K + 9; }
+        r.img_w = jb.img_w; r.img_h = jb.img_h;
+        r.h_model = model; r.min_nfa = &jb.min_nfa;
+    }
+    // kind 1: the slots hold { E, F }; kinds 2 / 3: the model matrix, F = it ('F') or zeros ('H') -- as clc_two_view_acransac
+    static void results(Job& jb, const GatherView& v, const size_t n, const int kind, const double* model)
+    {
+        if (jb.M) memcpy(jb.M, model, sizeof(double) * 9);
+        if (jb.F && kind != 3) memcpy(jb.F, kind == 1 ? model + 9 : model, sizeof(double) * 9);
+        if (jb.pair_q && n) memcpy(jb.pair_q, v.h_q, sizeof(int32_t) * n);
+        if (jb.pair_t && n) memcpy(jb.pair_t, v.h_t, sizeof(int32_t) * n);
+        if (jb.x1 && n) memcpy(jb.x1, v.h_a, sizeof(double) * 2 * n);
+        if (jb.x2 && n) memcpy(jb.x2, v.h_b, sizeof(double) * 2 * n);
+    }
+};
+
+template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typename Path::Job* jobs, const int n_jobs)
+{
+    clc_ctx* c0 = ctxs[0];
+    const std::string who = Path::who;
+    for (int i = 0; i < n_jobs; ++i) Path::reset(jobs[i]);
     CLC_HIP(c0, hipSetDevice(c0->device));
     hipStream_t st = c0->stream;
-    std::vector<TrackJobDev> dev((size_t)n_jobs);
+    std::vector<typename Path::Dev> dev((size_t)n_jobs);
     for (int i = 0; i < n_jobs; ++i) {
-        int rc = track_job_inputs(c0, jobs[i], dev[(size_t)i], "track_localize: bad argument");
-        if (rc == CLC_OK && jobs[i].max_iteration < 0) rc = fail(c0, CLC_ERR_BAD_ARG, "track_localize: negative max_iteration");
-        if (rc == CLC_OK) rc = ensure_track(ctxs[i], (size_t)std::min(jobs[i].nq, kAcrMaxN));
+        int rc = gather_inputs(c0, jobs[i], dev[(size_t)i], (who + ": bad argument").c_str());
+        if (rc == CLC_OK && jobs[i].max_iteration < 0) rc = fail(c0, CLC_ERR_BAD_ARG, (who + ": negative max_iteration").c_str());
+        if (rc == CLC_OK) rc = ensure_gather(ctxs[i], Path::block(ctxs[i]), (size_t)std::min(jobs[i].nq, kAcrMaxN), Path::layout);
         if (rc != CLC_OK) {
             if (ctxs[i] != c0) (void)fail(ctxs[i], rc, clc_last_error_string(c0));
             jobs[i].status = rc;
@@ -789,79 +856,63 @@ int track_localize(clc_ctx* const* ctxs, clc_track_job* jobs, const int n_jobs)
     // behind whatever produced the inputs: an event on the producer's stream, no host synchronisation
     for (int i = 0; i < n_jobs; ++i) {
         hipStream_t prod = (hipStream_t)jobs[i].after_stream;
-        if (!prod || prod == st) continue;
-        clc_ctx* c = ctxs[i];
-        const bool ok = (c->ev_track || hipEventCreateWithFlags(&c->ev_track, hipEventDisableTiming) == hipSuccess) &&
-                        hipEventRecord(c->ev_track, prod) == hipSuccess && hipStreamWaitEvent(st, c->ev_track, 0) == hipSuccess;
-        if (!ok) CLC_HIP(c, hipStreamSynchronize(prod));
+        if (prod && prod != st) CLC_HIP(ctxs[i], order_behind(ctxs[i]->ev_track, prod, &st, 1));
     }
-    // the tracks of all jobs: one launch per kMaxBatch of them
+    // the correspondences of all jobs: one launch per kMaxBatch of them
     for (int k = 0; k < n_jobs; k += kMaxBatch) {
         const int n = std::min(kMaxBatch, n_jobs - k);
-        TrackJobs pack{};
-        pack.map_X = c0->d_map_X; pack.map_n = c0->map_X_n;
+        typename Path::Jobs pack{};
+        Path::pack(pack, c0);
         for (int i = 0; i < n; ++i) {
-            const TrackBlock tb(ctxs[k + i]);
-            TrackJobDev& d = dev[(size_t)(k + i)];
-            d.X = tb.X; d.x = tb.x; d.query = tb.query; d.map = tb.map; d.n = tb.n;
-            d.h_n = tb.h_n;
-            d.h_query = jobs[k + i].track_query ? tb.h_query : nullptr;
-            d.h_map = jobs[k + i].track_map ? tb.h_map : nullptr;
+            const GatherView v(Path::block(ctxs[k + i]), Path::layout);
+            typename Path::Dev& d = dev[(size_t)(k + i)];
+            d.n = v.n; d.h_n = v.h_n;
             d.cap = std::min(jobs[k + i].nq, kAcrMaxN);
-            __atomic_store_n(tb.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
+            Path::outputs(d, v, jobs[k + i]);
+            __atomic_store_n(v.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
             pack.j[i] = d;
         }
-        CLC_HIP(c0, launch_track_build(pack, n, st));
+        CLC_HIP(c0, launch_gather(pack, n, st));
     }
-    const bool shared = acr_lockstep(0, n_jobs);
+    const bool shared = acr_lockstep(kind, n_jobs);
     if (!shared && n_jobs > 1) {
-        // every other run stages from its track block on its context's OWN stream: behind the track launch
-        bool ordered = (c0->ev_track || hipEventCreateWithFlags(&c0->ev_track, hipEventDisableTiming) == hipSuccess) &&
-                       hipEventRecord(c0->ev_track, st) == hipSuccess;
-        for (int i = 1; i < n_jobs && ordered; ++i) ordered = hipStreamWaitEvent(ctxs[i]->stream, c0->ev_track, 0) == hipSuccess;
-        if (!ordered) CLC_HIP(c0, hipStreamSynchronize(st));
+        // every other run stages from its block on its context's OWN stream: behind the gather launch
+        std::vector<hipStream_t> own;
+        for (int i = 0; i < n_jobs; ++i) own.push_back(ctxs[i]->stream);
+        CLC_HIP(c0, order_behind(c0->ev_track, st, own.data(), own.size()));
     }
     // the one number the host needs: poll the pinned words, the stream synchronisation as the fallback (which also surfaces errors)
     std::vector<AcrRun> runs((size_t)n_jobs);
-    std::vector<double> Ks((size_t)9 * n_jobs, 0.0);
+    std::vector<double> Ks((size_t)18 * n_jobs, 0.0), models((size_t)18 * n_jobs, 0.0);
     const auto t0 = std::chrono::steady_clock::now();
     bool synced = false;
     for (int i = 0; i < n_jobs; ++i) {
-        const TrackBlock tb(ctxs[i]);
-        uint32_t w = __atomic_load_n(tb.h_n, __ATOMIC_ACQUIRE);
-        for (uint32_t spins = 0; w == 0xFFFFFFFFu; w = __atomic_load_n(tb.h_n, __ATOMIC_ACQUIRE)) {
-            if (synced) return fail(c0, CLC_ERR_HIP, "track_localize: the track launch left no count");
+        const GatherView v(Path::block(ctxs[i]), Path::layout);
+        uint32_t w = __atomic_load_n(v.h_n, __ATOMIC_ACQUIRE);
+        for (uint32_t spins = 0; w == 0xFFFFFFFFu; w = __atomic_load_n(v.h_n, __ATOMIC_ACQUIRE)) {
+            if (synced) return fail(c0, CLC_ERR_HIP, (who + ": the gather launch left no count").c_str());
             if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
                 CLC_HIP(c0, hipStreamSynchronize(st));
                 synced = true;
             }
         }
-        clc_track_job& jb = jobs[i];
-        jb.n_tracks = (int)w;
-        double* K = &Ks[(size_t)9 * i];
-        K[0] = jb.cam.focal; K[2] = jb.cam.ppx; K[4] = jb.cam.focal; K[5] = jb.cam.ppy; K[8] = 1.0;      // Pinhole_Intrinsic_Radial_K3::K()
+        typename Path::Job& jb = jobs[i];
+        Path::count(jb) = (int)w;
         AcrRun& r = runs[(size_t)i];
-        r.ctx = ctxs[i]; r.kind = 0; r.N = jb.n_tracks; r.dev_a = tb.X; r.dev_b = tb.x; r.h_K1 = K;
+        r.ctx = ctxs[i]; r.kind = kind; r.N = (int)w; r.dev_a = v.a; r.dev_b = v.b;
         r.max_iteration = jb.max_iteration; r.seed = jb.seed; r.precision = jb.precision;
-        r.refine_huber = jb.refine ? (jb.huber_a > 0.0 ? jb.huber_a : 16.0) : -1.0;
-        r.h_model = jb.Rt; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers; r.error_max = &jb.error_max;
-        r.iterations = &jb.iterations; r.h_cov = jb.cov; r.rmse = &jb.rmse;
+        r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers; r.error_max = &jb.error_max;
+        r.iterations = &jb.iterations;
+        Path::solve(r, jb, kind, &Ks[(size_t)18 * i], &models[(size_t)18 * i]);
     }
     acr_drive(runs.data(), n_jobs, shared);
-    int worst = CLC_OK;
-    for (int i = 0; i < n_jobs; ++i) {
-        AcrRun& r = runs[(size_t)i];
-        clc_track_job& jb = jobs[i];
-        r.finish();
-        jb.status = r.status;
-        // trackedFeatures: the kernel wrote the pinned mirrors before the count came out
-        const TrackBlock tb(ctxs[i]);
-        const size_t nt = (size_t)std::min(jb.n_tracks, std::min(jb.nq, kAcrMaxN));
-        if (jb.track_query && nt) memcpy(jb.track_query, tb.h_query, sizeof(int32_t) * nt);
-        if (jb.track_map && nt) memcpy(jb.track_map, tb.h_map, sizeof(int32_t) * nt);
-        if (r.status != CLC_OK && worst == CLC_OK) worst = r.status;
-    }
-    return worst;
+    return finish_all(runs, [&](const size_t i, const int status) {
+        typename Path::Job& jb = jobs[i];
+        jb.status = status;
+        // the kernel wrote the pinned mirrors before the count came out
+        const GatherView v(Path::block(ctxs[i]), Path::layout);
+        Path::results(jb, v, (size_t)std::min(Path::count(jb), std::min(jb.nq, kAcrMaxN)), kind, &models[18 * i]);
+    });
 }
 
 } // namespace
@@ -874,148 +925,14 @@ int clc_track_localize_batch_dev(clc_ctx* const* ctxs, clc_track_job* jobs, int 
     if (n_jobs == 0) return CLC_OK;
     const int rc0 = check_batch_contexts(ctxs, n_jobs, "track_localize_batch: every job needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
-    return track_localize(ctxs, jobs, n_jobs);
+    return gather_solve<TrackPath>(ctxs, 0, jobs, n_jobs);
 }
 
 int clc_track_localize_dev(clc_ctx* ctx, clc_track_job* job)
 {
     if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "track_localize: null context / job");
-    return track_localize(&ctx, job, 1);
+    return gather_solve<TrackPath>(&ctx, 0, job, 1);
 }
-
-} // extern "C"
-
-// ---- RobustMatcher::computeRelativePose from device matches (include/coloc_hip.h: clc_pair_filter*_dev) ---------------------------------
-// The track path's twin.  The pair kernel (pair.hip) writes each job's correspondences, in PIXELS, into its context's pair block and the
-// count N into a pinned word; the host waits for that one number, then the runs go through acr_drive like every other two-view solve.
-// The staging launch reads x1 | x2 from the pair block -- and conditions them for 'F' / 'H' on the way, where it costs no launch and
-// leaves the block's pinned mirrors in pixels for the pose from E --, K1 / K2, the tables and the initial state from the pinned block.
-namespace {
-
-// the pair block of a context (ensure_pair): device [ x1 2 cap | x2 2 cap | q cap | t cap | n ], pinned [ word (64 B) | x1 | x2 | q | t ]
-struct PairBlock {
-    double *x1, *x2; int32_t *q, *t, *n; uint32_t* h_n; double *h_x1, *h_x2; int32_t *h_q, *h_t;
-    explicit PairBlock(const clc_ctx* c)
-    {
-        const size_t cap = c->pair_cap;
-        x1 = (double*)c->d_pair; x2 = x1 + 2 * cap; q = (int32_t*)(x2 + 2 * cap); t = q + cap; n = t + cap;
-        h_n = (uint32_t*)c->h_pair; h_x1 = (double*)(c->h_pair + 64); h_x2 = h_x1 + 2 * cap; h_q = (int32_t*)(h_x2 + 2 * cap); h_t = h_q + cap;
-    }
-};
-
-int pair_filter(clc_ctx* const* ctxs, const int kind, clc_pair_job* jobs, const int n_jobs)
-{
-    clc_ctx* c0 = ctxs[0];
-    for (int i = 0; i < n_jobs; ++i) {
-        clc_pair_job& jb = jobs[i];
-        if (jb.M) memset(jb.M, 0, sizeof(double) * 9);
-        if (jb.F) memset(jb.F, 0, sizeof(double) * 9);
-        jb.n_pairs = 0; jb.n_inliers = 0; jb.iterations = 0; jb.status = CLC_OK; jb.error_max = 0.0; jb.min_nfa = INFINITY;
-    }
-    CLC_HIP(c0, hipSetDevice(c0->device));
-    hipStream_t st = c0->stream;
-    std::vector<PairJobDev> dev((size_t)n_jobs);
-    for (int i = 0; i < n_jobs; ++i) {
-        int rc = pair_job_inputs(c0, jobs[i], dev[(size_t)i], "pair_filter: bad argument");
-        if (rc == CLC_OK && jobs[i].max_iteration < 0) rc = fail(c0, CLC_ERR_BAD_ARG, "pair_filter: negative max_iteration");
-        if (rc == CLC_OK) rc = ensure_pair(ctxs[i], (size_t)std::min(jobs[i].nq, kAcrMaxN));
-        if (rc != CLC_OK) {
-            if (ctxs[i] != c0) (void)fail(ctxs[i], rc, clc_last_error_string(c0));
-            jobs[i].status = rc;
-            return rc;
-        }
-    }
-    // behind whatever produced the inputs: an event on the producer's stream, no host synchronisation
-    for (int i = 0; i < n_jobs; ++i) {
-        hipStream_t prod = (hipStream_t)jobs[i].after_stream;
-        if (!prod || prod == st) continue;
-        clc_ctx* c = ctxs[i];
-        const bool ok = (c->ev_track || hipEventCreateWithFlags(&c->ev_track, hipEventDisableTiming) == hipSuccess) &&
-                        hipEventRecord(c->ev_track, prod) == hipSuccess && hipStreamWaitEvent(st, c->ev_track, 0) == hipSuccess;
-        if (!ok) CLC_HIP(c, hipStreamSynchronize(prod));
-    }
-    // the correspondences of all jobs: one launch per kMaxBatch of them
-    for (int k = 0; k < n_jobs; k += kMaxBatch) {
-        const int n = std::min(kMaxBatch, n_jobs - k);
-        PairJobs pack{};
-        for (int i = 0; i < n; ++i) {
-            const PairBlock pb(ctxs[k + i]);
-            const clc_pair_job& jb = jobs[k + i];
-            PairJobDev& d = dev[(size_t)(k + i)];
-            d.x1 = pb.x1; d.x2 = pb.x2; d.pair_q = pb.q; d.pair_t = pb.t; d.n = pb.n;
-            d.h_n = pb.h_n;
-            d.h_q = jb.pair_q ? pb.h_q : nullptr;
-            d.h_t = jb.pair_t ? pb.h_t : nullptr;
-            d.h_x1 = jb.x1 ? pb.h_x1 : nullptr;
-            d.h_x2 = jb.x2 ? pb.h_x2 : nullptr;
-            d.cap = std::min(jb.nq, kAcrMaxN);
-            __atomic_store_n(pb.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
-            pack.j[i] = d;
-        }
-        CLC_HIP(c0, launch_pair_build(pack, n, st));
-    }
-    const bool shared = acr_lockstep(kind, n_jobs);
-    if (!shared && n_jobs > 1) {
-        // every other run stages from its pair block on its context's OWN stream: behind the pair launch
-        bool ordered = (c0->ev_track || hipEventCreateWithFlags(&c0->ev_track, hipEventDisableTiming) == hipSuccess) &&
-                       hipEventRecord(c0->ev_track, st) == hipSuccess;
-        for (int i = 1; i < n_jobs && ordered; ++i) ordered = hipStreamWaitEvent(ctxs[i]->stream, c0->ev_track, 0) == hipSuccess;
-        if (!ordered) CLC_HIP(c0, hipStreamSynchronize(st));
-    }
-    // the one number the host needs: poll the pinned words, the stream synchronisation as the fallback (which also surfaces errors)
-    std::vector<AcrRun> runs((size_t)n_jobs);
-    std::vector<double> Ks((size_t)18 * n_jobs, 0.0), EF((size_t)18 * n_jobs, 0.0);
-    const auto t0 = std::chrono::steady_clock::now();
-    bool synced = false;
-    for (int i = 0; i < n_jobs; ++i) {
-        const PairBlock pb(ctxs[i]);
-        uint32_t w = __atomic_load_n(pb.h_n, __ATOMIC_ACQUIRE);
-        for (uint32_t spins = 0; w == 0xFFFFFFFFu; w = __atomic_load_n(pb.h_n, __ATOMIC_ACQUIRE)) {
-            if (synced) return fail(c0, CLC_ERR_HIP, "pair_filter: the pair launch left no count");
-            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                CLC_HIP(c0, hipStreamSynchronize(st));
-                synced = true;
-            }
-        }
-        clc_pair_job& jb = jobs[i];
-        jb.n_pairs = (int)w;
-        double* K = &Ks[(size_t)18 * i];                                  // Pinhole_Intrinsic_Radial_K3::K() of the two cameras
-        K[0] = jb.cam_a.focal; K[2] = jb.cam_a.ppx; K[4] = jb.cam_a.focal; K[5] = jb.cam_a.ppy; K[8] = 1.0;
-        K[9] = jb.cam_b.focal; K[11] = jb.cam_b.ppx; K[13] = jb.cam_b.focal; K[14] = jb.cam_b.ppy; K[17] = 1.0;
-        AcrRun& r = runs[(size_t)i];
-        r.ctx = ctxs[i]; r.kind = kind; r.N = jb.n_pairs; r.dev_a = pb.x1; r.dev_b = pb.x2;
-        if (kind == 1) { r.h_K1 = K; r.h_K2 = K + 9; }
-        r.img_w = jb.img_w; r.img_h = jb.img_h;
-        r.max_iteration = jb.max_iteration; r.seed = jb.seed; r.precision = jb.precision; r.refine_huber = -1.0;
-        r.h_model = &EF[(size_t)18 * i]; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers;
-        r.error_max = &jb.error_max; r.min_nfa = &jb.min_nfa; r.iterations = &jb.iterations;
-    }
-    acr_drive(runs.data(), n_jobs, shared);
-    int worst = CLC_OK;
-    for (int i = 0; i < n_jobs; ++i) {
-        AcrRun& r = runs[(size_t)i];
-        clc_pair_job& jb = jobs[i];
-        r.finish();
-        jb.status = r.status;
-        // kind 1: the slots hold { E, F }; kinds 2 / 3: the model matrix, F = it ('F') or zeros ('H') -- as clc_two_view_acransac
-        const double* ef = &EF[(size_t)18 * i];
-        if (jb.M) memcpy(jb.M, ef, sizeof(double) * 9);
-        if (jb.F && kind != 3) memcpy(jb.F, kind == 1 ? ef + 9 : ef, sizeof(double) * 9);
-        // the kernel wrote the pinned mirrors before the count came out
-        const PairBlock pb(ctxs[i]);
-        const size_t np = (size_t)std::min(jb.n_pairs, std::min(jb.nq, kAcrMaxN));
-        if (jb.pair_q && np) memcpy(jb.pair_q, pb.h_q, sizeof(int32_t) * np);
-        if (jb.pair_t && np) memcpy(jb.pair_t, pb.h_t, sizeof(int32_t) * np);
-        if (jb.x1 && np) memcpy(jb.x1, pb.h_x1, sizeof(double) * 2 * np);
-        if (jb.x2 && np) memcpy(jb.x2, pb.h_x2, sizeof(double) * 2 * np);
-        if (r.status != CLC_OK && worst == CLC_OK) worst = r.status;
-    }
-    return worst;
-}
-
-} // namespace
-
-extern "C" {
 
 int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* jobs, int n_jobs)
 {
@@ -1025,7 +942,7 @@ int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* job
     const int rc0 = check_batch_contexts(ctxs, n_jobs, "pair_filter_batch: every job needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
     if (kind < 0) return fail(ctxs[0], CLC_ERR_BAD_ARG, "pair_filter_batch: model must be 'E', 'F' or 'H'");
-    return pair_filter(ctxs, kind, jobs, n_jobs);
+    return gather_solve<PairPath>(ctxs, kind, jobs, n_jobs);
 }
 
 int clc_pair_filter_dev(clc_ctx* ctx, int model, clc_pair_job* job)
@@ -1033,7 +950,7 @@ int clc_pair_filter_dev(clc_ctx* ctx, int model, clc_pair_job* job)
     if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: null context / job");
     const int kind = two_view_kind(model);
     if (kind < 0) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: model must be 'E', 'F' or 'H'");
-    return pair_filter(&ctx, kind, job, 1);
+    return gather_solve<PairPath>(&ctx, kind, job, 1);
 }
 
 } // extern "C"

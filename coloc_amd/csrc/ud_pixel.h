@@ -1,15 +1,13 @@
 // ud_pixel.h -- Pinhole_Intrinsic_Radial_K3::get_ud_pixel (coloc_hip_geometry.hpp:97-135; OpenMVG's Pinhole_Intrinsic_Radial_K3) on the
-// device, the ONE copy the track kernel (track.hip) and the pair kernel (pair.hip) share: + - x / sqrt only, in the host's order, and the
+// device, the ONE copy the track kernel and the pair kernel (gather.hip) share: + - x / sqrt only, in the host's order, and the
 // library is built with -ffp-contract=off: the host's bits.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include "coloc_hip.h"
+#include "clc_internal.h"
 
 namespace clc {
-
-struct UdCamera { double focal, ppx, ppy, k1, k2, k3; };
 
 __device__ __forceinline__ double ud_disto(const double r2, const double k1, const double k2, const double k3)
 {

@@ -4,7 +4,7 @@
 Written from the reference's loop: for every putative match of the pair, in the order GPUMatcher::computeMatches emits them
 (IndMatch(i, h_matches[i]) for ascending i, GPUMatcher.hpp:215-220), the two feature positions, each undistorted through its own camera's
 Pinhole_Intrinsic_Radial_K3::get_ud_pixel.  Built on tests/track_host.py's feature_positions / get_ud_pixel; shares no code with
-coloc_amd/csrc/pair.hip.  Results are compared bit for bit.
+coloc_amd/csrc/gather.hip.  Results are compared bit for bit.
 """
 import numpy as np
 

@@ -1,7 +1,7 @@
 """Localizer::setupTracks in numpy float64 (reference include/coloc/Localizer.hpp:59-75), the yardstick of the device track kernel.
 
 Written from the reference's loop and from Pinhole_Intrinsic_Radial_K3::get_ud_pixel (coloc_amd/host/coloc_hip_geometry.hpp:97-135); shares
-no code with coloc_amd/csrc/track.hip.  Every operation is an IEEE + - x / sqrt on float32 / float64 arrays in the reference's order, so
+no code with coloc_amd/csrc/gather.hip.  Every operation is an IEEE + - x / sqrt on float32 / float64 arrays in the reference's order, so
 results are compared bit for bit.
 """
 import math

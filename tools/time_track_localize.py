@@ -1,7 +1,8 @@
 """The frame tail, from "d_match is ready on the device" to "pose and covariance on the host", two ways in one process and run:
   (a) today's path: matches and feature positions copied back, synchronisation, numpy gather, clc_pnp_localize_ac (bench_stream.py's solve_pose)
   (b) clc_track_localize_dev / clc_track_localize_batch_dev: tracks built on the device, the host waits for the track count only
-at ~1 000 tracks among 1 600 queries, 30 % outliers, for one camera and for a batch of 8; p50 over FRAMES frames each.  Then the track
+at ~1 000 tracks among 1 600 queries, 30 % outliers, for one camera and for a batch of 8; p50 over FRAMES frames each.  The host leg is
+timed TWICE (before and after the device leg): the difference between its two p50s is the run's noise.  Then the track
 kernel alone (clc_track_build_dev between two events on a stream of its own).
 usage: time_track_localize.py [frames]        both paths
        time_track_localize.py new [frames]    path (b) only -- the run to put under rocprofv3 --memory-copy-trace / --kernel-trace --stats"""
@@ -85,14 +86,21 @@ def p50(fn):
     return t[len(t) // 2], t[int(len(t) * 0.95)], r
 
 
-print("frame tail, %d tracks among %d queries, p50 / p95 over %d frames (us)" % (N, len(frames[0][0]), FRAMES))
-rows = [("(b) device tracks, 1 camera   ", new_one), ("(b) device tracks, batch of %d  " % NB, new_batch)]
-if not only_new:
-    rows = [("(a) host gather,   1 camera   ", old_one), ("(a) host gather,   batch of %d  " % NB, old_batch)] + rows
-for name, fn in rows:
-    a, b, r = p50(fn)
-    r0 = r[0] if isinstance(r, list) else r
-    print("%s p50 %8.1f  p95 %8.1f   inliers %d" % (name, a, b, len(r0["inliers"])))
+print("frame tail, %d tracks among %d queries, p50 / p95 over %d frames (us); host leg timed twice, |a1 - a2| = the run's noise" % (N, len(frames[0][0]), FRAMES))
+for what, old, new in (("1 camera  ", old_one, new_one), ("batch of %d" % NB, old_batch, new_batch)):
+    if only_new:
+        b, b95, r = p50(new)
+        print("%s (b) device tracks p50 %8.1f  p95 %8.1f" % (what, b, b95))
+        continue
+    a1, a1_95, ra = p50(old)
+    b, b95, rb = p50(new)
+    a2, a2_95, _ = p50(old)
+    ra0, rb0 = (ra[0], rb[0]) if isinstance(ra, list) else (ra, rb)
+    noise = abs(a1 - a2)
+    print("%s (a) host gather p50 %8.1f / %8.1f (p95 %8.1f / %8.1f)  (b) device tracks p50 %8.1f (p95 %8.1f)  noise %6.1f  "
+          "b - min(a) %+8.1f  %s   inliers %d%s" % (what, a1, a2, a1_95, a2_95, b, b95, noise, b - min(a1, a2),
+                                                    "not slower" if b <= min(a1, a2) + noise else "SLOWER", len(rb0["inliers"]),
+                                                    "" if np.array_equal(ra0["inliers"], rb0["inliers"]) else "  (!! inliers differ)"))
 
 # the track kernel alone: one launch between two events on a stream of its own
 st = torch.cuda.Stream()
