@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 
 using namespace clc;
 
@@ -53,88 +54,46 @@ int fail(clc_ctx* ctx, int code, const char* what, hipError_t e)
     return code;
 }
 
-
 int ensure_partial(clc_ctx* ctx, size_t elems)
 {
-    if (elems <= ctx->partial_cap) return CLC_OK;
+    bool fresh;
+    const int rc = grow(ctx, ctx->d_partial, elems * sizeof(uint2), 1, 4, true, "growing d_partial", &fresh);
+    if (rc != CLC_OK || !fresh) return rc;
+    CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial.ptr, 0xFF, ctx->d_partial.bytes, ctx->stream));   // armed top-2 rows (if this fails, fail() marks them dirty)
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_partial) CLC_HIP(ctx, hipFree(ctx->d_partial));
-    ctx->d_partial = nullptr;
-    ctx->partial_cap = 0;
-    size_t cap = elems + elems / 4;
-    CLC_HIP(ctx, hipMalloc((void**)&ctx->d_partial, cap * sizeof(uint2)));
-    CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial, 0xFF, cap * sizeof(uint2), ctx->stream));   // armed top-2 rows
-    CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->partial_cap = cap;
     return CLC_OK;
 }
 
-int ensure_pnp(clc_ctx* ctx, size_t doubles)
-{
-    if (doubles <= ctx->pnp_cap) return CLC_OK;
-    CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_pnp) CLC_HIP(ctx, hipFree(ctx->d_pnp));
-    ctx->d_pnp = nullptr;
-    ctx->pnp_cap = 0;
-    // half as much again: a stream of solves whose sizes creep upwards (map matches per frame) must not reallocate at every new maximum
-    const size_t cap = doubles + doubles / 2;
-    CLC_HIP(ctx, hipMalloc((void**)&ctx->d_pnp, cap * sizeof(double)));
-    ctx->pnp_cap = cap;
-    return CLC_OK;
-}
+// half as much again: a stream of solves whose sizes creep upwards (map matches per frame) must not reallocate at every new maximum
+int ensure_pnp(clc_ctx* ctx, size_t doubles) { return grow(ctx, ctx->d_pnp, doubles * sizeof(double), 1, 2, true, "growing d_pnp"); }
 
 // Host staging for the robust pose solve: ONE pinned buffer, ONE H2D copy in, ONE D2H copy out.
-int ensure_pinned(clc_ctx* ctx, size_t bytes)
-{
-    if (bytes <= ctx->pin_cap) return CLC_OK;
-    CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_pin) CLC_HIP(ctx, hipHostFree(ctx->h_pin));
-    ctx->h_pin = nullptr; ctx->pin_cap = 0;
-    const size_t cap = bytes + bytes / 2;           // (see ensure_pnp: a pinned allocation costs a millisecond)
-    CLC_HIP(ctx, hipHostMalloc(&ctx->h_pin, cap, hipHostMallocDefault));
-    ctx->pin_cap = cap;
-    return CLC_OK;
-}
+// (half as much again, see ensure_pnp: a pinned allocation costs a millisecond)
+int ensure_pinned(clc_ctx* ctx, size_t bytes) { return grow(ctx, ctx->h_pin, bytes, 1, 2, true, "growing h_pin"); }
 
 // room for the pyramids (+ score maps, keypoint masks, tile counts) of n cameras; slot 0 (the current single-image pyramid) does not
-// survive a growth -- every caller rebuilds it
+// survive a growth -- every caller rebuilds it.  A failed growth leaves the old arena in place.
 int ensure_slots(clc_ctx* ctx, int n, hipStream_t st)
 {
     if (n <= ctx->arena_slots) return CLC_OK;
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (st != ctx->stream) CLC_HIP(ctx, hipStreamSynchronize(st));
-    uint8_t *arena = nullptr, *score = nullptr;
-    uint64_t* kpmask = nullptr;
-    uint32_t* tcount = nullptr;
-    hipError_t e = hipMalloc((void**)&arena, ctx->arena_bytes * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&score, ctx->arena_bytes * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc((void**)&kpmask, (size_t)n * ctx->n_tiles * 16 * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&tcount, (size_t)n * ctx->n_tiles * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(arena, 0, ctx->arena_bytes * (size_t)n, st);
+    DevBuf arena, score, kpmask, tcount;
+    hipError_t e = arena.alloc(ctx->arena_bytes * (size_t)n);
+    if (e == hipSuccess) e = score.alloc(ctx->arena_bytes * (size_t)n);
+    if (e == hipSuccess) e = kpmask.alloc((size_t)n * ctx->n_tiles * 16 * sizeof(uint64_t));
+    if (e == hipSuccess) e = tcount.alloc((size_t)n * ctx->n_tiles * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(arena.ptr, 0, ctx->arena_bytes * (size_t)n, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        (void)hipFree(arena); (void)hipFree(score); (void)hipFree(kpmask); (void)hipFree(tcount);
-        return fail(ctx, CLC_ERR_HIP, "growing the pyramid arena", e);
-    }
+    if (e != hipSuccess) return fail(ctx, CLC_ERR_HIP, "growing the pyramid arena", e);
     ctx->pyramid_valid = false;
     ctx->detected = false;
-    (void)hipFree(ctx->d_arena); (void)hipFree(ctx->d_score); (void)hipFree(ctx->d_kpmask); (void)hipFree(ctx->d_tcount);
-    ctx->d_arena = arena; ctx->d_score = score; ctx->d_kpmask = kpmask; ctx->d_tcount = tcount;
+    ctx->d_arena = std::move(arena); ctx->d_score = std::move(score); ctx->d_kpmask = std::move(kpmask); ctx->d_tcount = std::move(tcount);
     ctx->arena_slots = n;
     return CLC_OK;
 }
 
-
-int ensure_results(clc_ctx* ctx, size_t bytes)
-{
-    if (bytes <= ctx->res_cap) return CLC_OK;
-    CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->h_res) CLC_HIP(ctx, hipHostFree(ctx->h_res));
-    ctx->h_res = nullptr; ctx->res_cap = 0;
-    CLC_HIP(ctx, hipHostMalloc((void**)&ctx->h_res, bytes, hipHostMallocDefault));
-    ctx->res_cap = bytes;
-    return CLC_OK;
-}
+int ensure_results(clc_ctx* ctx, size_t bytes) { return grow(ctx, ctx->h_res, bytes, 0, 1, true, "growing h_res"); }
 
 } // namespace clc
 
@@ -203,9 +162,9 @@ static int ensure_stage(clc_ctx* ctx)
     const size_t kps = ((size_t)ctx->dopts.maxkp * sizeof(clc_keypoint) + 255) & ~(size_t)255;
     const size_t desc = (size_t)ctx->dopts.maxkp * CLC_DESC_BYTES;
     ctx->stage_img = 0; ctx->stage_kps = img; ctx->stage_desc = img + kps; ctx->stage_cnt = img + kps + desc;
-    CLC_HIP(ctx, hipHostMalloc((void**)&ctx->h_stage, img + kps + desc + 256, hipHostMallocDefault));
-    memset(ctx->h_stage + ctx->stage_cnt, 0, 256);          // {written, found}
-    return CLC_OK;
+    const int rc = grow(ctx, ctx->h_stage, img + kps + desc + 256, 0, 1, false, "allocating h_stage");
+    if (rc == CLC_OK) memset(ctx->h_stage.as<uint8_t>() + ctx->stage_cnt, 0, 256);          // {written, found}
+    return rc;
 }
 
 } // namespace
@@ -283,41 +242,40 @@ int clc_ctx_create(int device_id, const clc_detector_opts* dopts, const clc_matc
         ctx->has_det = true;
         ctx->dopts = *dopts;
         plan_pyramid(*dopts, ctx->pd, ctx->arena_bytes);
-        CREATE_HIP(hipMalloc((void**)&ctx->d_arena, ctx->arena_bytes));
-        CREATE_HIP(hipMemsetAsync(ctx->d_arena, 0, ctx->arena_bytes, ctx->stream));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_kps, (size_t)dopts->maxkp * sizeof(clc_keypoint)));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_desc, (size_t)dopts->maxkp * CLC_DESC_BYTES));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_score, ctx->arena_bytes));
+        CREATE_HIP(ctx->d_arena.alloc(ctx->arena_bytes));
+        CREATE_HIP(hipMemsetAsync(ctx->d_arena.ptr, 0, ctx->arena_bytes, ctx->stream));
+        CREATE_HIP(ctx->d_kps.alloc((size_t)dopts->maxkp * sizeof(clc_keypoint)));
+        CREATE_HIP(ctx->d_desc.alloc((size_t)dopts->maxkp * CLC_DESC_BYTES));
+        CREATE_HIP(ctx->d_score.alloc(ctx->arena_bytes));
         ctx->n_tiles = detect_total_tiles(ctx->pd);
-        CREATE_HIP(hipMalloc((void**)&ctx->d_kpmask, (size_t)ctx->n_tiles * 16 * sizeof(uint64_t)));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_tcount, (size_t)ctx->n_tiles * sizeof(uint32_t)));
+        CREATE_HIP(ctx->d_kpmask.alloc((size_t)ctx->n_tiles * 16 * sizeof(uint64_t)));
+        CREATE_HIP(ctx->d_tcount.alloc((size_t)ctx->n_tiles * sizeof(uint32_t)));
         {   // the selection workspace is small (a few KB per camera): sized for a full batch here, so that no detect call ever allocates
             const size_t sel_bytes = (size_t)CLC_MAX_BATCH * detect_select_words(ctx->pd) * sizeof(uint32_t);
-            CREATE_HIP(hipMalloc((void**)&ctx->d_select, sel_bytes));
-            CREATE_HIP(hipMemsetAsync(ctx->d_select, 0, sel_bytes, ctx->stream));
+            CREATE_HIP(ctx->d_select.alloc(sel_bytes));
+            CREATE_HIP(hipMemsetAsync(ctx->d_select.ptr, 0, sel_bytes, ctx->stream));
         }
-        CREATE_HIP(hipMalloc((void**)&ctx->d_count, 4 * sizeof(uint32_t)));
-        CREATE_HIP(hipMemsetAsync(ctx->d_count, 0, 4 * sizeof(uint32_t), ctx->stream));
+        CREATE_HIP(ctx->d_count.alloc(4 * sizeof(uint32_t)));
+        CREATE_HIP(hipMemsetAsync(ctx->d_count.ptr, 0, 4 * sizeof(uint32_t), ctx->stream));
     }
     if (mopts) {
         ctx->has_mat = true;
         ctx->mopts = *mopts;
         const size_t cap = (size_t)mopts->maxkp;
-        CREATE_HIP(hipMalloc((void**)&ctx->d_q, cap * CLC_DESC_BYTES));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_t, cap * CLC_DESC_BYTES));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_m, cap * CLC_DESC_BYTES));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_match, cap * sizeof(int32_t)));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_best, cap * sizeof(uint16_t)));
-        CREATE_HIP(hipMalloc((void**)&ctx->d_second, cap * sizeof(uint16_t)));
+        CREATE_HIP(ctx->d_q.alloc(cap * CLC_DESC_BYTES));
+        CREATE_HIP(ctx->d_t.alloc(cap * CLC_DESC_BYTES));
+        CREATE_HIP(ctx->d_m.alloc(cap * CLC_DESC_BYTES));
+        CREATE_HIP(ctx->d_match.alloc(cap * sizeof(int32_t)));
+        CREATE_HIP(ctx->d_best.alloc(cap * sizeof(uint16_t)));
+        CREATE_HIP(ctx->d_second.alloc(cap * sizeof(uint16_t)));
     }
     // K2NN workspace: one armed {best, second} row per query suffices in atomic mode (a few pairs' worth
     // here); the slab fallback for train sets > 2^22 and larger job lists grow it on demand
     {
         const size_t cap = dopts || mopts ? (size_t)(mopts ? mopts->maxkp : dopts->maxkp) : 16384;
         const size_t elems = ((cap + 63) & ~(size_t)63) * 8 + 4096;
-        CREATE_HIP(hipMalloc((void**)&ctx->d_partial, elems * sizeof(uint2)));
-        CREATE_HIP(hipMemsetAsync(ctx->d_partial, 0xFF, elems * sizeof(uint2), ctx->stream));   // armed top-2 rows
-        ctx->partial_cap = elems;
+        CREATE_HIP(ctx->d_partial.alloc(elems * sizeof(uint2)));
+        CREATE_HIP(hipMemsetAsync(ctx->d_partial.ptr, 0xFF, elems * sizeof(uint2), ctx->stream));   // armed top-2 rows
     }
     CREATE_HIP(hipStreamSynchronize(ctx->stream));
 #undef CREATE_HIP
@@ -331,20 +289,10 @@ int clc_ctx_destroy(clc_ctx* ctx)
     if (!ctx) return CLC_ERR_BAD_ARG;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    void* bufs[] = { ctx->d_arena, ctx->d_kps, ctx->d_desc, ctx->d_score, ctx->d_kpmask, ctx->d_tcount, ctx->d_select, ctx->d_count, ctx->d_q, ctx->d_t, ctx->d_m, ctx->d_match,
-                     ctx->d_best, ctx->d_second, ctx->d_partial, ctx->d_pnp, ctx->d_pairs, ctx->d_map_X, ctx->trk.d, ctx->pair.d };
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (ctx->trk.h) (void)hipHostFree(ctx->trk.h);
-    if (ctx->pair.h) (void)hipHostFree(ctx->pair.h);
-    if (ctx->ev_track) (void)hipEventDestroy(ctx->ev_track);
     desc_drop_owner(ctx);                  // freeGPUMemory: what this context published dies with it
-    if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
-    if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-    if (ctx->h_res) (void)hipHostFree(ctx->h_res);
-    if (ctx->ev_group) (void)hipEventDestroy(ctx->ev_group);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t stream = ctx->stream;
+    delete ctx;                            // every buffer and event the context owns goes with it (clc_buf.h) ...
+    if (stream) (void)hipStreamDestroy(stream);   // ... and then the stream they were used on
     return CLC_OK;
 }
 
@@ -409,7 +357,7 @@ int clc_pyramid_build_dev(clc_ctx* ctx, const void* d_img, uint32_t width, uint3
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
     if (pitch > 0xFFFFFFFFull) return fail(ctx, CLC_ERR_BAD_ARG, "pyramid_build: pitch too large");
-    CLC_HIP(ctx, launch_pyramid(ctx->pd, ctx->d_arena, (const uint8_t*)d_img, (uint32_t)pitch, st, &ctx->prof));
+    CLC_HIP(ctx, launch_pyramid(ctx->pd, ctx->d_arena.as<uint8_t>(), (const uint8_t*)d_img, (uint32_t)pitch, st, &ctx->prof));
     ctx->pyramid_valid = true;
     return CLC_OK;
 }
@@ -422,9 +370,9 @@ int clc_pyramid_build(clc_ctx* ctx, const uint8_t* h_img, uint32_t width, uint32
         return fail(ctx, CLC_ERR_BAD_ARG, "pyramid_build: image size differs from DetectorOptions width/height");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     const LevelDesc& L0 = ctx->pd.lv[0];
-    CLC_HIP(ctx, hipMemcpy2DAsync(ctx->d_arena + L0.offset, L0.pitch, h_img, width, width, height,
+    CLC_HIP(ctx, hipMemcpy2DAsync(ctx->d_arena.as<uint8_t>() + L0.offset, L0.pitch, h_img, width, width, height,
                                   hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_pyramid(ctx->pd, ctx->d_arena, ctx->d_arena + L0.offset, L0.pitch, ctx->stream, &ctx->prof));
+    CLC_HIP(ctx, launch_pyramid(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->d_arena.as<uint8_t>() + L0.offset, L0.pitch, ctx->stream, &ctx->prof));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->pyramid_valid = true;
     return CLC_OK;
@@ -437,7 +385,7 @@ int clc_pyramid_level(const clc_ctx* ctx, int level, uint32_t* w, uint32_t* h, s
     if (w) *w = L.w;
     if (h) *h = L.h;
     if (pitch) *pitch = L.pitch;
-    if (d_ptr) *d_ptr = ctx->d_arena + L.offset;
+    if (d_ptr) *d_ptr = ctx->d_arena.as<uint8_t>() + L.offset;
     return CLC_OK;
 }
 
@@ -448,15 +396,15 @@ int clc_pyramid_download(clc_ctx* ctx, int level, uint8_t* h_out)
     if (!ctx->pyramid_valid) return fail(ctx, CLC_ERR_STATE, "pyramid_download before pyramid_build");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     const LevelDesc& L = ctx->pd.lv[level];
-    CLC_HIP(ctx, hipMemcpy2DAsync(h_out, L.w, ctx->d_arena + L.offset, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
+    CLC_HIP(ctx, hipMemcpy2DAsync(h_out, L.w, ctx->d_arena.as<uint8_t>() + L.offset, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CLC_OK;
 }
 
 /* ---- detect -------------------------------------------------------------------------------- */
 
-static uint32_t* count_ptr(clc_ctx* ctx) { return ctx->d_count; }
-static uint32_t* select_ptr(clc_ctx* ctx) { return ctx->selection == CLC_SELECT_STRONGEST ? ctx->d_select : nullptr; }
+static uint32_t* count_ptr(clc_ctx* ctx) { return ctx->d_count.as<uint32_t>(); }
+static uint32_t* select_ptr(clc_ctx* ctx) { return ctx->selection == CLC_SELECT_STRONGEST ? ctx->d_select.as<uint32_t>() : nullptr; }
 
 int clc_detect_set_selection(clc_ctx* ctx, int mode)
 {
@@ -477,9 +425,9 @@ int clc_detect_dev(clc_ctx* ctx, void* stream)
     // the counter that said how many rows clc_describe_detected_dev left in d_desc is about to describe another keypoint list
     if (ctx->rows_at == ROWS_OWN && ctx->own_rows < 0) ctx->rows_at = ROWS_NONE;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    clc_keypoint* kps[1] = { ctx->d_kps };
-    uint32_t* cnt[1] = { ctx->d_count };
-    CLC_HIP(ctx, launch_detect(ctx->pd, ctx->d_arena, ctx->arena_bytes, 1, ctx->d_score, ctx->d_kpmask, ctx->d_tcount, ctx->dopts.thresh,
+    clc_keypoint* kps[1] = { ctx->d_kps.as<clc_keypoint>() };
+    uint32_t* cnt[1] = { ctx->d_count.as<uint32_t>() };
+    CLC_HIP(ctx, launch_detect(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, 1, ctx->d_score.as<uint8_t>(), ctx->d_kpmask.as<uint64_t>(), ctx->d_tcount.as<uint32_t>(), ctx->dopts.thresh,
                                ctx->dopts.maxkp, kps, cnt, pick(ctx, stream), &ctx->prof, select_ptr(ctx), &ctx->select_dirty));
     ctx->detected = true;
     return CLC_OK;
@@ -515,22 +463,22 @@ int clc_detect_batch_dev(clc_ctx* ctx, int n_images, const void* const* d_imgs, 
     const int rc = ensure_slots(ctx, n_images, st);
     if (rc != CLC_OK) return rc;
     ctx->pyramid_valid = false;
-    CLC_HIP(ctx, launch_pyramid_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, srcs, n_images, (uint32_t)pitch, st, &ctx->prof));
+    CLC_HIP(ctx, launch_pyramid_batch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, srcs, n_images, (uint32_t)pitch, st, &ctx->prof));
     ctx->pyramid_valid = true;
     ctx->detected = false;               // the context's own keypoint list is not the one this call fills
-    CLC_HIP(ctx, launch_detect(ctx->pd, ctx->d_arena, ctx->arena_bytes, n_images, ctx->d_score, ctx->d_kpmask, ctx->d_tcount,
+    CLC_HIP(ctx, launch_detect(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, n_images, ctx->d_score.as<uint8_t>(), ctx->d_kpmask.as<uint64_t>(), ctx->d_tcount.as<uint32_t>(),
                                ctx->dopts.thresh, ctx->dopts.maxkp, d_kps, d_counts, st, &ctx->prof, select_ptr(ctx), &ctx->select_dirty));
     if (d_desc)
-        CLC_HIP(ctx, launch_clatch_counted_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, batch, cnts, n_images, st, &ctx->prof));
+        CLC_HIP(ctx, launch_clatch_counted_batch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, batch, cnts, n_images, st, &ctx->prof));
     return CLC_OK;
 }
 
 int clc_detect_buffers(clc_ctx* ctx, const clc_keypoint** d_kps, const uint32_t** d_count, void** d_desc)
 {
     if (!ctx || !ctx->has_det) return CLC_ERR_BAD_ARG;
-    if (d_kps) *d_kps = ctx->d_kps;
+    if (d_kps) *d_kps = ctx->d_kps.as<clc_keypoint>();
     if (d_count) *d_count = count_ptr(ctx);
-    if (d_desc) *d_desc = ctx->d_desc;
+    if (d_desc) *d_desc = ctx->d_desc.as<uint64_t>();
     return CLC_OK;
 }
 
@@ -544,7 +492,7 @@ int clc_detect(clc_ctx* ctx, clc_keypoint* h_kps, int capacity, int* n_written, 
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int n = (int)cnt[0] < capacity ? (int)cnt[0] : capacity;
     if (n > 0) {
-        CLC_HIP(ctx, hipMemcpyAsync(h_kps, ctx->d_kps, (size_t)n * sizeof(clc_keypoint), hipMemcpyDeviceToHost, ctx->stream));
+        CLC_HIP(ctx, hipMemcpyAsync(h_kps, ctx->d_kps.as<clc_keypoint>(), (size_t)n * sizeof(clc_keypoint), hipMemcpyDeviceToHost, ctx->stream));
         CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (n_written) *n_written = n;
@@ -558,8 +506,8 @@ static int describe_detected(clc_ctx* ctx, void* d_desc, void* stream)
     if (!ctx->detected) return fail(ctx, CLC_ERR_STATE, "describe_detected before detect");
     if ((uintptr_t)d_desc & 7u) return fail(ctx, CLC_ERR_BAD_ARG, "describe_detected: misaligned device pointer");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    CLC_HIP(ctx, launch_clatch_counted(ctx->pd, ctx->d_arena, ctx->d_kps, count_ptr(ctx), (int)ctx->dopts.maxkp,
-                                       d_desc ? (uint64_t*)d_desc : ctx->d_desc, pick(ctx, stream), &ctx->prof));
+    CLC_HIP(ctx, launch_clatch_counted(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->d_kps.as<clc_keypoint>(), count_ptr(ctx), (int)ctx->dopts.maxkp,
+                                       d_desc ? (uint64_t*)d_desc : ctx->d_desc.as<uint64_t>(), pick(ctx, stream), &ctx->prof));
     return CLC_OK;
 }
 
@@ -568,7 +516,7 @@ int clc_describe_detected_dev(clc_ctx* ctx, void* d_desc, void* stream)
     if (!ctx) return CLC_ERR_BAD_ARG;
     rows_leave(ctx);
     const int rc = describe_detected(ctx, d_desc, stream);
-    if (rc == CLC_OK && (!d_desc || d_desc == ctx->d_desc)) { ctx->rows_at = ROWS_OWN; ctx->own_rows = -1; }
+    if (rc == CLC_OK && (!d_desc || d_desc == ctx->d_desc.as<uint64_t>())) { ctx->rows_at = ROWS_OWN; ctx->own_rows = -1; }
     return rc;
 }
 
@@ -604,25 +552,25 @@ int clc_detect_and_describe_view(clc_ctx* ctx, const uint8_t* h_img, uint32_t wi
         desc_abandon(ctx->desc_pending);
         ctx->desc_pending = nullptr;
     }
-    if (!d_rows) d_rows = (uint8_t*)ctx->d_desc;
+    if (!d_rows) d_rows = (uint8_t*)ctx->d_desc.as<uint64_t>();
     const LevelDesc& L0 = ctx->pd.lv[0];
-    uint8_t* hp = ctx->h_stage;
+    uint8_t* hp = ctx->h_stage.as<uint8_t>();
     uint32_t* h_cnt = (uint32_t*)(hp + ctx->stage_cnt);
     memcpy(hp + ctx->stage_img, h_img, (size_t)width * height);
     // (the DMA engine; a compute-queue copy kernel reading the pinned block was measured 3 us slower per frame, round 6)
     if (L0.pitch == width)
-        CLC_HIP(ctx, hipMemcpyAsync(ctx->d_arena + L0.offset, hp + ctx->stage_img, (size_t)width * height, hipMemcpyHostToDevice, ctx->stream));
+        CLC_HIP(ctx, hipMemcpyAsync(ctx->d_arena.as<uint8_t>() + L0.offset, hp + ctx->stage_img, (size_t)width * height, hipMemcpyHostToDevice, ctx->stream));
     else
-        CLC_HIP(ctx, hipMemcpy2DAsync(ctx->d_arena + L0.offset, L0.pitch, hp + ctx->stage_img, width, width, height, hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_pyramid(ctx->pd, ctx->d_arena, ctx->d_arena + L0.offset, L0.pitch, ctx->stream, &ctx->prof));
+        CLC_HIP(ctx, hipMemcpy2DAsync(ctx->d_arena.as<uint8_t>() + L0.offset, L0.pitch, hp + ctx->stage_img, width, width, height, hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, launch_pyramid(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->d_arena.as<uint8_t>() + L0.offset, L0.pitch, ctx->stream, &ctx->prof));
     ctx->pyramid_valid = true;
     int rc = clc_detect_dev(ctx, nullptr);
     if (rc != CLC_OK) return rc;
     rc = describe_detected(ctx, d_rows, nullptr);
     if (rc != CLC_OK) return rc;
     const uint32_t blocks = (ctx->dopts.maxkp * 4u + 255u) / 256u;
-    hipLaunchKernelGGL(frontend_mirror_kernel, dim3(blocks ? blocks : 1u), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_kps, (const uint4*)d_rows,
-                       (const uint32_t*)ctx->d_count, (uint32_t*)(hp + ctx->stage_kps), (uint4*)(hp + ctx->stage_desc), h_cnt);
+    hipLaunchKernelGGL(frontend_mirror_kernel, dim3(blocks ? blocks : 1u), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_kps.as<clc_keypoint>(), (const uint4*)d_rows,
+                       (const uint32_t*)ctx->d_count.as<uint32_t>(), (uint32_t*)(hp + ctx->stage_kps), (uint4*)(hp + ctx->stage_desc), h_cnt);
     CLC_HIP(ctx, hipGetLastError());
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int n = (int)h_cnt[0];
@@ -659,7 +607,7 @@ int clc_detect_store_descriptors(clc_ctx* ctx, void* h_dst, int n, clc_desc_hand
     if (!ctx || n < 0 || (n > 0 && !h_dst)) return fail(ctx, CLC_ERR_BAD_ARG, "detect_store_descriptors: bad argument");
     if (!ctx->h_stage || ctx->staged_n < 0 || n > ctx->staged_n) return fail(ctx, CLC_ERR_STATE, "detect_store_descriptors: no staged frame of that many rows");
     if (n == 0) return CLC_OK;
-    const uint8_t* src = ctx->h_stage + ctx->stage_desc;
+    const uint8_t* src = ctx->h_stage.as<uint8_t>() + ctx->stage_desc;
     // a partial store (fewer rows than were found) or a context that does not publish: the copy alone
     if (ctx->cache_mode == CLC_DESC_CACHE_OFF || !ctx->desc_pending || n != ctx->staged_n) {
         memcpy(h_dst, src, (size_t)n * CLC_DESC_BYTES);
@@ -681,10 +629,10 @@ int clc_describe_dev(clc_ctx* ctx, const clc_keypoint* d_kps, int n, void* d_des
     if (!ctx->has_det) return fail(ctx, CLC_ERR_STATE, "describe: context created without detector options");
     if (!ctx->pyramid_valid) return fail(ctx, CLC_ERR_STATE, "describe before pyramid_build");
     if (((uintptr_t)d_desc & 7u) || ((uintptr_t)d_kps & 3u)) return fail(ctx, CLC_ERR_BAD_ARG, "describe: misaligned device pointer");
-    const bool own = d_desc && d_desc == ctx->d_desc;
+    const bool own = d_desc && d_desc == ctx->d_desc.as<uint64_t>();
     if (own && (uint32_t)n > ctx->dopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "describe: more keypoints than the context's descriptor array holds");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    CLC_HIP(ctx, launch_clatch(ctx->pd, ctx->d_arena, d_kps, n, (uint64_t*)d_desc, pick(ctx, stream), &ctx->prof));
+    CLC_HIP(ctx, launch_clatch(ctx->pd, ctx->d_arena.as<uint8_t>(), d_kps, n, (uint64_t*)d_desc, pick(ctx, stream), &ctx->prof));
     if (own) { ctx->rows_at = ROWS_OWN; ctx->own_rows = n; }
     return CLC_OK;
 }
@@ -720,9 +668,9 @@ int clc_describe_batch_dev(clc_ctx* ctx, int n_images, const void* const* d_imgs
         if (rc != CLC_OK) return rc;
     }
     ctx->pyramid_valid = false;
-    CLC_HIP(ctx, launch_pyramid_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, srcs, n_images, (uint32_t)pitch, st, &ctx->prof));
+    CLC_HIP(ctx, launch_pyramid_batch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, srcs, n_images, (uint32_t)pitch, st, &ctx->prof));
     ctx->pyramid_valid = true;
-    CLC_HIP(ctx, launch_clatch_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, batch, n_images, st, &ctx->prof));
+    CLC_HIP(ctx, launch_clatch_batch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, batch, n_images, st, &ctx->prof));
     return CLC_OK;
 }
 
@@ -737,9 +685,9 @@ int clc_describe(clc_ctx* ctx, const clc_keypoint* h_kps, int n, uint8_t* h_desc
     for (int i = 0; i < n; ++i)
         if (h_kps[i].scale >= ctx->pd.levels) return fail(ctx, CLC_ERR_BAD_ARG, "describe: keypoint scale >= scale_levels");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    CLC_HIP(ctx, hipMemcpyAsync(ctx->d_kps, h_kps, (size_t)n * sizeof(clc_keypoint), hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_clatch(ctx->pd, ctx->d_arena, ctx->d_kps, n, ctx->d_desc, ctx->stream, &ctx->prof));
-    CLC_HIP(ctx, hipMemcpyAsync(h_desc, ctx->d_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyDeviceToHost, ctx->stream));
+    CLC_HIP(ctx, hipMemcpyAsync(ctx->d_kps.as<clc_keypoint>(), h_kps, (size_t)n * sizeof(clc_keypoint), hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, launch_clatch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->d_kps.as<clc_keypoint>(), n, ctx->d_desc.as<uint64_t>(), ctx->stream, &ctx->prof));
+    CLC_HIP(ctx, hipMemcpyAsync(h_desc, ctx->d_desc.as<uint64_t>(), (size_t)n * CLC_DESC_BYTES, hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->rows_at = ROWS_OWN; ctx->own_rows = n;
     return CLC_OK;

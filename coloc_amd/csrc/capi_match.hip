@@ -32,10 +32,10 @@ int run_jobs(clc_ctx* ctx, std::vector<K2nnJobDev>& jobs, hipStream_t st, bool p
     if (rc != CLC_OK) return rc;
     if (!plan.atomic_merge) ctx->partial_dirty = true;           // slab mode scribbles over the armed rows
     else if (ctx->partial_dirty) {
-        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial, 0xFF, ctx->partial_cap * sizeof(uint2), st));
+        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial.ptr, 0xFF, ctx->d_partial.bytes, st));
         ctx->partial_dirty = false;
     }
-    const hipError_t e = launch_k2nn(jobs.data(), (int)jobs.size(), ctx->d_partial, st, probe ? nullptr : &ctx->prof, ctx->formulation, nullptr, probe);
+    const hipError_t e = launch_k2nn(jobs.data(), (int)jobs.size(), ctx->d_partial.as<uint2>(), st, probe ? nullptr : &ctx->prof, ctx->formulation, nullptr, probe);
     if (e != hipSuccess) { ctx->partial_dirty = true; return fail(ctx, CLC_ERR_HIP, "launch_k2nn", e); }
     return CLC_OK;
 }
@@ -70,11 +70,11 @@ void k2nn_probe_bias(clc_ctx* ctx)
     const int d = ctx->device;
     if (!pc.done[d]) {
         pc.done[d] = true; pc.a[d] = ctx->bias_a; pc.b[d] = ctx->bias_b;             // whatever happens below: probe once
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) (void)hipEventDestroy(e0); return; }
+        Event e0, e1;
+        if (e0.create(hipEventDefault) != hipSuccess || e1.create(hipEventDefault) != hipSuccess) return;
         const size_t words = (size_t)N * CLC_DESC_BYTES / 4;
-        hipLaunchKernelGGL(k2nn_probe_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t*)ctx->d_q, words, 1u);
-        hipLaunchKernelGGL(k2nn_probe_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t*)ctx->d_t, words, 2u);
+        hipLaunchKernelGGL(k2nn_probe_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_q.as<uint32_t>(), words, 1u);
+        hipLaunchKernelGGL(k2nn_probe_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d_t.as<uint32_t>(), words, 2u);
         std::vector<K2nnJobDev> jobs(1);
         auto sweep = [&](const int a, const int b, const int reps) -> bool {
             const int sa = ctx->bias_a, sb = ctx->bias_b;
@@ -82,7 +82,7 @@ void k2nn_probe_bias(clc_ctx* ctx)
             bool ok = true;
             for (int r = 0; r < reps && ok; ++r) {
                 jobs[0] = K2nnJobDev{};
-                jobs[0].q = (const uint4*)ctx->d_q; jobs[0].t = (const uint4*)ctx->d_t; jobs[0].out = ctx->d_match;
+                jobs[0].q = ctx->d_q.as<uint4>(); jobs[0].t = ctx->d_t.as<uint4>(); jobs[0].out = ctx->d_match.as<int32_t>();
                 jobs[0].nq = (uint32_t)N; jobs[0].nt = (uint32_t)N; jobs[0].thr = 40u;
                 ok = run_jobs(ctx, jobs, ctx->stream, true) == CLC_OK;
             }
@@ -106,7 +106,6 @@ void k2nn_probe_bias(clc_ctx* ctx)
         // the winner must beat rounds 4's default by more than the noise of such a short measurement (1 %), else the default stays
         if (ok && best_i >= 0 && pc.us[d][2] > 0.f && best < 0.99f * pc.us[d][2]) { pc.a[d] = kProbeCand[best_i][0]; pc.b[d] = kProbeCand[best_i][1]; }
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
         if (!ok) { ctx->partial_dirty = true; for (int c = 0; c < 4; ++c) pc.us[d][c] = 0.f; }
     }
     ctx->bias_a = pc.a[d]; ctx->bias_b = pc.b[d];
@@ -171,21 +170,20 @@ int clc_k2nn_clock_check(clc_ctx* ctx, const void* d_q, int nq, const void* d_t,
     int rc = ensure_partial(ctx, plan.partial_elems);
     if (rc != CLC_OK) return rc;
     if (ctx->partial_dirty) {
-        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial, 0xFF, ctx->partial_cap * sizeof(uint2), st));
+        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial.ptr, 0xFF, ctx->d_partial.bytes, st));
         ctx->partial_dirty = false;
     }
     // the launch grid pads the query blocks to a multiple of 8 (XCD-dealt order, k2nn.hip) and a stamped workgroup
     // writes row blockIdx.y * gridDim.x + blockIdx.x: size the buffer for the PADDED grid (rows of padding workgroups
     // stay zero and are skipped below)
     const size_t nwg = (size_t)((jobs[0].qblocks + 7u) & ~7u) * jobs[0].splits;
-    uint64_t* d_stamps = nullptr;
-    CLC_HIP(ctx, hipMalloc((void**)&d_stamps, nwg * 8 * sizeof(uint64_t)));
+    DevBuf d_stamps;
+    CLC_HIP(ctx, d_stamps.alloc(nwg * 8 * sizeof(uint64_t)));
     std::vector<uint64_t> h(nwg * 8);
-    hipError_t e = hipMemsetAsync(d_stamps, 0, nwg * 8 * sizeof(uint64_t), st);
-    if (e == hipSuccess) e = launch_k2nn(jobs.data(), 1, ctx->d_partial, st, nullptr, ctx->formulation, d_stamps);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_stamps, nwg * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    hipError_t e = hipMemsetAsync(d_stamps.ptr, 0, nwg * 8 * sizeof(uint64_t), st);
+    if (e == hipSuccess) e = launch_k2nn(jobs.data(), 1, ctx->d_partial.as<uint2>(), st, nullptr, ctx->formulation, d_stamps.as<uint64_t>());
+    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_stamps.ptr, nwg * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_stamps);
     if (e != hipSuccess) return fail(ctx, CLC_ERR_HIP, "k2nn_clock_check", e);
     if (const char* dump = getenv("CLC_K2NN_STAMP_DUMP")) {            // diagnostic: raw per-workgroup stamps for tools/archive/k2nn_timeline.py
         if (FILE* f = fopen(dump, "wb")) { fwrite(h.data(), sizeof(uint64_t), h.size(), f); fclose(f); }
@@ -287,9 +285,9 @@ int clc_describe_match_pair_dev(clc_ctx* ctx, const void* const* d_imgs, uint32_
     batch.kps[0] = d_kps[1]; batch.desc[0] = (uint64_t*)d_desc[1]; batch.n[0] = counts[1];
     batch.kps[1] = d_kps[0]; batch.desc[1] = (uint64_t*)d_desc[0]; batch.n[1] = counts[0];
     ctx->pyramid_valid = false;
-    CLC_HIP(ctx, launch_pyramid_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, srcs, 2, (uint32_t)pitch, st, &ctx->prof));
+    CLC_HIP(ctx, launch_pyramid_batch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, srcs, 2, (uint32_t)pitch, st, &ctx->prof));
     ctx->pyramid_valid = true;
-    CLC_HIP(ctx, launch_clatch_batch(ctx->pd, ctx->d_arena, ctx->arena_bytes, batch, 2, st, &ctx->prof));
+    CLC_HIP(ctx, launch_clatch_batch(ctx->pd, ctx->d_arena.as<uint8_t>(), ctx->arena_bytes, batch, 2, st, &ctx->prof));
     if (counts[0] == 0) return CLC_OK;
     std::vector<K2nnJobDev> jobs(1);
     jobs[0] = K2nnJobDev{};
@@ -422,6 +420,7 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
     const size_t off_best = nq * sizeof(int32_t), off_second = off_best + nq * sizeof(uint16_t);
     int rc = ensure_results(ctx, off_second + nq * sizeof(uint16_t) + 64);
     if (rc != CLC_OK) return rc;
+    uint8_t* const h_res = ctx->h_res.as<uint8_t>();
     HostSet* sets[2] = { &q, &t };
     for (HostSet* s : sets) { rc = resolve(ctx, *s); if (rc != CLC_OK) { release_sets(&q, 1); release_sets(&t, 1); return rc; } }
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -429,17 +428,17 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
         jobs[0] = K2nnJobDev{};
         jobs[0].q = (const uint4*)q.d;
         jobs[0].t = (const uint4*)t.d;
-        jobs[0].out = ctx->d_match;
-        jobs[0].best_out = h_best ? ctx->d_best : nullptr;
-        jobs[0].second_out = h_second ? ctx->d_second : nullptr;
+        jobs[0].out = ctx->d_match.as<int32_t>();
+        jobs[0].best_out = h_best ? ctx->d_best.as<uint16_t>() : nullptr;
+        jobs[0].second_out = h_second ? ctx->d_second.as<uint16_t>() : nullptr;
         jobs[0].nq = (uint32_t)q.n;
         jobs[0].nt = (uint32_t)t.n;
         rule.apply(jobs[0]);
         rc = run_jobs(ctx, jobs, ctx->stream);
         hipError_t e = hipSuccess;
-        if (rc == CLC_OK) e = hipMemcpyAsync(ctx->h_res, ctx->d_match, nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (rc == CLC_OK && e == hipSuccess && h_best) e = hipMemcpyAsync(ctx->h_res + off_best, ctx->d_best, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (rc == CLC_OK && e == hipSuccess && h_second) e = hipMemcpyAsync(ctx->h_res + off_second, ctx->d_second, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK) e = hipMemcpyAsync(h_res, ctx->d_match.ptr, nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK && e == hipSuccess && h_best) e = hipMemcpyAsync(h_res + off_best, ctx->d_best.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK && e == hipSuccess && h_second) e = hipMemcpyAsync(h_res + off_second, ctx->d_second.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
         if (rc == CLC_OK && e != hipSuccess) rc = fail(ctx, CLC_ERR_HIP, "match: result download", e);
         // the GPU is sweeping: now the pass over the host blocks that stand on published rows
         bool good = true;
@@ -449,9 +448,9 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
     }
     release_sets(&q, 1); release_sets(&t, 1);
     if (rc != CLC_OK) return rc;
-    memcpy(h_match, ctx->h_res, nq * sizeof(int32_t));
-    if (h_best) memcpy(h_best, ctx->h_res + off_best, nq * sizeof(uint16_t));
-    if (h_second) memcpy(h_second, ctx->h_res + off_second, nq * sizeof(uint16_t));
+    memcpy(h_match, h_res, nq * sizeof(int32_t));
+    if (h_best) memcpy(h_best, h_res + off_best, nq * sizeof(uint16_t));
+    if (h_second) memcpy(h_second, h_res + off_second, nq * sizeof(uint16_t));
     return CLC_OK;
 }
 
@@ -478,25 +477,20 @@ int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts,
     }
     const size_t desc_bytes = cam_off[ncams] * CLC_DESC_BYTES;
     const size_t need = desc_bytes + out_rows * sizeof(int32_t) + 256;
-    if (need > ctx->pairs_cap) {
-        CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_pairs) CLC_HIP(ctx, hipFree(ctx->d_pairs));
-        ctx->d_pairs = nullptr; ctx->pairs_cap = 0;
-        CLC_HIP(ctx, hipMalloc((void**)&ctx->d_pairs, need));
-        ctx->pairs_cap = need;
-    }
+    { const int rc = grow(ctx, ctx->d_pairs, need, 0, 1, true, "growing d_pairs"); if (rc != CLC_OK) return rc; }
+    uint8_t* const d_pairs = ctx->d_pairs.as<uint8_t>();
     { const int rc = ensure_results(ctx, out_rows * sizeof(int32_t) + 64); if (rc != CLC_OK) return rc; }
     // a camera whose block the front end published on this device is read where it lies; the others are uploaded
     std::vector<HostSet> cams((size_t)ncams);
     struct Release { std::vector<HostSet>& s; ~Release() { release_sets(s.data(), (int)s.size()); } } release{ cams };
     for (int c = 0; c < ncams; ++c) {
         HostSet& s = cams[(size_t)c];
-        s.h = h_desc[c]; s.n = counts[c]; s.d_upload = ctx->d_pairs + cam_off[c] * CLC_DESC_BYTES;
-        if (s.n <= 0) { s.d = ctx->d_pairs; continue; }
+        s.h = h_desc[c]; s.n = counts[c]; s.d_upload = d_pairs + cam_off[c] * CLC_DESC_BYTES;
+        if (s.n <= 0) { s.d = d_pairs; continue; }
         const int rc = resolve(ctx, s);
         if (rc != CLC_OK) return rc;
     }
-    int32_t* d_out = (int32_t*)(ctx->d_pairs + ((desc_bytes + 255) & ~(size_t)255));
+    int32_t* d_out = (int32_t*)(d_pairs + ((desc_bytes + 255) & ~(size_t)255));
     std::vector<size_t> out_off(npairs, 0);
     for (int attempt = 0; attempt < 2; ++attempt) {
         std::vector<K2nnJobDev> jobs;
@@ -519,7 +513,7 @@ int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts,
             const int rc = run_jobs(ctx, jobs, ctx->stream);
             if (rc != CLC_OK) return rc;
         }
-        if (out_rows) CLC_HIP(ctx, hipMemcpyAsync(ctx->h_res, d_out, out_rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_rows) CLC_HIP(ctx, hipMemcpyAsync(ctx->h_res.ptr, d_out, out_rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         bool good = true;
         { const int rc = verify_sets(ctx, cams.data(), ncams, &good); if (rc != CLC_OK) return rc; }
         CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -527,7 +521,7 @@ int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts,
     }
     for (int p = 0; p < npairs; ++p) {
         const int a = pairs[2 * p + q_side];
-        if (counts[a] > 0) memcpy(h_match[p], ctx->h_res + out_off[p] * sizeof(int32_t), (size_t)counts[a] * sizeof(int32_t));
+        if (counts[a] > 0) memcpy(h_match[p], ctx->h_res.as<uint8_t>() + out_off[p] * sizeof(int32_t), (size_t)counts[a] * sizeof(int32_t));
     }
     return CLC_OK;
 }
@@ -547,8 +541,8 @@ int clc_match_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt
     if (nq == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     HostSet q, t;
-    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
-    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t;
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q.as<uint8_t>();
+    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t.as<uint8_t>();
     return match_host(ctx, q, t, k2nn_rule(threshold), h_match, h_best, h_second);
 }
 
@@ -564,7 +558,7 @@ int clc_set_map(clc_ctx* ctx, const void* h_desc, int n)
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "set_map: context created without matcher options");
     if ((uint32_t)n > ctx->mopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "set_map: more descriptors than MatcherOptions.maxkp");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    if (n > 0) CLC_HIP(ctx, hipMemcpyAsync(ctx->d_m, h_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream));
+    if (n > 0) CLC_HIP(ctx, hipMemcpyAsync(ctx->d_m.ptr, h_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->map_n = n;
     return CLC_OK;
@@ -579,8 +573,8 @@ int clc_match_map(clc_ctx* ctx, const void* h_q, int nq, int threshold, int32_t*
     if (nq == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     HostSet q, t;
-    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
-    t.resident = true; t.d = ctx->d_m; t.n = ctx->map_n;      // the map is on the device already (clc_set_map)
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q.as<uint8_t>();
+    t.resident = true; t.d = ctx->d_m.as<uint8_t>(); t.n = ctx->map_n;      // the map is on the device already (clc_set_map)
     return match_host(ctx, q, t, k2nn_rule(threshold), h_match, nullptr, nullptr);
 }
 
@@ -589,7 +583,7 @@ int clc_match_map_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int3
     if (!ctx || nq < 0 || (nq > 0 && (!d_q || !d_match))) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_dev: bad argument");
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_dev: context created without matcher options");
     if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_dev before set_map");
-    return clc_match_2nn_dev(ctx, d_q, nq, ctx->d_m, ctx->map_n, threshold, d_match, stream);
+    return clc_match_2nn_dev(ctx, d_q, nq, ctx->d_m.ptr, ctx->map_n, threshold, d_match, stream);
 }
 
 /* ---- the distance-ratio rule: CPUMatcher's matches (include/coloc/CPUMatcher.hpp:56-98) ------------------------------------------
@@ -666,8 +660,8 @@ int clc_match_ratio_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, 
     if (nq == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     HostSet q, t;
-    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
-    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t;
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q.as<uint8_t>();
+    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t.as<uint8_t>();
     return match_host(ctx, q, t, ratio_rule(ratio), h_match, h_best, h_second);
 }
 
@@ -721,8 +715,8 @@ int clc_match_map_ratio(clc_ctx* ctx, const void* h_q, int nq, const float* xy_m
     if (nq == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     HostSet q, t;
-    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q;
-    t.resident = true; t.d = ctx->d_m; t.n = ctx->map_n;      // the map is the database (CPUMatcher.hpp:85-89)
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q.as<uint8_t>();
+    t.resident = true; t.d = ctx->d_m.as<uint8_t>(); t.n = ctx->map_n;      // the map is the database (CPUMatcher.hpp:85-89)
     std::vector<int32_t> m((size_t)nq, -1);
     int rc = match_host(ctx, q, t, ratio_rule(ratio), m.data(), nullptr, nullptr);
     if (rc != CLC_OK) return rc;
@@ -737,7 +731,7 @@ int clc_match_map_ratio_dev(clc_ctx* ctx, const void* d_q, int nq, float ratio, 
     if (!ctx || nq < 0 || (nq > 0 && (!d_q || !d_match))) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_ratio_dev: bad argument");
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_ratio_dev: context created without matcher options");
     if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_ratio_dev before set_map");
-    return clc_match_ratio_2nn_dev(ctx, d_q, nq, ctx->d_m, ctx->map_n, ratio, d_match, stream);
+    return clc_match_ratio_2nn_dev(ctx, d_q, nq, ctx->d_m.ptr, ctx->map_n, ratio, d_match, stream);
 }
 
 } // extern "C"

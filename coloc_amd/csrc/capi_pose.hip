@@ -20,7 +20,7 @@ static int pnp_upload(clc_ctx* ctx, const double* h_Rt, int H, const double* h_X
     const size_t need = (size_t)12 * H + (size_t)5 * N + 16 + extra;
     const int rc = ensure_pnp(ctx, need);
     if (rc != CLC_OK) return rc;
-    double* p = ctx->d_pnp;
+    double* p = ctx->d_pnp.as<double>();
     *dRt = p; p += (size_t)12 * H;
     *dX = p; p += (size_t)3 * N;
     *dx = p; p += (size_t)2 * N;
@@ -81,7 +81,7 @@ static int epipolar_impl(clc_ctx* ctx, const double* h_F, int H, const double* h
     const size_t out = h_err ? (size_t)H * N : (size_t)2 * H;
     const int rc = ensure_pnp(ctx, (size_t)9 * H + (size_t)4 * N + out + 8);
     if (rc != CLC_OK) return rc;
-    double* dF = ctx->d_pnp;
+    double* dF = ctx->d_pnp.as<double>();
     double* d1 = dF + (size_t)9 * H;
     double* d2 = d1 + (size_t)2 * N;
     double* dO = d2 + (size_t)2 * N;
@@ -149,19 +149,19 @@ static int pnp_ransac_impl(clc_ctx* ctx, const double* h_X, const double* h_x, i
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (in_d + out_d) * sizeof(double) + 64);
     if (rc != CLC_OK) return rc;
-    double* dX = ctx->d_pnp;
+    double* dX = ctx->d_pnp.as<double>();
     double* dx = dX + (size_t)3 * N;
     double* dK = dx + (size_t)2 * N;
     int32_t* dSamples = (int32_t*)(dK + 16);
-    double* dRt = ctx->d_pnp + in_d;
+    double* dRt = ctx->d_pnp.as<double>() + in_d;
     double* dCost = dRt + (size_t)48 * S;
     int32_t* dCount = (int32_t*)(dCost + (size_t)4 * S);
-    double* dRes = ctx->d_pnp + in_d + scr_d;
+    double* dRes = ctx->d_pnp.as<double>() + in_d + scr_d;
     uint8_t* dMask = (uint8_t*)(dRes + res_d);
     // Inputs go into the pinned buffer and stay there: the first launch reads them over PCIe and stages them into
     // device memory itself, the last launch writes record + mask back into the pinned buffer.  No copy commands: a
     // pose solve is three (four with refinement) kernel launches and one stream synchronisation.
-    double* hp = (double*)ctx->h_pin;
+    double* hp = ctx->h_pin.as<double>();
     double* hout = hp + in_d;
     memcpy(hp, h_X, sizeof(double) * 3 * N);
     memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
@@ -226,17 +226,17 @@ static int essential_impl(clc_ctx* ctx, const double* h_x1, const double* h_x2, 
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (in_d > out_d ? in_d : out_d) * sizeof(double) + 64);
     if (rc != CLC_OK) return rc;
-    double* d1 = ctx->d_pnp;
+    double* d1 = ctx->d_pnp.as<double>();
     double* d2 = d1 + (size_t)2 * N;
     double* dK1 = d2 + (size_t)2 * N;
     double* dK2 = dK1 + 16;
     int32_t* dSamples = (int32_t*)(dK2 + 16);
-    double* dFE = ctx->d_pnp + in_d;
+    double* dFE = ctx->d_pnp.as<double>() + in_d;
     double* dCost = dFE + (size_t)180 * S;
     int32_t* dCount = (int32_t*)(dCost + (size_t)10 * S);
-    double* dRes = ctx->d_pnp + in_d + scr_d;
+    double* dRes = ctx->d_pnp.as<double>() + in_d + scr_d;
     uint8_t* dMask = (uint8_t*)(dRes + res_d);
-    double* hp = (double*)ctx->h_pin;
+    double* hp = ctx->h_pin.as<double>();
     memcpy(hp, h_x1, sizeof(double) * 2 * N);
     memcpy(hp + (size_t)2 * N, h_x2, sizeof(double) * 2 * N);
     memcpy(hp + (size_t)4 * N, h_K1, sizeof(double) * 9);
@@ -295,13 +295,13 @@ int clc_pnp_refine(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (in_d > out_d ? in_d : out_d) * sizeof(double) + 64);
     if (rc != CLC_OK) return rc;
-    double* dX = ctx->d_pnp;
+    double* dX = ctx->d_pnp.as<double>();
     double* dx = dX + (size_t)3 * N;
     double* dK = dx + (size_t)2 * N;
     double* dRt = dK + 16;
     uint8_t* dMask = (uint8_t*)(dRt + 12);
-    double* dOut = ctx->d_pnp + in_d;
-    double* hp = (double*)ctx->h_pin;
+    double* dOut = ctx->d_pnp.as<double>() + in_d;
+    double* hp = ctx->h_pin.as<double>();
     memcpy(hp, h_X, sizeof(double) * 3 * N);
     memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
     memcpy(hp + (size_t)5 * N, h_K, sizeof(double) * 9);

@@ -2,6 +2,7 @@
 #ifndef CLC_CTX_H
 #define CLC_CTX_H
 
+#include "clc_buf.h"
 #include "clc_internal.h"
 
 #include <string>
@@ -44,20 +45,16 @@ struct Profiler {
         for (hipEvent_t e : pool) (void)hipEventDestroy(e);
     }
 };
-} // namespace clc
 
-namespace clc {
 struct DescEntry;
 // rows_at: STAGED = the frame of the last clc_detect_and_describe* call (pinned block / desc_pending, staged_n rows); OWN = the
 // context's own d_desc (own_rows); NONE = the last describing call wrote a caller buffer or failed, or nothing was described yet
 enum { ROWS_NONE = 0, ROWS_STAGED = 1, ROWS_OWN = 2 };
-}
 
-namespace clc {
 // A context's block of gathered correspondences, device and pinned, for `cap` of them (ensure_gather):
 //   device [ a (a_width cap doubles) | b (2 cap) | q cap | t cap | n ]     tracks: X | x | query | map, pairs: x1 | x2 | q | t
 //   pinned [ count word (64 B, 0xFF.. = not out yet) | a | b (where the points are mirrored: pairs) | q | t ]
-struct GatherBlock { uint8_t* d = nullptr; uint8_t* h = nullptr; size_t cap = 0; };
+struct GatherBlock { DevBuf d; PinBuf h; size_t cap = 0; };
 struct GatherLayout {
     int a_width; bool mirror_points;
     size_t d_row() const { return (size_t)(a_width + 2) * sizeof(double) + 2 * sizeof(int32_t); }
@@ -69,14 +66,14 @@ struct GatherView {
     double *a, *b; int32_t *q, *t, *n; uint32_t* h_n; double *h_a = nullptr, *h_b = nullptr; int32_t *h_q, *h_t;
     GatherView(const GatherBlock& g, const GatherLayout& lay)
     {
-        a = (double*)g.d; b = a + lay.a_width * g.cap; q = (int32_t*)(b + 2 * g.cap); t = q + g.cap; n = t + g.cap;
-        h_n = (uint32_t*)g.h;
-        double* hp = (double*)(g.h + 64);
+        a = g.d.as<double>(); b = a + lay.a_width * g.cap; q = (int32_t*)(b + 2 * g.cap); t = q + g.cap; n = t + g.cap;
+        h_n = g.h.as<uint32_t>();
+        double* hp = (double*)(g.h.as<uint8_t>() + 64);
         if (lay.mirror_points) { h_a = hp; h_b = hp + lay.a_width * g.cap; hp = h_b + 2 * g.cap; }
         h_q = (int32_t*)hp; h_t = h_q + g.cap;
     }
 };
-}
+} // namespace clc
 
 struct clc_ctx {
     int device = 0;
@@ -88,32 +85,28 @@ struct clc_ctx {
     clc_matcher_opts mopts{};
     // pyramid
     clc::PyramidDesc pd{};
-    uint8_t* d_arena = nullptr;
+    clc::DevBuf d_arena;         // (bytes)
     size_t arena_bytes = 0;      // one pyramid
     int arena_slots = 1;         // pyramids the arena holds (grown by clc_describe_batch_dev)
     bool pyramid_valid = false;
     // detect + describe
-    clc_keypoint* d_kps = nullptr;
-    uint64_t* d_desc = nullptr;
-    uint8_t* d_score = nullptr;      // arena-shaped FAST score maps (one per pyramid slot; only keypoint pixels are written and read)
-    uint64_t* d_kpmask = nullptr;    // [slot][tile][16] keypoint bits of a tile row (detect.hip)
-    uint32_t* d_tcount = nullptr;    // [slot][tile] keypoints of a tile
-    uint32_t* d_count = nullptr;     // {written, found} of the context's own keypoint list
+    clc::DevBuf d_kps;               // clc_keypoint
+    clc::DevBuf d_desc;              // uint64_t
+    clc::DevBuf d_score;             // arena-shaped FAST score maps (one per pyramid slot; only keypoint pixels are written and read)
+    clc::DevBuf d_kpmask;            // uint64_t [slot][tile][16] keypoint bits of a tile row (detect.hip)
+    clc::DevBuf d_tcount;            // uint32_t [slot][tile] keypoints of a tile
+    clc::DevBuf d_count;             // uint32_t {written, found} of the context's own keypoint list
     uint32_t n_tiles = 0;
     int selection = CLC_SELECT_FIRST;   // which keypoints a frame with more than maxkp keeps (clc_detect_set_selection)
-    uint32_t* d_select = nullptr;    // [CLC_MAX_BATCH][detect_select_words] score histograms, cutoffs, band counts of CLC_SELECT_STRONGEST
+    clc::DevBuf d_select;            // uint32_t [CLC_MAX_BATCH][detect_select_words] score histograms, cutoffs, band counts of CLC_SELECT_STRONGEST
     bool select_dirty = false;       // a selecting detect call failed between its launches: the histograms may not be zero
     bool detected = false;
     // match
-    uint8_t* d_q = nullptr;
-    uint8_t* d_t = nullptr;
-    uint8_t* d_m = nullptr;
+    clc::DevBuf d_q, d_t, d_m;       // descriptor rows (bytes)
     int map_n = -1;
-    int32_t* d_match = nullptr;
-    uint16_t* d_best = nullptr;
-    uint16_t* d_second = nullptr;
-    uint2* d_partial = nullptr;
-    size_t partial_cap = 0;
+    clc::DevBuf d_match;             // int32_t
+    clc::DevBuf d_best, d_second;    // uint16_t
+    clc::DevBuf d_partial;           // uint2: the armed top-2 rows + arrival counters of the K2NN sweeps
     bool partial_dirty = false;      // armed (all-ones) state of the atomic top-2 rows was lost
     int formulation = clc::K2NN_MATRIX;   // K2NN sweep formulation (k2nn.hip): FP4 matrix pipe, or round 1's popcount kernel for A/B runs
     int target_blocks = 0;           // K2NN sweep workgroups aimed at per launch; 0 = the formulation's default
@@ -123,23 +116,20 @@ struct clc_ctx {
     clc::K2nnDevice k2dev{};          // XCDs and CUs of this context's device (the sweep planner's balance arguments)
     int bias_source = 0;         // 0: built-in default, 1: CLC_K2NN_BIAS, 2: timed probe on this device (k2nn_probe_bias)
     float bias_probe_us[4] = {}; // the probe's sweep times per candidate (0: not probed)
-    hipEvent_t ev_group = nullptr;   // acr_drive (pose_batch.hip): orders a shared group's stream and the contexts' own streams
+    clc::Event ev_group;             // acr_drive (pose_batch.hip): orders a shared group's stream and the contexts' own streams
     int cache_mode = CLC_DESC_CACHE_VERIFY;   // how this context's host-pointer match entry points treat published blocks (clc_desc_cache_mode)
     // pnp
-    uint8_t* d_pairs = nullptr;   // clc_match_pairs arena: descriptors of all cameras, then results
-    size_t pairs_cap = 0;
-    double* d_pnp = nullptr;
-    size_t pnp_cap = 0;   // doubles
-    void* h_pin = nullptr;        // pinned staging for the pose solve
-    size_t pin_cap = 0;
+    clc::DevBuf d_pairs;          // clc_match_pairs arena (bytes): descriptors of all cameras, then results
+    clc::DevBuf d_pnp;            // double
+    clc::PinBuf h_pin;            // pinned staging for the pose solve
     // 2D-3D tracks and two-view correspondences (gather.hip)
-    double* d_map_X = nullptr;    // clc_set_map_points: the landmark of map descriptor row i, 3 doubles each
-    int map_X_n = -1, map_X_cap = 0;      // (-1: none set)
+    clc::DevBuf d_map_X;          // clc_set_map_points: the landmark of map descriptor row i, 3 doubles each
+    int map_X_n = -1;             // (-1: none set)
     clc::GatherBlock trk, pair;   // the tracks (clc_track_localize*_dev) / the pairs (clc_pair_filter*_dev) of this context's job
-    hipEvent_t ev_track = nullptr;   // orders the track / pair launch behind job.after_stream, and the contexts' streams behind the launch
+    clc::Event ev_track;             // orders the track / pair launch behind job.after_stream, and the contexts' streams behind the launch
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
-    uint8_t* h_stage = nullptr;
+    clc::PinBuf h_stage;          // (bytes)
     size_t stage_img = 0, stage_kps = 0, stage_desc = 0, stage_cnt = 0;      // byte offsets inside h_stage
     clc::DescEntry* desc_pending = nullptr;
     int staged_n = -1;            // rows of the last staged frame (-1: none)
@@ -147,8 +137,7 @@ struct clc_ctx {
     int rows_at = clc::ROWS_NONE;
     int own_rows = 0;             // ROWS_OWN: rows described into d_desc (-1: the detector's {written} counter tells)
     // host-pointer match entries: pinned mirror of the results (so that the host can verify published blocks while the GPU sweeps)
-    uint8_t* h_res = nullptr;
-    size_t res_cap = 0;
+    clc::PinBuf h_res;            // (bytes)
     clc::Profiler prof;
 };
 
@@ -169,6 +158,18 @@ inline bool pose_K_ok(const double* K) { return K[3] == 0.0 && K[6] == 0.0 && K[
     } while (0)
 
 inline hipStream_t pick(clc_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+
+// THE way a context's workspace grows: a buffer that holds `need` bytes stays; any other is freed and allocated anew with
+// need + need * num / den bytes -- behind a synchronisation of the context's stream where work in flight may still use the old block
+// (sync_first).  The contents do not survive.  `what` names the workspace in a failure's text; *fresh: a call that succeeds made a new block.
+template <class B> inline int grow(clc_ctx* ctx, B& b, size_t need, size_t num, size_t den, bool sync_first, const char* what, bool* fresh = nullptr)
+{
+    if (fresh) *fresh = need > b.bytes;
+    if (need <= b.bytes) return CLC_OK;
+    if (sync_first) CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const hipError_t e = b.grow(need, num, den);
+    return e == hipSuccess ? CLC_OK : fail(ctx, CLC_ERR_HIP, what, e);
+}
 
 // context-owned workspaces, grown on demand (capi_core.hip)
 int ensure_partial(clc_ctx* ctx, size_t elems);           // armed K2NN top-2 rows + arrival counters

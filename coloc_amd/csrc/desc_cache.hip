@@ -227,7 +227,7 @@ int clc_desc_cache_publish(clc_ctx* ctx, const void* d_src, const void* h_desc, 
         // NULL = the rows of this context's last describing call, and only if the host block holds exactly those rows: the fold
         // taken below proves only that the host rows do not change AFTER this call, never that the device rows equal them
         if (ctx->rows_at == ROWS_STAGED) {
-            if (n > ctx->staged_n || memcmp(h_desc, ctx->h_stage + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES) != 0)
+            if (n > ctx->staged_n || memcmp(h_desc, ctx->h_stage.as<uint8_t>() + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES) != 0)
                 return fail(ctx, CLC_ERR_STATE, "desc_cache_publish: the host rows are not the rows of the frame this context staged");
             // the rows already lie in a block of the table ...
             if (ctx->desc_pending && n == ctx->staged_n) e = ctx->desc_pending;
@@ -237,7 +237,7 @@ int clc_desc_cache_publish(clc_ctx* ctx, const void* d_src, const void* h_desc, 
                 uint8_t* d = nullptr;
                 e = desc_reserve(ctx, ctx->device, (size_t)n, &d);
                 if (!e) return CLC_OK;
-                hipError_t err = hipMemcpyAsync(d, ctx->h_stage + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream);
+                hipError_t err = hipMemcpyAsync(d, ctx->h_stage.as<uint8_t>() + ctx->stage_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream);
                 if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
                 if (err != hipSuccess) { desc_abandon(e); return fail(ctx, CLC_ERR_HIP, "desc_cache_publish", err); }
             }
@@ -245,7 +245,7 @@ int clc_desc_cache_publish(clc_ctx* ctx, const void* d_src, const void* h_desc, 
             // the device-resident flow (clc_describe_detected_dev / clc_describe_dev into d_desc) or clc_describe
             if (n > (ctx->own_rows >= 0 ? ctx->own_rows : (int)ctx->dopts.maxkp))
                 return fail(ctx, CLC_ERR_BAD_ARG, "desc_cache_publish: more rows than this context described");
-            d_src = ctx->d_desc;
+            d_src = ctx->d_desc.ptr;
             count_on_device = ctx->own_rows < 0;
         } else
             return fail(ctx, CLC_ERR_STATE, "desc_cache_publish: no rows of this context to publish (its last describing call wrote a caller buffer or failed)");
@@ -256,7 +256,7 @@ int clc_desc_cache_publish(clc_ctx* ctx, const void* d_src, const void* h_desc, 
         if (!e) return CLC_OK;                                                       // every entry in use: nothing is published
         uint32_t cnt[2] = { 0, 0 };
         hipError_t err = hipMemcpyAsync(d, d_src, (size_t)n * CLC_DESC_BYTES, hipMemcpyDeviceToDevice, ctx->stream);
-        if (err == hipSuccess && count_on_device) err = hipMemcpyAsync(cnt, ctx->d_count, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream);
+        if (err == hipSuccess && count_on_device) err = hipMemcpyAsync(cnt, ctx->d_count.ptr, sizeof cnt, hipMemcpyDeviceToHost, ctx->stream);
         if (err == hipSuccess) err = hipStreamSynchronize(ctx->stream);
         if (err != hipSuccess) { desc_abandon(e); return fail(ctx, CLC_ERR_HIP, "desc_cache_publish", err); }
         // (n <= maxkp was checked above, so the copy stayed inside d_desc; rows past the detector's count are not described rows)

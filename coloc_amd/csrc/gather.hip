@@ -169,13 +169,12 @@ int ensure_gather(clc_ctx* ctx, GatherBlock& g, size_t cap, const GatherLayout& 
     cap = (cap + 63) & ~(size_t)63;
     if (cap < 64) cap = 64;
     if (cap <= g.cap && g.d && g.h) return CLC_OK;
-    // (nothing of an earlier call is in flight: a solve returns after its staging launch has consumed the block)
-    if (g.d) { (void)hipFree(g.d); g.d = nullptr; }
-    if (g.h) { (void)hipHostFree(g.h); g.h = nullptr; }
+    // (no synchronisation: nothing of an earlier call is in flight, a solve returns after its staging launch has consumed the block)
     g.cap = 0;
-    CLC_HIP(ctx, hipMalloc((void**)&g.d, cap * lay.d_row() + 64));
-    CLC_HIP(ctx, hipHostMalloc((void**)&g.h, 64 + cap * lay.h_row(), hipHostMallocDefault));
-    memset(g.h, 0xFF, 64);
+    int rc = grow(ctx, g.d, cap * lay.d_row() + 64, 0, 1, false, "growing a gather block");
+    if (rc == CLC_OK) rc = grow(ctx, g.h, 64 + cap * lay.h_row(), 0, 1, false, "growing a pinned gather block");
+    if (rc != CLC_OK) return rc;
+    memset(g.h.ptr, 0xFF, 64);        // the count word: not out yet
     g.cap = cap;
     return CLC_OK;
 }
@@ -191,15 +190,10 @@ int clc_set_map_points(clc_ctx* ctx, const double* h_X, int n)
     if (!ctx || n < 0 || (n > 0 && !h_X)) return fail(ctx, CLC_ERR_BAD_ARG, "set_map_points: bad argument");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     if (n == 0) { ctx->map_X_n = -1; return CLC_OK; }
-    if (n > ctx->map_X_cap) {
-        CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->d_map_X) { (void)hipFree(ctx->d_map_X); ctx->d_map_X = nullptr; }
-        ctx->map_X_cap = 0; ctx->map_X_n = -1;
-        CLC_HIP(ctx, hipMalloc((void**)&ctx->d_map_X, (size_t)n * 3 * sizeof(double)));
-        ctx->map_X_cap = n;
-    }
     ctx->map_X_n = -1;
-    CLC_HIP(ctx, hipMemcpyAsync(ctx->d_map_X, h_X, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = grow(ctx, ctx->d_map_X, (size_t)n * 3 * sizeof(double), 0, 1, true, "growing d_map_X");
+    if (rc != CLC_OK) return rc;
+    CLC_HIP(ctx, hipMemcpyAsync(ctx->d_map_X.ptr, h_X, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->map_X_n = n;
     return CLC_OK;
@@ -219,7 +213,7 @@ int clc_track_build_dev(clc_ctx* ctx, const clc_track_job* job, double* d_X, dou
     if (job->nq == 0 && !d_n) return CLC_OK;
     jb.X = d_X; jb.x = d_x; jb.query = d_query; jb.map = d_map; jb.n = d_n;
     jb.cap = job->nq;
-    jobs.map_X = ctx->d_map_X; jobs.map_n = ctx->map_X_n;
+    jobs.map_X = ctx->d_map_X.as<double>(); jobs.map_n = ctx->map_X_n;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     CLC_HIP(ctx, launch_gather(jobs, 1, pick(ctx, stream)));
     return CLC_OK;

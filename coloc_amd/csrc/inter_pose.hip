@@ -27,11 +27,11 @@ int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (in_d + out_d) * sizeof(double) + 64);
     if (rc != CLC_OK) return rc;
-    double* dX = ctx->d_pnp;
+    double* dX = ctx->d_pnp.as<double>();
     double* dx = dX + (size_t)3 * N;
     double* dK = dx + (size_t)2 * N;
     double* dRt = dK + 16;
-    double* hp = (double*)ctx->h_pin;
+    double* hp = ctx->h_pin.as<double>();
     memcpy(hp, h_X, sizeof(double) * 3 * N);
     memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
     memset(hp + (size_t)5 * N, 0, sizeof(double) * 16);
@@ -41,8 +41,8 @@ int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     __atomic_store_n(&(*h_rec)->ready, 0, __ATOMIC_RELAXED);
     const double* src = hp;
     const size_t n_stage = (in_d + 1) & ~(size_t)1;
-    CLC_HIP(ctx, launch_acr_stage(&src, &ctx->d_pnp, &n_stage, 1, ctx->stream));                 // inputs by a launch, not a copy command
-    CLC_HIP(ctx, launch_pnp_refine(dRt, dX, dx, nullptr, N, dK, huber_a > 0.0 ? huber_a : 16.0, 50, ctx->d_pnp + in_d, ctx->stream, &ctx->prof, nullptr,
+    CLC_HIP(ctx, launch_acr_stage(&src, &dX, &n_stage, 1, ctx->stream));                 // inputs by a launch, not a copy command
+    CLC_HIP(ctx, launch_pnp_refine(dRt, dX, dx, nullptr, N, dK, huber_a > 0.0 ? huber_a : 16.0, 50, dX + in_d, ctx->stream, &ctx->prof, nullptr,
                                    *h_rec));
     return CLC_OK;
 }
@@ -67,12 +67,12 @@ int map_match_enqueue(clc_ctx* ctx, const clc_inter_pose_job& jb, const InterFro
     if (rc != CLC_OK) return rc;
     rc = ensure_pinned(ctx, (idx_d + match_d) * sizeof(double) + 64);
     if (rc != CLC_OK) return rc;
-    int32_t* h_idx = (int32_t*)ctx->h_pin;
-    *h_match = (int32_t*)((double*)ctx->h_pin + idx_d);
+    int32_t* h_idx = ctx->h_pin.as<int32_t>();
+    *h_match = (int32_t*)(ctx->h_pin.as<double>() + idx_d);
     for (size_t k = 0; k < nf; ++k) h_idx[k] = jb.first_feature[fr.corr[k]];
-    int32_t* d_idx = (int32_t*)ctx->d_pnp;
-    uint4* d_rows = (uint4*)(ctx->d_pnp + idx_d);
-    int32_t* d_match = (int32_t*)(ctx->d_pnp + idx_d + rows_d);
+    int32_t* d_idx = ctx->d_pnp.as<int32_t>();
+    uint4* d_rows = (uint4*)(ctx->d_pnp.as<double>() + idx_d);
+    int32_t* d_match = (int32_t*)(ctx->d_pnp.as<double>() + idx_d + rows_d);
     CLC_HIP(ctx, hipMemcpyAsync(d_idx, h_idx, nf * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((nf * 4 + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)jb.d_first_desc, (const int32_t*)d_idx,
                        d_rows, (uint32_t)nf);

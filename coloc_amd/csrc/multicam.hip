@@ -35,6 +35,7 @@
 //
 // Written against the public C ABI + the HIP runtime only.  The planner (clc_mc_plan) is pure host arithmetic and is
 // the C twin of coloc_amd/multicam.py shard_pairs (tests/test_multicam.py checks them against each other).
+#include "clc_buf.h"
 #include "clc_internal.h"
 
 #include <dlfcn.h>
@@ -102,11 +103,11 @@ struct clc_mc {
     int world = 1, rank = 0, cap = 0, device = 0;
     ncclComm_t comm = nullptr;
     int nbuf = 2;                          // arena buffers: 2 (steps on one stream), 3 (overlapped steps)
-    uint8_t* d_arena = nullptr;            // [nbuf][world][cap][64]: buffer (step % nbuf) receives step's blocks
-    int32_t* d_counts = nullptr;           // [nbuf][world + 1]: the gathered counts of a buffer, this rank's own count at [world]
-    int32_t* h_counts = nullptr;           // pinned, [nbuf][world + 1]: host mirror of the gathered counts (written by the device only)
+    clc::DevBuf d_arena;                   // [nbuf][world][cap][64]: buffer (step % nbuf) receives step's blocks
+    clc::DevBuf d_counts;                  // int32_t [nbuf][world + 1]: the gathered counts of a buffer, this rank's own count at [world]
+    clc::PinBuf h_counts;                  // int32_t, [nbuf][world + 1]: host mirror of the gathered counts (written by the device only)
     bool overlap = false;                  // exchange and sweep on different streams (clc_mc_set_overlap)
-    hipEvent_t ev_exch[3] = {}, ev_sweep[3] = {};   // behind the exchange / the sweep of the step a buffer holds
+    clc::Event ev_exch[3], ev_sweep[3];           // behind the exchange / the sweep of the step a buffer holds
     long exch_step[3] = { -1, -1, -1 }, sweep_step[3] = { -1, -1, -1 };   // which step those events stand for (-1: none recorded)
     long steps = 0;                        // exchanges enqueued so far = the number of the next step
     int fill = 0;                          // buffer the NEXT gather (and clc_mc_virtual_put) writes
@@ -137,16 +138,13 @@ int mc_fail(clc_mc* mc, int code, const char* what, hipError_t e = hipSuccess, n
 // the arena and the count rows for mc->nbuf buffers (again after clc_mc_set_overlap)
 int mc_alloc(clc_mc* mc)
 {
-    if (mc->d_arena) (void)hipFree(mc->d_arena);
-    if (mc->d_counts) (void)hipFree(mc->d_counts);
-    if (mc->h_counts) (void)hipHostFree(mc->h_counts);
-    mc->d_arena = nullptr; mc->d_counts = nullptr; mc->h_counts = nullptr;
+    (void)mc->d_arena.reset(); (void)mc->d_counts.reset(); (void)mc->h_counts.reset();
     const size_t nb = (size_t)mc->nbuf, rows = sizeof(int32_t) * (size_t)(mc->world + 1);
-    MC_HIP(mc, hipMalloc((void**)&mc->d_arena, nb * (size_t)mc->world * (size_t)mc->cap * CLC_DESC_BYTES));
-    MC_HIP(mc, hipMalloc((void**)&mc->d_counts, nb * rows));
-    MC_HIP(mc, hipMemset(mc->d_counts, 0, nb * rows));
-    MC_HIP(mc, hipHostMalloc((void**)&mc->h_counts, nb * rows, hipHostMallocDefault));
-    memset(mc->h_counts, 0, nb * rows);
+    MC_HIP(mc, mc->d_arena.alloc(nb * (size_t)mc->world * (size_t)mc->cap * CLC_DESC_BYTES));
+    MC_HIP(mc, mc->d_counts.alloc(nb * rows));
+    MC_HIP(mc, hipMemset(mc->d_counts.ptr, 0, nb * rows));
+    MC_HIP(mc, mc->h_counts.alloc(nb * rows));
+    memset(mc->h_counts.ptr, 0, nb * rows);
     mc->fill = 0; mc->cur = 0;
     return CLC_OK;
 }
@@ -158,19 +156,19 @@ int open_peers(clc_mc* mc, hipStream_t st)
     if (mc->peers_tried) return mc_fail(mc, CLC_ERR_STATE, "peer copy: mapping the peers' arenas failed earlier");
     mc->peers_tried = true;
     std::vector<uint8_t*> peers((size_t)mc->world, nullptr);
-    peers[(size_t)mc->rank] = mc->d_arena;
+    peers[(size_t)mc->rank] = mc->d_arena.as<uint8_t>();
     if (mc->world > 1) {
         hipIpcMemHandle_t mine;
-        MC_HIP(mc, hipIpcGetMemHandle(&mine, mc->d_arena));
-        hipIpcMemHandle_t* d_h = nullptr;
-        MC_HIP(mc, hipMalloc((void**)&d_h, sizeof(hipIpcMemHandle_t) * (size_t)(mc->world + 1)));
+        MC_HIP(mc, hipIpcGetMemHandle(&mine, mc->d_arena.ptr));
+        clc::DevBuf handles;
+        MC_HIP(mc, handles.alloc(sizeof(hipIpcMemHandle_t) * (size_t)(mc->world + 1)));
+        hipIpcMemHandle_t* d_h = handles.as<hipIpcMemHandle_t>();
         std::vector<hipIpcMemHandle_t> all((size_t)mc->world);
         hipError_t e = hipMemcpyAsync(d_h + mc->world, &mine, sizeof mine, hipMemcpyHostToDevice, st);
         ncclResult_t n = ncclSuccess;
         if (e == hipSuccess) n = rccl().AllGather(d_h + mc->world, d_h, sizeof(hipIpcMemHandle_t), ncclUint8, mc->comm, st);
         if (e == hipSuccess && n == ncclSuccess) e = hipMemcpyAsync(all.data(), d_h, sizeof(hipIpcMemHandle_t) * (size_t)mc->world, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess && n == ncclSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(d_h);
         if (e != hipSuccess || n != ncclSuccess) return mc_fail(mc, CLC_ERR_HIP, "peer copy: IPC handle exchange", e, n);
         for (int p = 0; p < mc->world; ++p) {
             if (p == mc->rank) continue;
@@ -269,8 +267,8 @@ int clc_mc_set_overlap(clc_mc* mc, int on)
     mc->nbuf = mc->overlap ? 3 : 2;
     if (mc->overlap)
         for (int b = 0; b < 3; ++b) {
-            if (!mc->ev_exch[b]) MC_HIP(mc, hipEventCreateWithFlags(&mc->ev_exch[b], hipEventDisableTiming));
-            if (!mc->ev_sweep[b]) MC_HIP(mc, hipEventCreateWithFlags(&mc->ev_sweep[b], hipEventDisableTiming));
+            MC_HIP(mc, mc->ev_exch[b].create(hipEventDisableTiming));
+            MC_HIP(mc, mc->ev_sweep[b].create(hipEventDisableTiming));
         }
     return mc_alloc(mc);
 }
@@ -296,11 +294,7 @@ int clc_mc_destroy(clc_mc* mc)
     for (int p = 0; p < (int)mc->peer_arena.size(); ++p)
         if (p != mc->rank && mc->peer_arena[(size_t)p]) (void)hipIpcCloseMemHandle(mc->peer_arena[(size_t)p]);
     if (mc->comm && rccl().ok) (void)rccl().CommDestroy(mc->comm);
-    for (int b = 0; b < 3; ++b) { if (mc->ev_exch[b]) (void)hipEventDestroy(mc->ev_exch[b]); if (mc->ev_sweep[b]) (void)hipEventDestroy(mc->ev_sweep[b]); }
-    if (mc->d_arena) (void)hipFree(mc->d_arena);
-    if (mc->d_counts) (void)hipFree(mc->d_counts);
-    if (mc->h_counts) (void)hipHostFree(mc->h_counts);
-    delete mc;
+    delete mc;                 // (its events, arena and count rows go with it)
     return CLC_OK;
 }
 
@@ -309,7 +303,7 @@ const char* clc_mc_last_error_string(const clc_mc* mc) { return mc ? mc->err.c_s
 int clc_mc_arena(const clc_mc* mc, void** d_arena, int* world, int* maxkp)
 {
     if (!mc) return CLC_ERR_BAD_ARG;
-    if (d_arena) *d_arena = mc->d_arena + (size_t)mc->cur * (size_t)mc->world * (size_t)mc->cap * CLC_DESC_BYTES;
+    if (d_arena) *d_arena = mc->d_arena.as<uint8_t>() + (size_t)mc->cur * (size_t)mc->world * (size_t)mc->cap * CLC_DESC_BYTES;
     if (world) *world = mc->world;
     if (maxkp) *maxkp = mc->cap;
     return CLC_OK;
@@ -327,9 +321,9 @@ static int mc_exchange(clc_mc* mc, const void* d_my_desc, int my_count, const in
         for (int bw = 0; bw < 3; ++bw)
             if (mc->sweep_step[bw] >= 0 && mc->sweep_step[bw] <= step - 2) MC_HIP(mc, hipStreamWaitEvent(st, mc->ev_sweep[bw], 0));
     }
-    uint8_t* arena = mc->d_arena + (size_t)b * buf;
-    int32_t* d_cnt = mc->d_counts + (size_t)b * (size_t)(mc->world + 1);
-    int32_t* h_cnt = mc->h_counts + (size_t)b * (size_t)(mc->world + 1);
+    uint8_t* arena = mc->d_arena.as<uint8_t>() + (size_t)b * buf;
+    int32_t* d_cnt = mc->d_counts.as<int32_t>() + (size_t)b * (size_t)(mc->world + 1);
+    int32_t* h_cnt = mc->h_counts.as<int32_t>() + (size_t)b * (size_t)(mc->world + 1);
     // rows to move: the valid ones when the host knows the count, the whole fixed-capacity block when only the device does
     const size_t rows = d_my_count ? (size_t)mc->cap : (size_t)my_count;
     if (d_my_count) MC_HIP(mc, hipMemcpyAsync(d_cnt + mc->world, d_my_count, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
@@ -378,7 +372,7 @@ int clc_mc_gather_dev(clc_mc* mc, const void* d_my_desc, int my_count, int mode,
     if (rc != CLC_OK) return rc;
     MC_HIP(mc, hipStreamSynchronize(st));                          // clc_mc_match_dev plans its shares from the counts
     mc->counts_on_host = true;
-    const int32_t* h_cnt = mc->h_counts + (size_t)mc->cur * (size_t)(mc->world + 1);
+    const int32_t* h_cnt = mc->h_counts.as<int32_t>() + (size_t)mc->cur * (size_t)(mc->world + 1);
     if (h_counts_out) for (int c = 0; c < mc->world; ++c) h_counts_out[c] = h_cnt[c];
     return CLC_OK;
 }
@@ -408,7 +402,7 @@ int clc_mc_counts(clc_mc* mc, int* h_counts_out, void* stream)
     MC_HIP(mc, hipSetDevice(mc->device));
     hipStream_t st = stream ? (hipStream_t)stream : (hipStream_t)clc_stream(mc->ctx);
     MC_HIP(mc, hipStreamSynchronize(st));
-    const int32_t* h_cnt = mc->h_counts + (size_t)mc->cur * (size_t)(mc->world + 1);
+    const int32_t* h_cnt = mc->h_counts.as<int32_t>() + (size_t)mc->cur * (size_t)(mc->world + 1);
     for (int c = 0; c < mc->world; ++c) h_counts_out[c] = h_cnt[c];
     return CLC_OK;
 }
@@ -423,9 +417,9 @@ int clc_mc_virtual_put(clc_mc* mc, int other_rank, const void* d_desc, int count
     const size_t block = (size_t)mc->cap * CLC_DESC_BYTES;
     if (mc->overlap && mc->sweep_step[mc->fill] >= 0) MC_HIP(mc, hipStreamWaitEvent(st, mc->ev_sweep[mc->fill], 0));   // (a real peer's copy comes behind the collective chain)
     if (count > 0)
-        MC_HIP(mc, hipMemcpyAsync(mc->d_arena + ((size_t)mc->fill * (size_t)mc->world + (size_t)other_rank) * block, d_desc,
+        MC_HIP(mc, hipMemcpyAsync(mc->d_arena.as<uint8_t>() + ((size_t)mc->fill * (size_t)mc->world + (size_t)other_rank) * block, d_desc,
                                   (size_t)count * CLC_DESC_BYTES, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(mc_set_count_kernel, dim3(1), dim3(1), 0, st, mc->d_counts + (size_t)mc->fill * (size_t)(mc->world + 1) + other_rank,
+    hipLaunchKernelGGL(mc_set_count_kernel, dim3(1), dim3(1), 0, st, mc->d_counts.as<int32_t>() + (size_t)mc->fill * (size_t)(mc->world + 1) + other_rank,
                        (int32_t)count);
     MC_HIP(mc, hipGetLastError());
     MC_HIP(mc, hipStreamSynchronize(st));                        // a rehearsal entry: on return the "peer's" block has arrived
@@ -444,7 +438,7 @@ static int mc_sweep(clc_mc* mc, const std::vector<int>& counts, bool device_coun
     if (n > share_capacity) return mc_fail(mc, CLC_ERR_CAPACITY, "mc_match: share array too small");
     std::vector<clc_match_job> jobs((size_t)n);
     std::vector<const int32_t*> cq, ct;
-    const int32_t* d_cnt = mc->d_counts + (size_t)mc->cur * (size_t)(mc->world + 1);
+    const int32_t* d_cnt = mc->d_counts.as<int32_t>() + (size_t)mc->cur * (size_t)(mc->world + 1);
     uint64_t rows = 0;
     for (int k = 0; k < n; ++k) {
         const clc_mc_share& s = shares[(size_t)k];
@@ -461,7 +455,7 @@ static int mc_sweep(clc_mc* mc, const std::vector<int>& counts, bool device_coun
     if (rows > (uint64_t)match_capacity) return mc_fail(mc, CLC_ERR_CAPACITY, "mc_match: result buffer too small");
     *n_shares = n;
     if (n == 0) return CLC_OK;
-    const uint8_t* arena = mc->d_arena + (size_t)mc->cur * (size_t)mc->world * (size_t)mc->cap * CLC_DESC_BYTES;
+    const uint8_t* arena = mc->d_arena.as<uint8_t>() + (size_t)mc->cur * (size_t)mc->world * (size_t)mc->cap * CLC_DESC_BYTES;
     hipStream_t sweep_st = stream ? (hipStream_t)stream : (hipStream_t)clc_stream(mc->ctx);
     if (mc->overlap && mc->exch_step[mc->cur] >= 0) MC_HIP(mc, hipStreamWaitEvent(sweep_st, mc->ev_exch[mc->cur], 0));
     if (device_counts) {
@@ -481,7 +475,7 @@ int clc_mc_match_dev(clc_mc* mc, int threshold, int32_t* d_match, int match_capa
         return mc_fail(mc, CLC_ERR_BAD_ARG, "mc_match: bad argument");
     if (!mc->counts_on_host) return mc_fail(mc, CLC_ERR_STATE, "mc_match: the last exchange was enqueue-only (use clc_mc_match_enqueue_dev, or clc_mc_gather_dev)");
     std::vector<int> counts((size_t)mc->world);
-    const int32_t* h_cnt = mc->h_counts + (size_t)mc->cur * (size_t)(mc->world + 1);
+    const int32_t* h_cnt = mc->h_counts.as<int32_t>() + (size_t)mc->cur * (size_t)(mc->world + 1);
     for (int c = 0; c < mc->world; ++c) counts[(size_t)c] = h_cnt[c];
     return mc_sweep(mc, counts, false, threshold, d_match, match_capacity, h_shares, share_capacity, n_shares, stream);
 }

@@ -53,9 +53,9 @@ size_t dbl(size_t bytes) { return (bytes + 7) / 8; }
 // Every consumer stream behind what `producer` holds now: ONE event (ev: its owner's, created on first use) recorded on the producer and
 // waited for by the consumers, no host synchronisation; where an event call fails the host waits for the producer instead, and what that
 // synchronisation reports is returned.
-hipError_t order_behind(hipEvent_t& ev, hipStream_t producer, const hipStream_t* consumers, const size_t n)
+hipError_t order_behind(Event& ev, hipStream_t producer, const hipStream_t* consumers, const size_t n)
 {
-    bool ok = (ev || hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) && hipEventRecord(ev, producer) == hipSuccess;
+    bool ok = ev.create(hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, producer) == hipSuccess;
     for (size_t i = 0; i < n && ok; ++i)
         if (consumers[i] != producer) ok = hipStreamWaitEvent(consumers[i], ev, 0) == hipSuccess;
     return ok ? hipSuccess : hipStreamSynchronize(producer);
@@ -164,7 +164,7 @@ struct AcrRun {
         const size_t inl_d = dbl(sizeof(int32_t) * (size_t)N);
         rc = ensure_pinned(ctx, (in_d + state_d + 1 + res_d + mask_d + inl_d + ref_d) * sizeof(double) + 64);   // (+1: the polled word)
         if (rc != CLC_OK) return rc;
-        double* d = ctx->d_pnp;
+        double* d = ctx->d_pnp.as<double>();
         d_a = d;                               d += (size_t)ad * N;
         d_b = d;                               d += (size_t)2 * N;
         d_K1 = d;                              d += 16;
@@ -180,7 +180,7 @@ struct AcrRun {
         d_res = (AcrResult*)d;                 d += res_d;
         d_mask = (uint8_t*)d;                  d += mask_d;
         d_ref = d;
-        double* hp = (double*)ctx->h_pin;
+        double* hp = ctx->h_pin.as<double>();
         if (kind >= 2) {
             // ACKernelAdaptor: NormalizePoints(x, &x_, &N_, w, h) for both point sets (x_n = d x + t, oracle/clc_oracle_twoview.c orc_tv_normalize)
             // (points from device memory: the staging launch applies the same two operations, launch_acr_stage's cond)
@@ -248,7 +248,7 @@ struct AcrRun {
         pb.max_threshold = std::isinf(precision) ? INFINITY : precision * (pb.norm * pb.norm);
         pb.seed = seed;
 
-        stage_src = hp; stage_dst = ctx->d_pnp; stage_n = (in_d + 1) & ~(size_t)1;      // (both blocks are sized past in_d + 1)
+        stage_src = hp; stage_dst = ctx->d_pnp.as<double>(); stage_n = (in_d + 1) & ~(size_t)1;      // (both blocks are sized past in_d + 1)
         // Upper bound of the batch a round can ask for, from what the host knows when it enqueues it (one or two rounds behind the
         // device): while the index set has not switched the batch doubles up to kAcrMaxBatch; afterwards it is what is left of the
         // reserve, remaining = n_iter - iter (+ a margin for the "no inliers: n_iter++" rule, once per round).
@@ -662,7 +662,7 @@ int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const doub
         q[2 * i] = h_x1[2 * i] * t.d + t.tx; q[2 * i + 1] = h_x1[2 * i + 1] * t.d + t.ty;
         q[(size_t)2 * N + 2 * i] = h_x2[2 * i] * t.d + t.tx; q[(size_t)2 * N + 2 * i + 1] = h_x2[2 * i + 1] * t.d + t.ty;
     }
-    double* d = ctx->d_pnp;
+    double* d = ctx->d_pnp.as<double>();
     int32_t* d_smp = (int32_t*)(d + pts);
     double* d_out = d + pts + smp;
     CLC_HIP(ctx, hipMemcpyAsync(d, q.data(), sizeof(double) * pts, hipMemcpyHostToDevice, ctx->stream));
@@ -772,7 +772,7 @@ struct TrackPath {
         if (jb.cov) memset(jb.cov, 0, sizeof(double) * 36);
         jb.n_tracks = 0; jb.n_inliers = 0; jb.iterations = 0; jb.status = CLC_OK; jb.error_max = 0.0; jb.rmse = 0.0;
     }
-    static void pack(Jobs& p, const clc_ctx* c0) { p.map_X = c0->d_map_X; p.map_n = c0->map_X_n; }
+    static void pack(Jobs& p, const clc_ctx* c0) { p.map_X = c0->d_map_X.as<double>(); p.map_n = c0->map_X_n; }
     static void outputs(Dev& d, const GatherView& v, const Job& jb)
     {
         d.X = v.a; d.x = v.b; d.query = v.q; d.map = v.t;
