@@ -8,8 +8,8 @@ loudly when the HIP library is missing.
 """
 from .abi import (CLCError, Context, DetectorOptions, MatcherOptions, KP_DTYPE, lib_path, load_library,  # noqa: F401
                   keypoints_to_features, cov_intersection, ratio_matches_to_pairs, MultiCam, mc_plan,
-                  SELECT_FIRST, SELECT_STRONGEST, pair_filter_batch_dev)
+                  SELECT_FIRST, SELECT_STRONGEST, pair_filter_batch_dev, inter_pose_batch_dev)
 
 __all__ = ["CLCError", "Context", "DetectorOptions", "MatcherOptions", "KP_DTYPE", "lib_path",
            "load_library", "keypoints_to_features", "cov_intersection", "ratio_matches_to_pairs", "MultiCam", "mc_plan",
-           "SELECT_FIRST", "SELECT_STRONGEST", "pair_filter_batch_dev"]
+           "SELECT_FIRST", "SELECT_STRONGEST", "pair_filter_batch_dev", "inter_pose_batch_dev"]

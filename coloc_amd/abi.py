@@ -101,6 +101,14 @@ class InterPoseJob(C.Structure):
                 ("n_front", C.c_int), ("n_common", C.c_int), ("n_refined", C.c_int), ("stage", C.c_int), ("n_map_matches", C.c_int)]
 
 
+class InterDevJob(C.Structure):
+    """clc_inter_dev_job (include/coloc_hip.h)"""
+    _fields_ = [("pair", PairJob), ("Rt_source", C.c_void_p), ("huber_a", C.c_double), ("lower_is_b", C.c_int), ("d_first_desc", C.c_void_p),
+                ("d_map_desc", C.c_void_p), ("d_map_match_a", C.c_void_p), ("match_threshold", C.c_int),
+                ("Rt", C.c_double * 12), ("cov", C.c_double * 36), ("rmse", C.c_double), ("scale", C.c_double),
+                ("n_front", C.c_int), ("n_common", C.c_int), ("n_refined", C.c_int), ("stage", C.c_int), ("n_map_matches", C.c_int)]
+
+
 EXPORTS = [
     "clc_abi_version", "clc_status_string", "clc_ctx_create", "clc_ctx_destroy", "clc_last_error_string",
     "clc_sync", "clc_stream", "clc_pyramid_build", "clc_pyramid_build_dev", "clc_pyramid_level",
@@ -118,6 +126,7 @@ EXPORTS = [
     "clc_ratio_matches_to_pairs", "clc_detect_set_selection", "clc_detect_selection",
     "clc_set_map_points", "clc_track_build_dev", "clc_track_localize_dev", "clc_track_localize_batch_dev",
     "clc_pair_build_dev", "clc_pair_filter_dev", "clc_pair_filter_batch_dev",
+    "clc_inter_pose_dev", "clc_inter_pose_batch_dev", "clc_inter_front_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -270,6 +279,9 @@ def load_library():
     lib.clc_pair_build_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.clc_pair_filter_dev.argtypes = [vp, ci, vp]
     lib.clc_pair_filter_batch_dev.argtypes = [vp, ci, vp, ci]
+    lib.clc_inter_pose_dev.argtypes = [vp, vp]
+    lib.clc_inter_pose_batch_dev.argtypes = [vp, vp, ci]
+    lib.clc_inter_front_dev.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -620,6 +632,43 @@ def pair_filter_batch_dev(ctxs, model, jobs):
     if rc != CLC_OK:
         raise CLCError(rc, "clc_pair_filter_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
     return [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
+def _inter_dev_fill(j, keep, Rt_source, huber_a=16.0, lower_is_b=False, d_first_desc=None, d_map_desc=None, d_map_match_a=None,
+                    match_threshold=60, **pair):
+    """fills an InterDevJob: the keywords of Context.pair_filter_dev for the pair, then the step's own"""
+    out = _pair_fill(j.pair, keep, **pair)
+    rs = np.ascontiguousarray(Rt_source, dtype=np.float64).reshape(12)
+    keep.append(rs)
+    j.Rt_source, j.huber_a, j.lower_is_b = rs.ctypes.data, float(huber_a), (1 if lower_is_b else 0)
+    j.d_first_desc, j.d_map_desc, j.d_map_match_a, j.match_threshold = d_first_desc, d_map_desc, d_map_match_a, int(match_threshold)
+    return out
+
+
+def _inter_dev_result(j, *out):
+    d = _pair_result(j.pair, *out)
+    d["E"] = d["M"]
+    d.update(Rt=np.array(j.Rt).reshape(3, 4), cov=np.array(j.cov).reshape(6, 6), rmse=j.rmse, scale=j.scale, n_front=j.n_front,
+             n_common=j.n_common, n_refined=j.n_refined, stage=j.stage, n_map_matches=j.n_map_matches)
+    return d
+
+
+def inter_pose_batch_dev(ctxs, jobs):
+    """clc_inter_pose_batch_dev: jobs = [dict(Rt_source=, d_map_match_a= | d_first_desc=, d_map_desc= [, lower_is_b, match_threshold],
+    huber_a=, and the pair's keywords of Context.pair_filter_dev), ...], job i on ctxs[i], the map points from ctxs[0]
+    (Context.set_map_points).  Returns a list of dicts shaped like inter_pose_batch's: the pair filter's result + Rt, cov, rmse, scale,
+    n_front, n_common, n_refined, n_map_matches, stage."""
+    lib = load_library()
+    n = len(jobs)
+    assert len(ctxs) == n
+    arr = (InterDevJob * n)()
+    keep = []
+    outs = [_inter_dev_fill(arr[i], keep, **jobs[i]) for i in range(n)]
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_inter_pose_batch_dev(hs, arr, n)
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_inter_pose_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    return [_inter_dev_result(arr[i], *outs[i]) for i in range(n)]
 
 
 def desc_handle_live(handle):
@@ -988,6 +1037,26 @@ class Context:
         out = _pair_fill(j, keep, **job)
         self._chk(self.lib.clc_pair_filter_dev(self.h, ord(model), C.byref(j)))
         return _pair_result(j, *out)
+
+    def inter_pose_dev(self, **job):
+        """clc_inter_pose_dev: the inter-camera step (pair gather, 'E' filter, temporary map, scale, first pose, refinement) from device
+        memory.  Keywords: Rt_source, huber_a, EITHER d_map_match_a (the shortcut) OR d_first_desc + d_map_desc [+ lower_is_b,
+        match_threshold] (the reference's chain), and the pair's keywords of pair_filter_dev.  The map points are this context's
+        (set_map_points).  Returns a dict shaped like inter_pose_batch's."""
+        j = InterDevJob()
+        keep = []
+        out = _inter_dev_fill(j, keep, **job)
+        self._chk(self.lib.clc_inter_pose_dev(self.h, C.byref(j)))
+        return _inter_dev_result(j, *out)
+
+    def inter_front_dev(self, d_x1, d_x2, n, d_inliers, n_inliers, cam_a, cam_b, motions, d_Xt, d_x2f, d_corr, d_record, d_rows=None,
+                        d_first=None, stream=None):
+        """clc_inter_front_dev: the chirality vote + temporary map kernel alone, enqueue only; motions = four [R|t] (4 x 3 x 4, host);
+        outputs are device pointers with room for n_inliers points, d_record four int32 {n_front, chosen, stage, 1}"""
+        ca, cb = CameraK3(*[float(v) for v in cam_a]), CameraK3(*[float(v) for v in cam_b])
+        mo = np.ascontiguousarray(motions, dtype=np.float64).reshape(48)
+        self._chk(self.lib.clc_inter_front_dev(self.h, d_x1, d_x2, int(n), d_inliers, int(n_inliers), C.byref(ca), C.byref(cb), _p(mo), d_rows,
+                                               d_Xt, d_x2f, d_corr, d_first, d_record, stream))
 
     def match_map_dev(self, d_q, nq, threshold, d_match, stream=None):
         self._chk(self.lib.clc_match_map_dev(self.h, d_q, nq, int(threshold), d_match, stream))

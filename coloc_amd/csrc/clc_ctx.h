@@ -127,6 +127,9 @@ struct clc_ctx {
     int map_X_n = -1;             // (-1: none set)
     clc::GatherBlock trk, pair;   // the tracks (clc_track_localize*_dev) / the pairs (clc_pair_filter*_dev) of this context's job
     clc::Event ev_track;             // orders the track / pair launch behind job.after_stream, and the contexts' streams behind the launch
+    // the inter-camera step from device memory (inter_dev.hip): temporary map, lists, the refinement's inputs / the pinned records
+    clc::DevBuf d_inter;
+    clc::PinBuf h_inter;
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     clc::PinBuf h_stage;          // (bytes)
@@ -191,6 +194,12 @@ void k2nn_probe_bias(clc_ctx* ctx);                       // once per process an
 // all two-view a-contrario filters of a batch (pose_batch.hip); jobs[i] on ctxs[i]
 int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind /* 1 'E', 2 'F', 3 'H' */);
 int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what);
+// clc_pair_filter_batch_dev under model 'E' (pose_batch.hip), which also says where each job's inlier list lies for the DEVICE:
+// inliers[i] = the list in job i's context's pinned block, in the filter's order, written by the round that completed the run before
+// its word (null: the job's solve did not start); it stands until the context's next solve
+int pair_filter_essential(clc_ctx* const* ctxs, clc_pair_job* jobs, int n_jobs, const int32_t** inliers);
+// rows idx[0 .. n) of a descriptor block (64 B each) -> dst, the index list on the device (inter_pose.hip)
+hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, uint32_t n, hipStream_t stream);
 
 } // namespace clc
 #endif

@@ -220,6 +220,13 @@ hipError_t launch_pnp_refine(const double* d_Rt_in, const double* d_X, const dou
                              Profiler* prof = nullptr, const int32_t* d_valid = nullptr, void* h_out = nullptr);
 // (h_out: pinned host record written INSTEAD of d_out, so that no device-to-host copy command is needed)
 
+// inter_scale_kernel (inter_dev.hip): what the scale step of the inter-camera path leaves in pinned memory
+struct InterScaleRec {
+    double scale;
+    int32_t stage, n_common, n_map_matches;
+    int32_t ready;      // written LAST (system-scope release)
+};
+
 // ---- a-contrario RANSAC (acransac.hip) -----------------------------------------------------------------------
 static constexpr int kAcrMaxBatch = 128;           // iterations evaluated per round
 static constexpr int kAcrMaxN = 16384;             // correspondences per solve: 8 B x 16 384 = 128 KB of LDS per model slot (16 elements per thread)

@@ -74,9 +74,7 @@ int map_match_enqueue(clc_ctx* ctx, const clc_inter_pose_job& jb, const InterFro
     uint4* d_rows = (uint4*)(ctx->d_pnp.as<double>() + idx_d);
     int32_t* d_match = (int32_t*)(ctx->d_pnp.as<double>() + idx_d + rows_d);
     CLC_HIP(ctx, hipMemcpyAsync(d_idx, h_idx, nf * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((nf * 4 + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)jb.d_first_desc, (const int32_t*)d_idx,
-                       d_rows, (uint32_t)nf);
-    CLC_HIP(ctx, hipGetLastError());
+    CLC_HIP(ctx, launch_gather_rows((const uint4*)jb.d_first_desc, d_idx, d_rows, (uint32_t)nf, ctx->stream));
     std::vector<K2nnJobDev> jobs(1);
     jobs[0] = K2nnJobDev{};
     jobs[0].q = (const uint4*)jb.d_map_desc; jobs[0].t = (const uint4*)d_rows; jobs[0].out = d_match;
@@ -89,6 +87,13 @@ int map_match_enqueue(clc_ctx* ctx, const clc_inter_pose_job& jb, const InterFro
 }
 
 } // namespace
+
+hipError_t clc::launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, const uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, src, d_idx, dst, n);
+    return hipGetLastError();
+}
 
 extern "C" {
 

@@ -835,7 +835,8 @@ struct PairPath {
     }
 };
 
-template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typename Path::Job* jobs, const int n_jobs)
+// inliers (nullable): where every run's inlier list lies for the device afterwards (pair_filter_essential, clc_ctx.h)
+template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typename Path::Job* jobs, const int n_jobs, const int32_t** inliers = nullptr)
 {
     clc_ctx* c0 = ctxs[0];
     const std::string who = Path::who;
@@ -908,6 +909,7 @@ template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typ
     acr_drive(runs.data(), n_jobs, shared);
     return finish_all(runs, [&](const size_t i, const int status) {
         typename Path::Job& jb = jobs[i];
+        if (inliers) inliers[i] = runs[i].p_inl;
         jb.status = status;
         // the kernel wrote the pinned mirrors before the count came out
         const GatherView v(Path::block(ctxs[i]), Path::layout);
@@ -916,6 +918,12 @@ template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typ
 }
 
 } // namespace
+
+int clc::pair_filter_essential(clc_ctx* const* ctxs, clc_pair_job* jobs, const int n_jobs, const int32_t** inliers)
+{
+    for (int i = 0; i < n_jobs; ++i) inliers[i] = nullptr;
+    return gather_solve<PairPath>(ctxs, 1, jobs, n_jobs, inliers);
+}
 
 extern "C" {
 

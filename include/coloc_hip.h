@@ -847,6 +847,61 @@ int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* job
 int clc_pair_build_dev(clc_ctx* ctx, const clc_pair_job* job, double* d_x1, double* d_x2, int32_t* d_pair_q, int32_t* d_pair_t,
                        int32_t* d_n, void* stream);
 
+/* ---- the inter-camera step from device memory: ColoC::interPoseEstimator (coloc.hpp:296-340) without a host trip --------------------
+ * What clc_inter_pose_batch computes, fed from the pair's d_match instead of host correspondences: the pair gather and the 'E' filter of
+ * clc_pair_filter_dev, then -- on the device, in the operation order of the host path, so with its bits -- the chirality vote over the
+ * four motions of E with the temporary map of the points in front of both cameras, the features that map shares with the global map,
+ * its scale (colocUtils.hpp:184-211 behind the depth-ratio screen), the destination's first pose, and the refinement with its
+ * covariance.  (Later under ABI 4: new entry points only.)
+ *
+ * job.pair: camera A = the SOURCE, camera B = the destination; the model is 'E'; its host outputs stay nullable.  The global map's
+ * points are the context's (clc_set_map_points; a batch: ctxs[0]'s), map_n = their number.  The common features come from one of two
+ * places, as in clc_inter_pose_job:
+ *   THE REFERENCE'S CHAIN  d_first_desc + d_map_desc (DEVICE, rows of 64 B, 16-byte aligned; d_map_desc map_n rows in the map points'
+ *       order): the descriptor of a temporary map point is the row of its correspondence in the block of the pair's camera with the
+ *       lower id -- camera A's (pair_q) with lower_is_b == 0, camera B's (pair_t) otherwise --, gathered on the device and swept against
+ *       the map's block (K2NN, threshold match_threshold, <= 0: 60);
+ *   THE SHORTCUT  d_map_match_a (DEVICE, int32 per row of camera A, at least nq of them): camera A's own match against the map
+ *       (clc_match_map_dev); an index outside [0, map_n) counts as "not a map feature".
+ * Exactly one of the two: anything else, a null Rt_source or a misaligned pointer is CLC_ERR_BAD_ARG, no map points CLC_ERR_STATE; the
+ * pair's own rules are clc_pair_filter_dev's.  The host waits for the pair count (as clc_pair_filter_dev does) and for ONE more number,
+ * the points in front of both cameras; matches, correspondences, map and temporary map are never copied in either direction.  Outputs as clc_inter_pose_job (stage says how far the job got;
+ * pair.status the job's status); ordering: pair.after_stream, as clc_track_job -- d_map_match_a and the descriptor blocks count among
+ * the inputs it orders.
+ *
+ * clc_inter_pose_batch_dev: n <= CLC_MAX_BATCH jobs, job i on ctxs[i] (a context of its own each, one device); every job's result is
+ * the single call's.
+ *
+ * clc_inter_front_dev: the first kernel alone, enqueue only on `stream` (capturable).  d_x1 / d_x2: n correspondences in undistorted
+ * pixels; d_inliers (nullable: 0 .. n_inliers - 1): indices into them, an index outside [0, n) is never in front; cam_a / cam_b: focal,
+ * ppx, ppy are read (K = { focal, 0, ppx; 0, focal, ppy; 0, 0, 1 }); h_motions: HOST, four candidate [R|t], 12 doubles each, passed by
+ * value; d_rows / d_first (both or neither): d_first[w] = d_rows[correspondence of kept point w].  Writes, for the FIRST candidate with
+ * the strictly largest number of inliers in front of both cameras, d_Xt (3 per point), d_x2f (2), d_corr -- in the inlier list's order,
+ * room for n_inliers points each -- and d_record = { n_front, chosen candidate, stage, 1 } (stage CLC_INTER_NO_MODEL below 13 inliers,
+ * CLC_INTER_NO_RELATIVE_POSE below 8 points in front: n_front = 0, chosen = -1). */
+typedef struct clc_inter_dev_job {
+    clc_pair_job   pair;          /* camera A = SOURCE, camera B = destination; the model is 'E' */
+    /* in */
+    const double*  Rt_source;     /* host, 12: [R|t] of the source camera */
+    double         huber_a;       /* <= 0: 16 */
+    int            lower_is_b;    /* the reference's chain: d_first_desc is camera B's block */
+    const void*    d_first_desc;  /* DEVICE; with d_map_desc: the chain.  Both NULL: the shortcut */
+    const void*    d_map_desc;    /* DEVICE: the global map's rows */
+    const int32_t* d_map_match_a; /* DEVICE, the shortcut: camera A's own d_match against the map */
+    int            match_threshold;
+    /* out */
+    double         Rt[12];
+    double         cov[36];
+    double         rmse, scale;
+    int            n_front, n_common, n_refined, stage;
+    int            n_map_matches;
+} clc_inter_dev_job;
+int clc_inter_pose_dev(clc_ctx* ctx, clc_inter_dev_job* job);
+int clc_inter_pose_batch_dev(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, int n_jobs);
+int clc_inter_front_dev(clc_ctx* ctx, const double* d_x1, const double* d_x2, int n, const int32_t* d_inliers, int n_inliers,
+                        const clc_camera_k3* cam_a, const clc_camera_k3* cam_b, const double* h_motions, const int32_t* d_rows,
+                        double* d_Xt, double* d_x2f, int32_t* d_corr, int32_t* d_first, int32_t* d_record, void* stream);
+
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
  * (include/coloc/CovIntersection.hpp:24-49, called at include/coloc/coloc.hpp:362-389): omega in [0,1]
