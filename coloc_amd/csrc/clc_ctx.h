@@ -5,6 +5,8 @@
 #include "clc_buf.h"
 #include "clc_internal.h"
 
+#include <chrono>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -198,8 +200,37 @@ int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what);
 // inliers[i] = the list in job i's context's pinned block, in the filter's order, written by the round that completed the run before
 // its word (null: the job's solve did not start); it stands until the context's next solve
 int pair_filter_essential(clc_ctx* const* ctxs, clc_pair_job* jobs, int n_jobs, const int32_t** inliers);
-// rows idx[0 .. n) of a descriptor block (64 B each) -> dst, the index list on the device (inter_pose.hip)
+// rows idx[0 .. n) of a descriptor block (64 B each) -> dst, the index list on the device (gather.hip)
 hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, uint32_t n, hipStream_t stream);
+// The map-to-map sweep of the reference's chain (coloc.hpp:317-323; inter_pose.hip), enqueued on `stream`: rows d_idx[0 .. nf) of
+// d_first_desc -> d_rows (the temporary map's descriptors), then K2NN with Q = the global map's map_n rows, T = d_rows, threshold <= 0:
+// 60 (GPUMatcher.hpp:162): d_match[q] = temporary map point matched by global map point q, or -1
+int map_sweep_enqueue(clc_ctx* ctx, const void* d_first_desc, const int32_t* d_idx, int nf, const void* d_map_desc, int map_n, uint4* d_rows,
+                      int32_t* d_match, int threshold, hipStream_t stream);
+
+// Every consumer stream behind what `producer` holds now (pose_batch.hip): ONE event (ev: its owner's, created on first use), no host
+// synchronisation; where an event call fails the host waits for the producer instead, and what that synchronisation reports is returned.
+hipError_t order_behind(Event& ev, hipStream_t producer, const hipStream_t* consumers, size_t n);
+
+// THE blocking wait for a word a kernel publishes in pinned memory (system-scope release): spins while *word == not_yet, looks at the
+// clock every 1 024 spins, and once `ms` have passed since t0 synchronises `stream` ONCE (which also surfaces errors); fails -- `what`
+// on ctx -- if that reports an error or the word is still not out.  What a failure means for the jobs in flight is the caller's.
+template <class T> int wait_pinned(clc_ctx* ctx, const T* word, T not_yet, hipStream_t stream, std::chrono::steady_clock::time_point t0, int ms, const char* what)
+{
+    for (uint32_t spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) == not_yet;) {
+        if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(ms)) {
+            const hipError_t e = hipStreamSynchronize(stream);
+            if (e != hipSuccess || __atomic_load_n(word, __ATOMIC_ACQUIRE) == not_yet) return fail(ctx, CLC_ERR_HIP, what, e);
+        }
+    }
+    return CLC_OK;
+}
+
+// a refinement's pinned record into the outputs of an inter-camera job (clc_inter_pose_job, clc_inter_dev_job)
+template <class Job> void take_refined(Job& jb, const RefineOut& f)
+{
+    memcpy(jb.Rt, f.Rt, sizeof jb.Rt); memcpy(jb.cov, f.cov, sizeof jb.cov); jb.rmse = f.rmse; jb.n_refined = f.n_used;
+}
 
 } // namespace clc
 #endif

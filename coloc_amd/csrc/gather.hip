@@ -5,7 +5,8 @@
 //   pairs   the gather of RobustMatcher::computeRelativePose (RobustMatcher.hpp:372-424, the loop at :393-398): the two cameras' keypoints
 //           (or feature positions) -> undistorted x1 | x2.  The points leave in PIXELS: the 'F' / 'H' conditioning is the staging launch's
 //           (acransac.hip: acr_stage_kernel), so the block and its pinned mirrors serve all three models.
-// Both are ONE ordered compaction (gather below) that differs only in what an accepted query writes.
+// Both are ONE ordered compaction (gather below, over wg_compact.h) that differs only in what an accepted query writes.  gather_rows_kernel:
+// rows of a descriptor block picked by an index list (the temporary map's descriptors of the inter-camera step, inter_pose.hip).
 //
 // One launch for a batch of jobs, blockIdx.y = job, ONE workgroup per job: nq <= maxkp is 5-10 k (the solve takes at most 16 384
 // correspondences), a few KB in and a few tens of KB out -- the launch is latency-bound, and one workgroup keeps the ordered compaction a
@@ -13,6 +14,7 @@
 // at this size that does not matter.
 #include "clc_ctx.h"
 #include "ud_pixel.h"
+#include "wg_compact.h"
 
 #include <cmath>
 #include <cstring>
@@ -66,14 +68,13 @@ __device__ __forceinline__ void emit(const PairJobs& jobs, const PairJobDev& jb,
     if (jb.h_x2) { jb.h_x2[2 * i] = u2[0]; jb.h_x2[2 * i + 1] = u2[1]; }
 }
 
-// The compaction, the ONE place that fixes the two rules the solves rest on: correspondence i is the i-th accepted query in ascending
-// query order (the sampler draws by position), and the count comes out last, behind a system-scope fence (the host reads the pinned
-// mirrors on the strength of that word).
+// The gather as an ordered compaction (wg_compact.h, which states the two rules it keeps): correspondence i is the i-th accepted query in
+// ascending query order, and the count comes out last, behind a system-scope fence.
 template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
 {
     const auto& jb = jobs.j[blockIdx.y];
     __shared__ uint32_t s_wave[kGatherThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     uint32_t nq = jb.nq > 0 ? (uint32_t)jb.nq : 0u;
     if (jb.a.count) { const uint32_t c = jb.a.count[0]; nq = c < nq ? c : nq; }
     const int32_t nt = train_rows(jobs, jb);
@@ -82,19 +83,8 @@ template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
         const uint32_t q = q0 + tid;
         const int32_t m = q < nq ? jb.match[q] : -1;
         const bool ok = m >= 0 && m < nt;
-        // ordered compaction: accepted lanes below this one in the wave (ballot + mbcnt), accepted queries of the waves before it (LDS)
-        const uint64_t b = __ballot(ok);
-        const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-        if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-        __syncthreads();
-        uint32_t off = base, total = 0;
-        for (uint32_t w = 0; w < kGatherThreads / 64; ++w) {
-            const uint32_t c = s_wave[w];
-            off += w < wave ? c : 0u;
-            total += c;
-        }
-        __syncthreads();                                 // (s_wave is written again in the next pass)
-        const uint32_t i = off + before;
+        uint32_t total;
+        const uint32_t i = base + ordered_slot<kGatherThreads>(ok, s_wave, &total);
         if (ok && i < (uint32_t)jb.cap) emit(jobs, jb, q, m, (size_t)i);
         base += total;
     }
@@ -111,6 +101,13 @@ template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
 // two instantiations, two kernels: each carries only its own emit
 __global__ __launch_bounds__(kGatherThreads) void track_build_kernel(const TrackJobs jobs) { gather(jobs); }
 __global__ __launch_bounds__(kGatherThreads) void pair_build_kernel(const PairJobs jobs) { gather(jobs); }
+
+// rows idx[0 .. n) of a descriptor block, 16 bytes per thread
+__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, const int32_t* __restrict__ idx, uint4* __restrict__ dst, const uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n * 4u) dst[i] = src[(size_t)idx[i >> 2] * 4u + (i & 3u)];
+}
 
 template <class Jobs> hipError_t launch(void (*kernel)(const Jobs), Jobs& jobs, const int n_jobs, hipStream_t stream)
 {
@@ -138,6 +135,13 @@ int gather_side(clc_ctx* ctx, const char* who, const uint32_t* count, const clc_
 
 hipError_t launch_gather(TrackJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(track_build_kernel, jobs, n_jobs, stream); }
 hipError_t launch_gather(PairJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(pair_build_kernel, jobs, n_jobs, stream); }
+
+hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, const uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, src, d_idx, dst, n);
+    return hipGetLastError();
+}
 
 int gather_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, const char* who)
 {

@@ -5,20 +5,20 @@
 //   inter_front_kernel   inter_relative: the chirality vote over the four motions of E, the closed-form two-ray depths, the ordered
 //                        compaction of the points in front of both cameras -> the temporary map Xt, x2f, corr, the descriptor row of
 //                        each kept point, and a pinned record {n_front, chosen motion, stage}
-//   gather_rows_kernel + the K2NN sweep (inter_pose.hip, capi_match.hip; the reference's chain only)
+//   gather_rows_kernel + the K2NN sweep (map_sweep_enqueue, inter_pose.hip; the reference's chain only)
 //   inter_scale_kernel   the common-feature walk and inter_scale_pose: ratios, median, screen, the consecutive-distance scale rule, the
 //                        composed first pose and the temporary map in world coordinates, straight into the refinement's layout
 //   pnp_refine_kernel    (pnp.hip) behind a device go / no-go word
 // Both kernels follow gather.hip: one launch for a batch, blockIdx.y = job, ONE workgroup per job (inliers <= 16 384, map_n a few
-// thousand: latency-bound), ordered compaction by ballot + a 16-entry LDS scan per 1 024 elements.  All arithmetic is fp64 in EXACTLY the
-// operation order of inter_geometry.cpp under -ffp-contract=off: the results have the host's bits.  The host waits for ONE number per job,
+// thousand: latency-bound), the ordered compaction of wg_compact.h.  All arithmetic is fp64 and is the statements of inter_math.h, the ones
+// inter_geometry.cpp runs on the host: the results have the host's bits by construction.  The host waits for ONE number per job,
 // n_front (the sweep's train count and the refinement's N are host arguments); nothing sized by N or map_n is copied in either direction.
 #include "clc_ctx.h"
+#include "inter_math.h"
+#include "wg_compact.h"
 #include "../host/HIPRobustMatcher.hpp"      // hipgeom::motion_from_essential (host arithmetic: nine numbers in, four motions out)
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -63,50 +63,8 @@ struct ScaleJobDev {
 struct ScaleJobs { ScaleJobDev j[kMaxBatch]; const double* map_X; int32_t map_n; };
 static_assert(sizeof(ScaleJobs) <= 4096 - 256, "ScaleJobs is passed as a kernel argument: it must stay within the 4 KB kernarg segment");
 
-// pixel -> normalised camera plane (inter_geometry.cpp: normalise_px with K[0] = K[4] = focal, K[1] = 0 -- the product stays)
-__device__ __forceinline__ void normalise_px(const InterCam& c, const double x, const double y, double* n)
-{
-    const double skew = 0.0;
-    n[1] = (y - c.ppy) / c.focal;
-    n[0] = (x - c.ppx - skew * n[1]) / c.focal;
-}
-
-// the depths along the two rays of correspondence (n1, n2) under motion Rt that bring them closest (inter_geometry.cpp: inter_relative)
-__device__ __forceinline__ bool two_ray_depths(const double* Rt, const double* n1, const double* n2, double* depth1)
-{
-    const double p[3] = { n1[0], n1[1], 1.0 }, b[3] = { n2[0], n2[1], 1.0 };
-    const double t[3] = { Rt[3], Rt[7], Rt[11] };
-    double a[3];
-    for (int r = 0; r < 3; ++r) a[r] = Rt[4 * r] * p[0] + Rt[4 * r + 1] * p[1] + Rt[4 * r + 2] * p[2];
-    const double aa = a[0] * a[0] + a[1] * a[1] + a[2] * a[2], bb = b[0] * b[0] + b[1] * b[1] + b[2] * b[2];
-    const double ab = a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
-    const double at = a[0] * t[0] + a[1] * t[1] + a[2] * t[2], bt = b[0] * t[0] + b[1] * t[1] + b[2] * t[2];
-    double det = aa * bb - ab * ab;
-    if (fabs(det) < 1e-18) det = 1e-18;
-    const double d1 = (-at * bb + bt * ab) / det, d2 = (-at * ab + bt * aa) / det;
-    *depth1 = d1;
-    return d1 > 0.0 && d2 > 0.0;
-}
-
-// Position of this thread's accepted element among the accepted elements of the pass, and their number: ballot + mbcnt inside the wave,
-// a 16-entry LDS scan across the waves (gather.hip's compaction).  Every thread of the workgroup calls it.
-__device__ __forceinline__ uint32_t ordered_slot(const bool ok, uint32_t* s_wave, uint32_t* total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t b = __ballot(ok);
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
-    if (lane == 0) s_wave[wave] = (uint32_t)__popcll(b);
-    __syncthreads();
-    uint32_t off = 0, tot = 0;
-    for (uint32_t w = 0; w < kInterThreads / 64; ++w) {
-        const uint32_t c = s_wave[w];
-        off += w < wave ? c : 0u;
-        tot += c;
-    }
-    __syncthreads();                                     // (s_wave is written again by the next call)
-    *total = tot;
-    return off + before;
-}
+// pixel -> normalised camera plane: K[0] = K[4] = focal, K[1] = 0 (inter_math.h keeps the product)
+__device__ __forceinline__ void cam_plane(const InterCam& c, const double x, const double y, double* n) { normalise_px(c.focal, 0.0, c.ppx, c.focal, c.ppy, x, y, n); }
 
 // candidate c of the job as [R|t], 3 x 4 row-major (c is the same in every thread)
 __device__ __forceinline__ void candidate(const FrontJobs& jobs, const FrontJobDev& jb, const int c, double* Rt)
@@ -136,8 +94,8 @@ __global__ __launch_bounds__(kInterThreads) void inter_front_kernel(const FrontJ
             if (jb.list && k < ni) jb.list[k] = i;
             double n1[2] = { 0.0, 0.0 }, n2[2] = { 0.0, 0.0 };
             if (i >= 0) {
-                normalise_px(jb.k1, jb.x1[2 * (size_t)i], jb.x1[2 * (size_t)i + 1], n1);
-                normalise_px(jb.k2, jb.x2[2 * (size_t)i], jb.x2[2 * (size_t)i + 1], n2);
+                cam_plane(jb.k1, jb.x1[2 * (size_t)i], jb.x1[2 * (size_t)i + 1], n1);
+                cam_plane(jb.k2, jb.x2[2 * (size_t)i], jb.x2[2 * (size_t)i + 1], n2);
             }
             for (int c = 0; c < 4; ++c) {
                 double Rt[12], d1;
@@ -174,12 +132,12 @@ __global__ __launch_bounds__(kInterThreads) void inter_front_kernel(const FrontJ
             bool front = false;
             if (i >= 0) {
                 u2[0] = jb.x2[2 * (size_t)i]; u2[1] = jb.x2[2 * (size_t)i + 1];
-                normalise_px(jb.k1, jb.x1[2 * (size_t)i], jb.x1[2 * (size_t)i + 1], n1);
-                normalise_px(jb.k2, u2[0], u2[1], n2);
+                cam_plane(jb.k1, jb.x1[2 * (size_t)i], jb.x1[2 * (size_t)i + 1], n1);
+                cam_plane(jb.k2, u2[0], u2[1], n2);
                 front = two_ray_depths(Rt, n1, n2, &d1);
             }
             uint32_t total;
-            const uint32_t w = base + ordered_slot(front, s_wave, &total);
+            const uint32_t w = base + ordered_slot<kInterThreads>(front, s_wave, &total);
             if (front) {                                 // (w < n_inliers: the blocks hold that many)
                 jb.Xt[3 * (size_t)w] = n1[0] * d1; jb.Xt[3 * (size_t)w + 1] = n1[1] * d1; jb.Xt[3 * (size_t)w + 2] = d1;
                 jb.x2f[2 * (size_t)w] = u2[0]; jb.x2f[2 * (size_t)w + 1] = u2[1];
@@ -267,15 +225,10 @@ __global__ __launch_bounds__(kInterThreads) void inter_scale_kernel(const ScaleJ
         const bool ok = k >= 0 && (uint32_t)k < nf && gi >= 0 && (uint32_t)gi < map_n;      // (an index outside the map: not a map feature)
         if (jb.match) n_raw += (uint32_t)__syncthreads_count(raw);
         uint32_t total;
-        const uint32_t c = n_com + ordered_slot(ok, s_wave, &total);
+        const uint32_t c = n_com + ordered_slot<kInterThreads>(ok, s_wave, &total);
         if (ok) {
-            const double* Xg = jobs.map_X + 3 * (size_t)gi;
-            double xs[3];
-            for (int r = 0; r < 3; ++r) xs[r] = Rs[4 * r] * Xg[0] + Rs[4 * r + 1] * Xg[1] + Rs[4 * r + 2] * Xg[2] + Rs[4 * r + 3];
-            const double ng = sqrt(xs[0] * xs[0] + xs[1] * xs[1] + xs[2] * xs[2]);
-            const double nt = sqrt(Xt[3 * (size_t)k] * Xt[3 * (size_t)k] + Xt[3 * (size_t)k + 1] * Xt[3 * (size_t)k + 1] + Xt[3 * (size_t)k + 2] * Xt[3 * (size_t)k + 2]);
             jb.cg[c] = gi; jb.ck[c] = k;
-            jb.ratio[c] = ng / (nt > 1e-12 ? nt : 1e-12);
+            jb.ratio[c] = depth_ratio(Rs, jobs.map_X + 3 * (size_t)gi, Xt + 3 * (size_t)k);
         }
         n_com += total;
     }
@@ -291,7 +244,7 @@ __global__ __launch_bounds__(kInterThreads) void inter_scale_kernel(const ScaleJ
             const uint32_t c = c0 + tid;
             const bool ok = c < n_com && fabs(jb.ratio[c] / med - 1.0) < 0.2;
             uint32_t total;
-            const uint32_t w = n_keep + ordered_slot(ok, s_wave, &total);
+            const uint32_t w = n_keep + ordered_slot<kInterThreads>(ok, s_wave, &total);
             if (ok) { jb.kg[w] = jb.cg[c]; jb.kk[w] = jb.ck[c]; }
             n_keep += total;
         }
@@ -301,15 +254,10 @@ __global__ __launch_bounds__(kInterThreads) void inter_scale_kernel(const ScaleJ
     }
     if (stage == CLC_INTER_OK) {
         // 3. colocUtils.hpp:201-204 over consecutive kept features: the terms in parallel, their SUM by one lane in list order (the host's
-        //    sum is sequential: the bits depend on it).  A term that the d2 > 1e-9f guard drops is stored as -1 (a ratio of norms is never
-        //    negative).
+        //    sum is sequential: the bits depend on it).  A term that the rule's guard drops is stored as -1 (scale_term).
         const uint32_t n_terms = n_keep - 1;
         for (uint32_t k = tid; k < n_terms; k += kInterThreads) {
-            const double* g0 = jobs.map_X + 3 * (size_t)jb.kg[k]; const double* g1 = jobs.map_X + 3 * (size_t)jb.kg[k + 1];
-            const double* t0 = Xt + 3 * (size_t)jb.kk[k]; const double* t1 = Xt + 3 * (size_t)jb.kk[k + 1];
-            const float d1 = (float)sqrt((g1[0] - g0[0]) * (g1[0] - g0[0]) + (g1[1] - g0[1]) * (g1[1] - g0[1]) + (g1[2] - g0[2]) * (g1[2] - g0[2]));
-            const float d2 = (float)sqrt((t1[0] - t0[0]) * (t1[0] - t0[0]) + (t1[1] - t0[1]) * (t1[1] - t0[1]) + (t1[2] - t0[2]) * (t1[2] - t0[2]));
-            jb.term[k] = d2 > 1e-9f ? (double)(d1 / d2) : -1.0;
+            jb.term[k] = scale_term(jobs.map_X + 3 * (size_t)jb.kg[k], jobs.map_X + 3 * (size_t)jb.kg[k + 1], Xt + 3 * (size_t)jb.kk[k], Xt + 3 * (size_t)jb.kk[k + 1]);
         }
         __syncthreads();
         double sum = 0.0; uint32_t good = 0;                         // (thread 0's)
@@ -321,38 +269,21 @@ __global__ __launch_bounds__(kInterThreads) void inter_scale_kernel(const ScaleJ
                 for (uint32_t k = 0; k < m; ++k) { const double v = s_term[k]; if (!(v < 0.0)) { sum += v; ++good; } }
             __syncthreads();
         }
-        if (tid == 0) {
-            int st = CLC_INTER_OK;
-            double scale = 0.0;
-            if (good == 0) st = CLC_INTER_NO_SCALE;
-            else {
-                scale = sum / (double)good;
-                if (!(scale > 0.0) || !isfinite(scale)) st = CLC_INTER_NO_SCALE;
-            }
-            s_scale = scale; s_stage = st;
-        }
+        if (tid == 0) { double scale; s_stage = scale_from_sum(sum, good, &scale); s_scale = scale; }
         __syncthreads();
         stage = s_stage;
     }
     double scale = 0.0;
     if (stage == CLC_INTER_OK) {
         scale = s_scale;
-        const double* Rb = jb.Rb; const double* tb = jb.tb;
-        // the destination's pose through the source: X_d = R_rel X_s + s t_rel, X_s = R_s X_w + t_s
-        if (tid < 12) {
-            const int r = (int)tid >> 2, q = (int)tid & 3;
-            jb.Rt[tid] = q < 3 ? Rb[3 * r] * Rs[q] + Rb[3 * r + 1] * Rs[4 + q] + Rb[3 * r + 2] * Rs[8 + q]
-                               : Rb[3 * r] * Rs[3] + Rb[3 * r + 1] * Rs[7] + Rb[3 * r + 2] * Rs[11] + scale * tb[r];
-        }
+        // the destination's pose through the source
+        if (tid < 12) jb.Rt[tid] = compose_pose_entry(jb.Rb, jb.tb, Rs, scale, (int)tid >> 2, (int)tid & 3);
         if (tid >= 64 && tid < 80) {
             const int e = (int)tid - 64;
             jb.K[e] = (e == 0 || e == 4) ? jb.k2.focal : (e == 2 ? jb.k2.ppx : (e == 5 ? jb.k2.ppy : (e == 8 ? 1.0 : 0.0)));
         }
-        // the temporary map in world coordinates: X_w = R_s^T (s X_tmp - t_s)
-        for (uint32_t k = tid; k < nf; k += kInterThreads) {
-            const double v[3] = { scale * Xt[3 * (size_t)k] - Rs[3], scale * Xt[3 * (size_t)k + 1] - Rs[7], scale * Xt[3 * (size_t)k + 2] - Rs[11] };
-            for (int q = 0; q < 3; ++q) jb.Xw[3 * (size_t)k + q] = Rs[q] * v[0] + Rs[4 + q] * v[1] + Rs[8 + q] * v[2];
-        }
+        // the temporary map in world coordinates
+        for (uint32_t k = tid; k < nf; k += kInterThreads) world_point(Rs, scale, Xt + 3 * (size_t)k, jb.Xw + 3 * (size_t)k);
     }
     __threadfence_system();
     __syncthreads();
@@ -393,28 +324,6 @@ int ensure_inter(clc_ctx* ctx, const size_t cap_in, const size_t map_n, InterVie
     uint8_t* h = ctx->h_inter.as<uint8_t>();
     v.h_front = (int32_t*)h; v.h_scale = (InterScaleRec*)(h + 64); v.h_ref = (RefineOut*)(h + 128);
     return CLC_OK;
-}
-
-// spins on a pinned word until it is non-zero; after `ms` without it, ONE synchronisation of the stream (which also surfaces errors)
-int wait_word(clc_ctx* ctx, const int32_t* word, hipStream_t st, const std::chrono::steady_clock::time_point t0, const int ms, const char* what)
-{
-    for (uint32_t spins = 0; __atomic_load_n(word, __ATOMIC_ACQUIRE) == 0;) {
-        if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(ms)) {
-            const hipError_t e = hipStreamSynchronize(st);
-            if (e != hipSuccess || __atomic_load_n(word, __ATOMIC_ACQUIRE) == 0) return fail(ctx, CLC_ERR_HIP, what, e);
-        }
-    }
-    return CLC_OK;
-}
-
-// `consumer` behind what `producer` holds now: an event, no host synchronisation
-hipError_t behind(Event& ev, hipStream_t producer, hipStream_t consumer)
-{
-    if (producer == consumer) return hipSuccess;
-    hipError_t e = ev.create(hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(ev, producer);
-    if (e == hipSuccess) e = hipStreamWaitEvent(consumer, ev, 0);
-    return e;
 }
 
 InterCam cam_of(const clc_camera_k3& c) { return InterCam{ c.focal, c.ppx, c.ppy }; }
@@ -500,17 +409,21 @@ int inter_batch(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, const int n_jobs)
     if (live.empty()) return worst;
     hipLaunchKernelGGL(inter_front_kernel, dim3(1, (unsigned)live.size()), dim3(kInterThreads), 0, st, fj);
     CLC_HIP(c0, hipGetLastError());
+    // the reference's chain sweeps on the job's own stream: those streams behind the front launch
+    std::vector<hipStream_t> own;
+    for (const int i : live) if (jobs[i].d_first_desc && ctxs[i]->stream != st) own.push_back(ctxs[i]->stream);
+    hipError_t e = own.empty() ? hipSuccess : order_behind(c0->ev_track, st, own.data(), own.size());
+    if (e != hipSuccess) return abort_all(fail(c0, CLC_ERR_HIP, "inter_pose_dev: ordering the sweeps behind the front launch", e));
     // 4. the one wait this path adds: the jobs' pinned n_front words
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int> go;
     ScaleJobs sj{};
     sj.map_X = c0->d_map_X.as<double>(); sj.map_n = map_n;
-    bool swept = false;
     for (size_t l = 0; l < live.size(); ++l) {
         const int i = live[l];
         clc_inter_dev_job& jb = jobs[i];
         const InterView& v = view[(size_t)i];
-        const int rc = wait_word(c0, &v.h_front[3], st, t0, 5, "inter_pose_dev: the front launch left no record");
+        const int rc = wait_pinned(c0, &v.h_front[3], 0, st, t0, 5, "inter_pose_dev: the front launch left no record");
         if (rc != CLC_OK) { if (ctxs[i] != c0) (void)fail(ctxs[i], rc, clc_last_error_string(c0)); return abort_all(rc); }
         jb.stage = v.h_front[2];
         if (jb.stage != CLC_INTER_OK) { done[(size_t)i] = 1; continue; }
@@ -520,20 +433,10 @@ int inter_batch(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, const int n_jobs)
         // 5. the reference's chain: the temporary map's descriptor rows by the index list the front kernel left, then the K2NN sweep
         //    (Q = global map, T = temporary map), on the job's own stream behind the front launch
         if (jb.d_first_desc) {
-            hipStream_t own = ctxs[i]->stream;
-            hipError_t e = hipSuccess;
-            if (!swept) { e = c0->ev_track.create(hipEventDisableTiming); if (e == hipSuccess) e = hipEventRecord(c0->ev_track, st); swept = true; }
-            if (e == hipSuccess && own != st) e = hipStreamWaitEvent(own, c0->ev_track, 0);
-            if (e == hipSuccess) e = launch_gather_rows((const uint4*)jb.d_first_desc, v.first, v.rows, (uint32_t)nf, own);
-            if (e != hipSuccess) return abort_all(fail(ctxs[i], CLC_ERR_HIP, "inter_pose_dev: ordering / gathering the temporary map's rows", e));
-            std::vector<K2nnJobDev> kj(1);
-            kj[0] = K2nnJobDev{};
-            kj[0].q = (const uint4*)jb.d_map_desc; kj[0].t = v.rows; kj[0].out = v.match;
-            kj[0].nq = (uint32_t)map_n; kj[0].nt = (uint32_t)nf;
-            kj[0].thr = (uint32_t)(uint8_t)(jb.match_threshold > 0 ? jb.match_threshold : 60);      // GPUMatcher.hpp:162
-            const int rk = run_jobs(ctxs[i], kj, own);
+            hipStream_t sweep = ctxs[i]->stream;
+            const int rk = map_sweep_enqueue(ctxs[i], jb.d_first_desc, v.first, nf, jb.d_map_desc, map_n, v.rows, v.match, jb.match_threshold, sweep);
             if (rk != CLC_OK) return abort_all(rk);
-            e = behind(ctxs[i]->ev_track, own, st);
+            e = sweep != st ? order_behind(ctxs[i]->ev_track, sweep, &st, 1) : hipSuccess;
             if (e != hipSuccess) return abort_all(fail(ctxs[i], CLC_ERR_HIP, "inter_pose_dev: ordering the scale launch behind the sweep", e));
         }
         ScaleJobDev& s = sj.j[go.size()];
@@ -551,19 +454,16 @@ int inter_batch(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, const int n_jobs)
     if (go.empty()) return worst;
     // 6. ONE scale launch, 7. the refinements behind it on the jobs' own streams, gated by the device go / no-go word
     hipLaunchKernelGGL(inter_scale_kernel, dim3(1, (unsigned)go.size()), dim3(kInterThreads), 0, st, sj);
-    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return abort_all(fail(c0, CLC_ERR_HIP, "inter_pose_dev: the scale launch", e)); }
-    bool marked = false;
+    if ((e = hipGetLastError()) != hipSuccess) return abort_all(fail(c0, CLC_ERR_HIP, "inter_pose_dev: the scale launch", e));
+    own.clear();
+    for (const int i : go) if (ctxs[i]->stream != st) own.push_back(ctxs[i]->stream);
+    e = own.empty() ? hipSuccess : order_behind(c0->ev_group, st, own.data(), own.size());
+    if (e != hipSuccess) return abort_all(fail(c0, CLC_ERR_HIP, "inter_pose_dev: ordering the refinements behind the scale launch", e));
     for (const int i : go) {
         clc_inter_dev_job& jb = jobs[i];
         const InterView& v = view[(size_t)i];
-        hipStream_t own = ctxs[i]->stream;
-        hipError_t e = hipSuccess;
-        if (own != st) {
-            if (!marked) { e = c0->ev_group.create(hipEventDisableTiming); if (e == hipSuccess) e = hipEventRecord(c0->ev_group, st); marked = true; }
-            if (e == hipSuccess) e = hipStreamWaitEvent(own, c0->ev_group, 0);
-        }
-        if (e == hipSuccess) e = launch_pnp_refine(v.Rt, v.Xw, v.x2f, nullptr, jb.n_front, v.K, jb.huber_a > 0.0 ? jb.huber_a : 16.0, 50, v.ref, own,
-                                                   &ctxs[i]->prof, v.valid, v.h_ref);
+        e = launch_pnp_refine(v.Rt, v.Xw, v.x2f, nullptr, jb.n_front, v.K, jb.huber_a > 0.0 ? jb.huber_a : 16.0, 50, v.ref, ctxs[i]->stream,
+                              &ctxs[i]->prof, v.valid, v.h_ref);
         if (e != hipSuccess) return abort_all(fail(ctxs[i], CLC_ERR_HIP, "inter_pose_dev: enqueueing the refinement", e));
     }
     // collect through the pinned records (the refinement's comes out behind the scale kernel's)
@@ -571,17 +471,14 @@ int inter_batch(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, const int n_jobs)
     for (const int i : go) {
         clc_inter_dev_job& jb = jobs[i];
         const InterView& v = view[(size_t)i];
-        int rc = wait_word(ctxs[i], &v.h_ref->ready, ctxs[i]->stream, t1, 5, "inter_pose_dev: refinement did not complete");
-        if (rc == CLC_OK) rc = wait_word(ctxs[i], &v.h_scale->ready, st, t1, 5, "inter_pose_dev: the scale launch left no record");
+        int rc = wait_pinned(ctxs[i], &v.h_ref->ready, 0, ctxs[i]->stream, t1, 5, "inter_pose_dev: refinement did not complete");
+        if (rc == CLC_OK) rc = wait_pinned(ctxs[i], &v.h_scale->ready, 0, st, t1, 5, "inter_pose_dev: the scale launch left no record");
         if (rc != CLC_OK) return abort_all(rc);
         done[(size_t)i] = 1;
         jb.stage = v.h_scale->stage; jb.n_common = v.h_scale->n_common; jb.n_map_matches = v.h_scale->n_map_matches;
         if (jb.stage != CLC_INTER_OK) continue;
         jb.scale = v.h_scale->scale;
-        memcpy(jb.Rt, v.h_ref->Rt, sizeof jb.Rt);
-        memcpy(jb.cov, v.h_ref->cov, sizeof jb.cov);
-        jb.rmse = v.h_ref->rmse;
-        jb.n_refined = v.h_ref->n_used;
+        take_refined(jb, *v.h_ref);
     }
     return worst;
 }

@@ -47,13 +47,6 @@ int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     return CLC_OK;
 }
 
-// rows idx[0 .. n) of a descriptor block, 16 bytes per thread
-__global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, const int32_t* __restrict__ idx, uint4* __restrict__ dst, const uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n * 4u) dst[i] = src[(size_t)idx[i >> 2] * 4u + (i & 3u)];
-}
-
 // matchMapFeatures(mapRegions, interMapRegions) for one pair (coloc.hpp:317-323): the temporary map's descriptors -- those of the
 // correspondences in front of both cameras, taken from the lower camera's block -- against the global map's; enqueue only, the
 // matches land in the context's pinned block: h_match[q] = temporary map point matched by global map point q, or -1
@@ -74,13 +67,7 @@ int map_match_enqueue(clc_ctx* ctx, const clc_inter_pose_job& jb, const InterFro
     uint4* d_rows = (uint4*)(ctx->d_pnp.as<double>() + idx_d);
     int32_t* d_match = (int32_t*)(ctx->d_pnp.as<double>() + idx_d + rows_d);
     CLC_HIP(ctx, hipMemcpyAsync(d_idx, h_idx, nf * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_gather_rows((const uint4*)jb.d_first_desc, d_idx, d_rows, (uint32_t)nf, ctx->stream));
-    std::vector<K2nnJobDev> jobs(1);
-    jobs[0] = K2nnJobDev{};
-    jobs[0].q = (const uint4*)jb.d_map_desc; jobs[0].t = (const uint4*)d_rows; jobs[0].out = d_match;
-    jobs[0].nq = (uint32_t)nm; jobs[0].nt = (uint32_t)nf;
-    jobs[0].thr = (uint32_t)(uint8_t)(jb.match_threshold > 0 ? jb.match_threshold : 60);          // GPUMatcher.hpp:162
-    rc = run_jobs(ctx, jobs, ctx->stream);
+    rc = map_sweep_enqueue(ctx, jb.d_first_desc, d_idx, (int)nf, jb.d_map_desc, jb.map_n, d_rows, d_match, jb.match_threshold, ctx->stream);
     if (rc != CLC_OK) return rc;
     CLC_HIP(ctx, hipMemcpyAsync(*h_match, d_match, nm * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     return CLC_OK;
@@ -88,11 +75,16 @@ int map_match_enqueue(clc_ctx* ctx, const clc_inter_pose_job& jb, const InterFro
 
 } // namespace
 
-hipError_t clc::launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, const uint32_t n, hipStream_t stream)
+int clc::map_sweep_enqueue(clc_ctx* ctx, const void* d_first_desc, const int32_t* d_idx, const int nf, const void* d_map_desc, const int map_n,
+                           uint4* d_rows, int32_t* d_match, const int threshold, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, src, d_idx, dst, n);
-    return hipGetLastError();
+    CLC_HIP(ctx, launch_gather_rows((const uint4*)d_first_desc, d_idx, d_rows, (uint32_t)nf, stream));
+    std::vector<K2nnJobDev> jobs(1);
+    jobs[0] = K2nnJobDev{};
+    jobs[0].q = (const uint4*)d_map_desc; jobs[0].t = d_rows; jobs[0].out = d_match;
+    jobs[0].nq = (uint32_t)map_n; jobs[0].nt = (uint32_t)nf;
+    jobs[0].thr = (uint32_t)(uint8_t)(threshold > 0 ? threshold : 60);          // GPUMatcher.hpp:162
+    return run_jobs(ctx, jobs, stream);
 }
 
 extern "C" {
@@ -156,28 +148,13 @@ int clc_inter_pose_batch(clc_ctx* const* ctxs, clc_inter_pose_job* jobs, int n_j
         if (rc != CLC_OK) { jb.tv.status = rc; jb.stage = CLC_INTER_NO_REFINEMENT; if (worst == CLC_OK) worst = rc; continue; }
         pend.push_back(p);
     }
-    // 4. collect: poll the pinned records, fall back to the stream synchronisation after 5 ms
+    // 4. collect through the pinned records (wait_pinned: the stream synchronisation after 5 ms)
     const auto t0 = std::chrono::steady_clock::now();
     for (const Pending& p : pend) {
         clc_inter_pose_job& jb = jobs[p.job];
-        uint32_t spins = 0;
-        while (__atomic_load_n(&p.rec->ready, __ATOMIC_ACQUIRE) == 0) {
-            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(5)) {
-                const hipError_t e = hipStreamSynchronize(ctxs[p.job]->stream);
-                if (e != hipSuccess || __atomic_load_n(&p.rec->ready, __ATOMIC_ACQUIRE) == 0) {
-                    jb.tv.status = fail(ctxs[p.job], CLC_ERR_HIP, "inter_pose_batch: refinement did not complete", e);
-                    jb.stage = CLC_INTER_NO_REFINEMENT;
-                    if (worst == CLC_OK) worst = jb.tv.status;
-                    break;
-                }
-            }
-        }
-        if (jb.stage != CLC_INTER_OK) continue;
-        const RefineOut& f = *p.rec;
-        memcpy(jb.Rt, f.Rt, sizeof f.Rt);
-        memcpy(jb.cov, f.cov, sizeof f.cov);
-        jb.rmse = f.rmse;
-        jb.n_refined = f.n_used;
+        const int rc = wait_pinned(ctxs[p.job], &p.rec->ready, 0, ctxs[p.job]->stream, t0, 5, "inter_pose_batch: refinement did not complete");
+        if (rc != CLC_OK) { jb.tv.status = rc; jb.stage = CLC_INTER_NO_REFINEMENT; if (worst == CLC_OK) worst = rc; continue; }
+        take_refined(jb, *p.rec);
     }
     return worst;
 }

@@ -50,17 +50,6 @@ void acr_tables(int n, int m, float* logc_n, float* logc_k, std::vector<float>& 
 
 size_t dbl(size_t bytes) { return (bytes + 7) / 8; }
 
-// Every consumer stream behind what `producer` holds now: ONE event (ev: its owner's, created on first use) recorded on the producer and
-// waited for by the consumers, no host synchronisation; where an event call fails the host waits for the producer instead, and what that
-// synchronisation reports is returned.
-hipError_t order_behind(Event& ev, hipStream_t producer, const hipStream_t* consumers, const size_t n)
-{
-    bool ok = ev.create(hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, producer) == hipSuccess;
-    for (size_t i = 0; i < n && ok; ++i)
-        if (consumers[i] != producer) ok = hipStreamWaitEvent(consumers[i], ev, 0) == hipSuccess;
-    return ok ? hipSuccess : hipStreamSynchronize(producer);
-}
-
 // kind 0: a = X (3 N), b = x (2 N), K1 = intrinsics; kind 1: a = x1, b = x2 (2 N each), K1 / K2, image 2 of img_w x img_h;
 // kinds 2 / 3 (round 6: RobustMatcher's 'F' / 'H' models, RobustMatcher.hpp:128-151, :188-239): a = x1, b = x2 in pixels, both images
 // img_w x img_h -- the points are conditioned by the image size on their way into the pinned block (ACKernelAdaptor), the rounds are
@@ -693,6 +682,14 @@ void two_view_run(AcrRun& r, clc_ctx* ctx, clc_two_view_job& jb, double* EF, con
 
 namespace clc {
 
+hipError_t order_behind(Event& ev, hipStream_t producer, const hipStream_t* consumers, const size_t n)
+{
+    bool ok = ev.create(hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, producer) == hipSuccess;
+    for (size_t i = 0; i < n && ok; ++i)
+        if (consumers[i] != producer) ok = hipStreamWaitEvent(consumers[i], ev, 0) == hipSuccess;
+    return ok ? hipSuccess : hipStreamSynchronize(producer);
+}
+
 int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what)
 {
     for (int i = 0; i < n_jobs; ++i) {
@@ -885,18 +882,12 @@ template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typ
     // the one number the host needs: poll the pinned words, the stream synchronisation as the fallback (which also surfaces errors)
     std::vector<AcrRun> runs((size_t)n_jobs);
     std::vector<double> Ks((size_t)18 * n_jobs, 0.0), models((size_t)18 * n_jobs, 0.0);
+    const std::string no_count = who + ": the gather launch left no count";
     const auto t0 = std::chrono::steady_clock::now();
-    bool synced = false;
     for (int i = 0; i < n_jobs; ++i) {
         const GatherView v(Path::block(ctxs[i]), Path::layout);
-        uint32_t w = __atomic_load_n(v.h_n, __ATOMIC_ACQUIRE);
-        for (uint32_t spins = 0; w == 0xFFFFFFFFu; w = __atomic_load_n(v.h_n, __ATOMIC_ACQUIRE)) {
-            if (synced) return fail(c0, CLC_ERR_HIP, (who + ": the gather launch left no count").c_str());
-            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
-                CLC_HIP(c0, hipStreamSynchronize(st));
-                synced = true;
-            }
-        }
+        if (const int rc = wait_pinned(c0, v.h_n, 0xFFFFFFFFu, st, t0, 2, no_count.c_str())) return rc;
+        const uint32_t w = __atomic_load_n(v.h_n, __ATOMIC_ACQUIRE);
         typename Path::Job& jb = jobs[i];
         Path::count(jb) = (int)w;
         AcrRun& r = runs[(size_t)i];

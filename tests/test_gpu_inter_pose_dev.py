@@ -8,14 +8,12 @@ import pytest
 
 import synth
 import track_host
+from inter_scenes import K, NO_MODEL, NO_RELATIVE_POSE, NO_SCALE, WH, pair as _pair
 
 pytestmark = pytest.mark.gpu
 
-K = np.array([[1000.0, 0, 640], [0, 1000.0, 360], [0, 0, 1]])
-WH = (1280, 720)
 CAM_A = (1000.0, 640.0, 360.0) + track_host.DISTORTIONS[1]
 CAM_B = (1000.0, 640.0, 360.0) + track_host.DISTORTIONS[2]
-NO_MODEL, NO_RELATIVE_POSE, NO_SCALE = 1, 2, 3
 
 
 def _torch():
@@ -37,35 +35,6 @@ def _bits(a):
 def _light_ctx():
     from coloc_amd import Context
     return Context(device=0, detector=False, matcher=False)
-
-
-def _rot(ax, a):
-    c, s = np.cos(a), np.sin(a)
-    return {"x": np.array([[1, 0, 0], [0, c, -s], [0, s, c]]), "y": np.array([[c, 0, s], [0, 1, 0], [-s, 0, c]]), "z": np.array([[c, -s, 0], [s, c, 0], [0, 0, 1]])}[ax]
-
-
-def _pair(seed, n=900, outliers=0.3, noise=0.4, in_map=0.6):
-    """the recipe of tests/test_gpu_two_view_batch.py: a world of n points, a source and a destination camera, n correspondences (30 % of
-    the destination's replaced), a global map that holds 60 % (in_map) of the points in a shuffled order"""
-    rng = np.random.default_rng(seed)
-    X = np.stack([rng.uniform(-5, 5, n), rng.uniform(-5, 5, n), rng.uniform(6, 18, n)], 1)
-    Rs, ts = _rot("y", rng.uniform(-0.1, 0.1)) @ _rot("x", rng.uniform(-0.05, 0.05)), rng.uniform(-0.3, 0.3, 3)
-    Rd = _rot("y", rng.uniform(0.1, 0.25)) @ _rot("z", rng.uniform(-0.05, 0.05)) @ Rs
-    td = ts + np.array([rng.uniform(0.6, 1.2), rng.uniform(-0.2, 0.2), rng.uniform(-0.2, 0.2)])
-
-    def proj(R, t):
-        u = (X @ R.T + t) @ K.T
-        return u[:, :2] / u[:, 2:3]
-    x1 = proj(Rs, ts) + rng.normal(0, noise, (n, 2))
-    x2 = proj(Rd, td) + rng.normal(0, noise, (n, 2))
-    out = rng.choice(n, int(outliers * n), replace=False)
-    x2[out] = np.stack([rng.uniform(0, WH[0], len(out)), rng.uniform(0, WH[1], len(out))], 1)
-    in_map = rng.random(n) < in_map
-    order = rng.permutation(np.nonzero(in_map)[0])
-    map_X = X[order] + rng.normal(0, 0.002, (len(order), 3))
-    map_index = np.full(n, -1, np.int32)
-    map_index[order] = np.arange(len(order), dtype=np.int32)
-    return dict(x1=x1, x2=x2, map_index=map_index, Rt_source=np.c_[Rs, ts], Rs=Rs, ts=ts, Rd=Rd, td=td, map_X=map_X)
 
 
 def _distort(x, cam):
