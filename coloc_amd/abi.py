@@ -77,6 +77,33 @@ class PairJob(C.Structure):
                 ("error_max", C.c_double), ("min_nfa", C.c_double)]
 
 
+MAX_BATCH, MAX_TRACK_PAIRS = 8, 28          # CLC_MAX_BATCH, CLC_MAX_TRACK_PAIRS
+
+
+class TracksPair(C.Structure):
+    """clc_tracks_pair (include/coloc_hip.h)"""
+    _fields_ = [("cam_a", C.c_int32), ("cam_b", C.c_int32), ("d_q", C.c_void_p), ("d_t", C.c_void_p), ("n", C.c_int), ("d_n", C.c_void_p),
+                ("d_index", C.c_void_p), ("n_list", C.c_int)]
+
+
+class TracksJob(C.Structure):
+    """clc_tracks_job (include/coloc_hip.h)"""
+    _fields_ = [("n_cams", C.c_int), ("rows", C.c_int * MAX_BATCH), ("n_pairs", C.c_int), ("pairs", C.POINTER(TracksPair))]
+
+
+class MapCamera(C.Structure):
+    """clc_map_camera (include/coloc_hip.h)"""
+    _fields_ = [("d_kps", C.c_void_p), ("d_feat", C.c_void_p), ("feat_stride", C.c_int), ("cam", CameraK3), ("d_desc", C.c_void_p)]
+
+
+class MapJob(C.Structure):
+    """clc_map_job (include/coloc_hip.h)"""
+    _fields_ = [("tracks", TracksJob), ("cams", MapCamera * MAX_BATCH), ("seed_pair", C.c_int), ("Rt_seed_a", C.c_double * 12),
+                ("Rt_seed_b", C.c_double * 12), ("after_stream", C.c_void_p), ("origin_R", C.c_double * 9), ("origin_C", C.c_double * 3),
+                ("scale", C.c_double), ("track_feat", C.c_void_p), ("map_track", C.c_void_p), ("map_row", C.c_void_p), ("X", C.c_void_p),
+                ("n_tracks", C.c_int), ("map_n", C.c_int), ("status", C.c_int), ("entered", C.c_int * MAX_TRACK_PAIRS)]
+
+
 ABI_VERSION = 4          # CLC_ABI_VERSION of include/coloc_hip.h
 DESC_CACHE_OFF, DESC_CACHE_VERIFY, DESC_CACHE_TRUST = 0, 1, 2
 
@@ -127,6 +154,7 @@ EXPORTS = [
     "clc_set_map_points", "clc_track_build_dev", "clc_track_localize_dev", "clc_track_localize_batch_dev",
     "clc_pair_build_dev", "clc_pair_filter_dev", "clc_pair_filter_batch_dev",
     "clc_inter_pose_dev", "clc_inter_pose_batch_dev", "clc_inter_front_dev",
+    "clc_tracks_build_dev", "clc_map_build_dev", "clc_map_init_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -282,6 +310,9 @@ def load_library():
     lib.clc_inter_pose_dev.argtypes = [vp, vp]
     lib.clc_inter_pose_batch_dev.argtypes = [vp, vp, ci]
     lib.clc_inter_front_dev.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.clc_tracks_build_dev.argtypes = [vp, vp, vp, vp, vp]
+    lib.clc_map_build_dev.argtypes = [vp, vp]
+    lib.clc_map_init_batch_dev.argtypes = [vp, vp, ci, vp]
     _lib = lib
     return lib
 
@@ -671,6 +702,93 @@ def inter_pose_batch_dev(ctxs, jobs):
     return [_inter_dev_result(arr[i], *outs[i]) for i in range(n)]
 
 
+def seed_poses(origin_R, origin_C, rel_R, rel_C, scale):
+    """The two seed cameras' [R|t] (3 x 4 each) as Reconstructor::triangulatePoints forms them (Reconstructor.hpp:215-221, 247-257):
+    camera I = the origin pose (rotation, centre), camera J = relativePoseToAbsolute(origin, Pose3(rel_R, scale * rel_C)) -- R = rel_R
+    origin_R, C = origin_C + scale rel_C, t = -R C.  The operations of coloc_amd/csrc/map_math.h in its order, one IEEE operation at a
+    time: the same bits as clc_map_init_batch_dev's."""
+    Ro = [float(v) for v in np.asarray(origin_R, dtype=np.float64).reshape(9)]
+    Co = [float(v) for v in np.asarray(origin_C, dtype=np.float64).reshape(3)]
+    Rr = [float(v) for v in np.asarray(rel_R, dtype=np.float64).reshape(9)]
+    Cr = [float(v) for v in np.asarray(rel_C, dtype=np.float64).reshape(3)]
+    scale = float(scale)
+    R = [Rr[3 * r] * Ro[q] + Rr[3 * r + 1] * Ro[3 + q] + Rr[3 * r + 2] * Ro[6 + q] for r in range(3) for q in range(3)]
+    Cj = [Co[q] + scale * Cr[q] for q in range(3)]
+    Rt_i, Rt_j = np.zeros((3, 4)), np.zeros((3, 4))
+    for r in range(3):
+        Rt_i[r, :3] = Ro[3 * r:3 * r + 3]
+        Rt_j[r, :3] = R[3 * r:3 * r + 3]
+        Rt_i[r, 3] = -(Ro[3 * r] * Co[0] + Ro[3 * r + 1] * Co[1] + Ro[3 * r + 2] * Co[2])
+        Rt_j[r, 3] = -(R[3 * r] * Cj[0] + R[3 * r + 1] * Cj[1] + R[3 * r + 2] * Cj[2])
+    return Rt_i, Rt_j
+
+
+def tracks_capacity(rows, pairs):
+    """tracks the table of clc_tracks_build_dev / clc_map_build_dev has room for: min(sum of n, (sum of rows) / 2)"""
+    return min(sum(int(p["n"]) for p in pairs), sum(int(r) for r in rows) // 2)
+
+
+def _tracks_fill(t, keep, rows, pairs):
+    """fills a TracksJob: rows = row capacity per camera, pairs = [dict(cam_a=, cam_b=, d_q=, d_t=, n= [, d_n, d_index, n_list]), ...]"""
+    t.n_cams = len(rows)
+    for c, r in enumerate(rows[:MAX_BATCH]):
+        t.rows[c] = int(r)
+    arr = (TracksPair * max(len(pairs), 1))()
+    for a, p in zip(arr, pairs):
+        a.cam_a, a.cam_b, a.d_q, a.d_t, a.n = int(p["cam_a"]), int(p["cam_b"]), p.get("d_q"), p.get("d_t"), int(p.get("n", 0))
+        a.d_n, a.d_index, a.n_list = p.get("d_n"), p.get("d_index"), int(p.get("n_list", 0))
+    keep.append(arr)
+    t.n_pairs, t.pairs = len(pairs), arr
+
+
+def _map_fill(j, keep, rows, pairs, cams, seed_pair=0, Rt_seed_a=None, Rt_seed_b=None, after_stream=None, origin_R=None, origin_C=None,
+              scale=1.0, outputs=True):
+    """fills a MapJob; cams = [dict(cam=(focal, ppx, ppy, k1, k2, k3), d_kps= | d_feat= [, feat_stride], d_desc=), ...]"""
+    _tracks_fill(j.tracks, keep, rows, pairs)
+    for m, c in zip(j.cams, cams):
+        m.d_kps, m.d_feat, m.feat_stride, m.d_desc = c.get("d_kps"), c.get("d_feat"), int(c.get("feat_stride", 4)), c.get("d_desc")
+        m.cam = CameraK3(*[float(v) for v in c["cam"]])
+    j.seed_pair, j.after_stream, j.scale = int(seed_pair), after_stream, float(scale)
+    for dst, src, n in ((j.Rt_seed_a, Rt_seed_a, 12), (j.Rt_seed_b, Rt_seed_b, 12), (j.origin_R, origin_R, 9), (j.origin_C, origin_C, 3)):
+        if src is not None:
+            dst[:] = [float(v) for v in np.asarray(src, dtype=np.float64).reshape(n)]
+    if not outputs:
+        return None
+    cap = max(sum(int(r) for r in rows) // 2, 1)             # (tracks_capacity before the pairs' counts are known)
+    tf = np.full((cap, len(rows)), -1, dtype=np.int32)
+    mt, mr, X = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int32), np.zeros((cap, 3))
+    keep.append((tf, mt, mr, X))
+    j.track_feat, j.map_track, j.map_row, j.X = (a.ctypes.data for a in (tf, mt, mr, X))
+    return tf, mt, mr, X
+
+
+def _map_result(j, tf, mt, mr, X):
+    n, k = max(j.map_n, 0), max(j.n_tracks, 0)
+    return dict(n_tracks=j.n_tracks, map_n=j.map_n, track_feat=tf[:k].copy(), map_track=mt[:n].copy(), map_row=mr[:n].copy(), X=X[:n].copy(),
+                seed_pair=j.seed_pair, Rt_seed_a=np.array(j.Rt_seed_a).reshape(3, 4), Rt_seed_b=np.array(j.Rt_seed_b).reshape(3, 4),
+                entered=[bool(v) for v in j.entered[:j.tracks.n_pairs]], status=j.status)
+
+
+def map_init_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0):
+    """clc_map_init_batch_dev: pair_jobs = [dict(the keywords of Context.pair_filter_dev), ...], job p on ctxs[p] and between the cameras
+    pair_cams[p] = (cam_a, cam_b); rows / cams as Context.map_build_dev.  The filters run under 'E'; the pairs with at least 13 inliers
+    and a successful chirality vote enter the tracks, the one with the most inliers is the seed; the map is installed on ctxs[0].
+    Returns (map result dict with seed_pair / Rt_seed_* / entered, [pair filter result dicts])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j = MapJob()
+    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_init_batch_dev(hs, arr, n, C.byref(j))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_init_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    return _map_result(j, *out), [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
 def desc_handle_live(handle):
     """1 while the publication the handle came from still stands (same host address, count and generation)."""
     return bool(load_library().clc_desc_handle_live(C.byref(handle)))
@@ -1002,6 +1120,26 @@ class Context:
         """clc_set_map_points: (n, 3) float64, row i = the landmark of map descriptor row i; an empty array clears"""
         X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
         self._chk(self.lib.clc_set_map_points(self.h, _p(X) if X.shape[0] else None, X.shape[0]))
+
+    def tracks_build_dev(self, rows, pairs, d_track_feat, d_n_tracks, stream=None):
+        """clc_tracks_build_dev: the multi-view tracks alone, enqueue only.  rows = row capacity per camera; pairs = [dict(cam_a=, cam_b=,
+        d_q=, d_t=, n= [, d_n, d_index, n_list]), ...] (device pointers as integers); d_track_feat: int32 [tracks_capacity(rows, pairs)]
+        [len(rows)], d_n_tracks: one int32"""
+        t = TracksJob()
+        keep = []
+        _tracks_fill(t, keep, rows, pairs)
+        self._chk(self.lib.clc_tracks_build_dev(self.h, C.byref(t), d_track_feat, d_n_tracks, stream))
+
+    def map_build_dev(self, rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream=None):
+        """clc_map_build_dev: tracks + the seed pair's triangulation, installed as this context's map (the state of set_map +
+        set_map_points).  cams = [dict(cam=(focal, ppx, ppy, k1, k2, k3), d_kps= | d_feat= [, feat_stride], d_desc=), ...] per camera;
+        Rt_seed_a / Rt_seed_b: [R|t] of the seed pair's two cameras (seed_poses).  Returns a dict: n_tracks, track_feat, map_n, map_track,
+        map_row, X."""
+        j = MapJob()
+        keep = []
+        out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
+        self._chk(self.lib.clc_map_build_dev(self.h, C.byref(j)))
+        return _map_result(j, *out)
 
     def track_build_dev(self, d_X, d_x, d_query, d_map, d_n, stream=None, **job):
         """clc_track_build_dev: the track kernel alone, enqueue only; job keywords as track_localize_dev (d_match, nq, cam, d_kps | d_feat,

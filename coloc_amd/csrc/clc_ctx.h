@@ -132,6 +132,10 @@ struct clc_ctx {
     // the inter-camera step from device memory (inter_dev.hip): temporary map, lists, the refinement's inputs / the pinned records
     clc::DevBuf d_inter;
     clc::PinBuf h_inter;
+    // the map built on the device (map_build.hip): union-find words, track table and the staged map lists; the next map's points, which
+    // change places with d_map_X when a build succeeds; the pinned count and the mirrors of the host outputs
+    clc::DevBuf d_mapb, d_map_X_next;
+    clc::PinBuf h_mapb;
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     clc::PinBuf h_stage;          // (bytes)

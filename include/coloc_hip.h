@@ -46,7 +46,8 @@ extern "C" {
  * the distance-ratio entries (clc_match_ratio_*, clc_match_map_ratio*, clc_ratio_matches_to_pairs) came later under 4: new entry points only;
  * so did the keypoint selection rule (clc_detect_set_selection, clc_detect_selection) and the device-side 2D-3D tracks
  * (clc_set_map_points, clc_track_build_dev, clc_track_localize_dev, clc_track_localize_batch_dev) and two-view correspondences
- * (clc_pair_build_dev, clc_pair_filter_dev, clc_pair_filter_batch_dev).
+ * (clc_pair_build_dev, clc_pair_filter_dev, clc_pair_filter_batch_dev), the inter-camera step from device memory (clc_inter_*_dev) and
+ * the map built on the device (clc_tracks_build_dev, clc_map_build_dev, clc_map_init_batch_dev).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -901,6 +902,113 @@ int clc_inter_pose_batch_dev(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, int 
 int clc_inter_front_dev(clc_ctx* ctx, const double* d_x1, const double* d_x2, int n, const int32_t* d_inliers, int n_inliers,
                         const clc_camera_k3* cam_a, const clc_camera_k3* cam_b, const double* h_motions, const int32_t* d_rows,
                         double* d_Xt, double* d_x2f, int32_t* d_corr, int32_t* d_first, int32_t* d_record, void* stream);
+
+/* ---- the map on the device: multi-view tracks and the seed pair's triangulation -----------------------------------------------------
+ * What ColoC::initMap (coloc.hpp:151-199) runs once and ColoC::updateMap (coloc.hpp:394-459) whenever tracking thins out, between
+ * filterMatches and setMapData: the tracks of Reconstructor::initializeTracks (Reconstructor.hpp:166-173: TracksBuilder Build, Filter,
+ * ExportToSTL), the seed pair's landmarks of Reconstructor::triangulatePoints (:185-239) and the map database of
+ * colocData::setupMapDatabase (colocData.hpp:89-121), from the pairs' correspondences where clc_pair_filter_batch_dev left them.  It
+ * ends where reconstructScene writes initial.ply: no resectionCamera, no bundle adjustment, no PLY.  (Later under ABI 4: new entry
+ * points only.)
+ *
+ * TRACKS.  A node is a (camera, feature row) named by a match; an edge is a match (cam_a, q)-(cam_b, t) of a pair cam_a < cam_b; a
+ * track is a connected component.  The rules are this project's statement of OpenMVG's TracksBuilder (an empty submodule in the
+ * reference tree, so unpinned, as for the ratio matcher):
+ *   - a component that holds two nodes of ONE camera is dropped whole (Filter), also where the conflict only arises through a third
+ *     camera (A5-B7, B7-C2, C2-A9).  K2NN is not one-to-one, so this is common;
+ *   - a surviving track has at least two nodes (Filter(2): every edge joins two cameras, so every component has);
+ *   - the survivors get ids 0, 1, ... in ascending order of their smallest node in (camera, row) order.  The SET of tracks does not
+ *     depend on that rule, only their order does; nothing depends on scheduling.
+ * An edge that names a row outside [0, rows[camera]) is ignored; repeated edges count once.
+ * A pair's edges: entries 0 .. min(n, *d_n) - 1 (d_n nullable: a count in DEVICE memory, n the planned size) of the lists d_q / d_t
+ * (DEVICE, int32) -- or, with d_index (nullable; DEVICE or pinned host memory), entries d_index[0 .. ) of lists of n_list entries: a
+ * filter's inlier list over the pair lists it was given; an index outside [0, n_list) names no edge.
+ *
+ * clc_tracks_build_dev: the tracks alone, enqueue only on `stream`, no host synchronisation between its launches.  Its union-find
+ * words live in ONE block of the context, shared with clc_map_build_dev: one tracks / map build in flight per context at a time (a
+ * second one, on whatever stream, is ordered behind the first by the caller).  The block grows on demand: a call that needs more
+ * nodes than any call before it synchronises the CONTEXT's stream and allocates anew -- such a call is not capturable and must not
+ * run while an earlier build is still in flight on another stream; every later call of that size or less only enqueues and is
+ * capturable (so: one call at the planned size before a capture).
+ * d_track_feat[track][camera] (int32, job->n_cams per track) = that camera's row or -1; room for min(sum of n, (sum of rows) / 2)
+ * tracks, all of it written (-1 past the tracks); *d_n_tracks (int32) the number of tracks, stored last.  n_cams in
+ * [2, CLC_MAX_BATCH], n_pairs in [0, CLC_MAX_TRACK_PAIRS]; a pair with cam_a >= cam_b or a camera outside [0, n_cams), a negative count,
+ * a misaligned pointer: CLC_ERR_BAD_ARG.
+ *
+ * clc_map_build_dev: tracks, then for every track that holds both cameras of pair seed_pair, in track-id order: the two rows'
+ * positions (d_kps with the pow(1.2f, level) scaling or d_feat + feat_stride, as clc_pair_job) through get_ud_pixel in fp64 (the
+ * host's bits), TriangulateDLT(P1, x1.homogeneous(), P2, x2.homogeneous(), &X) with P = K [R|t] (Reconstructor.hpp:223-225; the null
+ * vector by a one-sided Jacobi, coloc_amd/csrc/map_math.h), and the reference's acceptance as written: dropped iff the depth
+ * (R X + t)[2] is negative under BOTH poses (:227), or iff |X[2]| > 100 (:230) (or X is not finite).  The accepted points, in
+ * track-id order, are the map: row i = { X, the track id (mapRegionIdx), the row in the LOWER seed camera (obs.begin(),
+ * colocData.hpp:112-116) and that row's descriptor from the camera's block }.  It is installed as the context's map -- the state
+ * clc_set_map + clc_set_map_points leave, for clc_match_map_dev / clc_track_localize_dev and the rest.  No copy command is issued and
+ * no descriptor or point moves through the host: the host waits for ONE number, the map's row count, then enqueues the descriptor
+ * gather and returns when it has run (no data moves; as clc_set_map returns behind its upload).  ORDERING: on return the map is
+ * complete and none of the job's inputs is read any more -- a matcher call on any stream may follow at once, and the caller may
+ * describe the next frame into the seed camera's block.  What the call cannot know is work on OTHER streams that still reads the
+ * PREVIOUS map (d_m is rewritten in place, as by clc_set_map): such work is complete, or joined to the context's stream, before
+ * the call.  Host outputs (nullable): track_feat (room as d_track_feat), map_track / map_row (room for min(that, maxkp) entries), X (3
+ * doubles each), from pinned mirrors the kernels write.  Rt_seed_a / Rt_seed_b: [R|t] of the seed pair's cam_a / cam_b
+ * (relativePoseToAbsolute, :247-257, is the caller's: clc_map_init_batch_dev applies it).  Every camera below n_cams gives its 2-D
+ * side and camera; the descriptor block (rows of 64 B, 16-byte aligned) is read for the lower seed camera.  after_stream: as
+ * clc_track_job.  Fewer than two cameras, a bad pair, seed_pair outside the pairs, a misaligned pointer, both or neither of d_kps /
+ * d_feat: CLC_ERR_BAD_ARG; a context without matcher options: CLC_ERR_STATE; more map rows than MatcherOptions.maxkp:
+ * CLC_ERR_CAPACITY, and the previous map stays as it was; no accepted point: CLC_OK, map_n = 0 and no map points.
+ *
+ * clc_map_init_batch_dev: the composition initMap / updateMap call.  pair_jobs[p] on ctxs[p] (a context of its own each) is the pair
+ * job->tracks.pairs[p].cam_a < cam_b (the other fields of tracks.pairs are filled in here; tracks.n_pairs == n_pairs): the filters
+ * run as clc_pair_filter_batch_dev under 'E'; a pair enters the tracks by the rules of HIPRobustMatcher::computeRelativePoseDev -- at
+ * least 2.5 x 5 inliers and a successful chirality vote (RobustMatcher.hpp:176-183; the host vote of clc_inter_pose_batch, fed from
+ * the pinned mirrors); its edges are its inliers' pair_q / pair_t, read by the kernel from the context's block through the pinned
+ * inlier list.  The seed is the pair with strictly the most inliers, the first in pair order (Reconstructor.hpp:112-118); its [R|t]
+ * are seed_poses of (origin_R, origin_C, the vote's rotation and centre, scale).  Then clc_map_build_dev on ctxs[0].  Out: seed_pair
+ * (-1: no pair entered -- CLC_OK, the map is left alone, map_n = -1), Rt_seed_a / Rt_seed_b, entered[p]. */
+#define CLC_MAX_TRACK_PAIRS 28   /* CLC_MAX_BATCH cameras, every pair once */
+typedef struct clc_tracks_pair {
+    int32_t        cam_a, cam_b;  /* cam_a < cam_b */
+    const int32_t* d_q;           /* rows of camera a */
+    const int32_t* d_t;           /* rows of camera b */
+    int            n;             /* edges (the planned size where d_n is given) */
+    const int32_t* d_n;           /* nullable */
+    const int32_t* d_index;       /* nullable */
+    int            n_list;        /* with d_index: entries of d_q / d_t */
+} clc_tracks_pair;
+typedef struct clc_tracks_job {
+    int                    n_cams;
+    int                    rows[CLC_MAX_BATCH];  /* row capacity per camera */
+    int                    n_pairs;
+    const clc_tracks_pair* pairs;                /* host memory */
+} clc_tracks_job;
+typedef struct clc_map_camera {
+    const clc_keypoint* d_kps;        /* or */
+    const float*        d_feat;
+    int                 feat_stride;
+    clc_camera_k3       cam;
+    const void*         d_desc;       /* rows[camera] x 64 B */
+} clc_map_camera;
+typedef struct clc_map_job {
+    /* in */
+    clc_tracks_job  tracks;
+    clc_map_camera  cams[CLC_MAX_BATCH];
+    int             seed_pair;        /* index into tracks.pairs (clc_map_init_batch_dev: out) */
+    double          Rt_seed_a[12];    /* (clc_map_init_batch_dev: out) */
+    double          Rt_seed_b[12];
+    void*           after_stream;     /* nullable */
+    double          origin_R[9];      /* clc_map_init_batch_dev only: the origin pose (rotation, centre) and the baseline's scale */
+    double          origin_C[3];
+    double          scale;
+    /* out (pointers nullable, host memory) */
+    int32_t*        track_feat;
+    int32_t*        map_track;
+    int32_t*        map_row;
+    double*         X;
+    int             n_tracks, map_n, status;
+    int             entered[CLC_MAX_TRACK_PAIRS];   /* clc_map_init_batch_dev */
+} clc_map_job;
+int clc_tracks_build_dev(clc_ctx* ctx, const clc_tracks_job* job, int32_t* d_track_feat, int32_t* d_n_tracks, void* stream);
+int clc_map_build_dev(clc_ctx* ctx, clc_map_job* job);
+int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
