@@ -104,6 +104,15 @@ class MapJob(C.Structure):
                 ("n_tracks", C.c_int), ("map_n", C.c_int), ("status", C.c_int), ("entered", C.c_int * MAX_TRACK_PAIRS)]
 
 
+class MapAlign(C.Structure):
+    """clc_map_align (include/coloc_hip.h)"""
+    _fields_ = [("d_desc", C.c_void_p), ("d_rows", C.c_void_p), ("d_X", C.c_void_p), ("n_new", C.c_int), ("threshold", C.c_int),
+                ("install", C.c_int), ("after_stream", C.c_void_p), ("match", C.c_void_p), ("X", C.c_void_p),
+                ("n_old", C.c_int), ("n_common", C.c_int), ("n_terms", C.c_int), ("status", C.c_int), ("scale", C.c_double)]
+
+
+MAP_ALIGN_OK, MAP_ALIGN_NO_SCALE = 0, 1
+
 ABI_VERSION = 4          # CLC_ABI_VERSION of include/coloc_hip.h
 DESC_CACHE_OFF, DESC_CACHE_VERIFY, DESC_CACHE_TRUST = 0, 1, 2
 
@@ -155,6 +164,7 @@ EXPORTS = [
     "clc_pair_build_dev", "clc_pair_filter_dev", "clc_pair_filter_batch_dev",
     "clc_inter_pose_dev", "clc_inter_pose_batch_dev", "clc_inter_front_dev",
     "clc_tracks_build_dev", "clc_map_build_dev", "clc_map_init_batch_dev",
+    "clc_map_align_dev", "clc_map_update_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -313,6 +323,8 @@ def load_library():
     lib.clc_tracks_build_dev.argtypes = [vp, vp, vp, vp, vp]
     lib.clc_map_build_dev.argtypes = [vp, vp]
     lib.clc_map_init_batch_dev.argtypes = [vp, vp, ci, vp]
+    lib.clc_map_align_dev.argtypes = [vp, vp]
+    lib.clc_map_update_batch_dev.argtypes = [vp, vp, ci, vp, vp]
     _lib = lib
     return lib
 
@@ -789,6 +801,36 @@ def map_init_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3
     return _map_result(j, *out), [_pair_result(arr[i], *outs[i]) for i in range(n)]
 
 
+def _align_result(a, match, X):
+    n_old, n_new = max(a.n_old, 0), max(a.n_new, 0)
+    return dict(scale=float(a.scale), n_old=a.n_old, n_common=a.n_common, n_terms=a.n_terms, status=a.status,
+                match=None if match is None else match[:n_old].copy(), X=None if X is None else X[:n_new].copy())
+
+
+def map_update_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, threshold=0):
+    """clc_map_update_batch_dev: map_init_batch_dev's arguments; the new map is brought to the scale of the map ctxs[0] holds and replaces
+    it.  Returns (map result dict -- X and Rt_seed_* RESCALED -- with an "align" dict: scale, n_old, n_common, n_terms, status, match;
+    [pair filter result dicts])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j = MapJob()
+    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    al = MapAlign()
+    match = np.full(max(int(ctxs[0].mopts.maxkp), 1), -2, dtype=np.int32)
+    al.threshold, al.match = int(threshold), match.ctypes.data
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_update_batch_dev(hs, arr, n, C.byref(j), C.byref(al))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_update_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    res = _map_result(j, *out)
+    res["align"] = _align_result(al, match, None)
+    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
 def desc_handle_live(handle):
     """1 while the publication the handle came from still stands (same host address, count and generation)."""
     return bool(load_library().clc_desc_handle_live(C.byref(handle)))
@@ -1140,6 +1182,18 @@ class Context:
         out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
         self._chk(self.lib.clc_map_build_dev(self.h, C.byref(j)))
         return _map_result(j, *out)
+
+    def map_align_dev(self, d_desc, d_X, n_new, d_rows=None, threshold=0, install=True, after_stream=None, want_match=True, want_X=True):
+        """clc_map_align_dev: a new map in device memory (row i = row d_rows[i] of d_desc, landmark d_X[i]) brought to the scale of the
+        map this context holds and, with install, put in its place.  Returns a dict: scale, n_old, n_common, n_terms, status, match (new
+        row of every old row, or -1), X (the rescaled points)."""
+        a = MapAlign()
+        a.d_desc, a.d_rows, a.d_X, a.n_new, a.threshold, a.install, a.after_stream = d_desc, d_rows, d_X, int(n_new), int(threshold), int(bool(install)), after_stream
+        match = np.full(max(int(self.mopts.maxkp), 1), -2, dtype=np.int32) if want_match else None
+        X = np.zeros((max(int(n_new), 1), 3)) if want_X else None
+        a.match, a.X = (None if match is None else match.ctypes.data), (None if X is None else X.ctypes.data)
+        self._chk(self.lib.clc_map_align_dev(self.h, C.byref(a)))
+        return _align_result(a, match, X)
 
     def track_build_dev(self, d_X, d_x, d_query, d_map, d_n, stream=None, **job):
         """clc_track_build_dev: the track kernel alone, enqueue only; job keywords as track_localize_dev (d_match, nq, cam, d_kps | d_feat,

@@ -136,6 +136,11 @@ struct clc_ctx {
     // change places with d_map_X when a build succeeds; the pinned count and the mirrors of the host outputs
     clc::DevBuf d_mapb, d_map_X_next;
     clc::PinBuf h_mapb;
+    // the map replaced at the old map's scale (map_update.hip): the NEXT map's descriptor rows, allocated on first use at d_m's size --
+    // the sweep clamps its train reads to the last row (k2nn.hip), so nothing past the rows gathered is read and nothing is zeroed --
+    // which change places with d_m on install; the match and the common lists; the pinned record and the mirrors of the host outputs
+    clc::DevBuf d_m_next, d_align;
+    clc::PinBuf h_align;
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     clc::PinBuf h_stage;          // (bytes)
@@ -204,13 +209,26 @@ int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what);
 // inliers[i] = the list in job i's context's pinned block, in the filter's order, written by the round that completed the run before
 // its word (null: the job's solve did not start); it stands until the context's next solve
 int pair_filter_essential(clc_ctx* const* ctxs, clc_pair_job* jobs, int n_jobs, const int32_t** inliers);
-// rows idx[0 .. n) of a descriptor block (64 B each) -> dst, the index list on the device (gather.hip)
+// rows idx[0 .. n) of a descriptor block (64 B each) -> dst, the index list on the device (null: rows 0 .. n) (gather.hip)
 hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, uint32_t n, hipStream_t stream);
 // The map-to-map sweep of the reference's chain (coloc.hpp:317-323; inter_pose.hip), enqueued on `stream`: rows d_idx[0 .. nf) of
 // d_first_desc -> d_rows (the temporary map's descriptors), then K2NN with Q = the global map's map_n rows, T = d_rows, threshold <= 0:
 // 60 (GPUMatcher.hpp:162): d_match[q] = temporary map point matched by global map point q, or -1
 int map_sweep_enqueue(clc_ctx* ctx, const void* d_first_desc, const int32_t* d_idx, int nf, const void* d_map_desc, int map_n, uint4* d_rows,
                       int32_t* d_match, int threshold, hipStream_t stream);
+
+// A map build's two halves (map_build.hip).  map_stage: tracks, the seed launch, the wait for the row count, the capacity check, the host
+// outputs -- the new map's points in d_map_X_next, its rows of the lower seed camera's block in the map block, the context's map as it
+// was.  map_install: the rows gathered into d_m, the points swapped in (clc_map_build_dev, clc_map_init_batch_dev).
+struct MapStaged { int n = 0, cam_i = 0; const int32_t* d_row = nullptr; };
+int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out);
+int map_install(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged);
+// clc_map_init_batch_dev (align == null: map_install) / clc_map_update_batch_dev (map_align_staged) behind their extern "C" names
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align);
+// map_update.hip: CLC_ERR_STATE unless the context holds a map with points; the align step on a staged map, installing it, with the
+// job's host points and seed poses rescaled
+int map_align_state(clc_ctx* ctx, const char* who);
+int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align);
 
 // Every consumer stream behind what `producer` holds now (pose_batch.hip): ONE event (ev: its owner's, created on first use), no host
 // synchronisation; where an event call fails the host waits for the producer instead, and what that synchronisation reports is returned.

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(kGatherThreads) void pair_build_kernel(const PairJo
 __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, const int32_t* __restrict__ idx, uint4* __restrict__ dst, const uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n * 4u) dst[i] = src[(size_t)idx[i >> 2] * 4u + (i & 3u)];
+    if (i < n * 4u) dst[i] = src[(size_t)(idx ? (uint32_t)idx[i >> 2] : i >> 2) * 4u + (i & 3u)];
 }
 
 template <class Jobs> hipError_t launch(void (*kernel)(const Jobs), Jobs& jobs, const int n_jobs, hipStream_t stream)

@@ -11,6 +11,9 @@
 //   seed_triangulate_kernel  ONE workgroup: tracks with both seed cameras in id order -> get_ud_pixel (ud_pixel.h), the statements of
 //                         map_math.h, the ordered compaction of the accepted points; the count last, behind the system-scope fence
 //   gather_rows_kernel    (gather.hip) the map's descriptor rows, once the host knows how many; the call returns when it has run
+// A build is two halves: map_stage -- everything up to the row count, the capacity check and the host outputs -- and map_install -- the
+// gather into d_m and the swap of the points.  clc_map_update_batch_dev (map_update.hip) follows the same stage half with an install
+// of its own, at the old map's scale.
 // Sizes: 8 cameras x 10 k rows, 28 pairs are 80 k nodes and up to ~260 k edges.  The two single-workgroup kernels walk 80 k nodes /
 // some 10 k tracks in passes of 1 024: latency-bound like the gathers, and what keeps the order a matter of one ballot per wave.
 #include "clc_ctx.h"
@@ -243,8 +246,13 @@ hipError_t launch_tracks(const TrackGraph& g, const EdgePairs& ep, const int n_p
     return hipGetLastError();
 }
 
-int map_build(clc_ctx* ctx, clc_map_job& job)
+} // namespace
+
+// The STAGE half of a map build: tracks, the seed launch, the wait for the row count, the capacity check, the host outputs.  On CLC_OK
+// the new map's points lie in d_map_X_next and its row list in the map block (out.d_row); the context's map is as it was.
+int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out)
 {
+    out = MapStaged{};
     job.n_tracks = 0; job.map_n = 0; job.status = CLC_OK;
     if (!ctx->has_mat) return job.status = fail(ctx, CLC_ERR_STATE, "map_build: context created without matcher options");
     TrackGraph g; EdgePairs ep; int edge_rows = 0;
@@ -307,6 +315,17 @@ int map_build(clc_ctx* ctx, clc_map_job& job)
     if (job.map_row && n) memcpy(job.map_row, h_row, sizeof(int32_t) * n);
     if (job.X && n) memcpy(job.X, h_X, sizeof(double) * 3 * n);
     job.map_n = (int)n;
+    out.n = (int)n; out.cam_i = cam_i; out.d_row = d_row;
+    return CLC_OK;
+}
+
+// The INSTALL half (clc_map_build_dev, clc_map_init_batch_dev): the staged map becomes the context's.
+int map_install(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged)
+{
+    const uint32_t n = (uint32_t)staged.n;
+    const int cam_i = staged.cam_i;
+    const int32_t* d_row = staged.d_row;
+    hipStream_t st = ctx->stream;
     if (n == 0) { ctx->map_n = 0; ctx->map_X_n = -1; return CLC_OK; }
     // install: the points change places with the previous map's (whatever read those was enqueued on this stream before), the
     // descriptor rows are gathered from the lower seed camera's block straight into the matcher's map.  The map is published only
@@ -322,44 +341,27 @@ int map_build(clc_ctx* ctx, clc_map_job& job)
     return CLC_OK;
 }
 
+namespace {
+
+int map_build(clc_ctx* ctx, clc_map_job& job)
+{
+    MapStaged staged;
+    const int rc = map_stage(ctx, job, staged);
+    return rc == CLC_OK ? map_install(ctx, job, staged) : rc;
+}
+
 } // namespace
 
-} // namespace clc
-
-using namespace clc;
-
-extern "C" {
-
-int clc_tracks_build_dev(clc_ctx* ctx, const clc_tracks_job* job, int32_t* d_track_feat, int32_t* d_n_tracks, void* stream)
+// clc_map_init_batch_dev (align == null) and clc_map_update_batch_dev (map_update.hip): the filters, the selection, the seed poses and the
+// stage half are ONE path; what follows the stage half differs -- the install above, or the align step at the old map's scale.
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align)
 {
-    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: null context / job");
-    TrackGraph g; EdgePairs ep; int edge_rows = 0;
-    int rc = tracks_inputs(ctx, *job, g, ep, &edge_rows, "tracks_build");
-    if (rc != CLC_OK) return rc;
-    if (!d_n_tracks || (g.cap_tracks > 0 && !d_track_feat)) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: null output");
-    if (((uintptr_t)d_track_feat | (uintptr_t)d_n_tracks) & 3u) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: misaligned device pointer");
-    CLC_HIP(ctx, hipSetDevice(ctx->device));
-    int32_t* rest = nullptr;
-    rc = ensure_map_block(ctx, (size_t)g.n_nodes, 0, &rest);
-    if (rc != CLC_OK) return rc;
-    graph_words(ctx, g);
-    g.table = d_track_feat; g.h_table = nullptr; g.n_tracks = d_n_tracks;
-    CLC_HIP(ctx, launch_tracks(g, ep, job->n_pairs, edge_rows, pick(ctx, stream)));
-    return CLC_OK;
-}
-
-int clc_map_build_dev(clc_ctx* ctx, clc_map_job* job)
-{
-    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "map_build: null context / job");
-    return map_build(ctx, *job);
-}
-
-int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job)
-{
+    if (align) { align->n_old = 0; align->n_common = 0; align->n_terms = 0; align->status = CLC_MAP_ALIGN_NO_SCALE; align->scale = 1.0; }
     if (n_pairs < 1 || n_pairs > kMaxPairs || !ctxs || !pair_jobs || !job) return CLC_ERR_BAD_ARG;
     const int rc0 = check_batch_contexts(ctxs, n_pairs, "map_init_batch: every pair needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
     clc_ctx* c0 = ctxs[0];
+    if (align) { const int rs = map_align_state(c0, "map_update_batch"); if (rs != CLC_OK) return job->status = rs; }
     job->seed_pair = -1; job->n_tracks = 0; job->map_n = -1; job->status = CLC_OK;
     memset(job->entered, 0, sizeof job->entered);
     if (job->tracks.n_pairs != n_pairs || !job->tracks.pairs) return job->status = fail(c0, CLC_ERR_BAD_ARG, "map_init_batch: tracks.pairs must name the cameras of every pair job");
@@ -410,10 +412,47 @@ int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_
     const clc_tracks_pair* callers = job->tracks.pairs;
     void* const after = job->after_stream;
     job->tracks.pairs = tp.data(); job->seed_pair = seed; job->after_stream = nullptr;
-    const int rc = map_build(c0, *job);
+    MapStaged staged;
+    int rc = map_stage(c0, *job, staged);
+    if (rc == CLC_OK) rc = align ? map_align_staged(c0, *job, staged, *align) : map_install(c0, *job, staged);
     job->tracks.pairs = callers; job->after_stream = after;
     // (the union launch read the other contexts' blocks and pinned lists; it ran before the count the build waited for came out)
     return rc;
+}
+
+} // namespace clc
+
+using namespace clc;
+
+extern "C" {
+
+int clc_tracks_build_dev(clc_ctx* ctx, const clc_tracks_job* job, int32_t* d_track_feat, int32_t* d_n_tracks, void* stream)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: null context / job");
+    TrackGraph g; EdgePairs ep; int edge_rows = 0;
+    int rc = tracks_inputs(ctx, *job, g, ep, &edge_rows, "tracks_build");
+    if (rc != CLC_OK) return rc;
+    if (!d_n_tracks || (g.cap_tracks > 0 && !d_track_feat)) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: null output");
+    if (((uintptr_t)d_track_feat | (uintptr_t)d_n_tracks) & 3u) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: misaligned device pointer");
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    int32_t* rest = nullptr;
+    rc = ensure_map_block(ctx, (size_t)g.n_nodes, 0, &rest);
+    if (rc != CLC_OK) return rc;
+    graph_words(ctx, g);
+    g.table = d_track_feat; g.h_table = nullptr; g.n_tracks = d_n_tracks;
+    CLC_HIP(ctx, launch_tracks(g, ep, job->n_pairs, edge_rows, pick(ctx, stream)));
+    return CLC_OK;
+}
+
+int clc_map_build_dev(clc_ctx* ctx, clc_map_job* job)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "map_build: null context / job");
+    return map_build(ctx, *job);
+}
+
+int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job)
+{
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr);
 }
 
 } // extern "C"

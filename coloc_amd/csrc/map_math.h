@@ -123,6 +123,17 @@ static inline void pose_center(const double* R9, const double* t, double* C)
     for (int q = 0; q < 3; ++q) C[q] = -(R9[q] * t[0] + R9[3 + q] * t[1] + R9[6 + q] * t[2]);
 }
 
+// rescaleMap on a pose (colocUtils.hpp:213-223 multiplies the CENTRE): C = pose_center(R, t), C' = C * s, t' = -R C'.  Rt: [R|t], 3 x 4
+// row-major, t rewritten.  Host helper, as seed_poses below.
+static inline void rescale_pose(double* Rt, const double s)
+{
+    const double R[9] = { Rt[0], Rt[1], Rt[2], Rt[4], Rt[5], Rt[6], Rt[8], Rt[9], Rt[10] }, t[3] = { Rt[3], Rt[7], Rt[11] };
+    double C[3];
+    pose_center(R, t, C);
+    for (int q = 0; q < 3; ++q) C[q] = C[q] * s;
+    for (int r = 0; r < 3; ++r) Rt[4 * r + 3] = -(R[3 * r] * C[0] + R[3 * r + 1] * C[1] + R[3 * r + 2] * C[2]);
+}
+
 // The two seed cameras' [R|t] (3 x 4 row-major each): camera I = the origin pose (R_o, centre C_o), camera J = relativePoseToAbsolute
 // of the origin and Pose3(R_rel, scale * C_rel) (Reconstructor.hpp:215-221, 247-257) -- as odd as it is: R = R_rel R_o, C = C_o + scale
 // C_rel, t = -R C.  Host helper: the device receives the two [R|t].

@@ -1,0 +1,217 @@
+// map_update.hip -- the map replaced on the device at the OLD map's scale (include/coloc_hip.h: clc_map_align_dev,
+// clc_map_update_batch_dev): the tail of ColoC::updateMap (reference include/coloc/coloc.hpp:435-459) between setupMapDatabase and
+// data = updateData -- matchMapFeatures(old map, new map) (GPUMatcher.hpp:157-163), matchMaps (every match kept),
+// computeScaleDifference (colocUtils.hpp:184-211), rescaleMap (:213-223).  Launches, all enqueue-only on the context's stream:
+//   gather_rows_kernel + the K2NN sweep (map_sweep_enqueue, inter_pose.hip): the new map's rows straight into d_m_next, then
+//                        Q = the installed map (d_m), T = d_m_next, threshold 60 -> match[q] = new row of old row q, or -1
+//   map_align_kernel     ONE workgroup: the ordered compaction of wg_compact.h over the old rows -> the common lists cq / ct; the terms
+//                        of the scale rule (scale_term, inter_math.h) in parallel, a chunk of 1 024 at a time in LDS; their sum by ONE
+//                        lane in list order (the host's sum is sequential: the bits depend on it); scale_from_sum; the rescale, all
+//                        threads striding over 3 n_new doubles, into d_map_X_next; the pinned mirrors; the record last
+// The host waits for ONE word, the record's; an install is two swaps (d_m <-> d_m_next, d_map_X <-> d_map_X_next), so the previous
+// map is intact until the last launch has run and stays the context's on every failure.  The chunked one-lane sum is a second copy
+// of inter_scale_kernel's loop (inter_dev.hip), not shared with it: that kernel's code is left as it was.
+#include "clc_ctx.h"
+#include "inter_math.h"
+#include "map_math.h"
+#include "wg_compact.h"
+
+#include <chrono>
+#include <cstring>
+#include <utility>
+
+namespace clc {
+
+namespace {
+
+constexpr int kAlignThreads = 1024;
+constexpr int kSumChunk = 1024;              // terms of the scale rule staged in LDS per pass of the sequential sum: one per thread
+
+struct AlignRec { double scale; int32_t n_common, n_terms, status, ready; };      // pinned: `ready` comes out last
+struct AlignJob {
+    const int32_t* match;                    // n_old entries (null with n_old == 0: no sweep ran)
+    const double* old_X; const double* new_X;      // the installed map's points; the new map's (new_X may BE out_X: the staged map)
+    int32_t n_old, n_new;
+    int32_t* cq; int32_t* ct;                // scratch: the common lists, n_old entries each
+    double* out_X;                           // 3 n_new: the rescaled points
+    double* h_X; int32_t* h_match;           // pinned mirrors (nullable)
+    AlignRec* rec;
+};
+
+__global__ __launch_bounds__(kAlignThreads) void map_align_kernel(const AlignJob a)
+{
+    __shared__ uint32_t s_wave[kAlignThreads / 64];
+    __shared__ double s_term[kSumChunk];
+    __shared__ double s_scale;
+    __shared__ int s_status;
+    __shared__ uint32_t s_good;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n_old = a.n_old > 0 ? (uint32_t)a.n_old : 0u, n_new = a.n_new > 0 ? (uint32_t)a.n_new : 0u;
+    // 1. the common features in ascending old row (commonFeatures of the sweep, GPUMatcher.hpp:217); an index outside the new map: none
+    uint32_t n_com = 0;
+    for (uint32_t q0 = 0; q0 < n_old; q0 += kAlignThreads) {
+        const uint32_t q = q0 + tid;
+        int32_t t = -1;
+        if (q < n_old) {
+            t = a.match[q];
+            if (t < 0 || (uint32_t)t >= n_new) t = -1;
+            if (a.h_match) a.h_match[q] = t;
+        }
+        const bool ok = t >= 0;
+        uint32_t total;
+        const uint32_t c = n_com + ordered_slot<kAlignThreads>(ok, s_wave, &total);
+        if (ok) { a.cq[c] = (int32_t)q; a.ct[c] = t; }       // (c < n_old: the lists hold that many)
+        n_com += total;
+    }
+    __syncthreads();                                     // the lists of this workgroup are read back below (global memory, one workgroup)
+    // 2. colocUtils.hpp:201-204 over consecutive common features: a chunk of terms in parallel into LDS, their SUM by one lane in list
+    //    order.  A term that the rule's guard drops is stored as -1 (scale_term).
+    const uint32_t n_pairs = n_com >= 2u ? n_com - 1u : 0u;
+    double sum = 0.0; uint32_t good = 0;                             // (thread 0's)
+    for (uint32_t k0 = 0; k0 < n_pairs; k0 += kSumChunk) {
+        const uint32_t m = n_pairs - k0 < (uint32_t)kSumChunk ? n_pairs - k0 : (uint32_t)kSumChunk;
+        for (uint32_t k = tid; k < m; k += kAlignThreads) {
+            const uint32_t e = k0 + k;
+            s_term[k] = scale_term(a.old_X + 3 * (size_t)a.cq[e], a.old_X + 3 * (size_t)a.cq[e + 1], a.new_X + 3 * (size_t)a.ct[e], a.new_X + 3 * (size_t)a.ct[e + 1]);
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (uint32_t k = 0; k < m; ++k) { const double v = s_term[k]; if (!(v < 0.0)) { sum += v; ++good; } }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double scale;
+        const int st = scale_from_sum(sum, good, &scale);
+        s_scale = st == CLC_INTER_OK ? scale : 1.0;
+        s_status = st == CLC_INTER_OK ? CLC_MAP_ALIGN_OK : CLC_MAP_ALIGN_NO_SCALE;
+        s_good = good;
+    }
+    __syncthreads();                                     // (also: every term above was read from new_X before out_X, which may be new_X, changes)
+    // 3. rescaleMap: every component one multiply
+    const double scale = s_scale;
+    for (uint32_t i = tid; i < 3u * n_new; i += kAlignThreads) {
+        const double v = a.new_X[i] * scale;
+        a.out_X[i] = v;
+        if (a.h_X) a.h_X[i] = v;
+    }
+    // the record comes out last: every wave's stores are complete and visible system-wide before the word the host polls changes
+    __threadfence_system();
+    __syncthreads();
+    if (tid == 0) {
+        a.rec->scale = scale; a.rec->n_common = (int32_t)n_com; a.rec->n_terms = (int32_t)s_good; a.rec->status = s_status;
+        __hip_atomic_store(&a.rec->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+void align_outputs_none(clc_map_align& job)
+{
+    job.n_old = 0; job.n_common = 0; job.n_terms = 0; job.status = CLC_MAP_ALIGN_NO_SCALE; job.scale = 1.0;
+}
+
+// the step itself.  staged: d_X is the context's own d_map_X_next (the staged map), rescaled in place
+int map_align(clc_ctx* ctx, clc_map_align& job, const bool staged)
+{
+    align_outputs_none(job);
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "map_align: context created without matcher options");
+    if (job.n_new < 0 || (job.n_new > 0 && (!job.d_desc || !job.d_X))) return fail(ctx, CLC_ERR_BAD_ARG, "map_align: negative count / null block");
+    if (((uintptr_t)job.d_desc & 15u) || ((uintptr_t)job.d_rows & 3u) || ((uintptr_t)job.d_X & 7u)) return fail(ctx, CLC_ERR_BAD_ARG, "map_align: misaligned device pointer");
+    int rc = map_align_state(ctx, "map_align");
+    if (rc != CLC_OK) return rc;
+    if ((uint32_t)job.n_new > ctx->mopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "map_align: more map rows than MatcherOptions.maxkp (the previous map stays)");
+    const int n_old = ctx->map_n, n_new = job.n_new;
+    job.n_old = n_old;
+    if (n_new == 0) {
+        // nothing to match, nothing to scale: the empty map, as clc_map_build_dev installs it
+        if (job.match) for (int q = 0; q < n_old; ++q) job.match[q] = -1;
+        if (job.install) { ctx->map_n = 0; ctx->map_X_n = -1; }
+        return CLC_OK;
+    }
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // device [ match | cq | ct ] (n_old entries each); pinned [ record 64 B | X 3 n_new | match n_old ]
+    const size_t ro = ((size_t)n_old + 63) & ~(size_t)63;
+    rc = grow(ctx, ctx->d_m_next, ctx->d_m.bytes, 0, 1, true, "allocating the next map's descriptor rows");
+    if (rc == CLC_OK && !staged) rc = grow(ctx, ctx->d_map_X_next, (3 * (size_t)n_new + 8) * sizeof(double), 1, 4, true, "growing the next map's points");
+    if (rc == CLC_OK) rc = grow(ctx, ctx->d_align, (3 * ro + 64) * sizeof(int32_t), 1, 4, true, "growing the map alignment block");
+    if (rc == CLC_OK) rc = grow(ctx, ctx->h_align, 64 + 3 * (size_t)n_new * sizeof(double) + (ro + 64) * sizeof(int32_t), 1, 4, true, "growing the pinned map alignment block");
+    if (rc != CLC_OK) return rc;
+    AlignJob a{};
+    int32_t* d_match = ctx->d_align.as<int32_t>();
+    a.match = n_old > 0 ? d_match : nullptr;
+    a.cq = d_match + ro; a.ct = a.cq + ro;
+    a.old_X = ctx->d_map_X.as<double>(); a.new_X = job.d_X; a.out_X = ctx->d_map_X_next.as<double>();
+    a.n_old = n_old; a.n_new = n_new;
+    a.rec = ctx->h_align.as<AlignRec>();
+    double* h_X = (double*)(ctx->h_align.as<uint8_t>() + 64);
+    int32_t* h_match = (int32_t*)(h_X + 3 * (size_t)n_new);
+    a.h_X = job.X ? h_X : nullptr; a.h_match = job.match && n_old > 0 ? h_match : nullptr;
+    __atomic_store_n(&a.rec->ready, 0, __ATOMIC_RELAXED);
+    // behind whatever produced the new map: an event on the producer's stream, no host synchronisation
+    hipStream_t prod = (hipStream_t)job.after_stream;
+    if (prod && prod != st) CLC_HIP(ctx, order_behind(ctx->ev_track, prod, &st, 1));
+    // the new rows into the NEXT map's buffer (the installed map's rows are the sweep's queries: they stay where they are)
+    if (n_old > 0) {
+        rc = map_sweep_enqueue(ctx, job.d_desc, job.d_rows, n_new, ctx->d_m.ptr, n_old, ctx->d_m_next.as<uint4>(), d_match, job.threshold, st);
+        if (rc != CLC_OK) { (void)hipStreamSynchronize(st); return rc; }
+    } else if (job.install) {
+        CLC_HIP(ctx, launch_gather_rows((const uint4*)job.d_desc, job.d_rows, ctx->d_m_next.as<uint4>(), (uint32_t)n_new, st));
+    }
+    hipLaunchKernelGGL(map_align_kernel, dim3(1), dim3(kAlignThreads), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(ctx, CLC_ERR_HIP, "map_align: the align launch", e); }
+    // the one word the host needs; the kernel is the last launch, so the gather and the sweep have run when it is out
+    rc = wait_pinned(ctx, &a.rec->ready, 0, st, std::chrono::steady_clock::now(), 5, "map_align: the align launch left no record");
+    if (rc != CLC_OK) return rc;
+    job.scale = a.rec->scale; job.n_common = a.rec->n_common; job.n_terms = a.rec->n_terms; job.status = a.rec->status;
+    if (a.h_match) memcpy(job.match, h_match, sizeof(int32_t) * (size_t)n_old);
+    if (a.h_X) memcpy(job.X, h_X, sizeof(double) * 3 * (size_t)n_new);
+    if (job.install) {
+        std::swap(ctx->d_m, ctx->d_m_next);
+        std::swap(ctx->d_map_X, ctx->d_map_X_next);
+        ctx->map_n = n_new; ctx->map_X_n = n_new;
+    }
+    return CLC_OK;
+}
+
+} // namespace
+
+int map_align_state(clc_ctx* ctx, const char* who)
+{
+    if (ctx->map_n < 0 || ctx->map_X_n < 0 || ctx->map_X_n < ctx->map_n)
+        return fail(ctx, CLC_ERR_STATE, (std::string(who) + ": the context holds no map with points (clc_set_map + clc_set_map_points, or a build)").c_str());
+    return CLC_OK;
+}
+
+int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align)
+{
+    clc_map_align a{};
+    a.d_desc = job.cams[staged.cam_i].d_desc; a.d_rows = staged.d_row; a.d_X = ctx->d_map_X_next.as<double>(); a.n_new = staged.n;
+    a.threshold = align.threshold; a.install = 1; a.after_stream = nullptr;          // (the stage half ran on the context's stream)
+    a.match = align.match; a.X = job.X;
+    const int rc = map_align(ctx, a, true);
+    align.n_old = a.n_old; align.n_common = a.n_common; align.n_terms = a.n_terms; align.status = a.status; align.scale = a.scale;
+    if (rc != CLC_OK) return job.status = rc;
+    rescale_pose(job.Rt_seed_a, a.scale);
+    rescale_pose(job.Rt_seed_b, a.scale);
+    return CLC_OK;
+}
+
+} // namespace clc
+
+using namespace clc;
+
+extern "C" {
+
+int clc_map_align_dev(clc_ctx* ctx, clc_map_align* job)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "map_align: null context / job");
+    return map_align(ctx, *job, false);
+}
+
+int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align)
+{
+    if (!align) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, align);
+}
+
+} // extern "C"

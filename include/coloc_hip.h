@@ -47,7 +47,8 @@ extern "C" {
  * so did the keypoint selection rule (clc_detect_set_selection, clc_detect_selection) and the device-side 2D-3D tracks
  * (clc_set_map_points, clc_track_build_dev, clc_track_localize_dev, clc_track_localize_batch_dev) and two-view correspondences
  * (clc_pair_build_dev, clc_pair_filter_dev, clc_pair_filter_batch_dev), the inter-camera step from device memory (clc_inter_*_dev) and
- * the map built on the device (clc_tracks_build_dev, clc_map_build_dev, clc_map_init_batch_dev).
+ * the map built on the device (clc_tracks_build_dev, clc_map_build_dev, clc_map_init_batch_dev) and replaced at the old map's scale
+ * (clc_map_align_dev, clc_map_update_batch_dev).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -956,7 +957,8 @@ int clc_inter_front_dev(clc_ctx* ctx, const double* d_x1, const double* d_x2, in
  * d_feat: CLC_ERR_BAD_ARG; a context without matcher options: CLC_ERR_STATE; more map rows than MatcherOptions.maxkp:
  * CLC_ERR_CAPACITY, and the previous map stays as it was; no accepted point: CLC_OK, map_n = 0 and no map points.
  *
- * clc_map_init_batch_dev: the composition initMap / updateMap call.  pair_jobs[p] on ctxs[p] (a context of its own each) is the pair
+ * clc_map_init_batch_dev: the composition initMap calls, and the first half of updateMap's (coloc.hpp:394-429; the whole of it, with
+ * the tail that brings the new map to the old map's scale, is clc_map_update_batch_dev in the next section).  pair_jobs[p] on ctxs[p] (a context of its own each) is the pair
  * job->tracks.pairs[p].cam_a < cam_b (the other fields of tracks.pairs are filled in here; tracks.n_pairs == n_pairs): the filters
  * run as clc_pair_filter_batch_dev under 'E'; a pair enters the tracks by the rules of HIPRobustMatcher::computeRelativePoseDev -- at
  * least 2.5 x 5 inliers and a successful chirality vote (RobustMatcher.hpp:176-183; the host vote of clc_inter_pose_batch, fed from
@@ -1009,6 +1011,68 @@ typedef struct clc_map_job {
 int clc_tracks_build_dev(clc_ctx* ctx, const clc_tracks_job* job, int32_t* d_track_feat, int32_t* d_n_tracks, void* stream);
 int clc_map_build_dev(clc_ctx* ctx, clc_map_job* job);
 int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job);
+
+/* ---- the map replaced on the device at the old map's scale: updateMap's tail ---------------------------------------------------------
+ * What ColoC::updateMap (coloc.hpp:435-459) runs after reconstructScene and setupMapDatabase, before data = updateData / setMapData:
+ * matchMapFeatures(old map, new map) under threshold 60 (GPUMatcher.hpp:157-163), matchMaps keeping every match
+ * (HIPRobustMatcher.hpp:627-672), computeScaleDifference over consecutive common features (colocUtils.hpp:184-211) and rescaleMap of
+ * the new scene, landmarks and pose centres (:213-223).  A new map comes with an arbitrary baseline; this tail keeps the cameras'
+ * trajectory at one scale across map updates.  It needs the OLD map's descriptor rows after the new ones exist, so the new rows are
+ * gathered into a second buffer and the two change places.  (Later under ABI 4: new entry points only.)
+ *
+ * clc_map_align_dev: the step on a new map already in device memory -- new row i = row d_rows[i] of d_desc (d_rows NULL: row i),
+ * its landmark d_X[3 i ..].
+ *   COMMON FEATURES: the K2NN matches with Q = the context's installed map (map_n rows = n_old) and T = the new rows, threshold <= 0:
+ *     60, listed in ascending old row as computeMatches emits them; an index outside [0, n_new) is no match.  With n_old == 0 or
+ *     n_new == 0 no sweep is launched and the list is empty.
+ *   SCALE: for list entries k and k + 1 (k = 0 .. n_common - 2) one term, (float)|oldX[q_k+1] - oldX[q_k]| / (float)|newX[t_k+1] -
+ *     newX[t_k]| (scale_term, coloc_amd/csrc/inter_math.h).  A term whose denominator fails the d2 > 1e-9f guard is skipped: K2NN is
+ *     not one-to-one, two consecutive old rows matched to ONE new row are common, and the reference divides by zero there.  The kept
+ *     terms (n_terms of them) are summed by one lane in list order -- the bits depend on the order -- and divided by n_terms
+ *     (scale_from_sum).  Fewer than two common features, no kept term, or a mean that is not positive and finite: scale = 1.0 and
+ *     status = CLC_MAP_ALIGN_NO_SCALE.  (The reference returns 1.0 for the empty list and NaN for a single common feature; this call
+ *     gives 1.0 in both cases.)
+ *   RESCALE: X_new[i] = d_X[i] * scale, each component one multiply, into the context's staging buffer and -- where X was asked for --
+ *     a pinned mirror.  d_X itself is not written.
+ *   INSTALL (install != 0): the gathered rows and the rescaled points become the context's map by changing places with the previous
+ *     map's buffers; map rows = map points = n_new.  ORDERING as clc_map_build_dev: the call returns when its last launch has run, a
+ *     matcher call on any stream may follow at once; work on other streams that still reads the PREVIOUS map (or, still, the one
+ *     before it, whose buffers are the ones rewritten here) is complete, or joined to the context's stream, before the call.
+ *     n_new == 0 installs the empty map as clc_map_build_dev does (no map points), scale 1.0, CLC_MAP_ALIGN_NO_SCALE.
+ *   install == 0: report only, the context's map is left exactly as it was.
+ * The host waits for ONE word, the pinned record { scale, n_common, n_terms, status }, released last behind a system-scope fence; no
+ * descriptor, point or match is copied in either direction: match / X (nullable) come from pinned mirrors the kernel writes.
+ * after_stream: as clc_map_job.  ERRORS: no installed map with points (no clc_set_map / build, no map points, or fewer points than
+ * rows): CLC_ERR_STATE; a context without matcher options: CLC_ERR_STATE; n_new > MatcherOptions.maxkp: CLC_ERR_CAPACITY; a negative
+ * count, a null d_desc / d_X with n_new > 0, d_desc not 16-byte aligned, d_rows / d_X misaligned: CLC_ERR_BAD_ARG.  On every error
+ * the previous map serves exactly as before.
+ *
+ * clc_map_update_batch_dev: the composition updateMap calls.  Everything clc_map_init_batch_dev does up to and including the seed
+ * triangulation, the capacity check and the host outputs; then, instead of the gather into the matcher's map, the align step with
+ * d_desc = the lower seed camera's block, d_rows = the map's row list, d_X = the staged points, install = 1.  Of `align` only
+ * threshold and match are read; its out fields are written.  On return job->X holds the RESCALED landmarks and job->Rt_seed_a /
+ * Rt_seed_b the rescaled poses (rescale_pose, coloc_amd/csrc/map_math.h: C = -R^T t, C' = C * scale, t' = -R C'), align->scale what
+ * was applied.  No pair entered: exactly as clc_map_init_batch_dev -- CLC_OK, seed_pair = -1, map_n = -1, the map untouched -- with
+ * align->status = CLC_MAP_ALIGN_NO_SCALE, scale 1.0.  No previous map with points on ctxs[0]: CLC_ERR_STATE before any filter is
+ * launched. */
+enum { CLC_MAP_ALIGN_OK = 0, CLC_MAP_ALIGN_NO_SCALE = 1 };
+typedef struct clc_map_align {
+    /* in */
+    const void*    d_desc;       /* descriptor block, rows of 64 B, 16-byte aligned */
+    const int32_t* d_rows;       /* nullable: new map row i = row d_rows[i] of d_desc; NULL: row i */
+    const double*  d_X;          /* n_new x 3, NOT written */
+    int            n_new;
+    int            threshold;    /* <= 0: 60 (GPUMatcher.hpp:162) */
+    int            install;      /* 0: report only, the context's map is left exactly as it was */
+    void*          after_stream; /* nullable, as clc_map_job */
+    /* out */
+    int32_t*       match;        /* nullable host, n_old entries: new row matched by old row q, or -1 */
+    double*        X;            /* nullable host, n_new x 3: the rescaled points */
+    int            n_old, n_common, n_terms, status;
+    double         scale;
+} clc_map_align;
+int clc_map_align_dev(clc_ctx* ctx, clc_map_align* job);
+int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
