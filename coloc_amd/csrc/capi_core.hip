@@ -121,6 +121,13 @@ void plan_pyramid(const clc_detector_opts& o, PyramidDesc& pd, size_t& bytes)
         if (i) blk += (pd.lv[i].pitch / 4 * h + 255) / 256;
     }
     for (int i = pd.levels; i <= CLC_MAX_LEVELS; ++i) pd.blk_begin[i] = blk;
+    // behind the row-major levels: every level once more in column strips (clc_internal.h: LevelDesc).  pitch / 16 strips of
+    // 16 x align_up(h, 8) bytes = pitch x align_up(h, 8) bytes per level; the pyramid launch's stores end at row h - 1 of the last strip.
+    for (int i = 0; i < pd.levels; ++i) {
+        pd.lv[i].tiled_offset = off;
+        pd.lv[i].tiled_strip = 16 * align_up(pd.lv[i].h ? pd.lv[i].h : 1, 8);
+        off += align_up(pd.lv[i].pitch / 16 * pd.lv[i].tiled_strip, 256);
+    }
     bytes = off + 256;
 }
 

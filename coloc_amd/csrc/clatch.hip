@@ -15,7 +15,9 @@
 //     (and staggers the waves' phases: a persistent grid runs them in lockstep and measured 14 % slower).
 //   * only window rows/cols 5..60 are ever read by the learned patches, so only those 56x56 samples
 //     are gathered (49 steps of an 8x8 lane tile instead of 64: one gather instruction touches a
-//     ~11x11 pixel footprint of the L2-resident level, about a dozen cache lines).
+//     ~11x11 pixel footprint of the L2-resident level).  The gather source is the level's COLUMN-STRIP copy (16 pixels wide, rows
+//     contiguous inside a strip: a 128-byte line holds 8 rows x 16 pixels), where that footprint is about 4 cache lines; in the
+//     row-major level it was 11-16 (profiles/clatch_two_paths.txt: 65.6 -> 59.0 us per 2 x 10k launch).
 //   * the window lives in LDS four times, shifted by 0..3 bytes, so that EVERY patch row (8 pixels
 //     at an arbitrary byte offset) is a dword-aligned 8-byte LDS read (ds_read2_b32) from the copy
 //     selected by (offset & 3).
@@ -148,7 +150,10 @@ __global__ __launch_bounds__(64) void clatch_kernel(const ClatchArgs args, const
     const uint8_t* __restrict__ arena = arena_base + (size_t)cam * args.slot_stride;
     const int lv = min(scale, args.pd.levels - 1);
     const LevelDesc L = args.pd.lv[lv];
-    const uint8_t* __restrict__ img = arena + L.offset;
+    // the gather source is the level's column-strip copy (clc_internal.h: LevelDesc): pixel (x, y) at
+    // (x >> 4) * strip + y * 16 + (x & 15) = y * 16 + x + (x >> 4) * (strip - 16)
+    const uint8_t* __restrict__ img = arena + L.tiled_offset;
+    const uint32_t strip16 = L.tiled_strip - 16u;
     // (sin, cos) in fp64 per wave costs a few % of this kernel in isolation; preparing it in another launch and loading it here
     // measured no better in round 2: the load sits at the head of the same dependency chain.
     float s, c;
@@ -183,7 +188,11 @@ __global__ __launch_bounds__(64) void clatch_kernel(const ClatchArgs args, const
             const float fx = f.x, fy = f.y;
             const int sx = clamp_i32((int)fx, wmax);
             const int sy = clamp_i32((int)fy, hmax);
-            const uint32_t off = __umul24((uint32_t)sy, L.pitch) + (uint32_t)sx;
+            // three instructions (v_lshrrev, v_lshl_add, v_mad_u32_u24) where the row-major offset took one v_mad_u32_u24; spelled out
+            // because the compiler re-associates the sum into four (shift, multiply, shift, three-way add)
+            uint32_t row16, off;
+            asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(row16) : "v"(sy), "v"(sx));
+            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(off) : "v"((uint32_t)sx >> 4), "s"(strip16), "v"(row16));
             roi[(kTile0 - kRow0 + by * 8 + dy) * kStride + (kTile0 - kCol0 + bx * 8 + dx)] = img[off];
         }
     }

@@ -20,7 +20,15 @@ struct LevelDesc {
     uint32_t w, h;        // level size
     uint32_t pitch;       // bytes per row (multiple of 64)
     uint32_t offset;      // byte offset of the level inside the pyramid arena
+    // The same bytes a second time in 16-pixel-wide column strips (CLATCH's gather source; every other reader keeps the row-major
+    // level): pixel (x, y) lies at tiled_offset + (x >> 4) * tiled_strip + y * 16 + (x & 15), so a 128-byte line holds 8 rows x 16 pixels.
+    uint32_t tiled_offset;
+    uint32_t tiled_strip; // bytes per strip: 16 x (h padded to a multiple of 8); pitch / 16 strips
 };
+__host__ __device__ inline uint32_t tiled_pos(const LevelDesc& L, uint32_t x, uint32_t y)
+{
+    return L.tiled_offset + (x >> 4) * L.tiled_strip + y * 16u + (x & 15u);
+}
 struct PyramidDesc {
     LevelDesc lv[CLC_MAX_LEVELS];
     float     f[CLC_MAX_LEVELS];      // resampling factor of level i (f_0 = 1)

@@ -11,7 +11,8 @@
 // MI355X shape: the reference issues 7 launches on 7 streams (GPUDetector.hpp:250-255); here ALL
 // levels AND the level-0 copy into the pyramid arena are one launch -- for the frames of up to CLC_MAX_BATCH cameras at once (blockIdx.y = camera).  Each lane produces 4 horizontally adjacent output pixels and stores one
 // dword, so a wave writes 256 contiguous bytes; the source taps are plain byte loads from the
-// L2-resident level-0 image (640x480 = 300 KB).  HBM-trivial: writes 2.09 x W x H bytes.
+// L2-resident level-0 image (640x480 = 300 KB).  Every dword is stored twice: at its row-major place and in the level's column-strip
+// copy, which CLATCH gathers from (clc_internal.h: LevelDesc).  HBM-trivial: writes 2 x 2.09 x W x H bytes.
 #include "clc_internal.h"
 
 namespace clc {
@@ -19,7 +20,8 @@ namespace clc {
 struct LerpArgs {
     PyramidDesc pd;
     uint32_t src_pitch;      // bytes per row of the caller's level-0 image
-    uint32_t copy_blocks;    // leading workgroups that copy level 0 into the arena (0 = already there)
+    uint32_t copy_blocks;    // leading workgroups that copy level 0 into the arena, row-major and in strips
+    uint32_t in_place;       // level 0 is already in the arena (src = its row-major level): they write the strips only
     uint32_t slot_stride;    // bytes between the pyramids of consecutive images (blockIdx.y = image)
     const uint8_t* src[kMaxBatch];   // level-0 image of each camera
 };
@@ -52,7 +54,8 @@ __global__ __launch_bounds__(256) void pyramid_kernel(const LerpArgs a, uint8_t*
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (x0 + k < L0.w) packed |= (uint32_t)row[x0 + k] << (8 * k);
-        *reinterpret_cast<uint32_t*>(arena + L0.offset + (size_t)y * L0.pitch + x0) = packed;
+        if (!a.in_place) *reinterpret_cast<uint32_t*>(arena + L0.offset + (size_t)y * L0.pitch + x0) = packed;
+        *reinterpret_cast<uint32_t*>(arena + tiled_pos(L0, x0, y)) = packed;       // x0 is a multiple of 4: the dword stays inside its strip row
         return;
     }
     __shared__ float unorm[256];
@@ -99,6 +102,7 @@ __global__ __launch_bounds__(256) void pyramid_kernel(const LerpArgs a, uint8_t*
         packed |= v << (8 * k);
     }
     *reinterpret_cast<uint32_t*>(arena + L.offset + (size_t)y * L.pitch + x0) = packed;
+    *reinterpret_cast<uint32_t*>(arena + tiled_pos(L, x0, y)) = packed;
 }
 
 hipError_t launch_pyramid_batch(const PyramidDesc& pd, uint8_t* arena, size_t slot_stride, const uint8_t* const* d_src,
@@ -108,10 +112,11 @@ hipError_t launch_pyramid_batch(const PyramidDesc& pd, uint8_t* arena, size_t sl
     if (n_img > kMaxBatch || slot_stride > 0xFFFFFFFFull) return hipErrorInvalidValue;
     LerpArgs a;
     a.pd = pd;
-    // d_src == level 0 inside the arena (single image only): nothing to copy
+    // d_src == level 0 inside the arena (single image only): the row-major level is there, its strips are still to be written
     const bool in_place = n_img == 1 && d_src[0] == arena + pd.lv[0].offset;
     a.src_pitch = in_place ? pd.lv[0].pitch : src_pitch;
-    a.copy_blocks = in_place ? 0u : (pd.lv[0].pitch / 4 * pd.lv[0].h + 255) / 256;
+    a.in_place = in_place ? 1u : 0u;
+    a.copy_blocks = (pd.lv[0].pitch / 4 * pd.lv[0].h + 255) / 256;
     a.slot_stride = (uint32_t)slot_stride;
     for (int b = 0; b < kMaxBatch; ++b) a.src[b] = b < n_img ? d_src[b] : nullptr;
     const uint32_t nblk = a.copy_blocks + (pd.levels > 1 ? pd.blk_begin[pd.levels] : 0u);

@@ -2,11 +2,17 @@
 // C port and extension of tools/opt_latch_layout.py (which stays the generator of the geometry constants).
 //
 //   gcc -O2 -o tools/bin/latch_anneal tools/latch_anneal.c -lm
-//   tools/bin/latch_anneal <mode> <rot> <swap> <iterations> <seed> [out.inc]
+//   tools/bin/latch_anneal <mode> <rot> <swap> <iterations> <seed> [out.inc [b64 [copy shift mask [plan [keep plan [T0]]]]]]
 //     mode 0: any triplet in any slot (the kernel restores the descriptor bit order with ds_bpermute)
 //     mode 1: lane l evaluates the eight triplets of ONE descriptor byte (its eight sign bits ARE that byte: no un-permute)
 //     rot  1: a triplet may read its patch rows in the order 4..7, 0..3 (two base addresses per patch, same immediates)
 //     swap 1: a triplet may exchange the roles of its a and c patches (S changes sign: the bit is then S > 0)
+//     b64  1: a (round, kind) group whose 64 patch rows are all 8-byte aligned is costed as ONE access over 64 banks (ds_read_b64),
+//             every other group as two dword accesses over 32 banks
+//     plan:   the file tools/latch_plan_b64.py writes (copy shifts, the groups to keep aligned, a feasible assignment); keep plan 1 (default)
+//             holds every planned group aligned throughout -- first the most aligned groups, then the fewest conflicts --, 0 starts from
+//             the plan and minimises the modelled LDS cycles alone.  Measured on MI355X (profiles/clatch_two_paths.txt): the twelve-group
+//             table makes the kernel SLOWER (conflict cycles x 2.1), so the shipped table is still the all-dword one of degree sum 71.
 //
 // Model (same as the Python tool): a wave's two 32-lane halves are banked independently, 32 banks x 4 B; every row step adds
 // the same constant to all lanes' banks, so the conflict degree of a half-wave read is the largest multiplicity among the 32
@@ -87,6 +93,23 @@ static int group_cost(int r, int h, int* deg)
     return c;
 }
 
+static int total_deg_plain(void)   /* sum over half-wave, kind, row phase of the largest bank multiplicity (x2: two row phases), whatever the read form */
+{
+    int t = 0;
+    for (int r = 0; r < 8; ++r) for (int h = 0; h < 2; ++h) for (int k = 0; k < 3; ++k) {
+        const int al = use_b64 && round_aligned(r, k);
+        for (int ph = 0; ph < 2; ++ph) {
+            int cnt[32]; memset(cnt, 0, sizeof cnt);
+            for (int l = 32 * h; l < 32 * h + 32; ++l) {
+                const int n = slot_t[r][l]; const int kk = (swp[n] && k != 1) ? 2 - k : k;
+                cnt[((al ? pair64[n][kk] : bank[n][kk]) + (rot[n] ? (ph ? 8 : 24) : 0)) & 31]++;
+            }
+            int mx = 0; for (int b = 0; b < 32; ++b) if (cnt[b] > mx) mx = cnt[b];
+            t += mx;
+        }
+    }
+    return t;
+}
 double g_T0 = 60.0;
 static int gcost[8][2];
 static long total_cost(void) { long t = 0; for (int r = 0; r < 8; ++r) for (int h = 0; h < 2; ++h) t += gcost[r][h]; return t; }
@@ -197,14 +220,18 @@ int main(int argc, char** argv)
     const int d2 = total_deg2();
     int nrot = 0, nswp = 0; for (int i = 0; i < 512; ++i) { nrot += rot[i]; nswp += swp[i]; }
     int nb64 = 0; if (use_b64) for (int r = 0; r < 8; ++r) for (int k = 0; k < 3; ++k) nb64 += round_aligned(r, k);
+    printf("plain degree sum %.1f\n", total_deg_plain() / 2.0);
     printf("mode %d rot %d swap %d b64 %d shift %d%d%d%d: %s %.1f (today's layout: 162 half-steps = degree sum 81; bound 48), %d rotated, %d swapped, %d of 24 (round, kind) reads as ds_read_b64\n",
            mode, use_rot, use_swap, use_b64, copy_shift4[0], copy_shift4[1], copy_shift4[2], copy_shift4[3], use_b64 ? "LDS half-steps / 2" : "degree sum", d2 / (use_b64 ? 4.0 : 2.0), nrot, nswp, nb64);
     if (argc > 6) {
         FILE* o = fopen(argv[6], "w");
         if (!o) { perror(argv[6]); return 1; }
-        fprintf(o, "// GENERATED by tools/latch_anneal.c (mode %d rot %d swap %d, %ld iterations, seed %s): degree sum %.1f, lower bound 48.\n",
-                mode, use_rot, use_swap, iters, argv[5], d2 / 2.0);
-        fprintf(o, "// slot = round*64 + lane evaluates learned triplet (v & 511); bit 9: rows in the order 4..7,0..3; bit 10: a and c exchanged.\n");
+        fprintf(o, "// GENERATED by tools/latch_anneal.c; command line:");
+        for (int i = 0; i < argc; ++i) fprintf(o, " %s", i == 6 ? "<this file>" : argv[i]);
+        fprintf(o, "\n// (mode %d rot %d swap %d, %ld iterations, seed %s)  sum of half-wave conflict degrees %.1f (lower bound 48)", mode, use_rot, use_swap, iters, argv[5], total_deg_plain() / 2.0);
+        if (use_b64) fprintf(o, "; %d of 24 (round, kind) groups 8-byte aligned; modelled LDS cycles of the 48 half-wave group reads %.1f (two per\n// dword-pair access, one per aligned 8-byte access over 64 banks)", nb64, d2 / 2.0);
+        fprintf(o, ".\n");
+        fprintf(o, "// slot = round*64 + lane evaluates learned triplet (v & 511); bit 9: rows in the order 4..7,0..3; bit 10: the slot reads the triplet's a and c\n// patches in exchanged roles (it then computes -S, and its descriptor bit is S' > 0 instead of S < 0).  Geometry constants: latch_layout.inc;\n// LATCH_COPY_SHIFT4[k] = 1: shifted copy k starts 4 bytes behind LATCH_COPY_BASES[k], which turns its 8-byte aligned patch rows into the other half.\n// LATCH_ROUND_B64[r] = {a, b, c}: all 64 lanes of round r read that patch kind from 8-byte aligned rows (tests/test_latch_layout_table.py recomputes it).\n");
         fprintf(o, "#define LATCH_COPY_SHIFT4 { %d, %d, %d, %d }\n", copy_shift4[0], copy_shift4[1], copy_shift4[2], copy_shift4[3]);
         fprintf(o, "#define LATCH_ROUND_B64 { \\\n");
         for (int r = 0; r < 8; ++r) fprintf(o, "    { %d, %d, %d }, \\\n", use_b64 ? round_aligned(r, 0) : 0, use_b64 ? round_aligned(r, 1) : 0, use_b64 ? round_aligned(r, 2) : 0);
