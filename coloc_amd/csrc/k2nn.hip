@@ -17,8 +17,8 @@
 //     the A (train) operand carries the E8M0 block scale 2^12 and C = 2^23 + 2^21 + (train index inside the split,
 //     < 8192), so the accumulator is 2^23 + (d << 13) + index: an integer below 2^24, exact in fp32 in any order, whose
 //     FLOAT BITS 0x4B000000 + (d << 13) + index are already the (distance, index) key, ordered like the floats.
-//   Top-2 per query = two v_med3_f32 on the raw accumulator registers (lane = query column, the 16 accumulator
-//   registers = 16 train rows); no key-forming instruction.  Descriptors stay in their 64-byte bit form in memory:
+//   Top-2 per query = three-input min / med instructions on the raw accumulator registers (lane = query column, the 16
+//   accumulator registers = 16 train rows; the network of k2nn_top2.h, 21 per chain); no key-forming instruction.  Descriptors stay in their 64-byte bit form in memory:
 //   a wave expands its 64 queries into B operands once (registers), the workgroup expands each 32-train tile into
 //   LDS (coalesced 8-byte loads, 7 VALU ops per 16 bytes of FP4) for its four waves.
 //
@@ -45,6 +45,7 @@
 //     writes the int32 results and re-arms rows and counter -- no second launch, no spinning.
 //     Train sets beyond 2^22 vectors fall back to per-split slabs + an ordered merge kernel.
 #include "clc_internal.h"
+#include "k2nn_top2.h"
 #include <algorithm>
 
 namespace clc {
@@ -331,10 +332,9 @@ __device__ __forceinline__ u32x4 mx_expand_not(const uint32_t x)
     y.w = (~x & 0x88888888u) | 0x22222222u;
     return y;
 }
-// Keys are positive finite floats, "none" is +inf: float order == unsigned order of the bits.  v_med3_f32 through the
-// builtin, NOT inline asm: the compiler pads the MFMA-result -> VALU-read hazard only for instructions it can see
-// (an asm v_med3_u32 placed straight after the last MFMA of a tile read the PREVIOUS tile's accumulator register).
-__device__ __forceinline__ float mx_med3(const float a, const float b, const float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
+// Keys are positive finite floats, "none" is +inf: float order == unsigned order of the bits, and the top-2 network (k2nn_top2.h) runs on
+// the bits.  Plain C++ min / max nests there, NOT inline asm: the compiler pads the MFMA-result -> VALU-read hazard only for instructions
+// it can see (an asm v_med3_u32 placed straight after the last MFMA of a tile read the PREVIOUS tile's accumulator register).
 
 // accumulator bits -> the canonical key (distance << 22) | (t0 + index in split); kEmpty for "none" and for the
 // penalised padding rows of a partial last tile (their distance field is above 512)
@@ -453,9 +453,9 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
     float cinit[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) cinit[i] = 8388608.0f + 2097152.0f + (float)(8 * (i >> 2) + 4 * (int)(lane >> 5) + (i & 3));
-    float best[QT], second[QT];
+    uint32_t best[QT], second[QT];   // the running pairs, as key bits (k2nn_top2.h)
 #pragma unroll
-    for (int qt = 0; qt < QT; ++qt) { best[qt] = __uint_as_float(kMxInf); second[qt] = __uint_as_float(kMxInf); }
+    for (int qt = 0; qt < QT; ++qt) { best[qt] = kMxInf; second[qt] = kMxInf; }
 
     // this workgroup's train rows [s0, s1): t_per_split is a multiple of 32, so only the train set's last tile can be partial
     uint32_t s0 = min(split * job.t_per_split, job_nt);
@@ -521,6 +521,7 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
 #endif
         constexpr int kAhead = CLC_K2NN_AHEAD;
         u32x4 ring[kAhead];
+        clc::Top2Wait wait;
 #pragma unroll
         for (int k = 0; k < kAhead; ++k) ring[k] = s_a[buf][k * kStride + lane];
 #pragma unroll
@@ -539,27 +540,25 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
                 for (int i = 0; i < 16; ++i) ci[i] = cinit[i];
             } else ci = acc;
             acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, ci, 4, 4, 0, scale_a, 0, scale_b);
-            // two of the sixteen keys of the chain before, in this MFMA's shadow (32 cycles of matrix pipe, 8 of them holding the
-            // vector issue: four v_med3 fit)
+            // step j of the fold of the chain before (k2nn_top2.h: 21 three-input instructions for its sixteen keys, three or fewer per
+            // step), in this MFMA's shadow (32 cycles of matrix pipe, 8 of them holding the vector issue: four such instructions fit)
+            uint32_t pk[16];
 #pragma unroll
-            for (int i = 2 * j; i < 2 * j + 2; ++i) {
-                second[pq] = mx_med3(best[pq], second[pq], prev[i]);
-                best[pq] = mx_med3(best[pq], prev[i], 0.0f);
-            }
+            for (int i = 0; i < 16; ++i) pk[i] = __float_as_uint(prev[i]);
+            clc::top2_fold16_step(j, best[pq], second[pq], wait, pk);
             // the step back of the chain just folded in: instead of advancing the index part of the sixteen C registers per tile, the
             // running pair steps BACK by one tile -- its index field is then relative to the tile about to be processed (negative for
             // the tiles behind; the integer stays exact in fp32, order and tie rule unchanged: a lower global index is a lower value)
-            if (j == 7) { best[pq] -= 32.0f; second[pq] -= 32.0f; }
+            if (j == 7) { best[pq] = clc::top2_step_back(best[pq]); second[pq] = clc::top2_step_back(second[pq]); }
             __builtin_amdgcn_sched_barrier(0);                           // keep the groups in this order
         }
     }
     {                  // the last tile's second chain is still to be folded in
+        uint32_t pk[16];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            second[1] = mx_med3(best[1], second[1], acc1[i]);
-            best[1] = mx_med3(best[1], acc1[i], 0.0f);
-        }
-        best[1] -= 32.0f; second[1] -= 32.0f;
+        for (int i = 0; i < 16; ++i) pk[i] = __float_as_uint(acc1[i]);
+        clc::top2_fold16(best[1], second[1], pk);
+        best[1] = clc::top2_step_back(best[1]); second[1] = clc::top2_step_back(second[1]);
     }
 
     if (STAMP) {
@@ -574,7 +573,7 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
     // that thread i finishes query i of the block with coalesced rows
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-        const uint32_t mb = __float_as_uint(best[qt]), ms = __float_as_uint(second[qt]);
+        const uint32_t mb = best[qt], ms = second[qt];
         const uint32_t ob = __shfl_xor(mb, 32), os = __shfl_xor(ms, 32);
         if (lane < 32u) {
             const uint32_t slot = (wave * QT + qt) * 32u + lane;
