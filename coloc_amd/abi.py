@@ -113,6 +113,17 @@ class MapAlign(C.Structure):
 
 MAP_ALIGN_OK, MAP_ALIGN_NO_SCALE = 0, 1
 
+
+class MapGrow(C.Structure):
+    """clc_map_grow (include/coloc_hip.h)"""
+    _fields_ = [("max_iteration", C.c_int), ("seed", C.c_uint64), ("precision", C.c_double), ("resected", C.c_int * MAX_BATCH),
+                ("status", C.c_int * MAX_BATCH), ("n_corr", C.c_int * MAX_BATCH), ("n_inliers", C.c_int * MAX_BATCH),
+                ("error_max", C.c_double * MAX_BATCH), ("Rt", (C.c_double * 12) * MAX_BATCH), ("n_seed_rows", C.c_int), ("n_added", C.c_int),
+                ("map_cam", C.c_void_p), ("map_obs", C.c_void_p)]
+
+
+GROW_OK, GROW_NO_TRACKS, GROW_NO_POSE, GROW_CAPACITY = 0, 1, 2, 3
+
 ABI_VERSION = 4          # CLC_ABI_VERSION of include/coloc_hip.h
 DESC_CACHE_OFF, DESC_CACHE_VERIFY, DESC_CACHE_TRUST = 0, 1, 2
 
@@ -165,6 +176,7 @@ EXPORTS = [
     "clc_inter_pose_dev", "clc_inter_pose_batch_dev", "clc_inter_front_dev",
     "clc_tracks_build_dev", "clc_map_build_dev", "clc_map_init_batch_dev",
     "clc_map_align_dev", "clc_map_update_batch_dev",
+    "clc_map_build_grow_dev", "clc_map_init_grow_batch_dev", "clc_map_update_grow_batch_dev", "clc_map_resect_build_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -325,6 +337,10 @@ def load_library():
     lib.clc_map_init_batch_dev.argtypes = [vp, vp, ci, vp]
     lib.clc_map_align_dev.argtypes = [vp, vp]
     lib.clc_map_update_batch_dev.argtypes = [vp, vp, ci, vp, vp]
+    lib.clc_map_build_grow_dev.argtypes = [vp, vp, vp]
+    lib.clc_map_init_grow_batch_dev.argtypes = [vp, vp, ci, vp, vp]
+    lib.clc_map_update_grow_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp]
+    lib.clc_map_resect_build_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -831,6 +847,72 @@ def map_update_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye
     return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
 
 
+def _grow_fill(g, keep, rows, max_iteration=256, seed=0, precision=float("inf")):
+    """fills a MapGrow; -> (map_cam, map_obs) host arrays with room as _map_fill's map_track"""
+    g.max_iteration, g.seed, g.precision = int(max_iteration), int(seed), float(precision)
+    cap = max(sum(int(r) for r in rows) // 2, 1)
+    mc, mo = np.full(cap, -1, dtype=np.int32), np.zeros(cap, dtype=np.uint8)
+    keep.append((mc, mo))
+    g.map_cam, g.map_obs = mc.ctypes.data, mo.ctypes.data
+    return mc, mo
+
+
+def _grow_result(g, n_cams, map_n, mc, mo):
+    n = max(map_n, 0)
+    return dict(resected=[bool(v) for v in g.resected[:n_cams]], status=list(g.status[:n_cams]), n_corr=list(g.n_corr[:n_cams]),
+                n_inliers=list(g.n_inliers[:n_cams]), error_max=[float(v) for v in g.error_max[:n_cams]],
+                Rt=[np.array(g.Rt[c]).reshape(3, 4) for c in range(n_cams)], n_seed_rows=g.n_seed_rows, n_added=g.n_added,
+                map_cam=mc[:n].copy(), map_obs=mo[:n].copy())
+
+
+def map_init_grow_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, max_iteration=256, seed=0,
+                            precision=float("inf")):
+    """clc_map_init_grow_batch_dev: map_init_batch_dev's arguments + the resections' max_iteration / seed / precision; the map grown past
+    the seed pair is installed on ctxs[0].  Returns (map result dict with a "grow" dict: resected, status, n_corr, n_inliers, error_max,
+    Rt per camera, n_seed_rows, n_added, map_cam, map_obs; [pair filter result dicts])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j, g = MapJob(), MapGrow()
+    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_init_grow_batch_dev(hs, arr, n, C.byref(j), C.byref(g))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_init_grow_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    res = _map_result(j, *out)
+    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
+def map_update_grow_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, threshold=0,
+                              max_iteration=256, seed=0, precision=float("inf")):
+    """clc_map_update_grow_batch_dev: map_update_batch_dev on the grown map.  Returns (map result dict -- X, Rt_seed_* and grow["Rt"]
+    RESCALED -- with "align" and "grow" dicts; [pair filter result dicts])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j, g, al = MapJob(), MapGrow(), MapAlign()
+    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
+    match = np.full(max(int(ctxs[0].mopts.maxkp), 1), -2, dtype=np.int32)
+    al.threshold, al.match = int(threshold), match.ctypes.data
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_update_grow_batch_dev(hs, arr, n, C.byref(j), C.byref(al), C.byref(g))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_update_grow_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    res = _map_result(j, *out)
+    res["align"] = _align_result(al, match, None)
+    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
 def desc_handle_live(handle):
     """1 while the publication the handle came from still stands (same host address, count and generation)."""
     return bool(load_library().clc_desc_handle_live(C.byref(handle)))
@@ -1182,6 +1264,30 @@ class Context:
         out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
         self._chk(self.lib.clc_map_build_dev(self.h, C.byref(j)))
         return _map_result(j, *out)
+
+    def map_build_grow_dev(self, rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream=None, max_iteration=256, seed=0,
+                           precision=float("inf")):
+        """clc_map_build_grow_dev: map_build_dev, then every other camera resected against the map (the a-contrario solve of
+        pnp_acransac with seed + k for the k-th of them) and its tracks added; the grown map is installed.  Every camera needs d_desc.
+        Returns map_build_dev's dict for the GROWN map with a "grow" dict: resected, status, n_corr, n_inliers, error_max, Rt per
+        camera, n_seed_rows, n_added, map_cam, map_obs."""
+        j, g = MapJob(), MapGrow()
+        keep = []
+        out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
+        gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
+        self._chk(self.lib.clc_map_build_grow_dev(self.h, C.byref(j), C.byref(g)))
+        res = _map_result(j, *out)
+        res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+        return res
+
+    def map_resect_build_dev(self, rows, cams, camera, d_X, d_x, d_track, d_row, d_n, stream=None):
+        """clc_map_resect_build_dev: the resection list of `camera` on the per-track state of this context's last grown build, enqueue
+        only; rows / cams as map_build_dev (the camera's row capacity and 2-D side are read); outputs are device pointers with room
+        for rows[camera] entries (d_track / d_row nullable), d_n one int32"""
+        j = MapJob()
+        keep = []
+        _map_fill(j, keep, rows, [], cams, outputs=False)
+        self._chk(self.lib.clc_map_resect_build_dev(self.h, C.byref(j), int(camera), d_X, d_x, d_track, d_row, d_n, stream))
 
     def map_align_dev(self, d_desc, d_X, n_new, d_rows=None, threshold=0, install=True, after_stream=None, want_match=True, want_X=True):
         """clc_map_align_dev: a new map in device memory (row i = row d_rows[i] of d_desc, landmark d_X[i]) brought to the scale of the

@@ -141,6 +141,13 @@ struct clc_ctx {
     // which change places with d_m on install; the match and the common lists; the pinned record and the mirrors of the host outputs
     clc::DevBuf d_m_next, d_align;
     clc::PinBuf h_align;
+    // the map grown past the seed pair (map_grow.hip): device [ X per track | obs per track | the grown map's camera list ], pinned
+    // [ row count 64 B | camera list | masks ]; the per-track state of the last grown build, for clc_map_resect_build_dev -- the table
+    // lies in d_mapb, so whatever rewrites that block (a tracks / map build) ends it (grow_table = null)
+    clc::DevBuf d_growb;
+    clc::PinBuf h_growb;
+    const int32_t* grow_table = nullptr; const int32_t* grow_n_tracks = nullptr;
+    int grow_n_cams = 0, grow_cap = 0;
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     clc::PinBuf h_stage;          // (bytes)
@@ -216,19 +223,63 @@ hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst
 // 60 (GPUMatcher.hpp:162): d_match[q] = temporary map point matched by global map point q, or -1
 int map_sweep_enqueue(clc_ctx* ctx, const void* d_first_desc, const int32_t* d_idx, int nf, const void* d_map_desc, int map_n, uint4* d_rows,
                       int32_t* d_match, int threshold, hipStream_t stream);
+// its sweep alone, over nf rows already in d_rows
+int map_sweep_rows_enqueue(clc_ctx* ctx, int nf, const void* d_map_desc, int map_n, const uint4* d_rows, int32_t* d_match, int threshold,
+                           hipStream_t stream);
 
 // A map build's two halves (map_build.hip).  map_stage: tracks, the seed launch, the wait for the row count, the capacity check, the host
 // outputs -- the new map's points in d_map_X_next, its rows of the lower seed camera's block in the map block, the context's map as it
 // was.  map_install: the rows gathered into d_m, the points swapped in (clc_map_build_dev, clc_map_init_batch_dev).
-struct MapStaged { int n = 0, cam_i = 0; const int32_t* d_row = nullptr; };
+// d_cam: the per-row camera list of a GROWN stage (row i's descriptor = row d_row[i] of camera d_cam[i]'s block); null: every row from
+// cam_i's block
+struct MapStaged { int n = 0, cam_i = 0, cam_j = 0; const int32_t* d_row = nullptr; const int32_t* d_cam = nullptr; };
 int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out);
 int map_install(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged);
+
+// ---- the grow step (map_grow.hip; the host side in map_build.hip) --------------------------------------------------------------------
+// The per-track state every grow launch works on: the track table, the landmark X[t] and the observation mask obs[t] (0: no landmark).
+struct GrowState {
+    const int32_t* table; const int32_t* n_tracks;      // cap x n_cams, the count in device memory
+    int32_t n_cams, cap;
+    double* X; uint32_t* obs;                           // cap tracks each
+};
+// the cameras' 2-D sides (count unused) and what the grow launch needs of every camera: [R|t], P = K [R|t], valid or not
+struct GrowCams {
+    GatherSide side[kMaxBatch];
+    float scale[CLC_MAX_LEVELS];
+    double Rt[kMaxBatch][12], P[kMaxBatch][12];
+    uint32_t valid;
+};
+// the staged seed map (map_stage) into the per-track state: obs cleared, then { cam_a, cam_b } and X of the n seed rows
+hipError_t launch_grow_scatter(const GrowState& s, const int32_t* map_track, const double* map_X, int n_rows, uint32_t seed_bits, hipStream_t stream);
+// camera's resection list in ascending track id: X (3 N) | x (2 N) | track ids | rows, cap of each written; the count -- ALL of them, also
+// past cap -- last, into d_n (nullable) and the pinned word h_n (nullable).  h_track / h_row: pinned mirrors, nullable.
+struct ResectOut { double* X; double* x; int32_t* track; int32_t* row; int32_t* h_track; int32_t* h_row; int32_t* d_n; uint32_t* h_n; int32_t cap; };
+hipError_t launch_resect_gather(const GrowState& s, const GatherSide& side, int camera, const ResectOut& out, hipStream_t stream);
+// the grow of camera `camera` (valid in cams.valid): one thread per track
+hipError_t launch_grow(const GrowState& s, const GrowCams& cams, int camera, int n_tracks, hipStream_t stream);
+// the map of the tracks with a landmark, in ascending track id; the row count last into the pinned word h_n
+struct GrowMapOut {
+    double* X; int32_t* track; int32_t* cam; int32_t* row;            // device, cap rows
+    double* h_X; int32_t* h_track; int32_t* h_cam; int32_t* h_row; uint8_t* h_obs;      // pinned mirrors, nullable
+    uint32_t* h_n;
+};
+hipError_t launch_grow_compact(const GrowState& s, const GrowMapOut& out, hipStream_t stream);
+// dst row i = row d_idx[i] of block src[d_cam[i]] (64 B rows; gather.hip); a camera outside [0, kMaxBatch) or without a block: zeros
+struct RowSources { const uint4* src[kMaxBatch]; };
+hipError_t launch_gather_rows_multi(const RowSources& srcs, const int32_t* d_cam, const int32_t* d_idx, uint4* dst, uint32_t n, hipStream_t stream);
+// The a-contrario resection of the N correspondences in ctx->trk (kTrackLayout: X | x), through acr_drive like every solve
+// (pose_batch.hip): clc_pnp_acransac's result on the same correspondences, bit for bit.  Rt: 12 doubles, zeros without a model.
+int resect_solve(clc_ctx* ctx, int N, const clc_camera_k3& cam, int max_iteration, uint64_t seed, double precision, double* Rt, int* n_inliers,
+                 double* error_max);
 // clc_map_init_batch_dev (align == null: map_install) / clc_map_update_batch_dev (map_align_staged) behind their extern "C" names
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align);
+// (gr != null: the grown stage, clc_map_init_grow_batch_dev)
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr = nullptr);
 // map_update.hip: CLC_ERR_STATE unless the context holds a map with points; the align step on a staged map, installing it, with the
 // job's host points and seed poses rescaled
 int map_align_state(clc_ctx* ctx, const char* who);
-int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align);
+// (gr != null: a grown stage -- the rows gathered by the stage's camera list, the resected cameras' poses rescaled as well)
+int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align, clc_map_grow* gr = nullptr);
 
 // Every consumer stream behind what `producer` holds now (pose_batch.hip): ONE event (ev: its owner's, created on first use), no host
 // synchronisation; where an event call fails the host waits for the producer instead, and what that synchronisation reports is returned.

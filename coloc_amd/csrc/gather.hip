@@ -109,6 +109,18 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restric
     if (i < n * 4u) dst[i] = src[(size_t)(idx ? (uint32_t)idx[i >> 2] : i >> 2) * 4u + (i & 3u)];
 }
 
+// the same with a source block per row: row i = row idx[i] of block srcs.src[cam[i]] (the grown map's rows: map_grow.hip)
+__global__ __launch_bounds__(256) void gather_rows_multi_kernel(const RowSources srcs, const int32_t* __restrict__ cam, const int32_t* __restrict__ idx,
+                                                                uint4* __restrict__ dst, const uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n * 4u) return;
+    const int32_t c = cam[i >> 2], r = idx[i >> 2];
+    const uint4* src = nullptr;
+    for (int k = 0; k < kMaxBatch; ++k) if (k == c) src = srcs.src[k];      // (a select per block: the table stays in registers)
+    dst[i] = src && r >= 0 ? src[(size_t)r * 4u + (i & 3u)] : make_uint4(0u, 0u, 0u, 0u);
+}
+
 template <class Jobs> hipError_t launch(void (*kernel)(const Jobs), Jobs& jobs, const int n_jobs, hipStream_t stream)
 {
     if (n_jobs < 1 || n_jobs > kMaxBatch) return hipErrorInvalidValue;
@@ -140,6 +152,13 @@ hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, src, d_idx, dst, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather_rows_multi(const RowSources& srcs, const int32_t* d_cam, const int32_t* d_idx, uint4* dst, const uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_rows_multi_kernel, dim3((unsigned)(((size_t)n * 4 + 255) / 256)), dim3(256), 0, stream, srcs, d_cam, d_idx, dst, n);
     return hipGetLastError();
 }
 

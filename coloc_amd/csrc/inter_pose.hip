@@ -79,6 +79,12 @@ int clc::map_sweep_enqueue(clc_ctx* ctx, const void* d_first_desc, const int32_t
                            uint4* d_rows, int32_t* d_match, const int threshold, hipStream_t stream)
 {
     CLC_HIP(ctx, launch_gather_rows((const uint4*)d_first_desc, d_idx, d_rows, (uint32_t)nf, stream));
+    return map_sweep_rows_enqueue(ctx, nf, d_map_desc, map_n, d_rows, d_match, threshold, stream);
+}
+
+int clc::map_sweep_rows_enqueue(clc_ctx* ctx, const int nf, const void* d_map_desc, const int map_n, const uint4* d_rows, int32_t* d_match,
+                                const int threshold, hipStream_t stream)
+{
     std::vector<K2nnJobDev> jobs(1);
     jobs[0] = K2nnJobDev{};
     jobs[0].q = (const uint4*)d_map_desc; jobs[0].t = d_rows; jobs[0].out = d_match;

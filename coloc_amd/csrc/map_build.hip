@@ -13,7 +13,10 @@
 //   gather_rows_kernel    (gather.hip) the map's descriptor rows, once the host knows how many; the call returns when it has run
 // A build is two halves: map_stage -- everything up to the row count, the capacity check and the host outputs -- and map_install -- the
 // gather into d_m and the swap of the points.  clc_map_update_batch_dev (map_update.hip) follows the same stage half with an install
-// of its own, at the old map's scale.
+// of its own, at the old map's scale.  The GROWN forms (clc_map_build_grow_dev, clc_map_init_grow_batch_dev,
+// clc_map_update_grow_batch_dev) put map_stage_grown between the two halves: the resection loop over the other cameras, whose kernels
+// are map_grow.hip's and whose solve is the a-contrario launch path (resect_solve, pose_batch.hip); the capacity check and the host
+// outputs then describe the grown map, and the install gathers every row from the block of the camera the stage names for it.
 // Sizes: 8 cameras x 10 k rows, 28 pairs are 80 k nodes and up to ~260 k edges.  The two single-workgroup kernels walk 80 k nodes /
 // some 10 k tracks in passes of 1 024: latency-bound like the gathers, and what keeps the order a matter of one ballot per wave.
 #include "clc_ctx.h"
@@ -185,6 +188,18 @@ __global__ __launch_bounds__(kMapThreads) void seed_triangulate_kernel(const See
     if (threadIdx.x == 0) __hip_atomic_store(&s.h_words[0], base, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// What the grow phase needs of a stage (map_stage's `detail`): where the stage left its lists, and the cameras' sides.  A stage that
+// fills one leaves the capacity check and the host copies of the map's rows to the grow.
+struct StageDetail {
+    TrackGraph g;
+    GatherSide side[kMaxBatch];
+    int cam_i = 0, cam_j = 0;
+    size_t capr = 0;
+    int32_t* d_track = nullptr; int32_t* d_row = nullptr;
+    double* h_X = nullptr; int32_t* h_track = nullptr; int32_t* h_row = nullptr;
+};
+int map_stage_detail(clc_ctx* ctx, clc_map_job& job, MapStaged& out, StageDetail* detail);
+
 // a tracks job, validated, as the kernels take it.  *edge_rows: the widest pair (the union launch's grid)
 int tracks_inputs(clc_ctx* ctx, const clc_tracks_job& job, TrackGraph& g, EdgePairs& ep, int* edge_rows, const char* who)
 {
@@ -250,9 +265,14 @@ hipError_t launch_tracks(const TrackGraph& g, const EdgePairs& ep, const int n_p
 
 // The STAGE half of a map build: tracks, the seed launch, the wait for the row count, the capacity check, the host outputs.  On CLC_OK
 // the new map's points lie in d_map_X_next and its row list in the map block (out.d_row); the context's map is as it was.
-int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out)
+int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out) { return map_stage_detail(ctx, job, out, nullptr); }
+
+namespace {
+
+int map_stage_detail(clc_ctx* ctx, clc_map_job& job, MapStaged& out, StageDetail* detail)
 {
     out = MapStaged{};
+    ctx->grow_table = nullptr;                           // (the block the last grown build's table lies in is rewritten)
     job.n_tracks = 0; job.map_n = 0; job.status = CLC_OK;
     if (!ctx->has_mat) return job.status = fail(ctx, CLC_ERR_STATE, "map_build: context created without matcher options");
     TrackGraph g; EdgePairs ep; int edge_rows = 0;
@@ -296,6 +316,7 @@ int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out)
     projective_equivalent(side[cam_j].cam.focal, side[cam_j].cam.ppx, side[cam_j].cam.ppy, s.Rt_j, s.P_j);
     s.X = ctx->d_map_X_next.as<double>(); s.map_track = d_track; s.map_row = d_row;
     s.h_X = job.X ? h_X : nullptr; s.h_track = job.map_track ? h_track : nullptr; s.h_row = job.map_row ? h_row : nullptr;
+    if (detail) { s.h_X = nullptr; s.h_track = nullptr; s.h_row = nullptr; }      // (the grown map's rows go out instead)
     s.h_words = h_words;
     __atomic_store_n(&h_words[0], 0xFFFFFFFFu, __ATOMIC_RELAXED);
     // behind whatever produced the inputs: an event on the producer's stream, no host synchronisation
@@ -310,14 +331,23 @@ int map_stage(clc_ctx* ctx, clc_map_job& job, MapStaged& out)
     const uint32_t n = __atomic_load_n(&h_words[0], __ATOMIC_ACQUIRE);
     job.n_tracks = (int)h_words[1];
     if (job.track_feat && job.n_tracks > 0) memcpy(job.track_feat, h_table, sizeof(int32_t) * (size_t)job.n_tracks * (size_t)g.n_cams);
+    if (detail) {
+        detail->g = g; detail->cam_i = cam_i; detail->cam_j = cam_j; detail->capr = capr;
+        memcpy(detail->side, side, sizeof side);
+        detail->d_track = d_track; detail->d_row = d_row; detail->h_X = h_X; detail->h_track = h_track; detail->h_row = h_row;
+        out.n = (int)std::min<uint32_t>(n, (uint32_t)g.cap_tracks); out.cam_i = cam_i; out.cam_j = cam_j; out.d_row = d_row;
+        return CLC_OK;
+    }
     if (n > ctx->mopts.maxkp) return job.status = fail(ctx, CLC_ERR_CAPACITY, "map_build: more map rows than MatcherOptions.maxkp (the previous map stays)");
     if (job.map_track && n) memcpy(job.map_track, h_track, sizeof(int32_t) * n);
     if (job.map_row && n) memcpy(job.map_row, h_row, sizeof(int32_t) * n);
     if (job.X && n) memcpy(job.X, h_X, sizeof(double) * 3 * n);
     job.map_n = (int)n;
-    out.n = (int)n; out.cam_i = cam_i; out.d_row = d_row;
+    out.n = (int)n; out.cam_i = cam_i; out.cam_j = cam_j; out.d_row = d_row;
     return CLC_OK;
 }
+
+} // namespace
 
 // The INSTALL half (clc_map_build_dev, clc_map_init_batch_dev): the staged map becomes the context's.
 int map_install(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged)
@@ -333,7 +363,13 @@ int map_install(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged)
     // on ANOTHER stream straight after this one would otherwise sweep rows still being written, and a caller that describes its next
     // frame into the seed camera's block would change rows still being read.  (Some microseconds of device work, no data moved.)
     ctx->map_n = -1; ctx->map_X_n = -1;
-    hipError_t e = launch_gather_rows((const uint4*)job.cams[cam_i].d_desc, d_row, ctx->d_m.as<uint4>(), n, st);
+    hipError_t e;
+    if (staged.d_cam) {
+        // a grown map: every row from the block of the lowest camera that observes its landmark
+        RowSources srcs{};
+        for (int c = 0; c < job.tracks.n_cams; ++c) srcs.src[c] = (const uint4*)job.cams[c].d_desc;
+        e = launch_gather_rows_multi(srcs, staged.d_cam, d_row, ctx->d_m.as<uint4>(), n, st);
+    } else e = launch_gather_rows((const uint4*)job.cams[cam_i].d_desc, d_row, ctx->d_m.as<uint4>(), n, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return job.status = fail(ctx, CLC_ERR_HIP, "map_build: gathering the map's descriptors", e);
     std::swap(ctx->d_map_X, ctx->d_map_X_next);
@@ -350,12 +386,126 @@ int map_build(clc_ctx* ctx, clc_map_job& job)
     return rc == CLC_OK ? map_install(ctx, job, staged) : rc;
 }
 
+void grow_outputs_none(clc_map_grow& gr)
+{
+    for (int c = 0; c < kMaxBatch; ++c) {
+        gr.resected[c] = 0; gr.status[c] = CLC_GROW_OK; gr.n_corr[c] = 0; gr.n_inliers[c] = 0; gr.error_max[c] = 0.0;
+        memset(gr.Rt[c], 0, sizeof gr.Rt[c]);
+    }
+    gr.n_seed_rows = 0; gr.n_added = 0;
+}
+
+// The STAGE half of a grown build: map_stage, then -- between it and the install -- the resection loop of reconstructScene
+// (Reconstructor.hpp:153-154) on the per-track state and the grown map's rows.  Per camera the host waits for the resection count and
+// for the solve's rounds, as every a-contrario solve does; after the last camera for one more word, the grown map's row count.
+int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged& out)
+{
+    grow_outputs_none(gr);
+    if (gr.max_iteration < 0) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_grow: negative max_iteration");
+    if (job.tracks.n_cams >= 2 && job.tracks.n_cams <= kMaxBatch)
+        for (int c = 0; c < job.tracks.n_cams; ++c)
+            if (!job.cams[c].d_desc && job.tracks.rows[c] > 0) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_grow: every camera needs its descriptor block");
+    StageDetail d;
+    int rc = map_stage_detail(ctx, job, out, &d);
+    if (rc != CLC_OK) return rc;
+    const int n_cams = d.g.n_cams, nt = job.n_tracks, n_seed = out.n;
+    hipStream_t st = ctx->stream;
+    gr.n_seed_rows = n_seed;
+    memcpy(gr.Rt[d.cam_i], job.Rt_seed_a, sizeof gr.Rt[0]); memcpy(gr.Rt[d.cam_j], job.Rt_seed_b, sizeof gr.Rt[0]);
+    // device [ X per track 3 capr | obs capr | camera list capr ]; pinned [ row count 64 B | camera list capr | masks capr ]
+    const size_t capr = d.capr;
+    rc = grow(ctx, ctx->d_growb, 3 * capr * sizeof(double) + (2 * capr + 64) * sizeof(int32_t), 1, 4, true, "growing the map grow block");
+    if (rc == CLC_OK) rc = grow(ctx, ctx->h_growb, 64 + capr * sizeof(int32_t) + capr + 64, 1, 4, true, "growing the pinned map grow block");
+    // the resection lists: at most one entry per row of the camera, and the solve takes 16 384
+    int widest = 1;
+    for (int c = 0; c < n_cams; ++c) widest = std::max(widest, job.tracks.rows[c]);
+    if (rc == CLC_OK) rc = ensure_gather(ctx, ctx->trk, (size_t)std::min(widest, kAcrMaxN), kTrackLayout);
+    if (rc != CLC_OK) return job.status = rc;
+    GrowState s{};
+    s.table = d.g.table; s.n_tracks = d.g.n_tracks; s.n_cams = n_cams; s.cap = d.g.cap_tracks;
+    s.X = ctx->d_growb.as<double>(); s.obs = (uint32_t*)(s.X + 3 * capr);
+    int32_t* d_cam = (int32_t*)(s.obs + capr);
+    uint32_t* h_n = ctx->h_growb.as<uint32_t>();
+    int32_t* h_cam = (int32_t*)(ctx->h_growb.as<uint8_t>() + 64);
+    uint8_t* h_obs = (uint8_t*)(h_cam + capr);
+    GrowCams cams{};
+    memcpy(cams.side, d.side, sizeof cams.side);
+    for (int l = 0; l < CLC_MAX_LEVELS; ++l) cams.scale[l] = (float)std::pow((double)1.2f, (double)l);      // clc_keypoints_to_features' values
+    const auto set_pose = [&](const int c, const double* Rt) {
+        memcpy(cams.Rt[c], Rt, sizeof cams.Rt[c]);
+        projective_equivalent(cams.side[c].cam.focal, cams.side[c].cam.ppx, cams.side[c].cam.ppy, cams.Rt[c], cams.P[c]);
+        cams.valid |= 1u << c;
+    };
+    set_pose(d.cam_i, job.Rt_seed_a);
+    set_pose(d.cam_j, job.Rt_seed_b);
+    hipError_t e = launch_grow_scatter(s, d.d_track, ctx->d_map_X_next.as<double>(), n_seed, (1u << d.cam_i) | (1u << d.cam_j), st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the scatter launch", e); }
+    const GatherView v(ctx->trk, kTrackLayout);
+    const int block_cap = (int)std::min<size_t>(ctx->trk.cap, (size_t)kAcrMaxN);
+    int k = 0;
+    for (int I = 0; I < n_cams; ++I) {
+        if (I == d.cam_i || I == d.cam_j) continue;
+        const uint64_t seed = gr.seed + (uint64_t)k++;
+        // step 1: the resection list into the context's track block, its count into the block's pinned word
+        __atomic_store_n(v.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
+        const ResectOut ro{ v.a, v.b, v.q, v.t, v.h_q, v.h_t, v.n, v.h_n, block_cap };
+        e = launch_resect_gather(s, cams.side[I], I, ro, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the resect gather launch", e); }
+        rc = wait_pinned(ctx, v.h_n, 0xFFFFFFFFu, st, std::chrono::steady_clock::now(), 2, "map_grow: the resect gather left no count");
+        if (rc != CLC_OK) return job.status = rc;
+        const uint32_t N = __atomic_load_n(v.h_n, __ATOMIC_ACQUIRE);
+        gr.n_corr[I] = (int)N;
+        if (N == 0) { gr.status[I] = CLC_GROW_NO_TRACKS; continue; }                       // Reconstructor.hpp:274-277
+        if (N > (uint32_t)kAcrMaxN) { gr.status[I] = CLC_GROW_CAPACITY; continue; }         // (nothing is truncated silently)
+        // step 2: SfM_Localizer::Localize(P3P_KE_CVPR17): the a-contrario solve, success iff more than 2.5 x 3 inliers
+        rc = resect_solve(ctx, (int)N, job.cams[I].cam, gr.max_iteration > 0 ? gr.max_iteration : 256, seed, gr.precision, gr.Rt[I], &gr.n_inliers[I],
+                          &gr.error_max[I]);
+        if (rc != CLC_OK) return job.status = rc;
+        if (!(gr.n_inliers[I] > 2.5 * 3)) { gr.status[I] = CLC_GROW_NO_POSE; continue; }     // DEVIATION: skipped, not stored (:316)
+        gr.resected[I] = 1;
+        // step 3: the camera is valid; its tracks gain it or are triangulated against the valid cameras
+        set_pose(I, gr.Rt[I]);
+        e = launch_grow(s, cams, I, nt, st);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the grow launch", e); }
+    }
+    // setupMapDatabase over the landmarks: the rows in track-id order, over the staged seed map's lists
+    __atomic_store_n(h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
+    GrowMapOut mo{};
+    mo.X = ctx->d_map_X_next.as<double>(); mo.track = d.d_track; mo.cam = d_cam; mo.row = d.d_row;
+    mo.h_X = job.X ? d.h_X : nullptr; mo.h_track = job.map_track ? d.h_track : nullptr; mo.h_row = job.map_row ? d.h_row : nullptr;
+    mo.h_cam = gr.map_cam ? h_cam : nullptr; mo.h_obs = gr.map_obs ? h_obs : nullptr; mo.h_n = h_n;
+    e = launch_grow_compact(s, mo, st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the compaction launch", e); }
+    rc = wait_pinned(ctx, h_n, 0xFFFFFFFFu, st, std::chrono::steady_clock::now(), 2, "map_grow: the compaction left no count");
+    if (rc != CLC_OK) return job.status = rc;
+    const uint32_t n = __atomic_load_n(h_n, __ATOMIC_ACQUIRE);
+    ctx->grow_table = s.table; ctx->grow_n_tracks = s.n_tracks; ctx->grow_n_cams = n_cams; ctx->grow_cap = s.cap;
+    if (n > ctx->mopts.maxkp) return job.status = fail(ctx, CLC_ERR_CAPACITY, "map_grow: more map rows than MatcherOptions.maxkp (the previous map stays)");
+    if (job.map_track && n) memcpy(job.map_track, d.h_track, sizeof(int32_t) * n);
+    if (job.map_row && n) memcpy(job.map_row, d.h_row, sizeof(int32_t) * n);
+    if (job.X && n) memcpy(job.X, d.h_X, sizeof(double) * 3 * n);
+    if (gr.map_cam && n) memcpy(gr.map_cam, h_cam, sizeof(int32_t) * n);
+    if (gr.map_obs && n) memcpy(gr.map_obs, h_obs, n);
+    job.map_n = (int)n;
+    gr.n_added = (int)n - n_seed;
+    out.n = (int)n; out.d_cam = d_cam;
+    return CLC_OK;
+}
+
+int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr)
+{
+    MapStaged staged;
+    const int rc = map_stage_grown(ctx, job, gr, staged);
+    return rc == CLC_OK ? map_install(ctx, job, staged) : rc;
+}
+
 } // namespace
 
 // clc_map_init_batch_dev (align == null) and clc_map_update_batch_dev (map_update.hip): the filters, the selection, the seed poses and the
 // stage half are ONE path; what follows the stage half differs -- the install above, or the align step at the old map's scale.
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align)
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr)
 {
+    if (gr) grow_outputs_none(*gr);
     if (align) { align->n_old = 0; align->n_common = 0; align->n_terms = 0; align->status = CLC_MAP_ALIGN_NO_SCALE; align->scale = 1.0; }
     if (n_pairs < 1 || n_pairs > kMaxPairs || !ctxs || !pair_jobs || !job) return CLC_ERR_BAD_ARG;
     const int rc0 = check_batch_contexts(ctxs, n_pairs, "map_init_batch: every pair needs a context of its own");
@@ -413,8 +563,8 @@ int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, c
     void* const after = job->after_stream;
     job->tracks.pairs = tp.data(); job->seed_pair = seed; job->after_stream = nullptr;
     MapStaged staged;
-    int rc = map_stage(c0, *job, staged);
-    if (rc == CLC_OK) rc = align ? map_align_staged(c0, *job, staged, *align) : map_install(c0, *job, staged);
+    int rc = gr ? map_stage_grown(c0, *job, *gr, staged) : map_stage(c0, *job, staged);
+    if (rc == CLC_OK) rc = align ? map_align_staged(c0, *job, staged, *align, gr) : map_install(c0, *job, staged);
     job->tracks.pairs = callers; job->after_stream = after;
     // (the union launch read the other contexts' blocks and pinned lists; it ran before the count the build waited for came out)
     return rc;
@@ -440,6 +590,7 @@ int clc_tracks_build_dev(clc_ctx* ctx, const clc_tracks_job* job, int32_t* d_tra
     if (rc != CLC_OK) return rc;
     graph_words(ctx, g);
     g.table = d_track_feat; g.h_table = nullptr; g.n_tracks = d_n_tracks;
+    ctx->grow_table = nullptr;                           // (the block the last grown build's table lies in is rewritten)
     CLC_HIP(ctx, launch_tracks(g, ep, job->n_pairs, edge_rows, pick(ctx, stream)));
     return CLC_OK;
 }
@@ -453,6 +604,45 @@ int clc_map_build_dev(clc_ctx* ctx, clc_map_job* job)
 int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job)
 {
     return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr);
+}
+
+int clc_map_build_grow_dev(clc_ctx* ctx, clc_map_job* job, clc_map_grow* grow)
+{
+    if (!ctx || !job || !grow) return fail(ctx, CLC_ERR_BAD_ARG, "map_build_grow: null context / job / grow");
+    return map_build_grow(ctx, *job, *grow);
+}
+
+int clc_map_init_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow)
+{
+    if (!grow) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr, grow);
+}
+
+int clc_map_resect_build_dev(clc_ctx* ctx, const clc_map_job* job, int camera, double* d_X, double* d_x, int32_t* d_track, int32_t* d_row, int32_t* d_n,
+                             void* stream)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: null context / job");
+    if (job->tracks.n_cams < 2 || job->tracks.n_cams > kMaxBatch || camera < 0 || camera >= job->tracks.n_cams)
+        return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: camera must be one of the job's cameras");
+    if (!ctx->grow_table || ctx->grow_n_cams != job->tracks.n_cams)
+        return fail(ctx, CLC_ERR_STATE, "map_resect_build: the context holds no per-track state of a grown build with that many cameras");
+    const clc_map_camera& m = job->cams[camera];
+    if ((m.d_kps != nullptr) == (m.d_feat != nullptr)) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: exactly one of d_kps / d_feat");
+    if (m.d_feat && m.feat_stride < 2) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: feat_stride < 2");
+    if (!(m.cam.focal > 0.0)) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: focal must be positive");
+    if (job->tracks.rows[camera] < 0 || !d_n || (job->tracks.rows[camera] > 0 && (!d_X || !d_x))) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: null output");
+    if (((uintptr_t)m.d_kps & 3u) || ((uintptr_t)m.d_feat & 3u) || ((uintptr_t)d_X & 7u) || ((uintptr_t)d_x & 7u) || ((uintptr_t)d_track & 3u) ||
+        ((uintptr_t)d_row & 3u) || ((uintptr_t)d_n & 3u))
+        return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: misaligned device pointer");
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    GrowState s{};
+    s.table = ctx->grow_table; s.n_tracks = ctx->grow_n_tracks; s.n_cams = ctx->grow_n_cams; s.cap = ctx->grow_cap;
+    const size_t capr = ((size_t)s.cap + 63) & ~(size_t)63;
+    s.X = ctx->d_growb.as<double>(); s.obs = (uint32_t*)(s.X + 3 * capr);
+    const GatherSide side{ nullptr, m.d_kps, m.d_feat, m.feat_stride, UdCamera{ m.cam.focal, m.cam.ppx, m.cam.ppy, m.cam.k1, m.cam.k2, m.cam.k3 } };
+    const ResectOut ro{ d_X, d_x, d_track, d_row, nullptr, nullptr, d_n, nullptr, job->tracks.rows[camera] };
+    CLC_HIP(ctx, launch_resect_gather(s, side, camera, ro, pick(ctx, stream)));
+    return CLC_OK;
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
-// map_math.h -- the per-point fp64 statements of the map's seed triangulation (reference include/coloc/Reconstructor.hpp:185-257), host +
-// device inline and written ONCE, as inter_math.h is: seed_triangulate_kernel (map_build.hip) and the host build the tests hold it to
-// (tests/host/map_math_lib.cpp) run the very same statements, so the device has the host's bits by construction.  Contraction off: an
+// map_math.h -- the per-point fp64 statements of the map's seed triangulation (reference include/coloc/Reconstructor.hpp:185-257) and of
+// the grow step behind it (:329-414), host + device inline and written ONCE, as inter_math.h is: seed_triangulate_kernel (map_build.hip),
+// grow_kernel (map_grow.hip) and the host builds the tests hold them to (tests/host/map_math_lib.cpp, tests/host/map_grow_lib.cpp) run
+// the very same statements, so the device has the host's bits by construction.  Contraction off: an
 // expression is the IEEE operations written here, in this order.
 #ifndef CLC_MAP_MATH_H
 #define CLC_MAP_MATH_H
@@ -115,6 +116,49 @@ MAP_HD bool seed_point_accepted(const double* Rt_i, const double* Rt_j, const do
 MAP_HD bool seed_point(const double* P_i, const double* P_j, const double* Rt_i, const double* Rt_j, const double* x_i, const double* x_j, double* X)
 {
     return triangulate_dlt(P_i, x_i, P_j, x_j, X) && seed_point_accepted(Rt_i, Rt_j, X);
+}
+
+// ---- the grow step (Reconstructor::resectionCamera, Reconstructor.hpp:329-414; map_grow.hip) -----------------------------------------
+// The bearing of an UNDISTORTED pixel under K = { focal, 0, ppx; 0, focal, ppy; 0, 0, 1 }.
+MAP_HD void pixel_bearing(const double focal, const double ppx, const double ppy, const double* x_ud, double* b)
+{
+    b[0] = (x_ud[0] - ppx) / focal; b[1] = (x_ud[1] - ppy) / focal; b[2] = 1.0;
+}
+
+// R^T b of [R|t]: the bearing in world axes
+MAP_HD void world_ray(const double* Rt, const double* b, double* r)
+{
+    for (int q = 0; q < 3; ++q) r[q] = Rt[q] * b[0] + Rt[4 + q] * b[1] + Rt[8 + q] * b[2];
+}
+
+// cos(2 degrees) to 17 digits
+#define CLC_MAP_COS_2DEG 0.99939082701909573
+
+// AngleBetweenRay(...) > 2 degrees (Reconstructor.hpp:383) without acos: dot < cos(2 deg) * sqrt(n_I * n_J), the plain sums below.
+MAP_HD bool ray_angle_over_2deg(const double* r_i, const double* r_j)
+{
+    const double dot = r_i[0] * r_j[0] + r_i[1] * r_j[1] + r_i[2] * r_j[2];
+    const double n_i = r_i[0] * r_i[0] + r_i[1] * r_i[1] + r_i[2] * r_i[2];
+    const double n_j = r_j[0] * r_j[0] + r_j[1] * r_j[1] + r_j[2] * r_j[2];
+    return dot < CLC_MAP_COS_2DEG * sqrt(n_i * n_j);
+}
+
+// A landmark is observed by a camera iff it lies in front of it and |X[2]| < 1000 (Reconstructor.hpp:402-411).
+MAP_HD bool observation_ok(const double* Rt, const double* X) { return pose_depth(Rt, X) > 0.0 && fabs(X[2]) < 1000.0; }
+
+// One new landmark from the resected camera I and a valid camera J: cam = { focal, ppx, ppy }, undistorted pixels -> X.  Accepted iff the
+// ray angle is over 2 degrees, X is finite, both depths are positive and |X[2]| < 1000 (:383).  false: X is not to be used.
+MAP_HD bool grow_point(const double* cam_i, const double* cam_j, const double* P_i, const double* P_j, const double* Rt_i, const double* Rt_j,
+                       const double* x_i, const double* x_j, double* X)
+{
+    double b_i[3], b_j[3], r_i[3], r_j[3];
+    pixel_bearing(cam_i[0], cam_i[1], cam_i[2], x_i, b_i);
+    pixel_bearing(cam_j[0], cam_j[1], cam_j[2], x_j, b_j);
+    world_ray(Rt_i, b_i, r_i);
+    world_ray(Rt_j, b_j, r_j);
+    if (!ray_angle_over_2deg(r_i, r_j)) return false;
+    if (!triangulate_dlt(P_i, x_i, P_j, x_j, X)) return false;
+    return pose_depth(Rt_i, X) > 0.0 && pose_depth(Rt_j, X) > 0.0 && fabs(X[2]) < 1000.0;
 }
 
 // Pose3::center of [R|t]: C = -R^T t

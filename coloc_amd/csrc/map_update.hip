@@ -108,8 +108,9 @@ void align_outputs_none(clc_map_align& job)
     job.n_old = 0; job.n_common = 0; job.n_terms = 0; job.status = CLC_MAP_ALIGN_NO_SCALE; job.scale = 1.0;
 }
 
-// the step itself.  staged: d_X is the context's own d_map_X_next (the staged map), rescaled in place
-int map_align(clc_ctx* ctx, clc_map_align& job, const bool staged)
+// the step itself.  staged: d_X is the context's own d_map_X_next (the staged map), rescaled in place.  srcs + d_cam (both or neither):
+// a grown stage, new row i = row d_rows[i] of block srcs->src[d_cam[i]]
+int map_align(clc_ctx* ctx, clc_map_align& job, const bool staged, const RowSources* srcs = nullptr, const int32_t* d_cam = nullptr)
 {
     align_outputs_none(job);
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "map_align: context created without matcher options");
@@ -150,7 +151,13 @@ int map_align(clc_ctx* ctx, clc_map_align& job, const bool staged)
     hipStream_t prod = (hipStream_t)job.after_stream;
     if (prod && prod != st) CLC_HIP(ctx, order_behind(ctx->ev_track, prod, &st, 1));
     // the new rows into the NEXT map's buffer (the installed map's rows are the sweep's queries: they stay where they are)
-    if (n_old > 0) {
+    if (srcs) {
+        CLC_HIP(ctx, launch_gather_rows_multi(*srcs, d_cam, job.d_rows, ctx->d_m_next.as<uint4>(), (uint32_t)n_new, st));
+        if (n_old > 0) {
+            rc = map_sweep_rows_enqueue(ctx, n_new, ctx->d_m.ptr, n_old, ctx->d_m_next.as<uint4>(), d_match, job.threshold, st);
+            if (rc != CLC_OK) { (void)hipStreamSynchronize(st); return rc; }
+        }
+    } else if (n_old > 0) {
         rc = map_sweep_enqueue(ctx, job.d_desc, job.d_rows, n_new, ctx->d_m.ptr, n_old, ctx->d_m_next.as<uint4>(), d_match, job.threshold, st);
         if (rc != CLC_OK) { (void)hipStreamSynchronize(st); return rc; }
     } else if (job.install) {
@@ -182,17 +189,23 @@ int map_align_state(clc_ctx* ctx, const char* who)
     return CLC_OK;
 }
 
-int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align)
+int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align, clc_map_grow* gr)
 {
+    RowSources srcs{};
+    for (int c = 0; c < job.tracks.n_cams && c < kMaxBatch; ++c) srcs.src[c] = (const uint4*)job.cams[c].d_desc;
     clc_map_align a{};
     a.d_desc = job.cams[staged.cam_i].d_desc; a.d_rows = staged.d_row; a.d_X = ctx->d_map_X_next.as<double>(); a.n_new = staged.n;
     a.threshold = align.threshold; a.install = 1; a.after_stream = nullptr;          // (the stage half ran on the context's stream)
     a.match = align.match; a.X = job.X;
-    const int rc = map_align(ctx, a, true);
+    const int rc = staged.d_cam ? map_align(ctx, a, true, &srcs, staged.d_cam) : map_align(ctx, a, true);
     align.n_old = a.n_old; align.n_common = a.n_common; align.n_terms = a.n_terms; align.status = a.status; align.scale = a.scale;
     if (rc != CLC_OK) return job.status = rc;
     rescale_pose(job.Rt_seed_a, a.scale);
     rescale_pose(job.Rt_seed_b, a.scale);
+    // rescaleMap multiplies every pose's centre (colocUtils.hpp:213-223): the resected cameras' too
+    if (gr)
+        for (int c = 0; c < job.tracks.n_cams; ++c)
+            if (gr->resected[c] || c == staged.cam_i || c == staged.cam_j) rescale_pose(gr->Rt[c], a.scale);
     return CLC_OK;
 }
 
@@ -212,6 +225,12 @@ int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int 
 {
     if (!align) return CLC_ERR_BAD_ARG;
     return map_init_batch(ctxs, pair_jobs, n_pairs, job, align);
+}
+
+int clc_map_update_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* grow)
+{
+    if (!align || !grow) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, align, grow);
 }
 
 } // extern "C"

@@ -916,6 +916,21 @@ int clc::pair_filter_essential(clc_ctx* const* ctxs, clc_pair_job* jobs, const i
     return gather_solve<PairPath>(ctxs, 1, jobs, n_jobs, inliers);
 }
 
+// The resection of the grow step (map_build.hip): ONE AcrRun filled from the context's track block as gather_solve fills it -- kind 0, no
+// refinement -- and driven like every other solve.
+int clc::resect_solve(clc_ctx* ctx, const int N, const clc_camera_k3& cam, const int max_iteration, const uint64_t seed, const double precision,
+                      double* Rt, int* n_inliers, double* error_max)
+{
+    const double K[9] = { cam.focal, 0.0, cam.ppx, 0.0, cam.focal, cam.ppy, 0.0, 0.0, 1.0 };      // Pinhole_Intrinsic_Radial_K3::K()
+    memset(Rt, 0, sizeof(double) * 12);
+    const GatherView v(ctx->trk, kTrackLayout);
+    AcrRun run;
+    run.ctx = ctx; run.kind = 0; run.N = N; run.dev_a = v.a; run.dev_b = v.b; run.h_K1 = K;
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
+    run.h_model = Rt; run.n_inliers = n_inliers; run.error_max = error_max;
+    return solve_one(run);
+}
+
 extern "C" {
 
 int clc_track_localize_batch_dev(clc_ctx* const* ctxs, clc_track_job* jobs, int n_jobs)

@@ -909,8 +909,8 @@ int clc_inter_front_dev(clc_ctx* ctx, const double* d_x1, const double* d_x2, in
  * filterMatches and setMapData: the tracks of Reconstructor::initializeTracks (Reconstructor.hpp:166-173: TracksBuilder Build, Filter,
  * ExportToSTL), the seed pair's landmarks of Reconstructor::triangulatePoints (:185-239) and the map database of
  * colocData::setupMapDatabase (colocData.hpp:89-121), from the pairs' correspondences where clc_pair_filter_batch_dev left them.  It
- * ends where reconstructScene writes initial.ply: no resectionCamera, no bundle adjustment, no PLY.  (Later under ABI 4: new entry
- * points only.)
+ * ends where reconstructScene writes initial.ply; the resectionCamera loop behind it is clc_map_build_grow_dev's (the section after
+ * the next); no bundle adjustment, no PLY.  (Later under ABI 4: new entry points only.)
  *
  * TRACKS.  A node is a (camera, feature row) named by a match; an edge is a match (cam_a, q)-(cam_b, t) of a pair cam_a < cam_b; a
  * track is a connected component.  The rules are this project's statement of OpenMVG's TracksBuilder (an empty submodule in the
@@ -1073,6 +1073,80 @@ typedef struct clc_map_align {
 } clc_map_align;
 int clc_map_align_dev(clc_ctx* ctx, clc_map_align* job);
 int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align);
+
+/* ---- the map grown past the seed pair: resect the other cameras, add their tracks ---------------------------------------------------
+ * What Reconstructor::reconstructScene runs after the seed triangulation: `for (auto resectionId : resectionList)
+ * resectionCamera(resectionId)` (Reconstructor.hpp:153-154, 259-415), and setupMapDatabase (colocData.hpp:89-121) over the landmarks
+ * that loop leaves.  Bundle adjustment (:160-161) and the PLY files are NOT covered.  OpenMVG is an empty submodule in the reference
+ * tree: as for the tracks and the ratio matcher, the rules below are this project's statement of SfM_Localizer::Localize,
+ * TriangulateDLT and AngleBetweenRay, and their parity with OpenMVG is unpinned.  (Later under ABI 4: new entry points only.)
+ *
+ * STATE, per track t (Landmarks is a map keyed by track id): a landmark X[t] and an observation mask obs[t], one bit per camera; 0 =
+ * no landmark.  After the seed triangulation the accepted seed tracks have obs = { seed cam_a, seed cam_b }.  The VALID cameras start
+ * as the two seed cameras.  The other cameras are taken in ascending order (:135-139); the k-th of them, camera I:
+ *   1. RESECTION LIST (:261-303): the tracks with track_feat[t][I] >= 0 and obs[t] != 0 in ascending track id; pt3D = X[t], pt2D =
+ *      get_ud_pixel of the row's position (both position forms of clc_map_camera).  An empty list: the camera fails
+ *      (CLC_GROW_NO_TRACKS, :274-277).  More than 16 384 entries: CLC_GROW_CAPACITY, nothing is truncated.
+ *   2. SOLVE (:305-307): the a-contrario solve of clc_pnp_acransac on that list -- K of the camera, max_iteration, precision, seed + k
+ *      -- through the same launch path, so with its bits.  Success iff more than 2.5 x 3 inliers (HIP_SfM_Localizer::Localize).
+ *      DEVIATION 1: the reference stores the pose and goes on even when the resection failed (:316), which would triangulate against
+ *      an identity pose.  Here a failed camera is SKIPPED (CLC_GROW_NO_POSE): it does not become valid and adds nothing.
+ *   3. GROW (:329-414), I now valid, for every track t with track_feat[t][I] >= 0, each independent of the others:
+ *      - obs[t] != 0: the candidate set is { I };
+ *      - otherwise the valid cameras J != I with track_feat[t][J] >= 0 in ascending J: until a landmark exists, TriangulateDLT of the
+ *        two undistorted pixels under P = K [R|t], accepted iff the ray angle is > 2 degrees, the depth under I > 0, the depth under
+ *        J > 0 and |X[2]| < 1000 (:383; grow_point, coloc_amd/csrc/map_math.h); on acceptance X[t] = X and I becomes a candidate;
+ *        every J visited, before or after acceptance, is a candidate (:360, :391);
+ *      - with a landmark: bit J of obs[t] is set for every candidate J with depth of X[t] under J > 0 and |X[t][2]| < 1000 (:402-411).
+ *      RAY ANGLE: between R_I^T b_I and R_J^T b_J, b = ((x_ud - ppx) / focal, (y_ud - ppy) / focal, 1) of the UNDISTORTED pixel,
+ *      decided without acos: dot < cos(2 deg) * sqrt(n_I * n_J), one literal constant and the plain sums of map_math.h, so host and
+ *      device agree bit for bit.  DEVIATION 2: the two `residual` values the reference computes and never reads are not computed.
+ * THE MAP after the last camera: rows in ascending track id over the tracks with obs != 0 -- new landmarks INTERLEAVE with the
+ * seed's --, row i = { X, track id, the camera of the LOWEST set bit of obs (obs.begin()), that camera's row, that row's descriptor }.
+ * A resected camera below the seed's cam_a takes over the descriptor of every landmark it observes.
+ *
+ * clc_map_build_grow_dev: clc_map_build_dev with the loop above between the seed triangulation and the install.  job's outputs
+ * (map_track, map_row, X, map_n) describe the GROWN map; grow's per-camera outputs are indexed by camera (seed cameras: status
+ * CLC_GROW_OK, resected 0, Rt = their seed pose; a camera that failed: Rt zeros).  Every camera with rows needs its d_desc block
+ * (CLC_ERR_BAD_ARG otherwise).  The capacity check against MatcherOptions.maxkp is made on the grown map: CLC_ERR_CAPACITY, and the
+ * previous map stays.  The host waits, per resected camera, for the resection count and the solve's rounds, and after the last camera
+ * for one more word, the grown map's row count; no descriptor, point or track moves through the host.  ORDERING, after_stream and
+ * the other errors: as clc_map_build_dev.  With two cameras there is nothing to resect and every output equals clc_map_build_dev's.
+ *
+ * clc_map_init_grow_batch_dev: clc_map_init_batch_dev with clc_map_build_grow_dev in place of clc_map_build_dev.
+ *
+ * clc_map_update_grow_batch_dev: clc_map_update_batch_dev on the GROWN stage: the align step's new rows are gathered by the stage's
+ * per-row camera list, the capacity check is the grown map's (CLC_ERR_CAPACITY: the previous map stays), and align's rescale
+ * multiplies the centres of the resected cameras' poses in grow->Rt as well as the seed poses' (rescaleMap, colocUtils.hpp:213-223).
+ *
+ * clc_map_resect_build_dev: step 1 alone for `camera` on the per-track state the context's last grown build left (the state AFTER
+ * its last camera), enqueue only on `stream`: d_X (3 N) / d_x (2 N) / d_track / d_row (N int32; nullable) with room for
+ * job->tracks.rows[camera] entries, *d_n = N.  Of job, tracks.n_cams, tracks.rows[camera] and cams[camera]'s 2-D side and camera are
+ * read.  A camera outside [0, n_cams), a null job or d_n, a misaligned pointer: CLC_ERR_BAD_ARG; no grown build on the context since
+ * its block was last rewritten (any tracks / map build), or one of another camera count: CLC_ERR_STATE. */
+enum { CLC_GROW_OK = 0, CLC_GROW_NO_TRACKS = 1, CLC_GROW_NO_POSE = 2, CLC_GROW_CAPACITY = 3 };
+typedef struct clc_map_grow {
+    /* in */
+    int      max_iteration;            /* 0: 256 */
+    uint64_t seed;                     /* k-th resected camera: seed + k */
+    double   precision;                /* +inf: a-contrario threshold */
+    /* out, per camera index (seed cameras: status CLC_GROW_OK, resected 0, Rt = their seed pose) */
+    int      resected[CLC_MAX_BATCH];  /* 1: the camera became valid through a resection */
+    int      status[CLC_MAX_BATCH];
+    int      n_corr[CLC_MAX_BATCH], n_inliers[CLC_MAX_BATCH];
+    double   error_max[CLC_MAX_BATCH];
+    double   Rt[CLC_MAX_BATCH][12];
+    int      n_seed_rows, n_added;     /* map rows before / landmarks added by the grow */
+    /* out, nullable host memory, room as clc_map_job.map_track */
+    int32_t* map_cam;                  /* camera of the row's descriptor / map_row */
+    uint8_t* map_obs;                  /* observation mask of the row */
+} clc_map_grow;
+int clc_map_build_grow_dev(clc_ctx* ctx, clc_map_job* job, clc_map_grow* grow);
+int clc_map_init_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow);
+int clc_map_update_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align,
+                                  clc_map_grow* grow);
+int clc_map_resect_build_dev(clc_ctx* ctx, const clc_map_job* job, int camera, double* d_X, double* d_x, int32_t* d_track, int32_t* d_row,
+                             int32_t* d_n, void* stream);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
