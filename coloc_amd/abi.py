@@ -124,6 +124,23 @@ class MapGrow(C.Structure):
 
 GROW_OK, GROW_NO_TRACKS, GROW_NO_POSE, GROW_CAPACITY = 0, 1, 2, 3
 
+
+class MapBa(C.Structure):
+    """clc_map_ba (include/coloc_hip.h)"""
+    _fields_ = [("max_iterations", C.c_int), ("huber_a", C.c_double), ("function_tolerance", C.c_double),
+                ("status", C.c_int), ("iterations", C.c_int), ("n_cams", C.c_int), ("n_points", C.c_int), ("n_obs", C.c_int),
+                ("cost_initial", C.c_double), ("cost_final", C.c_double), ("rmse", C.c_double)]
+
+
+class BaJob(C.Structure):
+    """clc_ba_job (include/coloc_hip.h)"""
+    _fields_ = [("n_cams", C.c_int), ("cam_mask", C.c_uint32), ("cam", CameraK3 * MAX_BATCH), ("Rt", (C.c_double * 12) * MAX_BATCH),
+                ("n_points", C.c_int), ("d_X", C.c_void_p), ("d_obs", C.c_void_p), ("d_x", C.c_void_p), ("after_stream", C.c_void_p),
+                ("ba", MapBa)]
+
+
+BA_OK, BA_MAX_ITERATIONS, BA_STALLED, BA_BAD_START, BA_EMPTY = 0, 1, 2, 3, 4
+
 ABI_VERSION = 4          # CLC_ABI_VERSION of include/coloc_hip.h
 DESC_CACHE_OFF, DESC_CACHE_VERIFY, DESC_CACHE_TRUST = 0, 1, 2
 
@@ -177,6 +194,7 @@ EXPORTS = [
     "clc_tracks_build_dev", "clc_map_build_dev", "clc_map_init_batch_dev",
     "clc_map_align_dev", "clc_map_update_batch_dev",
     "clc_map_build_grow_dev", "clc_map_init_grow_batch_dev", "clc_map_update_grow_batch_dev", "clc_map_resect_build_dev",
+    "clc_ba_dev", "clc_map_build_grow_ba_dev", "clc_map_init_grow_ba_batch_dev", "clc_map_update_grow_ba_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -341,6 +359,10 @@ def load_library():
     lib.clc_map_init_grow_batch_dev.argtypes = [vp, vp, ci, vp, vp]
     lib.clc_map_update_grow_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp]
     lib.clc_map_resect_build_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp, vp]
+    lib.clc_ba_dev.argtypes = [vp, vp]
+    lib.clc_map_build_grow_ba_dev.argtypes = [vp, vp, vp, vp]
+    lib.clc_map_init_grow_ba_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp]
+    lib.clc_map_update_grow_ba_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -913,6 +935,66 @@ def map_update_grow_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=n
     return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
 
 
+def _ba_fill(b, max_iterations=0, huber_a=0.0, function_tolerance=0.0):
+    b.max_iterations, b.huber_a, b.function_tolerance = int(max_iterations), float(huber_a), float(function_tolerance)
+
+
+def _ba_result(b):
+    return dict(status=b.status, iterations=b.iterations, n_cams=b.n_cams, n_points=b.n_points, n_obs=b.n_obs,
+                cost_initial=float(b.cost_initial), cost_final=float(b.cost_final), rmse=float(b.rmse))
+
+
+def map_init_grow_ba_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, max_iteration=256, seed=0,
+                               precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
+    """clc_map_init_grow_ba_batch_dev: map_init_grow_batch_dev with the grown map bundle-adjusted before it is installed.  Returns (map
+    result dict -- X, Rt_seed_* and grow["Rt"] REFINED -- with "grow" and "ba" dicts; [pair filter result dicts])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j, g, b = MapJob(), MapGrow(), MapBa()
+    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b_) for a, b_ in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
+    _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_init_grow_ba_batch_dev(hs, arr, n, C.byref(j), C.byref(g), C.byref(b))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_init_grow_ba_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    res = _map_result(j, *out)
+    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+    res["ba"] = _ba_result(b)
+    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
+def map_update_grow_ba_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, threshold=0,
+                                 max_iteration=256, seed=0, precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
+    """clc_map_update_grow_ba_batch_dev: map_update_grow_batch_dev with the grown map bundle-adjusted before the align step.  Returns (map
+    result dict -- X, Rt_seed_* and grow["Rt"] REFINED, then RESCALED -- with "align", "grow" and "ba" dicts; [pair filter result dicts])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j, g, al, b = MapJob(), MapGrow(), MapAlign(), MapBa()
+    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b_) for a, b_ in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
+    _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
+    match = np.full(max(int(ctxs[0].mopts.maxkp), 1), -2, dtype=np.int32)
+    al.threshold, al.match = int(threshold), match.ctypes.data
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_update_grow_ba_batch_dev(hs, arr, n, C.byref(j), C.byref(al), C.byref(g), C.byref(b))
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_update_grow_ba_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    res = _map_result(j, *out)
+    res["align"] = _align_result(al, match, None)
+    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+    res["ba"] = _ba_result(b)
+    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
 def desc_handle_live(handle):
     """1 while the publication the handle came from still stands (same host address, count and generation)."""
     return bool(load_library().clc_desc_handle_live(C.byref(handle)))
@@ -1278,6 +1360,40 @@ class Context:
         self._chk(self.lib.clc_map_build_grow_dev(self.h, C.byref(j), C.byref(g)))
         res = _map_result(j, *out)
         res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+        return res
+
+    def map_build_grow_ba_dev(self, rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream=None, max_iteration=256, seed=0,
+                              precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
+        """clc_map_build_grow_ba_dev: map_build_grow_dev with the grown map -- the valid cameras' poses and every landmark -- bundle-adjusted
+        before it is installed.  Returns map_build_grow_dev's dict (X, Rt_seed_* and grow["Rt"] refined) with a "ba" dict: status,
+        iterations, n_cams, n_points, n_obs, cost_initial, cost_final, rmse."""
+        j, g, b = MapJob(), MapGrow(), MapBa()
+        keep = []
+        out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
+        gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
+        _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
+        self._chk(self.lib.clc_map_build_grow_ba_dev(self.h, C.byref(j), C.byref(g), C.byref(b)))
+        res = _map_result(j, *out)
+        res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+        res["ba"] = _ba_result(b)
+        return res
+
+    def ba_dev(self, cams, cam_mask, Rt, n_points, d_X, d_obs, d_x, after_stream=None, max_iterations=0, huber_a=0.0, function_tolerance=0.0):
+        """clc_ba_dev: the bundle adjustment alone on arrays in device memory (pointers as integers): cams = [(focal, ppx, ppy, k1, k2,
+        k3), ...], Rt (n_cams, 3, 4), d_X n_points x 3 float64 (rewritten), d_obs n_points uint32 masks, d_x n_points x n_cams x 2 float64.
+        Returns a dict: clc_map_ba's out fields and Rt (n_cams, 3, 4), refined for the cameras of cam_mask."""
+        j = BaJob()
+        n = len(cams)
+        j.n_cams, j.cam_mask, j.n_points = n, int(cam_mask), int(n_points)
+        Rt = np.asarray(Rt, dtype=np.float64).reshape(n, 12)
+        for c in range(min(n, MAX_BATCH)):
+            j.cam[c] = CameraK3(*[float(v) for v in cams[c]])
+            j.Rt[c][:] = [float(v) for v in Rt[c]]
+        j.d_X, j.d_obs, j.d_x, j.after_stream = d_X, d_obs, d_x, after_stream
+        _ba_fill(j.ba, max_iterations, huber_a, function_tolerance)
+        self._chk(self.lib.clc_ba_dev(self.h, C.byref(j)))
+        res = _ba_result(j.ba)
+        res["Rt"] = np.array([list(j.Rt[c]) for c in range(min(n, MAX_BATCH))]).reshape(-1, 3, 4)
         return res
 
     def map_resect_build_dev(self, rows, cams, camera, d_X, d_x, d_track, d_row, d_n, stream=None):

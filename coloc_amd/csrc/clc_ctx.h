@@ -148,6 +148,10 @@ struct clc_ctx {
     clc::PinBuf h_growb;
     const int32_t* grow_table = nullptr; const int32_t* grow_n_tracks = nullptr;
     int grow_n_cams = 0, grow_cap = 0;
+    // the bundle adjustment (map_ba.hip): device [ state | compaction lists | per-observation and per-point records | trial points |
+    // the workgroups' partial sums | the pixels of a composition ], pinned the record the host waits for
+    clc::DevBuf d_bab;
+    clc::PinBuf h_bab;
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
     // in and out through, and the block of the descriptor table (desc_cache.h) the frame's descriptors are written into on the device
     clc::PinBuf h_stage;          // (bytes)
@@ -273,8 +277,23 @@ hipError_t launch_gather_rows_multi(const RowSources& srcs, const int32_t* d_cam
 int resect_solve(clc_ctx* ctx, int N, const clc_camera_k3& cam, int max_iteration, uint64_t seed, double precision, double* Rt, int* n_inliers,
                  double* error_max);
 // clc_map_init_batch_dev (align == null: map_install) / clc_map_update_batch_dev (map_align_staged) behind their extern "C" names
-// (gr != null: the grown stage, clc_map_init_grow_batch_dev)
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr = nullptr);
+// (gr != null: the grown stage, clc_map_init_grow_batch_dev; ba != null: the grown stage bundle-adjusted, the _grow_ba_ entries)
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr = nullptr,
+                   clc_map_ba* ba = nullptr);
+int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, clc_map_ba* ba);
+// ---- the bundle adjustment (map_ba.hip) ---------------------------------------------------------------------------------------------
+// ba's in fields checked (CLC_ERR_BAD_ARG on `who`) and its out fields cleared
+int ba_check(clc_ctx* ctx, clc_map_ba* ba, const char* who);
+// The problem in device memory: cameras 0 .. n_cams - 1, those of `mask` adjusted; X / obs of n_points points.  x: the dense pixel block
+// (n_points x n_cams x 2), or null: formed first from the track table and the cameras' 2-D sides (cams, table: a composition).
+struct BaProblem {
+    int n_cams, n_points; uint32_t mask;
+    double K[kMaxBatch][3], Rt[kMaxBatch][12];           // Rt in / out (rewritten for the masked cameras when a step was accepted)
+    double* X; const uint32_t* obs; const double* x;
+    const GrowCams* cams; const int32_t* table;
+};
+// the whole step on the context's stream: the rounds, the waits, ba's out fields.  Returns CLC_OK for every CLC_BA_* status.
+int ba_drive(clc_ctx* ctx, BaProblem& pb, clc_map_ba& ba);
 // map_update.hip: CLC_ERR_STATE unless the context holds a map with points; the align step on a staged map, installing it, with the
 // job's host points and seed poses rescaled
 int map_align_state(clc_ctx* ctx, const char* who);

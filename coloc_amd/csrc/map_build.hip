@@ -16,7 +16,8 @@
 // of its own, at the old map's scale.  The GROWN forms (clc_map_build_grow_dev, clc_map_init_grow_batch_dev,
 // clc_map_update_grow_batch_dev) put map_stage_grown between the two halves: the resection loop over the other cameras, whose kernels
 // are map_grow.hip's and whose solve is the a-contrario launch path (resect_solve, pose_batch.hip); the capacity check and the host
-// outputs then describe the grown map, and the install gathers every row from the block of the camera the stage names for it.
+// outputs then describe the grown map, and the install gathers every row from the block of the camera the stage names for it.  The
+// _grow_ba_ forms (map_ba.hip) bundle-adjust the per-track state behind the loop's last camera, before the rows are compacted.
 // Sizes: 8 cameras x 10 k rows, 28 pairs are 80 k nodes and up to ~260 k edges.  The two single-workgroup kernels walk 80 k nodes /
 // some 10 k tracks in passes of 1 024: latency-bound like the gathers, and what keeps the order a matter of one ballot per wave.
 #include "clc_ctx.h"
@@ -398,7 +399,7 @@ void grow_outputs_none(clc_map_grow& gr)
 // The STAGE half of a grown build: map_stage, then -- between it and the install -- the resection loop of reconstructScene
 // (Reconstructor.hpp:153-154) on the per-track state and the grown map's rows.  Per camera the host waits for the resection count and
 // for the solve's rounds, as every a-contrario solve does; after the last camera for one more word, the grown map's row count.
-int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged& out)
+int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged& out, clc_map_ba* ba = nullptr)
 {
     grow_outputs_none(gr);
     if (gr.max_iteration < 0) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_grow: negative max_iteration");
@@ -468,6 +469,22 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
         e = launch_grow(s, cams, I, nt, st);
         if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the grow launch", e); }
     }
+    // refinePose (Reconstructor.hpp:160-161; map_ba.hip): the valid cameras' poses and the landmarks X[t] adjusted where they lie.  obs is
+    // not written, so every discrete output below is the one of a build without the step.
+    if (ba) {
+        BaProblem pb{};
+        pb.n_cams = n_cams; pb.n_points = std::max(0, std::min(nt, (int)s.cap)); pb.mask = cams.valid;
+        for (int c = 0; c < n_cams; ++c) {
+            pb.K[c][0] = cams.side[c].cam.focal; pb.K[c][1] = cams.side[c].cam.ppx; pb.K[c][2] = cams.side[c].cam.ppy;
+            memcpy(pb.Rt[c], cams.Rt[c], sizeof pb.Rt[c]);
+        }
+        pb.X = s.X; pb.obs = s.obs; pb.x = nullptr; pb.cams = &cams; pb.table = s.table;
+        rc = ba_drive(ctx, pb, *ba);
+        if (rc != CLC_OK) return job.status = rc;
+        for (int c = 0; c < n_cams; ++c)
+            if ((cams.valid >> c) & 1u) memcpy(gr.Rt[c], pb.Rt[c], sizeof gr.Rt[c]);
+        memcpy(job.Rt_seed_a, pb.Rt[d.cam_i], sizeof job.Rt_seed_a); memcpy(job.Rt_seed_b, pb.Rt[d.cam_j], sizeof job.Rt_seed_b);
+    }
     // setupMapDatabase over the landmarks: the rows in track-id order, over the staged seed map's lists
     __atomic_store_n(h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
     GrowMapOut mo{};
@@ -492,18 +509,18 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
     return CLC_OK;
 }
 
-int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr)
+} // namespace
+
+int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, clc_map_ba* ba)
 {
     MapStaged staged;
-    const int rc = map_stage_grown(ctx, job, gr, staged);
+    const int rc = map_stage_grown(ctx, job, gr, staged, ba);
     return rc == CLC_OK ? map_install(ctx, job, staged) : rc;
 }
 
-} // namespace
-
 // clc_map_init_batch_dev (align == null) and clc_map_update_batch_dev (map_update.hip): the filters, the selection, the seed poses and the
 // stage half are ONE path; what follows the stage half differs -- the install above, or the align step at the old map's scale.
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr)
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr, clc_map_ba* ba)
 {
     if (gr) grow_outputs_none(*gr);
     if (align) { align->n_old = 0; align->n_common = 0; align->n_terms = 0; align->status = CLC_MAP_ALIGN_NO_SCALE; align->scale = 1.0; }
@@ -563,7 +580,7 @@ int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, c
     void* const after = job->after_stream;
     job->tracks.pairs = tp.data(); job->seed_pair = seed; job->after_stream = nullptr;
     MapStaged staged;
-    int rc = gr ? map_stage_grown(c0, *job, *gr, staged) : map_stage(c0, *job, staged);
+    int rc = gr ? map_stage_grown(c0, *job, *gr, staged, ba) : map_stage(c0, *job, staged);
     if (rc == CLC_OK) rc = align ? map_align_staged(c0, *job, staged, *align, gr) : map_install(c0, *job, staged);
     job->tracks.pairs = callers; job->after_stream = after;
     // (the union launch read the other contexts' blocks and pinned lists; it ran before the count the build waited for came out)
@@ -609,7 +626,7 @@ int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_
 int clc_map_build_grow_dev(clc_ctx* ctx, clc_map_job* job, clc_map_grow* grow)
 {
     if (!ctx || !job || !grow) return fail(ctx, CLC_ERR_BAD_ARG, "map_build_grow: null context / job / grow");
-    return map_build_grow(ctx, *job, *grow);
+    return map_build_grow(ctx, *job, *grow, nullptr);
 }
 
 int clc_map_init_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow)

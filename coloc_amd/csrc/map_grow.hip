@@ -12,7 +12,8 @@
 //   grow_compact_kernel    ONE workgroup: the ordered compaction over the tracks with a landmark -> the map's rows in track-id order,
 //                          row = { X, track, camera of the lowest set bit, that camera's row, mask }; the count last
 // The solve between the gather and the grow is the a-contrario launch path itself (resect_solve, pose_batch.hip).  Some 10 k tracks:
-// latency-bound like the seed launch; nothing here is tuned and nothing is claimed of its speed.
+// latency-bound like the seed launch; nothing here is tuned and nothing is claimed of its speed.  The bundle adjustment that follows the
+// loop in the reference (Reconstructor.hpp:160-161) works on this state between the last grow_kernel and grow_compact_kernel: map_ba.hip.
 #include "clc_ctx.h"
 #include "map_math.h"
 #include "ud_pixel.h"

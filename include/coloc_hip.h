@@ -910,7 +910,8 @@ int clc_inter_front_dev(clc_ctx* ctx, const double* d_x1, const double* d_x2, in
  * ExportToSTL), the seed pair's landmarks of Reconstructor::triangulatePoints (:185-239) and the map database of
  * colocData::setupMapDatabase (colocData.hpp:89-121), from the pairs' correspondences where clc_pair_filter_batch_dev left them.  It
  * ends where reconstructScene writes initial.ply; the resectionCamera loop behind it is clc_map_build_grow_dev's (the section after
- * the next); no bundle adjustment, no PLY.  (Later under ABI 4: new entry points only.)
+ * the next) and the bundle adjustment behind that loop clc_map_build_grow_ba_dev's (the section after that); no PLY.  (Later under
+ * ABI 4: new entry points only.)
  *
  * TRACKS.  A node is a (camera, feature row) named by a match; an edge is a match (cam_a, q)-(cam_b, t) of a pair cam_a < cam_b; a
  * track is a connected component.  The rules are this project's statement of OpenMVG's TracksBuilder (an empty submodule in the
@@ -1077,7 +1078,8 @@ int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int 
 /* ---- the map grown past the seed pair: resect the other cameras, add their tracks ---------------------------------------------------
  * What Reconstructor::reconstructScene runs after the seed triangulation: `for (auto resectionId : resectionList)
  * resectionCamera(resectionId)` (Reconstructor.hpp:153-154, 259-415), and setupMapDatabase (colocData.hpp:89-121) over the landmarks
- * that loop leaves.  Bundle adjustment (:160-161) and the PLY files are NOT covered.  OpenMVG is an empty submodule in the reference
+ * that loop leaves.  The bundle adjustment behind the loop (:160-161) is the next section's (clc_map_build_grow_ba_dev); the PLY files
+ * are NOT covered.  OpenMVG is an empty submodule in the reference
  * tree: as for the tracks and the ratio matcher, the rules below are this project's statement of SfM_Localizer::Localize,
  * TriangulateDLT and AngleBetweenRay, and their parity with OpenMVG is unpinned.  (Later under ABI 4: new entry points only.)
  *
@@ -1147,6 +1149,85 @@ int clc_map_update_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs,
                                   clc_map_grow* grow);
 int clc_map_resect_build_dev(clc_ctx* ctx, const clc_map_job* job, int camera, double* d_X, double* d_x, int32_t* d_track, int32_t* d_row,
                              int32_t* d_n, void* stream);
+
+/* ---- the grown map bundle-adjusted: every valid camera's pose and every landmark, by Schur Levenberg-Marquardt ----------------------
+ * What Reconstructor::reconstructScene ends with: `if (Adjust) refiner.refinePose(*scene, ba_refine_options, rmse, cov)`
+ * (Reconstructor.hpp:160-161; both call sites pass Adjust = true) under intrinsics NONE, extrinsics ADJUST_ALL, structure ADJUST_ALL
+ * and ceres::HuberLoss(Square(4.0)) (Refiner.hpp:47-239).  Ceres is absent from the reference tree, so -- as for clc_pnp_refine -- this
+ * is a Levenberg-Marquardt of this project's on the same cost, and iterate parity is unpinned.  (Later under ABI 4: new entry points
+ * only.)  The arithmetic is stated once, host + device, in coloc_amd/csrc/ba_math.h; the kernels are coloc_amd/csrc/map_ba.hip.
+ *
+ * COST  1/2 sum rho(|r|^2) over every set bit of obs[t] that names a camera of cam_mask: r = x_ud - (focal (R X + t).hnormalized() +
+ *   pp), x_ud the UNDISTORTED pixel (get_ud_pixel, as the grow uses it), rho(s) = s for s <= a^2, 2 a sqrt(s) - a^2 beyond, weights 1 /
+ *   a / |r| (clc_pnp_refine's), a = huber_a, 16 where huber_a <= 0.  Intrinsics are constant.  DEVIATION 1: Ceres' Radial_K3 functor
+ *   distorts inside the projection, here the observation is undistorted instead; the two agree at k = 0.
+ * PARAMETERS  per camera [angle-axis | t], per landmark X; NO block is held constant, as in the reference.  The seven gauge directions
+ *   (the similarity that moves cameras and points together) are left to the damping: only gauge-invariant quantities -- the cost, the
+ *   reprojections -- mean anything across two runs of different arithmetic.
+ * STEP  the Schur complement on the landmarks: S = U + lambda diag(U) - sum_t W (V_t + lambda diag V_t)^-1 W^T over the 6 n_cams <=
+ *   48 camera unknowns, dense Cholesky, landmarks by back-substitution.  lambda starts at 1e-4; an accepted step multiplies it by 0.1
+ *   (floor 1e-12), a rejected one by 10; a step is rejected when its cost is not finite or not lower, or when a factorisation fails.  A
+ *   trial point at depth <= 0 under an observing camera costs +inf.  A landmark with ONE observation stays in (the reference hands it to
+ *   Ceres): its V has rank 2 and the damping makes it invertible.
+ * STOP  CLC_BA_OK: relative cost decrease < function_tolerance (0: 1e-8, Refiner.hpp:167), or clc_pnp_refine's gradient / parameter
+ *   tests; CLC_BA_MAX_ITERATIONS after max_iterations steps (0: 500, Refiner.hpp:159), rejected ones counted; CLC_BA_STALLED at lambda >
+ *   1e10.  The result is the last ACCEPTED iterate: cost_final <= cost_initial always; with no accepted step nothing is written.
+ *   rmse = sqrt(cost_final / (2 n_obs)) (Refiner.hpp:223).  n_points counts the points with an observation that counts, n_cams the
+ *   cameras of cam_mask.  DEVIATION 2: the 6 x 6 covariance block the reference computes here is never read by reconstructScene; it is
+ *   not computed.
+ * CLC_BA_BAD_START: the cost at the start is not finite (a point at depth <= 0 under an observing camera).  CLC_BA_EMPTY: no
+ *   observation counts.  Both return CLC_OK, write nothing, and a composition installs the map unadjusted.
+ * DETERMINISM  no floating-point atomics.  The points that carry an observation are first compacted in ascending index; every sum over
+ *   points is formed over that list -- 128 consecutive entries per workgroup in order, the workgroups' sums in order.  Two runs on one
+ *   input give the same bits; appending or interleaving points with obs = 0 changes no bit, and such points are not touched.
+ *
+ * clc_ba_dev: the step alone on arrays in device memory.  Rt[c] of the cameras in cam_mask and d_X are read and -- when a step was
+ * accepted -- rewritten; cameras outside cam_mask, points without a bit of cam_mask and d_obs / d_x are never written; x of (t, c) is
+ * read only where bit c of d_obs[t] is set.  The launches are enqueue-only on the CONTEXT's stream -- an iteration is a chain of five
+ * short launches, no kernel waits for another workgroup -- in rounds of several iterations; per round the host waits for ONE pinned
+ * record { state, iterations, cost_initial, cost, lambda, poses }, released last behind a system-scope fence.  No array moves through
+ * the host.  ORDERING: on return every launch has run and the arrays are final.  after_stream: as clc_map_job -- the launches are
+ * ordered behind that stream's work by one event.  The scratch lives in one block of the context that grows on demand: a call that
+ * needs more than any call before it synchronises the context's stream and allocates anew.  ERRORS (CLC_ERR_BAD_ARG): a null job,
+ * n_cams outside [1, CLC_MAX_BATCH], a negative n_points / max_iterations / function_tolerance, a null or misaligned pointer with
+ * n_points > 0, a focal <= 0 of a camera in cam_mask.
+ *
+ * clc_map_build_grow_ba_dev / clc_map_init_grow_ba_batch_dev / clc_map_update_grow_ba_batch_dev: their _grow_ namesakes with the step
+ * between the last camera's grow and the compaction into map rows, over tracks 0 .. n_tracks - 1 of the per-track state (X[t], obs[t])
+ * and the valid cameras, pixels through get_ud_pixel from the cameras' 2-D sides.  The discrete outputs -- map_track, map_row,
+ * map_cam, map_obs, map_n, n_added, every resection field -- are those of the call without the step; job->X, grow->Rt and
+ * job->Rt_seed_a / Rt_seed_b come back refined, and in the update form the align step then rescales the refined points and centres.
+ * With no resected camera the two seed cameras and their tracks are adjusted.  Of `ba` max_iterations, huber_a and
+ * function_tolerance are read.  A null ba, a negative count or tolerance: CLC_ERR_BAD_ARG before anything is launched; on every error
+ * the previous map serves as before.  Ordering, after_stream and the other errors: as the _grow_ calls. */
+enum { CLC_BA_OK = 0, CLC_BA_MAX_ITERATIONS = 1, CLC_BA_STALLED = 2 /* lambda > 1e10 */, CLC_BA_BAD_START = 3, CLC_BA_EMPTY = 4 };
+typedef struct clc_map_ba {
+    /* in */
+    int    max_iterations;       /* 0: 500 */
+    double huber_a;              /* <= 0: 16 */
+    double function_tolerance;   /* 0: 1e-8 */
+    /* out */
+    int    status, iterations, n_cams, n_points, n_obs;
+    double cost_initial, cost_final, rmse;
+} clc_map_ba;
+typedef struct clc_ba_job {          /* the step alone, on arrays the caller holds in device memory */
+    int             n_cams;
+    uint32_t        cam_mask;                  /* bit c: camera c is adjusted and its observations count */
+    clc_camera_k3   cam[CLC_MAX_BATCH];        /* focal, ppx, ppy are read */
+    double          Rt[CLC_MAX_BATCH][12];     /* in / out */
+    int             n_points;
+    double*         d_X;                       /* n_points x 3, in / out */
+    const uint32_t* d_obs;                     /* n_points masks, 0 = no point */
+    const double*   d_x;                       /* n_points x n_cams x 2 undistorted pixels, read where the bit is set */
+    void*           after_stream;              /* nullable */
+    clc_map_ba      ba;
+} clc_ba_job;
+int clc_ba_dev(clc_ctx* ctx, clc_ba_job* job);
+int clc_map_build_grow_ba_dev(clc_ctx* ctx, clc_map_job* job, clc_map_grow* grow, clc_map_ba* ba);
+int clc_map_init_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow,
+                                   clc_map_ba* ba);
+int clc_map_update_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align,
+                                     clc_map_grow* grow, clc_map_ba* ba);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
