@@ -77,6 +77,15 @@ class PairJob(C.Structure):
                 ("error_max", C.c_double), ("min_nfa", C.c_double)]
 
 
+class GuidedJob(C.Structure):
+    """clc_guided_job (include/coloc_hip.h)"""
+    _fields_ = [("d_q", C.c_void_p), ("nq", C.c_int), ("d_t", C.c_void_p), ("nt", C.c_int), ("d_count_a", C.c_void_p), ("d_count_b", C.c_void_p),
+                ("d_kps_a", C.c_void_p), ("d_feat_a", C.c_void_p), ("feat_stride_a", C.c_int),
+                ("d_kps_b", C.c_void_p), ("d_feat_b", C.c_void_p), ("feat_stride_b", C.c_int),
+                ("cam_a", CameraK3), ("cam_b", CameraK3), ("F", C.c_double * 9), ("band", C.c_float), ("threshold", C.c_int),
+                ("d_match", C.c_void_p), ("d_best", C.c_void_p), ("d_second", C.c_void_p), ("d_line", C.c_void_p), ("d_tpos", C.c_void_p)]
+
+
 MAX_BATCH, MAX_TRACK_PAIRS = 8, 28          # CLC_MAX_BATCH, CLC_MAX_TRACK_PAIRS
 
 
@@ -195,6 +204,7 @@ EXPORTS = [
     "clc_map_align_dev", "clc_map_update_batch_dev",
     "clc_map_build_grow_dev", "clc_map_init_grow_batch_dev", "clc_map_update_grow_batch_dev", "clc_map_resect_build_dev",
     "clc_ba_dev", "clc_map_build_grow_ba_dev", "clc_map_init_grow_ba_batch_dev", "clc_map_update_grow_ba_batch_dev",
+    "clc_match_guided_dev", "clc_match_guided_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -363,6 +373,8 @@ def load_library():
     lib.clc_map_build_grow_ba_dev.argtypes = [vp, vp, vp, vp]
     lib.clc_map_init_grow_ba_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp]
     lib.clc_map_update_grow_ba_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    lib.clc_match_guided_dev.argtypes = [vp, vp, vp]
+    lib.clc_match_guided_batch_dev.argtypes = [vp, vp, ci, vp]
     _lib = lib
     return lib
 
@@ -697,6 +709,18 @@ def _pair_result(j, M, F, pq, pt, x1, x2, inl, mask):
     return dict(M=M.reshape(3, 3).copy() if found else None, F=F.reshape(3, 3).copy() if found else None, n_pairs=j.n_pairs,
                 pair_q=pq[:n].copy(), pair_t=pt[:n].copy(), x1=x1[:n].copy(), x2=x2[:n].copy(), inliers=inl[:j.n_inliers].copy(),
                 mask=mask[:n].astype(bool), error_max=j.error_max, min_nfa=j.min_nfa, iterations=j.iterations, status=j.status)
+
+
+def _guided_fill(j, d_q, nq, d_t, nt, cam_a, cam_b, F, band, threshold, d_match, d_kps_a=None, d_feat_a=None, feat_stride_a=4, d_kps_b=None,
+                 d_feat_b=None, feat_stride_b=4, d_count_a=None, d_count_b=None, d_best=None, d_second=None, d_line=None, d_tpos=None):
+    """fills a GuidedJob; cam_* = (focal, ppx, ppy, k1, k2, k3), F = 9 numbers row-major (pixels, x_b^T F x_a = 0); device pointers as integers"""
+    j.d_q, j.nq, j.d_t, j.nt, j.d_count_a, j.d_count_b = d_q, int(nq), d_t, int(nt), d_count_a, d_count_b
+    j.d_kps_a, j.d_feat_a, j.feat_stride_a = d_kps_a, d_feat_a, int(feat_stride_a)
+    j.d_kps_b, j.d_feat_b, j.feat_stride_b = d_kps_b, d_feat_b, int(feat_stride_b)
+    j.cam_a, j.cam_b = CameraK3(*[float(v) for v in cam_a]), CameraK3(*[float(v) for v in cam_b])
+    j.F = (C.c_double * 9)(*[float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)])
+    j.band, j.threshold = float(band), int(threshold)
+    j.d_match, j.d_best, j.d_second, j.d_line, j.d_tpos = d_match, d_best, d_second, d_line, d_tpos
 
 
 def pair_filter_batch_dev(ctxs, model, jobs):
@@ -1440,6 +1464,22 @@ class Context:
         j = PairJob()
         _pair_fill(j, None, outputs=False, **job)
         self._chk(self.lib.clc_pair_build_dev(self.h, C.byref(j), d_x1, d_x2, d_pair_q, d_pair_t, d_n, stream))
+
+    def match_guided_dev(self, stream=None, **job):
+        """clc_match_guided_dev: K2NN over the train rows within `band` pixels of the query's epipolar line under F, enqueue only.
+        Keywords: d_q, nq, d_t, nt, cam_a / cam_b = (focal, ppx, ppy, k1, k2, k3), d_kps_a or d_feat_a (+ feat_stride_a), the same for b,
+        d_count_a, d_count_b, F (9, pixels, x_b^T F x_a = 0), band, threshold, d_match and the nullable d_best, d_second, d_line, d_tpos."""
+        j = GuidedJob()
+        _guided_fill(j, **job)
+        self._chk(self.lib.clc_match_guided_dev(self.h, C.byref(j), stream))
+
+    def match_guided_batch_dev(self, jobs, stream=None):
+        """clc_match_guided_batch_dev: jobs = [dict(the keywords of match_guided_dev), ...], at most MAX_TRACK_PAIRS, one sweep launch."""
+        n = len(jobs)
+        arr = (GuidedJob * max(n, 1))()
+        for i in range(n):
+            _guided_fill(arr[i], **jobs[i])
+        self._chk(self.lib.clc_match_guided_batch_dev(self.h, arr, n, stream))
 
     def pair_filter_dev(self, model, **job):
         """clc_pair_filter_dev: computeRelativePose's gather + the a-contrario filter of model 'E' | 'F' | 'H' from device memory.  Keywords:

@@ -1,0 +1,401 @@
+// k2nn_guided.hip -- the guided match: K2NN's top-2 and acceptance over the train rows within `band` pixels of the query's epipolar
+// line under a known F (include/coloc_hip.h, clc_match_guided_dev / clc_match_guided_batch_dev, which state the rule).
+//
+// Two kernels, both enqueue-only on the caller's stream:
+//   guided_prep_kernel        one thread per row of either camera: feature position, get_ud_pixel in fp64 (ud_pixel.h, the copy the pair
+//                             kernel runs), then guided_line (guided_math.h) for a query row -> L, 3 floats; the pixel rounded to float for a
+//                             train row -> (x, y), 2 floats.  Rows past a device-side count, and queries without a line, carry NaNs: they
+//                             can never pass the gate.
+//   k2nn_sweep_guided_kernel  the popcount sweep of k2nn.hip (lane = query, the train row wave-uniform in SGPRs, the same 2-D
+//                             decomposition, plan, atomic fold and arrival-counter finalize) with the gate: the lane keeps the lines of its
+//                             kR queries in six VGPRs, the train point arrives as the train row does -- one s_load_dwordx2 beside the
+//                             s_load_dwordx16, a vector ahead --, and a non-candidate's key becomes kEmpty in front of the med3 / min pair
+//                             (v_fma, v_fma, v_cmp, v_cndmask per pair: no branch).  Each v_fma reads ONE scalar operand (the train
+//                             coordinate) next to two vector operands, the v_cmp one (the band): within the one-SGPR-per-instruction rule
+//                             of the gfx9 vector ALU, so no v_mov copies a scalar into the loop.
+// It runs whatever formulation the context is set to: a per-pair gate has no place in the matrix sweep, whose C operand is per tile.
+// The jobs travel in records of their own (GuidedJobList), not in K2nnJobDev: the existing sweep kernels are compiled as they were.
+#include "clc_ctx.h"
+#include "guided_math.h"
+#include "k2nn_sweep.h"
+#include "k2nn_top2.h"
+#include "ud_pixel.h"
+
+#include <cmath>
+#include <vector>
+
+namespace clc {
+
+namespace {
+
+constexpr int kGuidedMaxJobs = CLC_MAX_TRACK_PAIRS;
+// One prep record is 272 bytes (two cameras and F in fp64), so a 4 KB kernel argument carries 14 of them: a batch of up to 14 jobs is
+// ONE prep launch, a larger one (up to kGuidedMaxJobs = 28) two.  The sweep's records are smaller: always ONE sweep launch.
+constexpr int kGuidedPrepJobs = 14;
+
+struct GuidedPrepJob {
+    GatherSide a, b;                  // the two cameras' rows, counts and intrinsics, as the pair kernel takes them
+    double F[9];
+    uint32_t nq, nt;                  // planned rows
+    float* L; float* pos;             // the context's scratch: 3 nq / 2 nt floats
+    float* line_out; float* tpos_out; // the caller's copies, nullable
+};
+struct GuidedPrepList {
+    GuidedPrepJob j[kGuidedPrepJobs];
+    float scale[CLC_MAX_LEVELS];      // as PairJobs::scale
+};
+static_assert(sizeof(GuidedPrepList) <= 4096, "GuidedPrepList is passed as a kernel argument: it must stay within the 4 KB kernarg segment");
+
+struct GuidedJobDev {
+    const uint4* q; const uint4* t;
+    int32_t* out; uint16_t* best_out; uint16_t* second_out;
+    const float* L; const float* pos;
+    const uint32_t* cnt_q; const uint32_t* cnt_t;                     // nullable: the detectors' count words
+    uint32_t nq, nt, thr;
+    uint32_t qblocks, splits, t_per_split, partial_off, cnt_off;      // k2nn_plan's, popcount formulation, atomic fold
+    float band;
+    uint32_t pad_;
+};
+struct GuidedJobList { GuidedJobDev j[kGuidedMaxJobs]; };
+static_assert(sizeof(GuidedJobList) <= 4096, "GuidedJobList is passed as a kernel argument: it must stay within the 4 KB kernarg segment");
+
+typedef const u32x2 __attribute__((address_space(4)))* const_u2_ptr;
+typedef const float __attribute__((address_space(1)))* global_cf_ptr;
+
+__device__ __forceinline__ uint32_t counted(const uint32_t planned, const uint32_t* count)
+{
+    if (!count) return planned;
+    const uint32_t c = count[0];
+    return c < planned ? c : planned;
+}
+
+__global__ __launch_bounds__(256) void guided_prep_kernel(const GuidedPrepList jobs)
+{
+    const GuidedPrepJob& jb = jobs.j[blockIdx.y];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= jb.nq + jb.nt) return;
+    const bool is_q = i < jb.nq;
+    const uint32_t row = is_q ? i : i - jb.nq;
+    const GatherSide& s = is_q ? jb.a : jb.b;
+    const bool there = row < counted(is_q ? jb.nq : jb.nt, s.count);
+    double u[2] = { 0.0, 0.0 };
+    if (there) {
+        float fx, fy;
+        feature_position(s.kps, s.feat, s.feat_stride, row, jobs.scale, &fx, &fy);
+        ud_pixel(fx, fy, s.cam, u);
+    }
+    if (is_q) {
+        float L[3] = { guided_none(), guided_none(), guided_none() };
+        if (there) guided_line(jb.F, u[0], u[1], L);
+        float* o = jb.L + 3u * (size_t)row;
+        o[0] = L[0]; o[1] = L[1]; o[2] = L[2];
+        if (jb.line_out) { float* c = jb.line_out + 3u * (size_t)row; c[0] = L[0]; c[1] = L[1]; c[2] = L[2]; }
+    } else {
+        const float x = there ? (float)u[0] : guided_none(), y = there ? (float)u[1] : guided_none();
+        float* o = jb.pos + 2u * (size_t)row;
+        o[0] = x; o[1] = y;
+        if (jb.tpos_out) { float* c = jb.tpos_out + 2u * (size_t)row; c[0] = x; c[1] = y; }
+    }
+}
+
+// One train vector (16 wave-uniform dwords in SGPRs) and its point (2 more) against the R queries of this lane: sweep_one of k2nn.hip --
+// the same xor / popcount pairs, in its measured issue pattern (see there) -- with the key formed and gated in C++ behind them:
+// key = (distance << 22) + index, or kEmpty outside the band (guided_in_band, the one statement of the gate); then the med3 / min pair.
+template <int R>
+__device__ __forceinline__ void sweep_one_guided(const uint32_t (&q)[R][16], const float (&L)[R][3], const u32x4 a, const u32x4 b, const u32x4 c,
+                                                 const u32x4 d, const u32x2 p, const float band, const uint32_t t_rel, uint32_t (&best)[R],
+                                                 uint32_t (&second)[R])
+{
+    const float x = __uint_as_float(p.x), y = __uint_as_float(p.y);
+#define K2NN_PAIR(t, q, accin) "v_xor_b32 %1, " t ", " q "\n\tv_bcnt_u32_b32 %0, %1, " accin "\n\ts_nop 0\n\t"
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        uint32_t acc, tmp;
+        asm volatile(K2NN_PAIR("%10", "%2", "0") K2NN_PAIR("%11", "%3", "%0") K2NN_PAIR("%12", "%4", "%0") K2NN_PAIR("%13", "%5", "%0")
+                     K2NN_PAIR("%14", "%6", "%0") K2NN_PAIR("%15", "%7", "%0") K2NN_PAIR("%16", "%8", "%0") K2NN_PAIR("%17", "%9", "%0")
+                     : "=&v"(acc), "=&v"(tmp)
+                     : "v"(q[r][0]), "v"(q[r][1]), "v"(q[r][2]), "v"(q[r][3]), "v"(q[r][4]), "v"(q[r][5]), "v"(q[r][6]), "v"(q[r][7]),
+                       "s"(a.x), "s"(a.y), "s"(a.z), "s"(a.w), "s"(b.x), "s"(b.y), "s"(b.z), "s"(b.w));
+        asm volatile(K2NN_PAIR("%10", "%2", "%0") K2NN_PAIR("%11", "%3", "%0") K2NN_PAIR("%12", "%4", "%0") K2NN_PAIR("%13", "%5", "%0")
+                     K2NN_PAIR("%14", "%6", "%0") K2NN_PAIR("%15", "%7", "%0") K2NN_PAIR("%16", "%8", "%0") K2NN_PAIR("%17", "%9", "%0")
+                     : "+v"(acc), "=&v"(tmp)
+                     : "v"(q[r][8]), "v"(q[r][9]), "v"(q[r][10]), "v"(q[r][11]), "v"(q[r][12]), "v"(q[r][13]), "v"(q[r][14]), "v"(q[r][15]),
+                       "s"(c.x), "s"(c.y), "s"(c.z), "s"(c.w), "s"(d.x), "s"(d.y), "s"(d.z), "s"(d.w));
+        uint32_t key = (acc << kKeyShift) + t_rel;
+        key = guided_in_band(L[r][0], L[r][1], L[r][2], x, y, band) ? key : kEmpty;
+        second[r] = top2_med3(best[r], second[r], key);
+        best[r] = top2_min(best[r], key);
+    }
+#undef K2NN_PAIR
+}
+
+template <int R>
+__global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const GuidedJobList jobs, uint2* __restrict__ partial)
+{
+    __shared__ uint32_t s_best[kWaves - 1][R][64], s_second[kWaves - 1][R][64];
+    const GuidedJobDev& job = jobs.j[blockIdx.y];
+    if (job.nt == 0u) return;                                             // nothing planned to sweep: guided_nomatch_kernel answers
+    const uint32_t job_nq = counted(job.nq, job.cnt_q), job_nt = counted(job.nt, job.cnt_t);
+    const uint32_t nblk = job.qblocks * job.splits;
+    if (blockIdx.x >= nblk) return;
+    const uint32_t qblock = blockIdx.x / job.splits;                      // (a multiple of 8 splits pins a train split to an XCD: k2nn.hip)
+    const uint32_t split = blockIdx.x - qblock * job.splits;
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t qbase = qblock * (64u * R) + lane;
+
+    uint32_t q[R][16];
+    float L[R][3];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        uint32_t qi = qbase + 64u * r;
+        if (qi >= job_nq) qi = job_nq ? job_nq - 1u : 0u;   // clamp: duplicate work, never stored (row 0 of the block always exists)
+        const global_cu4_ptr qp = (global_cu4_ptr)(uintptr_t)job.q + (size_t)qi * 4u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u32x4 v = qp[k];
+            q[r][4 * k + 0] = v.x; q[r][4 * k + 1] = v.y; q[r][4 * k + 2] = v.z; q[r][4 * k + 3] = v.w;
+        }
+        const global_cf_ptr lp = (global_cf_ptr)(uintptr_t)job.L + (size_t)qi * 3u;
+        L[r][0] = lp[0]; L[r][1] = lp[1]; L[r][2] = lp[2];
+    }
+    uint32_t best[R], second[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { best[r] = kEmpty; second[r] = kEmpty; }
+    const float band = job.band;
+
+    // this wave's share [t0, t1) of the workgroup's split [s0, s1)
+    const uint32_t s0 = min(split * job.t_per_split, job_nt);
+    const uint32_t s1 = min(s0 + job.t_per_split, job_nt);
+    const uint32_t per_wave = (s1 - s0 + kWaves - 1) / kWaves;
+    const uint32_t t0 = min(s0 + wave * per_wave, s1);
+    const uint32_t t1 = min(t0 + per_wave, s1);
+
+    // the software-pipelined scalar loads of k2nn_sweep_kernel, the train point riding beside the train row in both buffers; neither
+    // prefetch reads past the slice
+    const_u4_ptr tp = (const_u4_ptr)(uintptr_t)job.t + (size_t)t0 * 4u;   // wave-uniform -> s_load_dwordx16
+    const_u2_ptr pp = (const_u2_ptr)(uintptr_t)job.pos + (size_t)t0;      // wave-uniform -> s_load_dwordx2
+    if (t0 < t1) {
+        const uint32_t n = t1 - t0;
+        u32x4 a0 = tp[0], b0 = tp[1], c0 = tp[2], d0 = tp[3];
+        u32x2 p0 = pp[0];
+        uint32_t t = t0;
+        for (uint32_t pair = 0; pair < (n >> 1); ++pair, t += 2) {
+            __builtin_amdgcn_s_waitcnt(0xC07F);                 // lgkmcnt(0): buffer 0 (vector t) has landed
+            __builtin_amdgcn_sched_barrier(0);
+            const u32x4 a1 = tp[4], b1 = tp[5], c1 = tp[6], d1 = tp[7];          // vector t+1 -> buffer 1
+            const u32x2 p1 = pp[1];
+            __builtin_amdgcn_sched_barrier(0);
+            sweep_one_guided<R>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0xC07F);                 // buffer 1 has landed
+            __builtin_amdgcn_sched_barrier(0);
+            const bool more = t + 2 < t1;                       // vector t+2 -> buffer 0 (never past the slice)
+            const_u4_ptr np = more ? tp + 8 : tp;
+            const_u2_ptr npp = more ? pp + 2 : pp;
+            a0 = np[0]; b0 = np[1]; c0 = np[2]; d0 = np[3];
+            p0 = npp[0];
+            __builtin_amdgcn_sched_barrier(0);
+            sweep_one_guided<R>(q, L, a1, b1, c1, d1, p1, band, t + 1 - s0, best, second);
+            __builtin_amdgcn_sched_barrier(0);
+            tp += 8;
+            pp += 2;
+        }
+        if (n & 1u) sweep_one_guided<R>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
+    }
+
+    // fold the kWaves waves through LDS (k2nn_sweep_kernel)
+    if (wave != 0) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) { s_best[wave - 1][r][lane] = best[r]; s_second[wave - 1][r][lane] = second[r]; }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+#pragma unroll
+    for (int w = 0; w < kWaves - 1; ++w) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const uint32_t ob = s_best[w][r][lane], os = s_second[w][r][lane];
+            second[r] = min(min(second[r], os), max(best[r], ob));
+            best[r] = min(best[r], ob);
+        }
+    }
+
+    // the atomic fold and the arrival-counter finalize of k2nn_sweep_kernel, statement for statement (see there for why the returning
+    // atomics and the vmcnt(0) make the last arrival's exchange see every split, without a fence)
+    unsigned int* top = reinterpret_cast<unsigned int*>(partial + job.partial_off);
+    uint32_t seen = 0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t qi = qbase + 64u * r;
+        if (qi < job_nq && best[r] != kEmpty) {
+            const uint32_t bkey = best[r] + s0;
+            const uint32_t skey = second[r] == kEmpty ? kEmpty : second[r] + s0;
+            const uint32_t old = atomicMin(top + 2u * qi, bkey);
+            const uint32_t cand = bkey < old ? min(old, skey) : bkey;
+            seen |= old;
+            if (cand != kEmpty) seen |= atomicMin(top + 2u * qi + 1u, cand);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(seen) : : "memory");
+    unsigned int* cnt = reinterpret_cast<unsigned int*>(partial) + job.cnt_off + qblock;
+    uint32_t arrival = 0;
+    if (lane == 0) arrival = atomicAdd(cnt, 1u) + 1u;
+    arrival = __builtin_amdgcn_readfirstlane(arrival);
+    if (arrival != job.splits - 1u) return;
+    if (lane == 0) atomicExch(cnt, kEmpty);
+    K2nnJobDev fin{};                                     // what emit_result reads of a job
+    fin.out = job.out; fin.best_out = job.best_out; fin.second_out = job.second_out; fin.thr = job.thr;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t qi = qbase + 64u * r;
+        if (qi < job.nq) {          // every PLANNED row gets an answer; rows past a device-side count hold no key -> -1
+            const uint32_t bkey = atomicExch(top + 2u * qi, kEmpty);
+            const uint32_t skey = atomicExch(top + 2u * qi + 1u, kEmpty);
+            emit_result<false>(fin, qi, bkey, skey);
+        }
+    }
+}
+
+// jobs with an EMPTY planned train set: no sweep workgroup exists that could finalize them (k2nn_nomatch_kernel's part)
+__global__ __launch_bounds__(256) void guided_nomatch_kernel(const GuidedJobList jobs)
+{
+    const GuidedJobDev& job = jobs.j[blockIdx.y];
+    const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
+    if (job.nt != 0u || qi >= job.nq) return;
+    K2nnJobDev fin{};
+    fin.out = job.out; fin.best_out = job.best_out; fin.second_out = job.second_out; fin.thr = job.thr;
+    emit_result<false>(fin, qi, kEmpty, kEmpty);
+}
+
+// the arguments of one job, checked; its two sides into `pd`
+int guided_inputs(clc_ctx* ctx, const clc_guided_job& job, PairJobDev& pd)
+{
+    const auto bad = [&](const char* what) { return fail(ctx, CLC_ERR_BAD_ARG, what); };
+    if (job.nq < 0 || job.nt < 0 || (job.nq > 0 && (!job.d_q || !job.d_match)) || (job.nt > 0 && !job.d_t)) return bad("match_guided: negative count / null block");
+    if (((uintptr_t)job.d_q & 15u) || ((uintptr_t)job.d_t & 15u)) return bad("match_guided: descriptor rows must be 16-byte aligned");
+    if (((uintptr_t)job.d_match & 3u) || ((uintptr_t)job.d_best & 1u) || ((uintptr_t)job.d_second & 1u) || ((uintptr_t)job.d_line & 3u) ||
+        ((uintptr_t)job.d_tpos & 3u))
+        return bad("match_guided: misaligned device pointer");
+    if (!(job.band > 0.f) || !std::isfinite(job.band)) return bad("match_guided: band must be finite and positive");
+    clc_pair_job pj{};
+    pj.d_match = job.d_match; pj.nq = job.nq; pj.nt = job.nt;
+    pj.d_count_a = job.d_count_a; pj.d_count_b = job.d_count_b;
+    pj.d_kps_a = job.d_kps_a; pj.d_feat_a = job.d_feat_a; pj.feat_stride_a = job.feat_stride_a;
+    pj.d_kps_b = job.d_kps_b; pj.d_feat_b = job.d_feat_b; pj.feat_stride_b = job.feat_stride_b;
+    pj.cam_a = job.cam_a; pj.cam_b = job.cam_b;
+    const int rc = gather_inputs(ctx, pj, pd, "match_guided: bad argument");           // the sides' rules are the pair kernel's
+    if (rc != CLC_OK) return rc;
+    if ((uint32_t)job.nt > kIdxMask + 1u) return fail(ctx, CLC_ERR_CAPACITY, "match_guided: more than 2^22 train rows");
+    return CLC_OK;
+}
+
+int guided_batch(clc_ctx* ctx, const clc_guided_job* jobs, const int n_jobs, void* stream)
+{
+    if (!ctx || n_jobs < 0 || n_jobs > kGuidedMaxJobs || (n_jobs > 0 && !jobs)) return fail(ctx, CLC_ERR_BAD_ARG, "match_guided: null context / jobs, or a job count outside 0 .. CLC_MAX_TRACK_PAIRS");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_guided: context created without matcher options");
+    // everything is checked before anything is enqueued
+    std::vector<PairJobDev> sides((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const int rc = guided_inputs(ctx, jobs[j], sides[(size_t)j]);
+        if (rc != CLC_OK) return rc;
+    }
+    std::vector<int> live;                                                   // a job without query rows has nothing to answer
+    for (int j = 0; j < n_jobs; ++j) if (jobs[j].nq > 0) live.push_back(j);
+    if (live.empty()) return CLC_OK;
+    const int n = (int)live.size();
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+
+    // the popcount formulation's plan, whatever the context's sweeps run
+    std::vector<K2nnJobDev> kj((size_t)n);
+    for (int k = 0; k < n; ++k) { kj[(size_t)k] = K2nnJobDev{}; kj[(size_t)k].nq = (uint32_t)jobs[live[(size_t)k]].nq; kj[(size_t)k].nt = (uint32_t)jobs[live[(size_t)k]].nt; }
+    const int target = ctx->target_blocks > 0 && ctx->formulation == K2NN_POPCOUNT ? ctx->target_blocks : default_target_blocks(K2NN_POPCOUNT, ctx->k2dev);
+    const K2nnPlan plan = k2nn_plan(kj.data(), n, target, ctx->xcd_map, K2NN_POPCOUNT, 0, 0, ctx->k2dev);
+    if (!plan.atomic_merge) return fail(ctx, CLC_ERR_CAPACITY, "match_guided: more than 2^22 train rows");
+
+    // scratch: every job's lines, then its train points, each block starting on 16 bytes
+    std::vector<size_t> off_L((size_t)n), off_P((size_t)n);
+    size_t floats = 0;
+    for (int k = 0; k < n; ++k) {
+        off_L[(size_t)k] = floats; floats += (3 * (size_t)kj[(size_t)k].nq + 3) & ~(size_t)3;
+        off_P[(size_t)k] = floats; floats += (2 * (size_t)kj[(size_t)k].nt + 3) & ~(size_t)3;
+    }
+    int rc = grow(ctx, ctx->d_guided, floats * sizeof(float), 1, 4, true, "growing d_guided");
+    if (rc == CLC_OK) rc = ensure_partial(ctx, plan.partial_elems);
+    if (rc != CLC_OK) return rc;
+    if (ctx->partial_dirty) {
+        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial.ptr, 0xFF, ctx->d_partial.bytes, st));
+        ctx->partial_dirty = false;
+    }
+
+    GuidedJobList list{};
+    uint32_t grid_x = 0, max_nq_empty = 0;
+    for (int k = 0; k < n; ++k) {
+        const clc_guided_job& job = jobs[live[(size_t)k]];
+        const PairJobDev& pd = sides[(size_t)live[(size_t)k]];
+        const K2nnJobDev& p = kj[(size_t)k];
+        GuidedJobDev& g = list.j[k];
+        g.q = (const uint4*)job.d_q; g.t = (const uint4*)job.d_t;
+        g.out = job.d_match; g.best_out = job.d_best; g.second_out = job.d_second;
+        g.L = ctx->d_guided.as<float>() + off_L[(size_t)k]; g.pos = ctx->d_guided.as<float>() + off_P[(size_t)k];
+        g.cnt_q = pd.a.count; g.cnt_t = pd.b.count;
+        g.nq = p.nq; g.nt = p.nt; g.thr = (uint32_t)(uint8_t)job.threshold;            // CUDAK2NN.cu:46: the kernel parameter is uint8_t
+        g.qblocks = p.qblocks; g.splits = p.splits; g.t_per_split = p.t_per_split; g.partial_off = p.partial_off; g.cnt_off = p.cnt_off;
+        g.band = job.band;
+        if (p.nt) grid_x = std::max(grid_x, p.qblocks * p.splits);
+        else max_nq_empty = std::max(max_nq_empty, p.nq);
+    }
+
+    for (int base = 0; base < n; base += kGuidedPrepJobs) {
+        const int cnt = std::min(kGuidedPrepJobs, n - base);
+        GuidedPrepList prep{};
+        for (int l = 0; l < CLC_MAX_LEVELS; ++l) prep.scale[l] = (float)std::pow((double)1.2f, (double)l);      // as launch_gather (gather.hip)
+        uint32_t rows = 0;
+        for (int k = 0; k < cnt; ++k) {
+            const clc_guided_job& job = jobs[live[(size_t)(base + k)]];
+            const PairJobDev& pd = sides[(size_t)live[(size_t)(base + k)]];
+            GuidedPrepJob& pj = prep.j[k];
+            pj.a = pd.a; pj.b = pd.b;
+            for (int i = 0; i < 9; ++i) pj.F[i] = job.F[i];
+            pj.nq = (uint32_t)job.nq; pj.nt = (uint32_t)job.nt;
+            pj.L = const_cast<float*>(list.j[base + k].L); pj.pos = const_cast<float*>(list.j[base + k].pos);
+            pj.line_out = job.d_line; pj.tpos_out = job.d_tpos;
+            rows = std::max(rows, pj.nq + pj.nt);
+        }
+        hipLaunchKernelGGL(guided_prep_kernel, dim3((rows + 255u) / 256u, (unsigned)cnt), dim3(256), 0, st, prep);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && grid_x > 0) {
+        hipLaunchKernelGGL(k2nn_sweep_guided_kernel<kR>, dim3(grid_x, (unsigned)n), dim3(64 * kWaves), 0, st, list, ctx->d_partial.as<uint2>());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && max_nq_empty > 0) {
+        hipLaunchKernelGGL(guided_nomatch_kernel, dim3((max_nq_empty + 255u) / 256u, (unsigned)n), dim3(256), 0, st, list);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { ctx->partial_dirty = true; return fail(ctx, CLC_ERR_HIP, "match_guided: launch", e); }
+    return CLC_OK;
+}
+
+} // namespace
+
+} // namespace clc
+
+using namespace clc;
+
+extern "C" {
+
+int clc_match_guided_dev(clc_ctx* ctx, const clc_guided_job* job, void* stream)
+{
+    if (!job) return fail(ctx, CLC_ERR_BAD_ARG, "match_guided: null job");
+    return guided_batch(ctx, job, 1, stream);
+}
+
+int clc_match_guided_batch_dev(clc_ctx* ctx, const clc_guided_job* jobs, int n_jobs, void* stream)
+{
+    return guided_batch(ctx, jobs, n_jobs, stream);
+}
+
+} // extern "C"

@@ -615,6 +615,57 @@ public:
         return status;
     }
 
+    // The guided match of a pair whose model is known (clc_match_guided_dev, which states the rule): K2NN over the rows of camera B
+    // within `band` pixels of each query's epipolar line.  This is the step RobustMatcher::matchMaps began (the residual under a known F,
+    // :295-362) and never finished; it has no counterpart member in the reference.  relativePose_info is what filterMatchesPair[Dev] left
+    // in relativePoses[pair]: under params->model 'F' its essential_matrix slot holds F (pixels); under 'E' F = K2^-T E K1^-1; 'H' is not
+    // an epipolar model (kModelNotOnGpuPath).  d_desc_a / d_desc_b: the cameras' descriptor rows on the device; d_match_out[nq]: device,
+    // the shape filterMatchesPairDev and the track builder take.  Enqueue only, on `after_stream` -- the stream that produced the
+    // descriptors and keypoints, so the sweep is ordered behind them without a host wait (nullptr: the context's own stream).
+    // Returns EXIT_SUCCESS (false) when the launches were enqueued.
+    bool guidedMatchesPairDev(openMVG::Pair current_pair, const void* d_desc_a, int nq, const void* d_desc_b, int nt, const PairSideDev& a,
+                              const PairSideDev& b, const openMVG::sfm::RelativePose_Info& relativePose_info, float band, int threshold,
+                              int32_t* d_match_out, void* after_stream)
+    {
+        last_status_ = kOk;
+        const char model = params->model;
+        if (model != 'E' && model != 'F') return not_on_gpu_path(model, "a guided match needs an epipolar model, 'E' or 'F'");
+        const auto& Ka = params->K[current_pair.first];
+        const auto& Kb = params->K[current_pair.second];
+        const auto& da = params->dist[current_pair.first];
+        const auto& db = params->dist[current_pair.second];
+        openMVG::Mat3 F = relativePose_info.essential_matrix;
+        if (model == 'E') {
+            const openMVG::cameras::Pinhole_Intrinsic_Radial_K3 camL(params->imageSize.first, params->imageSize.second, Ka(0, 0), Ka(0, 2), Ka(1, 2),
+                                                                     da[0], da[1], da[2]),
+                camR(params->imageSize.first, params->imageSize.second, Kb(0, 0), Kb(0, 2), Kb(1, 2), db[0], db[1], db[2]);
+            F = hipgeom::mul(hipgeom::mul(hipgeom::transpose(camR.Kinv()), relativePose_info.essential_matrix), camL.Kinv());
+        }
+        clc_guided_job jb{};
+        jb.d_q = d_desc_a; jb.nq = nq; jb.d_t = d_desc_b; jb.nt = nt;
+        jb.d_count_a = a.d_count; jb.d_count_b = b.d_count;
+        jb.d_kps_a = a.d_kps; jb.d_feat_a = a.d_feat; jb.feat_stride_a = a.feat_stride;
+        jb.d_kps_b = b.d_kps; jb.d_feat_b = b.d_feat; jb.feat_stride_b = b.feat_stride;
+        jb.cam_a = clc_camera_k3{ Ka(0, 0), Ka(0, 2), Ka(1, 2), da[0], da[1], da[2] };
+        jb.cam_b = clc_camera_k3{ Kb(0, 0), Kb(0, 2), Kb(1, 2), db[0], db[1], db[2] };
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) jb.F[3 * i + j] = F(i, j);
+        jb.band = band; jb.threshold = threshold;
+        jb.d_match = d_match_out;
+        // the sweep needs a context with matcher options (its top-2 workspace); the filter's context has none: one more, on first use
+        if (!guided_ctx_.h) {
+            clc_matcher_opts mo{ params->matcherOptions.distRatio, params->matcherOptions.thresh,
+                                 params->matcherOptions.maxkp > 0 ? params->matcherOptions.maxkp : 1u };
+            if (clc_ctx_create(0, nullptr, &mo, &guided_ctx_.h) != CLC_OK) guided_ctx_.h = nullptr;
+        }
+        const int rc = guided_ctx_.h ? clc_match_guided_dev(guided_ctx_.h, &jb, after_stream) : CLC_ERR_STATE;
+        if (rc != CLC_OK) {
+            last_status_ = kEstimateFailed;
+            std::cerr << "HIPRobustMatcher: clc_match_guided_dev: " << (guided_ctx_.h ? clc_last_error_string(guided_ctx_.h) : "no context") << std::endl;
+            return EXIT_FAILURE;
+        }
+        return EXIT_SUCCESS;
+    }
+
     // RobustMatcher::filterMatches (:455-483): every pair that has putative matches
     void filterMatches(FeatureMap& regions, openMVG::matching::PairWiseMatches& putativeMatches, openMVG::matching::PairWiseMatches& geometricMatches,
                        InterPoseMap& relativePoses)
@@ -705,6 +756,9 @@ private:
     Status last_status_ = kOk;
     clc_ctx* ctx_ = nullptr;
     colocParams* params;
+    // guidedMatchesPairDev's matcher context, which frees itself (the class is not copyable)
+    struct OwnedCtx { clc_ctx* h = nullptr; ~OwnedCtx() { if (h) clc_ctx_destroy(h); } };
+    OwnedCtx guided_ctx_;
 };
 
 } // namespace coloc

@@ -849,6 +849,74 @@ int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* job
 int clc_pair_build_dev(clc_ctx* ctx, const clc_pair_job* job, double* d_x1, double* d_x2, int32_t* d_pair_q, int32_t* d_pair_t,
                        int32_t* d_n, void* stream);
 
+/* ---- the guided match: K2NN along epipolar lines under a known F -------------------------------------------------------------------
+ * The reference began this step and never finished it: RobustMatcher::matchMaps (RobustMatcher.hpp:295-362) evaluates f1^T F f2 for
+ * every putative match, sorts by it and keeps everything (the gate and the "best two" variant are commented out).  What follows is THIS
+ * library's statement of the step, as clc_match_ratio_2nn_dev and CLC_SELECT_STRONGEST are; OpenMVG is an empty submodule of the
+ * reference, so parity with its geometry_aware::GuidedMatching is NOT pinned.  (Later under ABI 4: new entry points only.)
+ *
+ * K2NN's acceptance is global: a query is accepted only if its best Hamming distance beats its second best over ALL train rows by more
+ * than the threshold (CUDAK2NN.cu:75), so on repeated structure the true match loses to, or ties with, a look-alike elsewhere in the
+ * image.  Once a pair has a model -- clc_pair_filter_dev's F, or two poses -- the match of x_a lies on the line F x_a: the guided match
+ * takes the top-2 over the train rows near that line only.
+ *
+ * THE RULE.  Camera A is the query side, camera B the train side.  F: 9 doubles, row-major, in undistorted PIXELS, x_b^T F x_a = 0 --
+ * the orientation and units of clc_pair_job.F, so the filter's output is usable as it is.
+ *   positions   feature position (d_kps: scale * (float)x in float; d_feat + stride: the floats as they are), then get_ud_pixel in fp64,
+ *               for every row of A and of B: exactly what clc_pair_job's gather computes, rows from d_kps_* or d_feat_* per side with
+ *               clc_camera_k3 per side, row counts nq / nt, clipped by d_count_a[0] / d_count_b[0] where given.
+ *   line of q   l = F (u, v, 1) in fp64 (each row (F0 u + F1 v) + F2, no contraction), n = sqrt(l0 l0 + l1 l1), L = (l0 / n, l1 / n,
+ *               l2 / n), each rounded ONCE to float.  n zero or not finite, or a component of L not finite: the query has NO candidates.
+ *   train point (x, y) = the undistorted pixel, each rounded once to float.
+ *   gate        in fp32 with explicit fused operations: e = fmaf(L0, x, fmaf(L1, y, L2)); train row t is a CANDIDATE of q iff
+ *               fabsf(e) <= band.  band: the caller's half-width in pixels, finite and > 0.
+ *   top-2       CUDAK2NN.cu:54-75 over the CANDIDATES only, in train-index order: the lowest index wins a tie for the minimum; the
+ *               sentinels are second = 100000 with exactly one candidate, best = 100000 (second = 200000) with none; accept iff
+ *               second - best > threshold (threshold truncated to 8 bits as the reference's kernel parameter is).  So a lone candidate
+ *               is accepted, a query without candidates is -1, and a tie for the minimum INSIDE the band is rejected.
+ *   outputs     d_match[nq] (train row or -1), d_best / d_second (nullable; distances, sentinels saturated to 65535) as the other
+ *               entries write them; d_line (3 nq floats) / d_tpos (2 nt floats), nullable: the lines and train points the sweep read.  A
+ *               query without a line, and every row at or past a device-side count, holds quiet NaNs (0x7FC00000) there; planned query
+ *               rows past d_count_a[0] are answered -1, train rows past d_count_b[0] are never candidates.
+ * The gate is the ONE-SIDED point-to-line distance in image B.  That is a choice: the symmetric form would need B's lines in A too
+ * (a second prep pass and two more fused operations per pair).
+ *
+ * Both entries are enqueue-only on `stream` (0: the context's), capturable once the context's scratch has its size, no host wait: F and
+ * band are host arguments.  They run the popcount formulation of the sweep with the gate in its loop, whatever formulation the context
+ * is set to (the matrix formulation is not touched), preceded by a prep launch that writes the lines and the train points.
+ * clc_match_guided_batch_dev: n_jobs in [0, CLC_MAX_TRACK_PAIRS] on one context, every job's result the single call's, ONE sweep
+ * launch; the prep is ONE launch for up to 14 jobs and two beyond (a prep record carries two cameras and F in fp64: 14 of them fill the
+ * 4 KB of kernel arguments).
+ * Limits and errors: nt > 2^22 (where the plain sweep changes to its slab path): CLC_ERR_CAPACITY; nt == 0: every query -1; both or
+ * neither of d_kps / d_feat for a camera, a misaligned pointer (descriptor rows: 16 bytes), a non-positive focal, a band that is not
+ * finite and positive, a null context or job: CLC_ERR_BAD_ARG; a context without matcher options: CLC_ERR_STATE.
+ * d_match feeds clc_pair_build_dev, clc_pair_filter_dev, clc_tracks_pair and clc_map_build_dev unchanged. */
+typedef struct clc_guided_job {
+    const void*         d_q;            /* camera A's descriptors: nq rows of 64 bytes, 16-byte aligned */
+    int                 nq;
+    const void*         d_t;            /* camera B's */
+    int                 nt;
+    const uint32_t*     d_count_a;      /* nullable, as clc_pair_job */
+    const uint32_t*     d_count_b;
+    const clc_keypoint* d_kps_a;        /* or */
+    const float*        d_feat_a;
+    int                 feat_stride_a;
+    const clc_keypoint* d_kps_b;        /* or */
+    const float*        d_feat_b;
+    int                 feat_stride_b;
+    clc_camera_k3       cam_a, cam_b;
+    double              F[9];
+    float               band;
+    int                 threshold;
+    int32_t*            d_match;        /* nq, device */
+    uint16_t*           d_best;         /* nullable, device */
+    uint16_t*           d_second;
+    float*              d_line;         /* nullable, device: 3 nq floats */
+    float*              d_tpos;         /* nullable, device: 2 nt floats */
+} clc_guided_job;
+int clc_match_guided_dev(clc_ctx* ctx, const clc_guided_job* job, void* stream);
+int clc_match_guided_batch_dev(clc_ctx* ctx, const clc_guided_job* jobs, int n_jobs, void* stream);
+
 /* ---- the inter-camera step from device memory: ColoC::interPoseEstimator (coloc.hpp:296-340) without a host trip --------------------
  * What clc_inter_pose_batch computes, fed from the pair's d_match instead of host correspondences: the pair gather and the 'E' filter of
  * clc_pair_filter_dev, then -- on the device, in the operation order of the host path, so with its bits -- the chirality vote over the
