@@ -114,6 +114,24 @@ CLC_TV_HD int cubic_roots(const double a, const double b, const double c, double
         double x0 = nrm * cos(theta / 3.0) - a3;
         double x1 = nrm * cos((theta + 2.0 * M_PI) / 3.0) - a3;
         double x2 = nrm * cos((theta - 2.0 * M_PI) / 3.0) - a3;
+        // Where |a| is far above two of the roots, those two are what is left of nrm cos(.) - a / 3 after cancellation, and the angle
+        // carries the square root of a rounding: 1e-5 relative at |a| = 1e6, 3e-2 at 1e8 (tests/test_twoview_reference.py).  The root
+        // of largest magnitude has no such cancellation; the other two are the roots of the quadratic x^2 + p x + q it leaves when
+        // divided out from the constant term upwards (q = -c / xb, p = (q - b) / xb: stable for the largest root), solved without
+        // cancellation.
+        double xb = x0;
+        if (fabs(x1) > fabs(xb)) xb = x1;
+        if (fabs(x2) > fabs(xb)) xb = x2;
+        if (xb != 0.0) {
+            const double qq = -c / xb;
+            const double pp = (qq - b) / xb;
+            const double disc = pp * pp - 4.0 * qq;
+            const double sd = disc > 0.0 ? sqrt(disc) : 0.0;
+            const double h = -0.5 * (pp + (pp >= 0.0 ? sd : -sd));
+            x0 = xb;
+            x1 = h;
+            x2 = (disc > 0.0 && h != 0.0) ? qq / h : h;
+        }
         double t;
         if (x0 > x1) { t = x0; x0 = x1; x1 = t; }
         if (x1 > x2) { t = x1; x1 = x2; x2 = t; if (x0 > x1) { t = x0; x0 = x1; x1 = t; } }
@@ -123,9 +141,56 @@ CLC_TV_HD int cubic_roots(const double a, const double b, const double c, double
     const double sgn = R >= 0.0 ? 1.0 : -1.0;
     const double A = -sgn * cbrt(fabs(R) + sqrt(R2 - Q3));
     const double Bq = Q / A;
-    x[0] = (A + Bq) - a3;
+    // (A + Bq) - a / 3 is off by roundings of |a| / 3, far more than a rounding of the root where the complex pair is far larger
+    // than the root: two Newton steps on the cubic itself, in Horner form, whose own error is the cubic's backward error.
+    double x0 = (A + Bq) - a3;
+    for (int s = 0; s < 2; ++s) {
+        const double p = ((x0 + a) * x0 + b) * x0 + c;
+        const double dp = (3.0 * x0 + 2.0 * a) * x0 + b;
+        const double xn = x0 - p / dp;
+        if (fabs(xn) <= 1.7976931348623157e308) x0 = xn;
+    }
+    x[0] = x0;
     x[1] = x[2] = x[0];
     return 1;
+}
+
+// The closed form above is held to a backward error of 64 roundings of the cubic's coefficients (tests/test_twoview_reference.py),
+// and those coefficients are sums of determinants divided by c3, each with its own rounding: the root is that of a nearby cubic,
+// not quite the sample's pencil.  One Newton step on det(a + x b) ITSELF brings each real root to the pencil's: the value is the
+// determinant of the matrix the model will be, evaluated afresh; the slope is the cubic's, c1 + 2 c2 x + 3 c3 x^2 -- a slope that is
+// off by the coefficients' rounding does not move the limit, which is the zero of the value.  From an error e the step leaves
+// e^2 / (separation of the roots); DESIGN.md section 11 has the measurement behind the step count.  The polished set is kept only if
+// every root stays finite and the ascending order is unchanged (an exact double root has a zero slope: the set stays as it was); the
+// count does not change.
+#ifndef CLC_TV_POLISH_STEPS
+#define CLC_TV_POLISH_STEPS 1
+#endif
+CLC_TV_HD void polish_pencil_roots(const double* a, const double* b, const double c1, const double c2, const double c3, const int nr, double (&x)[3])
+{
+    double r[3];
+    bool ok = true;
+    CLC_TV_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        double xk = x[k];
+        if (k < nr) {
+            CLC_TV_UNROLL
+            for (int s = 0; s < CLC_TV_POLISH_STEPS; ++s) {
+                double m[9];
+                CLC_TV_UNROLL
+                for (int e = 0; e < 9; ++e) m[e] = a[e] + xk * b[e];
+                const double p = det3(m, m + 3, m + 6);
+                const double dp = (3.0 * c3 * xk + 2.0 * c2) * xk + c1;
+                xk = xk - p / dp;
+            }
+        } else {
+            xk = r[0];                                               // (one real root: the three slots repeat it, as cubic_roots leaves them)
+        }
+        r[k] = xk;
+        ok = ok && fabs(xk) <= 1.7976931348623157e308;               // (false for a NaN)
+    }
+    ok = ok && r[0] <= r[1] && r[1] <= r[2];
+    if (ok) { x[0] = r[0]; x[1] = r[1]; x[2] = r[2]; }
 }
 
 // x1 / x2: the sample's 7 normalised correspondences {u, v}.  F[k] (row-major 9, x2^T F x1 = 0), k < the count returned (0..3).
@@ -151,6 +216,7 @@ CLC_TV_HD int seven_point(const double (&x1)[7][2], const double (&x2)[7][2], do
     if (!(c3 != 0.0) || !(fabs(c3) <= 1.7976931348623157e308)) return 0;       // (a quadratic, or a NaN sample: no model)
     double roots[3];
     const int nr = cubic_roots(c2 / c3, c1 / c3, c0 / c3, roots);
+    polish_pencil_roots(a, b, c1, c2, c3, nr, roots);
     CLC_TV_UNROLL
     for (int k = 0; k < 3; ++k) {
         CLC_TV_UNROLL

@@ -31,6 +31,19 @@ def solve(q1, q2):
     return [E[9 * k:9 * k + 9].reshape(3, 3).copy() for k in range(n)]
 
 
+def class_slots(x1, x2, K):
+    """The models of a batch of samples in pixels (n, 5, 2) under one K: (n, 10, 9) in calibrated coordinates, NaN where a sample has
+    fewer models."""
+    Ki = np.linalg.inv(np.asarray(K, dtype=np.float64).reshape(3, 3))
+    out = np.full((len(x1), 10, 9), np.nan)
+    for i in range(len(x1)):
+        q1 = (np.c_[x1[i], np.ones(5)] @ Ki.T)[:, :2]
+        q2 = (np.c_[x2[i], np.ones(5)] @ Ki.T)[:, :2]
+        for k, E in enumerate(solve(q1, q2)):
+            out[i, k] = E.reshape(9)
+    return out
+
+
 def random_two_view(rng):
     """A random relative pose and 5 points in front of both cameras: (q1, q2, E_true)."""
     ax = 0.3 * rng.uniform(-1, 1, 3)

@@ -1,0 +1,263 @@
+"""The seven-point and four-point solvers against a high-precision reference, on the CPU: the reference against itself, the fixture
+against a recomputation, the host build of coloc_amd/csrc/twoview_min.h against the two rules of DESIGN.md section 11 on every class of
+tests/twoview_cases.py, and cubic_roots alone against mp.polyroots.
+
+The rules (models in conditioned coordinates at unit norm; bound_i = 4096 * max(2^-53 max(w, h), r_ref_i)):
+  backward   'F': the model's smallest singular value zeroed at 60 digits, worst point-to-epipolar-line distance of the sample (the smaller
+             of the two per pair) in pixels; 'H': worst |x2 - H x1| in pixels; <= bound_i.
+  forward    every in-range reference solution has a returned model within J_k bound_i + 16 * 2^-53 in all nine entries, and every
+             returned model is within that bound of some reference solution (so: the right count of real roots).
+Run with -s to see the measured figures of every class.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import twoview_cases as cases
+import twoview_host as tvh
+import twoview_mp
+from mpmath import mp, mpf
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ALL = cases.all_classes()
+IDS = ["%s-%s" % mc for mc in ALL]
+
+
+@pytest.fixture(scope="module")
+def fx():
+    return cases.load_fixture()
+
+
+@pytest.mark.parametrize("model,name", ALL, ids=IDS)
+def test_reference_certifies_itself_and_agrees_with_90_digits(fx, model, name):
+    x1, x2, wh = cases.class_inputs(model, name, fx)
+    for i in (0, cases.N_PER_CLASS - 1):
+        a = twoview_mp.solve(model, x1[i], x2[i], wh)
+        b = twoview_mp.solve(model, x1[i], x2[i], wh, dps=max(90, a["dps"] + 30))
+        assert len(a["sols"]) == len(b["sols"]) == a["nreal"] == b["nreal"] and len(a["sols"]) > 0
+        with mp.workdps(120):
+            assert abs(a["rho"] - b["rho"]) <= mpf(10) ** -40
+            for sa, sb in zip(a["sols"], b["sols"]):
+                assert sa["cert"] <= twoview_mp.CERT_TOL and sb["cert"] <= twoview_mp.CERT_TOL
+                assert max(abs(p - q) for p, q in zip(sa["M"], sb["M"])) <= mpf(10) ** -40
+
+
+def test_rho_does_not_depend_on_the_null_space_basis(fx):
+    x1, x2, wh = cases.class_inputs("F", "exact", fx)
+    with mp.workdps(60):
+        q1, q2 = twoview_mp.condition(x1[0].tolist(), wh)[0], twoview_mp.condition(x2[0].tolist(), wh)[0]
+        a, b = twoview_mp.nullspace(twoview_mp.rows("F", q1, q2), 2)
+        c, s = mp.cos(mpf("0.7")), mp.sin(mpf("0.7"))
+        a2, b2 = [c * p + s * q for p, q in zip(a, b)], [c * q - s * p for p, q in zip(a, b)]
+        rho = []
+        for u, v in ((a, b), (a2, b2)):
+            r = mp.polyroots(list(reversed(twoview_mp.pencil_cubic(u, v))), maxsteps=400, extraprec=240)
+            rho.append(min(twoview_mp.chordal(r[i], r[j]) for i in range(3) for j in range(i)))
+        assert abs(rho[0] - rho[1]) <= mpf(10) ** -45 and abs(rho[0] - mpf(float(fx["rho"][0]))) <= mpf(2) ** -24 * rho[0]
+
+
+def test_fixture_inputs_are_the_case_table(fx):
+    for model, name in ALL:
+        a, b = cases.class_inputs(model, name, fx), cases.class_inputs(model, name)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2], (model, name)
+
+
+def test_classes_are_what_they_claim(fx):
+    for model, name in ALL:
+        x1, x2, wh = cases.class_inputs(model, name, fx)
+        assert x1.shape == (cases.N_PER_CLASS, cases.M_OF[model], 2)
+        if name == "tinyquad":
+            assert max(np.linalg.norm(q[:, None] - q[None], axis=2).max() for q in x1) <= 10.0
+        if name == "corners":
+            cs = np.array([[0.0, 0.0], [wh[0], 0.0], [0.0, wh[1]], [wh[0], wh[1]]])
+            for q in x1:
+                assert sorted(np.linalg.norm(q[:, None] - cs[None], axis=2).argmin(1)) == [0, 1, 2, 3]
+                assert np.linalg.norm(q[:, None] - cs[None], axis=2).min(1).max() <= 2.0
+        if name == "collinear":
+            for q in x1:
+                best = np.inf
+                for k in range(4):
+                    p = np.delete(q, k, axis=0)
+                    span = max(np.linalg.norm(p[i] - p[j]) for i in range(3) for j in range(i))
+                    d = p[1:] - p[0]
+                    best = min(best, abs(d[0, 0] * d[1, 1] - d[0, 1] * d[1, 0]) / span ** 2)
+                assert best <= 1.01e-3
+        if name == "neardouble":
+            rho = fx["rho"][cases.class_offset(model, name):][:cases.N_PER_CLASS]
+            assert ((rho >= 1e-6) & (rho <= 1e-3)).all()
+
+
+def test_fixture_size(fx):
+    golden = os.path.dirname(cases.FIXTURE)
+    others = [os.path.getsize(os.path.join(golden, f)) for f in os.listdir(golden) if not f.endswith("view_reference.npz")]
+    assert os.path.getsize(cases.FIXTURE) <= max(others) == 74200
+
+
+@pytest.mark.parametrize("model,name", ALL, ids=IDS)
+def test_fixture_subset_recomputes_unchanged(fx, model, name):
+    x1, x2, wh = cases.class_inputs(model, name, fx)
+    stored = cases.class_references(fx, model, name)
+    for i in (3, 22):
+        rho, r_ref, sols = stored[i]
+        r = cases.reference_problem(model, x1[i], x2[i], wh)
+        assert r is not None and r["rho"] == rho and r["r_ref"] == r_ref and len(r["sols"]) == len(sols)
+        for a, b in zip(r["sols"], sols):
+            assert np.array_equal(a["M"], b["M"]) and np.array_equal(cases.half_to_float(a["J"]), b["J"]) and a["in_range"] == b["in_range"]
+
+
+def test_caps_hold_on_the_reference_alone(fx):
+    """What the generator refuses to write: a solution out of range in an asserted class; more than 25 % of a hard class out of range or
+    under the rho cap (neardouble is under the cap by construction: there the condition is on the range alone)."""
+    for model, name in ALL:
+        refs = cases.class_references(fx, model, name)
+        assert all(rho >= 0 and len(ss) > 0 for rho, _, ss in refs), (model, name)
+        sols = [(rho, s) for rho, _, ss in refs for s in ss]
+        out = sum(not s["in_range"] for _, s in sols)
+        capped = sum(s["in_range"] and rho < cases.RHO_CAP for rho, s in sols)
+        if name in cases.ASSERTED[model]:
+            assert out == 0, (model, name)
+        else:
+            assert out + (0 if name == "neardouble" else capped) <= 0.25 * len(sols), (model, name)
+
+
+@pytest.mark.parametrize("model,name", ALL, ids=IDS)
+def test_stored_solutions_lead_back_to_certified_ones(fx, model, name):
+    table = cases.class_table(fx, model, name)[3]
+    assert all(r["cert"] <= float(twoview_mp.CERT_TOL) and np.abs(r["lo"]).max() <= 2.0 ** -53 for row in table for r in row["refs"])
+
+
+@pytest.mark.parametrize("model,name", ALL, ids=IDS)
+def test_host_build_meets_both_rules(fx, model, name):
+    x1, x2, wh = cases.class_inputs(model, name, fx)
+    fig = cases.evaluate(model, name, tvh.class_slots(model, x1, x2, wh), fx)
+    print("\n%s %s (host): %s" % (model, name, fig))
+    assert fig["models"] > 0
+    assert fig["backward_ratio"] <= 1.0
+    assert fig["missed"] == 0 and fig["spurious"] == 0
+
+
+# ---- cubic_roots alone -----------------------------------------------------------------------------------------------------------
+def _from_roots(r1, r2, r3):
+    with mp.workdps(60):
+        r1, r2, r3 = mpf(r1), mpf(r2), mpf(r3)
+        return float(-(r1 + r2 + r3)), float(r1 * r2 + r1 * r3 + r2 * r3), float(-r1 * r2 * r3)
+
+
+def _from_real_and_pair(r, re, im):
+    """(x - r)((x - re)^2 + im^2)"""
+    with mp.workdps(60):
+        r, re, im = mpf(r), mpf(re), mpf(im)
+        return float(-r - 2 * re), float(re * re + im * im + 2 * r * re), float(-r * (re * re + im * im))
+
+
+CUBICS = {
+    "double_R_pos": (0.0, -3.0, 2.0),                                  # (x - 1)^2 (x + 2): CR2 == CQ3, R > 0
+    "double_R_neg": (0.0, -3.0, -2.0),                                 # (x + 1)^2 (x - 2): CR2 == CQ3, R < 0
+    "double_with_a": (-3.0, 0.0, 4.0),                                 # (x - 2)^2 (x + 1)
+    "triple": (-3.0, 3.0, -1.0),                                       # (x - 1)^3: R == 0 and Q == 0
+    "triple_zero": (0.0, 0.0, 0.0),
+    "three_real": _from_roots("-1.5", "0.25", "3"),
+    "three_real_small": _from_roots("1e-3", "-2e-3", "5e-3"),
+    "near_double_1e-4": _from_roots("1", "1.0001", "-2.5"),
+    "near_double_1e-5": _from_roots("1", "1.00001", "-2.5"),
+    "near_double_1e-6": _from_roots("1", "1.000001", "-2.5"),
+    "near_double_1e-7": _from_roots("-0.7", "-0.7000001", "1.9"),
+    "near_double_1e-8": _from_roots("1", "1.00000001", "-2.5"),
+    "near_double_complex_1e-6": _from_real_and_pair("-2.5", "1", "1e-6"),
+    "big_a_1e6": _from_roots("-1e6", "0.5", "2"),                       # |a| >> the two small roots: the cancellation in ... - a / 3
+    "big_a_1e8": _from_roots("1e8", "-1", "3"),
+    "big_a_one_real": _from_real_and_pair("3e7", "0.5", "2"),
+    "big_a_one_real_small": _from_real_and_pair("0.5", "3e7", "2"),
+    "one_real_R_pos": (0.0, 1.0, 1.0),
+    "one_real_R_neg": (0.0, 1.0, -1.0),
+    "one_real_R_pos_a": _from_real_and_pair("-3", "-0.5", "2"),
+    "one_real_R_neg_a": _from_real_and_pair("3", "0.5", "2"),
+}
+CUBIC_ETA = 64.0 * 2.0 ** -53
+
+
+@pytest.mark.parametrize("name", list(CUBICS))
+def test_cubic_roots_against_polyroots(name):
+    """Every root cubic_roots returns is an exact root of a cubic whose four coefficients differ from the given ones by at most
+    64 * 2^-53 relative (the smallest such perturbation is |p(x)| / (|x|^3 + |a| x^2 + |b| |x| + |c|), evaluated at 60 digits), and every
+    real root of the given cubic (mp.polyroots) is met by a returned root to within the condition of that root times the same
+    perturbation; the count of real roots is the reference's wherever the discriminant is not within rounding of zero."""
+    a, b, c = CUBICS[name]
+    got = tvh.cubic(a, b, c)
+    with mp.workdps(60):
+        A, B, Cc = mpf(a), mpf(b), mpf(c)
+        for x in got:
+            X = mpf(float(x))
+            scale = abs(X) ** 3 + abs(A) * X * X + abs(B) * abs(X) + abs(Cc)
+            eta = abs(X ** 3 + A * X * X + B * X + Cc) / scale if scale else mpf(0)
+            print("%s: root %.17g backward error %.3g x 2^-53" % (name, x, float(eta) * 2.0 ** 53))
+            assert eta <= CUBIC_ETA, (name, x, float(eta))
+        roots = mp.polyroots([mpf(1), A, B, Cc], maxsteps=400, extraprec=400) if name not in ("triple", "triple_zero") else [-A / 3] * 3
+        terms = [18 * A * B * Cc, -4 * A ** 3 * Cc, A * A * B * B, -4 * B ** 3, -27 * Cc * Cc]
+        disc = sum(terms)
+        if abs(disc) > CUBIC_ETA * sum(abs(t) for t in terms):
+            assert len(got) == (3 if disc > 0 else 1)
+            real = [mp.re(r) for r in roots if abs(mp.im(r)) <= mpf(10) ** -30 * (1 + abs(r))]
+            assert len(real) == len(got)
+            for r, x in zip(sorted(real), got):
+                cond = (abs(r) ** 3 + abs(A) * r * r + abs(B) * abs(r) + abs(Cc)) / abs(3 * r * r + 2 * A * r + B)
+                assert abs(mpf(float(x)) - r) <= 2 * CUBIC_ETA * cond + 2 * mpf(2) ** -53 * abs(r), (name, x)
+        elif name.startswith("double") or name.startswith("triple"):
+            assert len(got) == 3
+
+
+def test_cubic_table_takes_its_branches():
+    """The exact double and triple rows satisfy the guards' equalities in float64 as cubic_roots evaluates them."""
+    for name in ("double_R_pos", "double_R_neg", "double_with_a", "triple", "triple_zero"):
+        a, b, c = CUBICS[name]
+        q = a * a - 3.0 * b
+        r = (2.0 * a * a * a - 9.0 * a * b) + 27.0 * c
+        assert 729.0 * r * r == 2916.0 * q * q * q
+        assert (r == 0.0 and q == 0.0) == name.startswith("triple")
+        got = tvh.cubic(a, b, c)
+        assert len(got) == 3 and (got[0] == got[1] or got[1] == got[2])
+    assert CUBICS["one_real_R_pos"][2] > 0 > CUBICS["one_real_R_neg"][2]
+
+
+# ---- five points: the reference and the figures, report only ---------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fx_e():
+    return cases.load_fixture("E")
+
+
+def test_five_point_fixture_is_the_case_table_and_within_the_size_limit(fx_e):
+    for name in cases.REPORT["E"]:
+        a, b = cases.class_inputs("E", name, fx_e), cases.class_inputs("E", name)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), name
+    assert os.path.getsize(cases.FIXTURE_E) <= 74200
+
+
+@pytest.mark.parametrize("name", cases.REPORT["E"])
+def test_five_point_reference_recomputes_and_agrees_with_90_digits(fx_e, name):
+    x1, x2, K = cases.class_inputs("E", name, fx_e)
+    stored = cases.class_references(fx_e, "E", name)
+    i = 7
+    r = cases.reference_problem("E", x1[i], x2[i], K)
+    assert r is not None and r["r_ref"] == stored[i][1] and len(r["sols"]) == len(stored[i][2]) > 0
+    for a, b in zip(r["sols"], stored[i][2]):
+        assert np.array_equal(a["M"].astype(np.float64), b["M"]) and np.array_equal(cases.half_to_float(a["J"]), b["J"]) and a["in_range"] == b["in_range"]
+    lo, hi = twoview_mp.solve_five(x1[i], x2[i], K), twoview_mp.solve_five(x1[i], x2[i], K, dps=90)
+    assert len(lo["sols"]) == len(hi["sols"])
+    with mp.workdps(120):
+        for sa, sb in zip(lo["sols"], hi["sols"]):
+            assert sa["cert"] <= twoview_mp.CERT_TOL and sb["cert"] <= twoview_mp.CERT_TOL
+            assert max(abs(p - q) for p, q in zip(sa["M"], sb["M"])) <= mpf(10) ** -40
+
+
+@pytest.mark.parametrize("name", cases.REPORT["E"])
+def test_five_point_host_build_keeps_its_structure(fx_e, name):
+    """No rule is asserted (DESIGN.md section 11 has the figures): at most ten slots per sample, each all NaN or wholly finite, and no
+    two returned models matched to one reference solution; every stored solution that is used leads back to a certified one.  Printed:
+    backward error over the class; missed and spurious counts and the worst forward ratio over its first cases.N_REPORT_REF problems."""
+    import fivept_host
+    x1, x2, K = cases.class_inputs("E", name, fx_e)
+    fig = cases.evaluate("E", name, fivept_host.class_slots(x1, x2, K), fx_e)
+    print("\nE %s (host, report only): %s" % (name, fig))
+    assert all(r["cert"] <= float(twoview_mp.CERT_TOL) for row in cases.class_table(fx_e, "E", name)[3] for r in row["refs"] or [])
+    assert fig["models"] > 0 and fig["doubled"] == 0

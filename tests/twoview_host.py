@@ -43,6 +43,18 @@ def four_point(q1, q2):
     return H
 
 
+def class_slots(model, x1, x2, wh):
+    """The models of a batch of samples in pixels (n, m, 2), conditioned as clc_two_view_minimal conditions them: (n, 3 | 1, 9), NaN
+    where a sample has fewer models."""
+    t = normalizer(wh)
+    out = np.full((len(x1), 3 if model == "F" else 1, 9), np.nan)
+    for i in range(len(x1)):
+        q1, q2 = x1[i] * t[0] + t[1:], x2[i] * t[0] + t[1:]
+        for k, M in enumerate(seven_point(q1, q2) if model == "F" else [four_point(q1, q2)]):
+            out[i, k] = M
+    return out
+
+
 def normalizer(wh):
     t = np.zeros(3)
     lib().tv_host_normalizer(C.c_int(int(wh[0])), C.c_int(int(wh[1])), _p(t))
