@@ -86,6 +86,13 @@ class GuidedJob(C.Structure):
                 ("d_match", C.c_void_p), ("d_best", C.c_void_p), ("d_second", C.c_void_p), ("d_line", C.c_void_p), ("d_tpos", C.c_void_p)]
 
 
+class MapGuidedJob(C.Structure):
+    """clc_map_guided_job (include/coloc_hip.h)"""
+    _fields_ = [("d_q", C.c_void_p), ("nq", C.c_int), ("d_count", C.c_void_p), ("d_kps", C.c_void_p), ("d_feat", C.c_void_p),
+                ("feat_stride", C.c_int), ("cam", CameraK3), ("Rt", C.c_double * 12), ("radius", C.c_float), ("threshold", C.c_int),
+                ("d_match", C.c_void_p), ("d_best", C.c_void_p), ("d_second", C.c_void_p), ("d_qpos", C.c_void_p), ("d_proj", C.c_void_p)]
+
+
 MAX_BATCH, MAX_TRACK_PAIRS = 8, 28          # CLC_MAX_BATCH, CLC_MAX_TRACK_PAIRS
 
 
@@ -205,6 +212,7 @@ EXPORTS = [
     "clc_map_build_grow_dev", "clc_map_init_grow_batch_dev", "clc_map_update_grow_batch_dev", "clc_map_resect_build_dev",
     "clc_ba_dev", "clc_map_build_grow_ba_dev", "clc_map_init_grow_ba_batch_dev", "clc_map_update_grow_ba_batch_dev",
     "clc_match_guided_dev", "clc_match_guided_batch_dev",
+    "clc_match_map_guided_dev", "clc_match_map_guided_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -375,6 +383,8 @@ def load_library():
     lib.clc_map_update_grow_ba_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     lib.clc_match_guided_dev.argtypes = [vp, vp, vp]
     lib.clc_match_guided_batch_dev.argtypes = [vp, vp, ci, vp]
+    lib.clc_match_map_guided_dev.argtypes = [vp, vp, vp]
+    lib.clc_match_map_guided_batch_dev.argtypes = [vp, vp, ci, vp]
     _lib = lib
     return lib
 
@@ -721,6 +731,17 @@ def _guided_fill(j, d_q, nq, d_t, nt, cam_a, cam_b, F, band, threshold, d_match,
     j.F = (C.c_double * 9)(*[float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)])
     j.band, j.threshold = float(band), int(threshold)
     j.d_match, j.d_best, j.d_second, j.d_line, j.d_tpos = d_match, d_best, d_second, d_line, d_tpos
+
+
+def _map_guided_fill(j, d_q, nq, cam, Rt, radius, threshold, d_match, d_kps=None, d_feat=None, feat_stride=4, d_count=None, d_best=None,
+                     d_second=None, d_qpos=None, d_proj=None):
+    """fills a MapGuidedJob; cam = (focal, ppx, ppy, k1, k2, k3), Rt = 12 numbers, the predicted [R|t] row-major 3 x 4; device pointers as
+    integers"""
+    j.d_q, j.nq, j.d_count, j.d_kps, j.d_feat, j.feat_stride = d_q, int(nq), d_count, d_kps, d_feat, int(feat_stride)
+    j.cam = CameraK3(*[float(v) for v in cam])
+    j.Rt = (C.c_double * 12)(*[float(v) for v in np.asarray(Rt, dtype=np.float64).reshape(12)])
+    j.radius, j.threshold = float(radius), int(threshold)
+    j.d_match, j.d_best, j.d_second, j.d_qpos, j.d_proj = d_match, d_best, d_second, d_qpos, d_proj
 
 
 def pair_filter_batch_dev(ctxs, model, jobs):
@@ -1480,6 +1501,23 @@ class Context:
         for i in range(n):
             _guided_fill(arr[i], **jobs[i])
         self._chk(self.lib.clc_match_guided_batch_dev(self.h, arr, n, stream))
+
+    def match_map_guided_dev(self, stream=None, **job):
+        """clc_match_map_guided_dev: K2NN over the map rows whose landmark projects within `radius` pixels of the query under the predicted
+        pose, enqueue only.  Keywords: d_q, nq, cam = (focal, ppx, ppy, k1, k2, k3), d_kps or d_feat (+ feat_stride), d_count, Rt (12, the
+        predicted [R|t], world to camera), radius, threshold, d_match and the nullable d_best, d_second, d_qpos, d_proj."""
+        j = MapGuidedJob()
+        _map_guided_fill(j, **job)
+        self._chk(self.lib.clc_match_map_guided_dev(self.h, C.byref(j), stream))
+
+    def match_map_guided_batch_dev(self, jobs, stream=None):
+        """clc_match_map_guided_batch_dev: jobs = [dict(the keywords of match_map_guided_dev), ...], at most MAX_BATCH (the cameras of one
+        frame against the context's map), one prep and one sweep launch."""
+        n = len(jobs)
+        arr = (MapGuidedJob * max(n, 1))()
+        for i in range(n):
+            _map_guided_fill(arr[i], **jobs[i])
+        self._chk(self.lib.clc_match_map_guided_batch_dev(self.h, arr, n, stream))
 
     def pair_filter_dev(self, model, **job):
         """clc_pair_filter_dev: computeRelativePose's gather + the a-contrario filter of model 'E' | 'F' | 'H' from device memory.  Keywords:

@@ -15,8 +15,20 @@
 //                             of the gfx9 vector ALU, so no v_mov copies a scalar into the loop.
 // It runs whatever formulation the context is set to: a per-pair gate has no place in the matrix sweep, whose C operand is per tile.
 // The jobs travel in records of their own (GuidedJobList), not in K2nnJobDev: the existing sweep kernels are compiled as they were.
+//
+// The same sweep serves the map match guided by a predicted pose (clc_match_map_guided_dev / clc_match_map_guided_batch_dev): the GATE is a
+// template parameter of k2nn_sweep_guided_kernel / sweep_one_guided, so ONE pipelined loop, one LDS fold, one atomic fold and one finalize
+// stand behind both.
+//   LineGate   3 floats per query (the line), limit = band:  v_fma, v_fma, v_cmp, v_cndmask per pair
+//   PointGate  2 floats per query (the undistorted pixel), limit = r2 = radius^2; the train point is the landmark's projection under the
+//              predicted [R|t]:  v_sub, v_sub, v_mul, v_fma, v_cmp, v_cndmask per pair (proj_in_radius, proj_math.h) -- each still reads at
+//              most one scalar operand.  (A lane holds two queries, and the compiler pairs them in packed fp32: v_pk_add_f32 twice,
+//              v_pk_mul_f32, v_pk_fma_f32 per train row, then v_cmp and v_cndmask per query -- IEEE fp32 per half, the same bits.)
+//   proj_prep_kernel  one thread per row: a query row's undistorted pixel (what the track kernel computes for pt2D), a map row's
+//              projection (proj_point from the context's d_map_X), each rounded once to float
 #include "clc_ctx.h"
 #include "guided_math.h"
+#include "proj_math.h"
 #include "k2nn_sweep.h"
 #include "k2nn_top2.h"
 #include "ud_pixel.h"
@@ -49,15 +61,40 @@ static_assert(sizeof(GuidedPrepList) <= 4096, "GuidedPrepList is passed as a ker
 struct GuidedJobDev {
     const uint4* q; const uint4* t;
     int32_t* out; uint16_t* best_out; uint16_t* second_out;
-    const float* L; const float* pos;
+    const float* L; const float* pos;                                 // the gate's floats of every query row (Gate::kF each) / train points
     const uint32_t* cnt_q; const uint32_t* cnt_t;                     // nullable: the detectors' count words
     uint32_t nq, nt, thr;
     uint32_t qblocks, splits, t_per_split, partial_off, cnt_off;      // k2nn_plan's, popcount formulation, atomic fold
-    float band;
+    float band;                                                       // the gate's limit: LineGate's band, PointGate's r2
     uint32_t pad_;
 };
 struct GuidedJobList { GuidedJobDev j[kGuidedMaxJobs]; };
 static_assert(sizeof(GuidedJobList) <= 4096, "GuidedJobList is passed as a kernel argument: it must stay within the 4 KB kernarg segment");
+
+// The map match's prep records: the frame's rows and camera, the predicted [R|t]; the landmarks are the context's, the same for every job.
+struct ProjPrepJob {
+    GatherSide a;
+    double Rt[12];
+    uint32_t nq, pad_;
+    float* qpos; float* proj;         // the context's scratch: 2 nq / 2 nm floats
+    float* qpos_out; float* proj_out; // the caller's copies, nullable
+};
+struct ProjPrepList {
+    ProjPrepJob j[kMaxBatch];
+    const double* map_X; uint32_t nm; // the landmarks of the map rows (d_map_X), nm = the context's map rows
+    float scale[CLC_MAX_LEVELS];      // as PairJobs::scale
+};
+static_assert(sizeof(ProjPrepList) <= 4096, "ProjPrepList is passed as a kernel argument: a batch of CLC_MAX_BATCH cameras is ONE prep launch");
+
+// The two gates.  kF floats of a query stay in the lane's registers; pass() is the ONE statement of the gate (guided_math.h / proj_math.h).
+struct LineGate {
+    static constexpr int kF = 3;
+    static __device__ __forceinline__ bool pass(const float (&g)[3], const float x, const float y, const float lim) { return guided_in_band(g[0], g[1], g[2], x, y, lim); }
+};
+struct PointGate {
+    static constexpr int kF = 2;
+    static __device__ __forceinline__ bool pass(const float (&g)[2], const float x, const float y, const float lim) { return proj_in_radius(g[0], g[1], x, y, lim); }
+};
 
 typedef const u32x2 __attribute__((address_space(4)))* const_u2_ptr;
 typedef const float __attribute__((address_space(1)))* global_cf_ptr;
@@ -98,11 +135,38 @@ __global__ __launch_bounds__(256) void guided_prep_kernel(const GuidedPrepList j
     }
 }
 
+__global__ __launch_bounds__(256) void proj_prep_kernel(const ProjPrepList jobs)
+{
+    const ProjPrepJob& jb = jobs.j[blockIdx.y];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= jb.nq + jobs.nm) return;
+    float xy[2] = { guided_none(), guided_none() };
+    if (i < jb.nq) {
+        if (i < counted(jb.nq, jb.a.count)) {
+            float fx, fy;
+            double u[2];
+            feature_position(jb.a.kps, jb.a.feat, jb.a.feat_stride, i, jobs.scale, &fx, &fy);
+            ud_pixel(fx, fy, jb.a.cam, u);
+            xy[0] = (float)u[0]; xy[1] = (float)u[1];
+        }
+        float* o = jb.qpos + 2u * (size_t)i;
+        o[0] = xy[0]; o[1] = xy[1];
+        if (jb.qpos_out) { float* c = jb.qpos_out + 2u * (size_t)i; c[0] = xy[0]; c[1] = xy[1]; }
+    } else {
+        const uint32_t row = i - jb.nq;
+        const ProjCamera cam{ jb.a.cam.focal, jb.a.cam.ppx, jb.a.cam.ppy };
+        proj_point(jb.Rt, cam, jobs.map_X + 3u * (size_t)row, xy);
+        float* o = jb.proj + 2u * (size_t)row;
+        o[0] = xy[0]; o[1] = xy[1];
+        if (jb.proj_out) { float* c = jb.proj_out + 2u * (size_t)row; c[0] = xy[0]; c[1] = xy[1]; }
+    }
+}
+
 // One train vector (16 wave-uniform dwords in SGPRs) and its point (2 more) against the R queries of this lane: sweep_one of k2nn.hip --
 // the same xor / popcount pairs, in its measured issue pattern (see there) -- with the key formed and gated in C++ behind them:
-// key = (distance << 22) + index, or kEmpty outside the band (guided_in_band, the one statement of the gate); then the med3 / min pair.
-template <int R>
-__device__ __forceinline__ void sweep_one_guided(const uint32_t (&q)[R][16], const float (&L)[R][3], const u32x4 a, const u32x4 b, const u32x4 c,
+// key = (distance << 22) + index, or kEmpty where the gate says no (Gate::pass, the one statement of each gate); then the med3 / min pair.
+template <int R, class Gate>
+__device__ __forceinline__ void sweep_one_guided(const uint32_t (&q)[R][16], const float (&L)[R][Gate::kF], const u32x4 a, const u32x4 b, const u32x4 c,
                                                  const u32x4 d, const u32x2 p, const float band, const uint32_t t_rel, uint32_t (&best)[R],
                                                  uint32_t (&second)[R])
 {
@@ -122,14 +186,14 @@ __device__ __forceinline__ void sweep_one_guided(const uint32_t (&q)[R][16], con
                      : "v"(q[r][8]), "v"(q[r][9]), "v"(q[r][10]), "v"(q[r][11]), "v"(q[r][12]), "v"(q[r][13]), "v"(q[r][14]), "v"(q[r][15]),
                        "s"(c.x), "s"(c.y), "s"(c.z), "s"(c.w), "s"(d.x), "s"(d.y), "s"(d.z), "s"(d.w));
         uint32_t key = (acc << kKeyShift) + t_rel;
-        key = guided_in_band(L[r][0], L[r][1], L[r][2], x, y, band) ? key : kEmpty;
+        key = Gate::pass(L[r], x, y, band) ? key : kEmpty;
         second[r] = top2_med3(best[r], second[r], key);
         best[r] = top2_min(best[r], key);
     }
 #undef K2NN_PAIR
 }
 
-template <int R>
+template <int R, class Gate>
 __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const GuidedJobList jobs, uint2* __restrict__ partial)
 {
     __shared__ uint32_t s_best[kWaves - 1][R][64], s_second[kWaves - 1][R][64];
@@ -146,7 +210,7 @@ __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const Gu
     const uint32_t qbase = qblock * (64u * R) + lane;
 
     uint32_t q[R][16];
-    float L[R][3];
+    float L[R][Gate::kF];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         uint32_t qi = qbase + 64u * r;
@@ -157,8 +221,9 @@ __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const Gu
             const u32x4 v = qp[k];
             q[r][4 * k + 0] = v.x; q[r][4 * k + 1] = v.y; q[r][4 * k + 2] = v.z; q[r][4 * k + 3] = v.w;
         }
-        const global_cf_ptr lp = (global_cf_ptr)(uintptr_t)job.L + (size_t)qi * 3u;
-        L[r][0] = lp[0]; L[r][1] = lp[1]; L[r][2] = lp[2];
+        const global_cf_ptr lp = (global_cf_ptr)(uintptr_t)job.L + (size_t)qi * (size_t)Gate::kF;
+#pragma unroll
+        for (int k = 0; k < Gate::kF; ++k) L[r][k] = lp[k];
     }
     uint32_t best[R], second[R];
 #pragma unroll
@@ -187,7 +252,7 @@ __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const Gu
             const u32x4 a1 = tp[4], b1 = tp[5], c1 = tp[6], d1 = tp[7];          // vector t+1 -> buffer 1
             const u32x2 p1 = pp[1];
             __builtin_amdgcn_sched_barrier(0);
-            sweep_one_guided<R>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
+            sweep_one_guided<R, Gate>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_waitcnt(0xC07F);                 // buffer 1 has landed
             __builtin_amdgcn_sched_barrier(0);
@@ -197,12 +262,12 @@ __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const Gu
             a0 = np[0]; b0 = np[1]; c0 = np[2]; d0 = np[3];
             p0 = npp[0];
             __builtin_amdgcn_sched_barrier(0);
-            sweep_one_guided<R>(q, L, a1, b1, c1, d1, p1, band, t + 1 - s0, best, second);
+            sweep_one_guided<R, Gate>(q, L, a1, b1, c1, d1, p1, band, t + 1 - s0, best, second);
             __builtin_amdgcn_sched_barrier(0);
             tp += 8;
             pp += 2;
         }
-        if (n & 1u) sweep_one_guided<R>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
+        if (n & 1u) sweep_one_guided<R, Gate>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
     }
 
     // fold the kWaves waves through LDS (k2nn_sweep_kernel)
@@ -269,6 +334,60 @@ __global__ __launch_bounds__(256) void guided_nomatch_kernel(const GuidedJobList
     emit_result<false>(fin, qi, kEmpty, kEmpty);
 }
 
+// What the two gates share behind their argument checks.  kj: the live jobs' nq / nt.  The popcount formulation's plan, whatever the
+// context's sweeps run; the scratch -- every job's query floats (qf per row), then its train points, each block starting on 16 bytes --
+// through d_guided's one grow path; the top-2 workspace, cleared if need be; and the sweep's record of every job as far as the plan and
+// the scratch decide it.
+int guided_plan(clc_ctx* ctx, const char* over_capacity, std::vector<K2nnJobDev>& kj, const int qf, hipStream_t st, GuidedJobList& list)
+{
+    const int n = (int)kj.size();
+    const int target = ctx->target_blocks > 0 && ctx->formulation == K2NN_POPCOUNT ? ctx->target_blocks : default_target_blocks(K2NN_POPCOUNT, ctx->k2dev);
+    const K2nnPlan plan = k2nn_plan(kj.data(), n, target, ctx->xcd_map, K2NN_POPCOUNT, 0, 0, ctx->k2dev);
+    if (!plan.atomic_merge) return fail(ctx, CLC_ERR_CAPACITY, over_capacity);
+
+    std::vector<size_t> off_L((size_t)n), off_P((size_t)n);
+    size_t floats = 0;
+    for (int k = 0; k < n; ++k) {
+        off_L[(size_t)k] = floats; floats += ((size_t)qf * (size_t)kj[(size_t)k].nq + 3) & ~(size_t)3;
+        off_P[(size_t)k] = floats; floats += (2 * (size_t)kj[(size_t)k].nt + 3) & ~(size_t)3;
+    }
+    int rc = grow(ctx, ctx->d_guided, floats * sizeof(float), 1, 4, true, "growing d_guided");
+    if (rc == CLC_OK) rc = ensure_partial(ctx, plan.partial_elems);
+    if (rc != CLC_OK) return rc;
+    if (ctx->partial_dirty) {
+        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial.ptr, 0xFF, ctx->d_partial.bytes, st));
+        ctx->partial_dirty = false;
+    }
+    for (int k = 0; k < n; ++k) {
+        const K2nnJobDev& p = kj[(size_t)k];
+        GuidedJobDev& g = list.j[k];
+        g.L = ctx->d_guided.as<float>() + off_L[(size_t)k]; g.pos = ctx->d_guided.as<float>() + off_P[(size_t)k];
+        g.nq = p.nq; g.nt = p.nt;
+        g.qblocks = p.qblocks; g.splits = p.splits; g.t_per_split = p.t_per_split; g.partial_off = p.partial_off; g.cnt_off = p.cnt_off;
+    }
+    return CLC_OK;
+}
+
+// the sweep behind a prep launch (e: what that launch left) and, for the jobs with an empty train side, the answer without one
+template <class Gate> int guided_sweep(clc_ctx* ctx, const char* who, hipError_t e, const GuidedJobList& list, const int n, hipStream_t st)
+{
+    uint32_t grid_x = 0, max_nq_empty = 0;
+    for (int k = 0; k < n; ++k) {
+        if (list.j[k].nt) grid_x = std::max(grid_x, list.j[k].qblocks * list.j[k].splits);
+        else max_nq_empty = std::max(max_nq_empty, list.j[k].nq);
+    }
+    if (e == hipSuccess && grid_x > 0) {
+        hipLaunchKernelGGL((k2nn_sweep_guided_kernel<kR, Gate>), dim3(grid_x, (unsigned)n), dim3(64 * kWaves), 0, st, list, ctx->d_partial.as<uint2>());
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && max_nq_empty > 0) {
+        hipLaunchKernelGGL(guided_nomatch_kernel, dim3((max_nq_empty + 255u) / 256u, (unsigned)n), dim3(256), 0, st, list);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { ctx->partial_dirty = true; return fail(ctx, CLC_ERR_HIP, who, e); }
+    return CLC_OK;
+}
+
 // the arguments of one job, checked; its two sides into `pd`
 int guided_inputs(clc_ctx* ctx, const clc_guided_job& job, PairJobDev& pd)
 {
@@ -308,44 +427,20 @@ int guided_batch(clc_ctx* ctx, const clc_guided_job* jobs, const int n_jobs, voi
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = pick(ctx, stream);
 
-    // the popcount formulation's plan, whatever the context's sweeps run
     std::vector<K2nnJobDev> kj((size_t)n);
     for (int k = 0; k < n; ++k) { kj[(size_t)k] = K2nnJobDev{}; kj[(size_t)k].nq = (uint32_t)jobs[live[(size_t)k]].nq; kj[(size_t)k].nt = (uint32_t)jobs[live[(size_t)k]].nt; }
-    const int target = ctx->target_blocks > 0 && ctx->formulation == K2NN_POPCOUNT ? ctx->target_blocks : default_target_blocks(K2NN_POPCOUNT, ctx->k2dev);
-    const K2nnPlan plan = k2nn_plan(kj.data(), n, target, ctx->xcd_map, K2NN_POPCOUNT, 0, 0, ctx->k2dev);
-    if (!plan.atomic_merge) return fail(ctx, CLC_ERR_CAPACITY, "match_guided: more than 2^22 train rows");
-
-    // scratch: every job's lines, then its train points, each block starting on 16 bytes
-    std::vector<size_t> off_L((size_t)n), off_P((size_t)n);
-    size_t floats = 0;
-    for (int k = 0; k < n; ++k) {
-        off_L[(size_t)k] = floats; floats += (3 * (size_t)kj[(size_t)k].nq + 3) & ~(size_t)3;
-        off_P[(size_t)k] = floats; floats += (2 * (size_t)kj[(size_t)k].nt + 3) & ~(size_t)3;
-    }
-    int rc = grow(ctx, ctx->d_guided, floats * sizeof(float), 1, 4, true, "growing d_guided");
-    if (rc == CLC_OK) rc = ensure_partial(ctx, plan.partial_elems);
-    if (rc != CLC_OK) return rc;
-    if (ctx->partial_dirty) {
-        CLC_HIP(ctx, hipMemsetAsync(ctx->d_partial.ptr, 0xFF, ctx->d_partial.bytes, st));
-        ctx->partial_dirty = false;
-    }
-
     GuidedJobList list{};
-    uint32_t grid_x = 0, max_nq_empty = 0;
+    const int rc = guided_plan(ctx, "match_guided: more than 2^22 train rows", kj, LineGate::kF, st, list);
+    if (rc != CLC_OK) return rc;
     for (int k = 0; k < n; ++k) {
         const clc_guided_job& job = jobs[live[(size_t)k]];
         const PairJobDev& pd = sides[(size_t)live[(size_t)k]];
-        const K2nnJobDev& p = kj[(size_t)k];
         GuidedJobDev& g = list.j[k];
         g.q = (const uint4*)job.d_q; g.t = (const uint4*)job.d_t;
         g.out = job.d_match; g.best_out = job.d_best; g.second_out = job.d_second;
-        g.L = ctx->d_guided.as<float>() + off_L[(size_t)k]; g.pos = ctx->d_guided.as<float>() + off_P[(size_t)k];
         g.cnt_q = pd.a.count; g.cnt_t = pd.b.count;
-        g.nq = p.nq; g.nt = p.nt; g.thr = (uint32_t)(uint8_t)job.threshold;            // CUDAK2NN.cu:46: the kernel parameter is uint8_t
-        g.qblocks = p.qblocks; g.splits = p.splits; g.t_per_split = p.t_per_split; g.partial_off = p.partial_off; g.cnt_off = p.cnt_off;
+        g.thr = (uint32_t)(uint8_t)job.threshold;                                       // CUDAK2NN.cu:46: the kernel parameter is uint8_t
         g.band = job.band;
-        if (p.nt) grid_x = std::max(grid_x, p.qblocks * p.splits);
-        else max_nq_empty = std::max(max_nq_empty, p.nq);
     }
 
     for (int base = 0; base < n; base += kGuidedPrepJobs) {
@@ -366,17 +461,83 @@ int guided_batch(clc_ctx* ctx, const clc_guided_job* jobs, const int n_jobs, voi
         }
         hipLaunchKernelGGL(guided_prep_kernel, dim3((rows + 255u) / 256u, (unsigned)cnt), dim3(256), 0, st, prep);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && grid_x > 0) {
-        hipLaunchKernelGGL(k2nn_sweep_guided_kernel<kR>, dim3(grid_x, (unsigned)n), dim3(64 * kWaves), 0, st, list, ctx->d_partial.as<uint2>());
-        e = hipGetLastError();
+    return guided_sweep<LineGate>(ctx, "match_guided: launch", hipGetLastError(), list, n, st);
+}
+
+// ---- the map match guided by a predicted pose --------------------------------------------------------------------------------------------
+// the arguments of one job, checked; its 2-D side into `side`
+int proj_inputs(clc_ctx* ctx, const clc_map_guided_job& job, GatherSide& side)
+{
+    const auto bad = [&](const char* what) { return fail(ctx, CLC_ERR_BAD_ARG, what); };
+    if (job.nq < 0 || (job.nq > 0 && (!job.d_q || !job.d_match))) return bad("match_map_guided: negative count / null block");
+    if ((uintptr_t)job.d_q & 15u) return bad("match_map_guided: descriptor rows must be 16-byte aligned");
+    if (((uintptr_t)job.d_match & 3u) || ((uintptr_t)job.d_best & 1u) || ((uintptr_t)job.d_second & 1u) || ((uintptr_t)job.d_qpos & 3u) ||
+        ((uintptr_t)job.d_proj & 3u))
+        return bad("match_map_guided: misaligned device pointer");
+    const float r2 = job.radius * job.radius;                                          // the gate's limit, formed once, in float
+    if (!(job.radius > 0.f) || !std::isfinite(job.radius) || !(r2 > 0.f) || !std::isfinite(r2))
+        return bad("match_map_guided: radius and its square must be finite and positive");
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(job.Rt[i])) return bad("match_map_guided: Rt is not finite");
+    clc_pair_job pj{};                                                                  // the side's rules are the gathers' (gather.hip)
+    pj.d_count_a = pj.d_count_b = job.d_count;
+    pj.d_kps_a = pj.d_kps_b = job.d_kps; pj.d_feat_a = pj.d_feat_b = job.d_feat; pj.feat_stride_a = pj.feat_stride_b = job.feat_stride;
+    pj.cam_a = pj.cam_b = job.cam;
+    PairJobDev pd;
+    const int rc = gather_inputs(ctx, pj, pd, "match_map_guided: bad argument");
+    side = pd.a;
+    return rc;
+}
+
+int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, void* stream)
+{
+    if (!ctx || n_jobs < 0 || n_jobs > kMaxBatch || (n_jobs > 0 && !jobs)) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_guided: null context / jobs, or a job count outside 0 .. CLC_MAX_BATCH");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_guided: context created without matcher options");
+    if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_guided before set_map");
+    if (ctx->map_n > 0 && ctx->map_X_n < ctx->map_n)
+        return fail(ctx, CLC_ERR_STATE, "match_map_guided: fewer map points (set_map_points) than map descriptors (set_map)");
+    // everything is checked before anything is enqueued
+    std::vector<GatherSide> sides((size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        const int rc = proj_inputs(ctx, jobs[j], sides[(size_t)j]);
+        if (rc != CLC_OK) return rc;
     }
-    if (e == hipSuccess && max_nq_empty > 0) {
-        hipLaunchKernelGGL(guided_nomatch_kernel, dim3((max_nq_empty + 255u) / 256u, (unsigned)n), dim3(256), 0, st, list);
-        e = hipGetLastError();
+    if ((uint32_t)ctx->map_n > kIdxMask + 1u) return fail(ctx, CLC_ERR_CAPACITY, "match_map_guided: more than 2^22 map rows");
+    std::vector<int> live;                                                   // a job without query rows has nothing to answer
+    for (int j = 0; j < n_jobs; ++j) if (jobs[j].nq > 0) live.push_back(j);
+    if (live.empty()) return CLC_OK;
+    const int n = (int)live.size();
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = pick(ctx, stream);
+
+    const uint32_t nm = (uint32_t)ctx->map_n;
+    std::vector<K2nnJobDev> kj((size_t)n);
+    for (int k = 0; k < n; ++k) { kj[(size_t)k] = K2nnJobDev{}; kj[(size_t)k].nq = (uint32_t)jobs[live[(size_t)k]].nq; kj[(size_t)k].nt = nm; }
+    GuidedJobList list{};
+    const int rc = guided_plan(ctx, "match_map_guided: more than 2^22 map rows", kj, PointGate::kF, st, list);
+    if (rc != CLC_OK) return rc;
+
+    ProjPrepList prep{};
+    for (int l = 0; l < CLC_MAX_LEVELS; ++l) prep.scale[l] = (float)std::pow((double)1.2f, (double)l);          // as launch_gather (gather.hip)
+    prep.map_X = ctx->d_map_X.as<double>(); prep.nm = nm;
+    uint32_t rows = 0;
+    for (int k = 0; k < n; ++k) {
+        const clc_map_guided_job& job = jobs[live[(size_t)k]];
+        GuidedJobDev& g = list.j[k];
+        g.q = (const uint4*)job.d_q; g.t = ctx->d_m.as<uint4>();
+        g.out = job.d_match; g.best_out = job.d_best; g.second_out = job.d_second;
+        g.cnt_q = sides[(size_t)live[(size_t)k]].count; g.cnt_t = nullptr;
+        g.thr = (uint32_t)(uint8_t)job.threshold;                                       // CUDAK2NN.cu:46: the kernel parameter is uint8_t
+        g.band = job.radius * job.radius;
+        ProjPrepJob& pj = prep.j[k];
+        pj.a = sides[(size_t)live[(size_t)k]];
+        for (int i = 0; i < 12; ++i) pj.Rt[i] = job.Rt[i];
+        pj.nq = g.nq;
+        pj.qpos = const_cast<float*>(g.L); pj.proj = const_cast<float*>(g.pos);
+        pj.qpos_out = job.d_qpos; pj.proj_out = job.d_proj;
+        rows = std::max(rows, pj.nq + nm);
     }
-    if (e != hipSuccess) { ctx->partial_dirty = true; return fail(ctx, CLC_ERR_HIP, "match_guided: launch", e); }
-    return CLC_OK;
+    hipLaunchKernelGGL(proj_prep_kernel, dim3((rows + 255u) / 256u, (unsigned)n), dim3(256), 0, st, prep);
+    return guided_sweep<PointGate>(ctx, "match_map_guided: launch", hipGetLastError(), list, n, st);
 }
 
 } // namespace
@@ -396,6 +557,17 @@ int clc_match_guided_dev(clc_ctx* ctx, const clc_guided_job* job, void* stream)
 int clc_match_guided_batch_dev(clc_ctx* ctx, const clc_guided_job* jobs, int n_jobs, void* stream)
 {
     return guided_batch(ctx, jobs, n_jobs, stream);
+}
+
+int clc_match_map_guided_dev(clc_ctx* ctx, const clc_map_guided_job* job, void* stream)
+{
+    if (!job) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_guided: null job");
+    return proj_batch(ctx, job, 1, stream);
+}
+
+int clc_match_map_guided_batch_dev(clc_ctx* ctx, const clc_map_guided_job* jobs, int n_jobs, void* stream)
+{
+    return proj_batch(ctx, jobs, n_jobs, stream);
 }
 
 } // extern "C"

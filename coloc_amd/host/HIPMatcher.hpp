@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "coloc_hip.h"
+#include "coloc_hip_geometry.hpp"
 #include "coloc_hip_types.hpp"
 
 static_assert(CLC_ABI_VERSION >= 3, "this policy header uses entry points of ABI version 3 (clc_detect_and_describe_view, clc_desc_handle)");
@@ -153,6 +154,38 @@ public:
         kpQuery_ = static_cast<unsigned int>(data.regions[droneId]->RegionCount());
         queryRef_ = data.regions[droneId]->DescriptorRawData();
         mapMatches = matchWithMap(queryRef_, static_cast<int>(kpQuery_));
+    }
+
+    // The landmarks of the map's descriptor rows, in mapRegionIdx order, into the MATCHER's context (clc_set_map_points), as
+    // HIPLocalizer::setMapPoints puts them into the localizer's: call it beside setMapData.  Only matchSceneWithMapGuidedDev reads them.
+    // false = success.
+    bool setMapPoints(colocData& data)
+    {
+        std::vector<double> X(3 * data.mapRegionIdx.size());
+        for (size_t i = 0; i < data.mapRegionIdx.size(); ++i) {
+            const auto& P = data.scene.GetLandmarks().at(data.mapRegionIdx[i]).X;
+            for (int r = 0; r < 3; ++r) X[3 * i + r] = P[r];
+        }
+        return !check(clc_set_map_points(ctx_, X.data(), static_cast<int>(data.mapRegionIdx.size())), "setMapPoints");
+    }
+
+    // matchSceneWithMap around a PREDICTED pose (clc_match_map_guided_dev, which states the rule; no counterpart in the reference): a
+    // keypoint is matched only against the map rows whose landmark projects within `radius` pixels of it under predictedPose -- the last
+    // pose, or the filter's statePre -- with the threshold of MatcherOptions.  Everything stays on the device: d_desc / d_kps / d_count are
+    // the detector's blocks for this frame (nq planned rows), d_match_out[nq] is what clc_match_map_dev would leave (a map row or -1) and
+    // feeds HIPLocalizer::localizeImageDev unchanged.  Enqueue only, on `after_stream` -- the stream that produced the descriptors and
+    // keypoints (nullptr: the context's own).  Too few tracks is the caller's cue to fall back on the unguided match.  false = enqueued.
+    bool matchSceneWithMapGuidedDev(const openMVG::geometry::Pose3& predictedPose, const clc_camera_k3& intrinsics, const void* d_desc, int nq,
+                                    const clc_keypoint* d_kps, const uint32_t* d_count, float radius, int32_t* d_match_out, void* after_stream)
+    {
+        clc_map_guided_job jb{};
+        jb.d_q = d_desc; jb.nq = nq; jb.d_count = d_count; jb.d_kps = d_kps;
+        jb.cam = intrinsics;
+        const openMVG::Vec3 t = predictedPose.translation();                     // t = -R C
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) jb.Rt[4 * i + j] = predictedPose.rotation()(i, j); jb.Rt[4 * i + 3] = t[i]; }
+        jb.radius = radius; jb.threshold = matchThreshold_;
+        jb.d_match = d_match_out;
+        return !check(clc_match_map_guided_dev(ctx_, &jb, after_stream), "matchSceneWithMapGuidedDev");
     }
 
     // GPUMatcher.hpp:180-226: IndMatch(i_ = query index, j_ = train index); dmatches(train, query, 0)

@@ -917,6 +917,64 @@ typedef struct clc_guided_job {
 int clc_match_guided_dev(clc_ctx* ctx, const clc_guided_job* job, void* stream);
 int clc_match_guided_batch_dev(clc_ctx* ctx, const clc_guided_job* jobs, int n_jobs, void* stream);
 
+/* ---- tracking by projection: K2NN against the map around a predicted pose ------------------------------------------------------------
+ * The step every frame runs, matchSceneWithMap / clc_match_map_dev (coloc.hpp:219), sweeps every query against every map row whatever
+ * the camera is known to be looking at, so K2NN's global acceptance (CUDAK2NN.cu:75) lets a look-alike landmark anywhere in the map
+ * kill a true match.  From the second frame on a pose prediction exists (the previous pose, or the filter's statePre), and the map's
+ * landmarks are in the context (clc_set_map_points and every clc_map_*_dev install): a keypoint is matched only against the landmarks
+ * that PROJECT near it under the predicted pose.  The same call serves as a re-match under the pose a solve has just returned.  The
+ * reference has no such step: like the guided match above this is THIS library's statement, parity with nothing is pinned, and no
+ * existing entry changes.  (Later under ABI 4: new entry points only.)
+ *
+ * THE RULE.  The train side is the context's map: the rows of clc_set_map and the landmarks of clc_set_map_points (or of an install),
+ * map_n = the number of map rows, as for clc_match_map_dev.
+ *   query point  feature position (d_kps: scale * (float)x in float; d_feat + stride: the floats as they are), then get_ud_pixel in
+ *                fp64: exactly what the track kernel computes for pt2D (clc_track_job).  Each coordinate rounded ONCE to float.  Rows
+ *                at or past d_count[0] hold quiet NaNs (0x7FC00000) and are answered -1.
+ *   train point  of map row i, in fp64, source order, no contraction: Xc = R X_i + t, each row ((R0 X0 + R1 X1) + R2 X2) + t;
+ *                u = focal * (Xc[0] / Xc[2]) + ppx, v = focal * (Xc[1] / Xc[2]) + ppy, each rounded once to float.  The row has NO
+ *                projection (two quiet NaNs) unless Xc[2] > 0 and both floats are finite.  This is the UNDISTORTED pixel, the space the
+ *                solve works in: no distortion is applied to the projection (k1, k2, k3 act on the query side only).
+ *   gate         in fp32 with explicit operations: dx = x_t - x_q, dy = y_t - y_q, d2 = fmaf(dx, dx, dy * dy); map row t is a CANDIDATE
+ *                of q iff d2 <= r2, where r2 = radius * radius is formed once on the host in float.  A NaN anywhere gives false; a
+ *                distance of exactly `radius` is inside.
+ *   top-2        word for word the guided match's: CUDAK2NN.cu:54-75 over the CANDIDATES only, in map-row order; a lone candidate is
+ *                accepted, no candidate gives -1, a tie for the minimum inside the window is rejected; the threshold is truncated to 8
+ *                bits; d_best / d_second (nullable) are saturated to 65535.
+ *   outputs      d_match[nq]: a map row or -1, clc_match_map_dev's orientation, so it feeds clc_track_localize_dev / _batch_dev /
+ *                clc_track_build_dev unchanged.  d_qpos (2 nq floats) / d_proj (2 map_n floats), nullable: the points the sweep read.
+ *   Rt           HOST, 12 doubles: the PREDICTED [R|t], world to camera, row-major 3 x 4 -- the layout clc_track_job.Rt returns.
+ *
+ * Both entries are enqueue-only on `stream` (0: the context's), capturable once the context's scratch has its size, no host wait.  They
+ * run the popcount formulation of the sweep with the gate in its loop (the guided match's kernel, instantiated with this gate),
+ * preceded by ONE prep launch that writes the query points and the projections.  clc_match_map_guided_batch_dev: the cameras of one
+ * frame against the context's one map, n_jobs in [0, CLC_MAX_BATCH], every job's result the single call's, one prep and one sweep launch.
+ * Errors, all checked before anything is enqueued: radius or radius * radius not finite and positive, a non-finite Rt, both or neither
+ * of d_kps / d_feat, a misaligned pointer (descriptor rows: 16 bytes), a non-positive focal, a null context or job, n_jobs out of range:
+ * CLC_ERR_BAD_ARG; a context without matcher options, without a map, or with fewer map points than map rows (the rule of
+ * clc_track_localize_dev): CLC_ERR_STATE; more than 2^22 map rows: CLC_ERR_CAPACITY.  nq == 0: nothing is written.  An empty map
+ * (map_n == 0): every query -1.  The fallback is the caller's: a wrong prediction yields few matches, never wrong geometry, and fewer
+ * tracks than wanted means calling clc_match_map_dev. */
+typedef struct clc_map_guided_job {
+    const void*         d_q;            /* the frame's descriptors: nq rows of 64 bytes, 16-byte aligned */
+    int                 nq;
+    const uint32_t*     d_count;        /* nullable, as clc_track_job */
+    const clc_keypoint* d_kps;          /* or */
+    const float*        d_feat;
+    int                 feat_stride;
+    clc_camera_k3       cam;
+    double              Rt[12];         /* host: the predicted pose */
+    float               radius;         /* pixels */
+    int                 threshold;
+    int32_t*            d_match;        /* nq, device */
+    uint16_t*           d_best;         /* nullable, device */
+    uint16_t*           d_second;
+    float*              d_qpos;         /* nullable, device: 2 nq floats */
+    float*              d_proj;         /* nullable, device: 2 map_n floats */
+} clc_map_guided_job;
+int clc_match_map_guided_dev(clc_ctx* ctx, const clc_map_guided_job* job, void* stream);
+int clc_match_map_guided_batch_dev(clc_ctx* ctx, const clc_map_guided_job* jobs, int n_jobs, void* stream);
+
 /* ---- the inter-camera step from device memory: ColoC::interPoseEstimator (coloc.hpp:296-340) without a host trip --------------------
  * What clc_inter_pose_batch computes, fed from the pair's d_match instead of host correspondences: the pair gather and the 'E' filter of
  * clc_pair_filter_dev, then -- on the device, in the operation order of the host path, so with its bits -- the chirality vote over the
