@@ -64,13 +64,6 @@ int ensure_partial(clc_ctx* ctx, size_t elems)
     return CLC_OK;
 }
 
-// half as much again: a stream of solves whose sizes creep upwards (map matches per frame) must not reallocate at every new maximum
-int ensure_pnp(clc_ctx* ctx, size_t doubles) { return grow(ctx, ctx->d_pnp, doubles * sizeof(double), 1, 2, true, "growing d_pnp"); }
-
-// Host staging for the robust pose solve: ONE pinned buffer, ONE H2D copy in, ONE D2H copy out.
-// (half as much again, see ensure_pnp: a pinned allocation costs a millisecond)
-int ensure_pinned(clc_ctx* ctx, size_t bytes) { return grow(ctx, ctx->h_pin, bytes, 1, 2, true, "growing h_pin"); }
-
 // room for the pyramids (+ score maps, keypoint masks, tile counts) of n cameras; slot 0 (the current single-image pyramid) does not
 // survive a growth -- every caller rebuilds it.  A failed growth leaves the old arena in place.
 int ensure_slots(clc_ctx* ctx, int n, hipStream_t st)
@@ -92,8 +85,6 @@ int ensure_slots(clc_ctx* ctx, int n, hipStream_t st)
     ctx->arena_slots = n;
     return CLC_OK;
 }
-
-int ensure_results(clc_ctx* ctx, size_t bytes) { return grow(ctx, ctx->h_res, bytes, 0, 1, true, "growing h_res"); }
 
 } // namespace clc
 

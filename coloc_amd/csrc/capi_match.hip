@@ -417,10 +417,9 @@ void release_sets(HostSet* sets, int n_sets)
 int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
 {
     const size_t nq = (size_t)q.n;
-    const size_t off_best = nq * sizeof(int32_t), off_second = off_best + nq * sizeof(uint16_t);
-    int rc = ensure_results(ctx, off_second + nq * sizeof(uint16_t) + 64);
+    MatchPin pin;
+    int rc = ensure_results(ctx, [&](Carve& c) { pin.carve(c, nq); });
     if (rc != CLC_OK) return rc;
-    uint8_t* const h_res = ctx->h_res.as<uint8_t>();
     HostSet* sets[2] = { &q, &t };
     for (HostSet* s : sets) { rc = resolve(ctx, *s); if (rc != CLC_OK) { release_sets(&q, 1); release_sets(&t, 1); return rc; } }
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -436,9 +435,9 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
         rule.apply(jobs[0]);
         rc = run_jobs(ctx, jobs, ctx->stream);
         hipError_t e = hipSuccess;
-        if (rc == CLC_OK) e = hipMemcpyAsync(h_res, ctx->d_match.ptr, nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (rc == CLC_OK && e == hipSuccess && h_best) e = hipMemcpyAsync(h_res + off_best, ctx->d_best.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (rc == CLC_OK && e == hipSuccess && h_second) e = hipMemcpyAsync(h_res + off_second, ctx->d_second.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK) e = hipMemcpyAsync(pin.match, ctx->d_match.ptr, nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK && e == hipSuccess && h_best) e = hipMemcpyAsync(pin.best, ctx->d_best.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK && e == hipSuccess && h_second) e = hipMemcpyAsync(pin.second, ctx->d_second.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
         if (rc == CLC_OK && e != hipSuccess) rc = fail(ctx, CLC_ERR_HIP, "match: result download", e);
         // the GPU is sweeping: now the pass over the host blocks that stand on published rows
         bool good = true;
@@ -448,9 +447,9 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
     }
     release_sets(&q, 1); release_sets(&t, 1);
     if (rc != CLC_OK) return rc;
-    memcpy(h_match, h_res, nq * sizeof(int32_t));
-    if (h_best) memcpy(h_best, h_res + off_best, nq * sizeof(uint16_t));
-    if (h_second) memcpy(h_second, h_res + off_second, nq * sizeof(uint16_t));
+    memcpy(h_match, pin.match, nq * sizeof(int32_t));
+    if (h_best) memcpy(h_best, pin.best, nq * sizeof(uint16_t));
+    if (h_second) memcpy(h_second, pin.second, nq * sizeof(uint16_t));
     return CLC_OK;
 }
 
@@ -479,7 +478,8 @@ int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts,
     const size_t need = desc_bytes + out_rows * sizeof(int32_t) + 256;
     { const int rc = grow(ctx, ctx->d_pairs, need, 0, 1, true, "growing d_pairs"); if (rc != CLC_OK) return rc; }
     uint8_t* const d_pairs = ctx->d_pairs.as<uint8_t>();
-    { const int rc = ensure_results(ctx, out_rows * sizeof(int32_t) + 64); if (rc != CLC_OK) return rc; }
+    int32_t* h_out = nullptr;                                     // the pinned mirror: every pair's rows behind each other, and 64 B
+    { const int rc = ensure_results(ctx, [&](Carve& c) { h_out = c.take<int32_t>(out_rows + 16); }); if (rc != CLC_OK) return rc; }
     // a camera whose block the front end published on this device is read where it lies; the others are uploaded
     std::vector<HostSet> cams((size_t)ncams);
     struct Release { std::vector<HostSet>& s; ~Release() { release_sets(s.data(), (int)s.size()); } } release{ cams };
@@ -513,7 +513,7 @@ int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts,
             const int rc = run_jobs(ctx, jobs, ctx->stream);
             if (rc != CLC_OK) return rc;
         }
-        if (out_rows) CLC_HIP(ctx, hipMemcpyAsync(ctx->h_res.ptr, d_out, out_rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_rows) CLC_HIP(ctx, hipMemcpyAsync(h_out, d_out, out_rows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         bool good = true;
         { const int rc = verify_sets(ctx, cams.data(), ncams, &good); if (rc != CLC_OK) return rc; }
         CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -521,7 +521,7 @@ int match_pairs_host(clc_ctx* ctx, const void* const* h_desc, const int* counts,
     }
     for (int p = 0; p < npairs; ++p) {
         const int a = pairs[2 * p + q_side];
-        if (counts[a] > 0) memcpy(h_match[p], ctx->h_res.as<uint8_t>() + out_off[p] * sizeof(int32_t), (size_t)counts[a] * sizeof(int32_t));
+        if (counts[a] > 0) memcpy(h_match[p], h_out + out_off[p], (size_t)counts[a] * sizeof(int32_t));
     }
     return CLC_OK;
 }

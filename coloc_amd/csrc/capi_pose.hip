@@ -17,15 +17,10 @@ extern "C" {
 static int pnp_upload(clc_ctx* ctx, const double* h_Rt, int H, const double* h_X, const double* h_x, int N,
                       const double* h_K, size_t extra, double** dRt, double** dX, double** dx, double** dK, double** dExtra)
 {
-    const size_t need = (size_t)12 * H + (size_t)5 * N + 16 + extra;
-    const int rc = ensure_pnp(ctx, need);
+    PnpScoreDev dv;
+    const int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, (size_t)H, (size_t)N, extra); });
     if (rc != CLC_OK) return rc;
-    double* p = ctx->d_pnp.as<double>();
-    *dRt = p; p += (size_t)12 * H;
-    *dX = p; p += (size_t)3 * N;
-    *dx = p; p += (size_t)2 * N;
-    *dK = p; p += 16;
-    *dExtra = p;
+    *dRt = dv.Rt; *dX = dv.X; *dx = dv.x; *dK = dv.K; *dExtra = dv.extra;
     CLC_HIP(ctx, hipMemcpyAsync(*dRt, h_Rt, sizeof(double) * 12 * H, hipMemcpyHostToDevice, ctx->stream));
     if (N > 0) {
         CLC_HIP(ctx, hipMemcpyAsync(*dX, h_X, sizeof(double) * 3 * N, hipMemcpyHostToDevice, ctx->stream));
@@ -79,12 +74,10 @@ static int epipolar_impl(clc_ctx* ctx, const double* h_F, int H, const double* h
     if (H > 65535) return fail(ctx, CLC_ERR_CAPACITY, "epipolar: more than 65535 hypotheses per call");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t out = h_err ? (size_t)H * N : (size_t)2 * H;
-    const int rc = ensure_pnp(ctx, (size_t)9 * H + (size_t)4 * N + out + 8);
+    EpipolarDev dv;
+    const int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, (size_t)H, (size_t)N, out); });
     if (rc != CLC_OK) return rc;
-    double* dF = ctx->d_pnp.as<double>();
-    double* d1 = dF + (size_t)9 * H;
-    double* d2 = d1 + (size_t)2 * N;
-    double* dO = d2 + (size_t)2 * N;
+    double *dF = dv.F, *d1 = dv.x1, *d2 = dv.x2, *dO = dv.out;
     CLC_HIP(ctx, hipMemcpyAsync(dF, h_F, sizeof(double) * 9 * H, hipMemcpyHostToDevice, ctx->stream));
     if (N > 0) {
         CLC_HIP(ctx, hipMemcpyAsync(d1, h_x1, sizeof(double) * 2 * N, hipMemcpyHostToDevice, ctx->stream));
@@ -136,56 +129,40 @@ static int pnp_ransac_impl(clc_ctx* ctx, const double* h_X, const double* h_x, i
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<int32_t> drawn;
     if (!h_samples) { draw_samples(seed, S, N, drawn); h_samples = drawn.data(); }
-    // device workspace, in doubles:  [ X 3N | x 2N | K 16 | samples (3S int32) ]  <- one H2D copy
-    //                               [ Rt 48S | cost 4S | count (4S int32) ]      scratch
-    //                               [ result record | mask N bytes ]             <- one D2H copy
-    const size_t in_d = (size_t)5 * N + 16 + ((size_t)3 * S + 1) / 2;
-    const size_t scr_d = (size_t)48 * S + (size_t)4 * S + ((size_t)4 * S + 1) / 2;
+    // RansacDev / RansacPin: [ X 3N | x 2N | K 16 | samples ] in, 4 slots of [R|t] per sample, [ result | refine record | mask ] out
     const bool refine = refine_huber > 0.0;
-    const size_t ref_d = refine ? (sizeof(RefineOut) + 7) / 8 : 0;      // refine record rides in front of the mask
-    const size_t res_d = (sizeof(PnpResult) + 7) / 8 + ref_d;
-    const size_t out_d = res_d + ((size_t)N + 7) / 8;
-    int rc = ensure_pnp(ctx, in_d + scr_d + out_d + 8);
+    const RansacDims dims{ (size_t)N, (size_t)S, 5, 1, 3, 4, 12, sizeof(PnpResult), refine ? sizeof(RefineOut) : 0 };
+    RansacDev dv; RansacPin pin;
+    int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, dims); });
+    if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, dims, false); });
     if (rc != CLC_OK) return rc;
-    rc = ensure_pinned(ctx, (in_d + out_d) * sizeof(double) + 64);
-    if (rc != CLC_OK) return rc;
-    double* dX = ctx->d_pnp.as<double>();
-    double* dx = dX + (size_t)3 * N;
-    double* dK = dx + (size_t)2 * N;
-    int32_t* dSamples = (int32_t*)(dK + 16);
-    double* dRt = ctx->d_pnp.as<double>() + in_d;
-    double* dCost = dRt + (size_t)48 * S;
-    int32_t* dCount = (int32_t*)(dCost + (size_t)4 * S);
-    double* dRes = ctx->d_pnp.as<double>() + in_d + scr_d;
-    uint8_t* dMask = (uint8_t*)(dRes + res_d);
+    double *dX = dv.in.pts, *dx = dX + (size_t)3 * N, *dK = dv.in.K, *dRt = dv.models;
+    uint8_t* dMask = dv.out.mask;
     // Inputs go into the pinned buffer and stay there: the first launch reads them over PCIe and stages them into
     // device memory itself, the last launch writes record + mask back into the pinned buffer.  No copy commands: a
     // pose solve is three (four with refinement) kernel launches and one stream synchronisation.
-    double* hp = ctx->h_pin.as<double>();
-    double* hout = hp + in_d;
-    memcpy(hp, h_X, sizeof(double) * 3 * N);
-    memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
-    memcpy(hp + (size_t)5 * N, h_K, sizeof(double) * 9);
-    memcpy(hp + (size_t)5 * N + 16, h_samples, sizeof(int32_t) * 3 * S);
-    const size_t ref_off = (sizeof(PnpResult) + 7) / 8;
+    memcpy(pin.in.pts, h_X, sizeof(double) * 3 * N);
+    memcpy(pin.in.pts + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
+    memcpy(pin.in.K, h_K, sizeof(double) * 9);
+    memcpy(pin.in.samples, h_samples, sizeof(int32_t) * 3 * S);
     PnpHostStage hs;
-    hs.src = hp;
-    hs.n_doubles = (int)in_d;
-    hs.h_mask = (uint8_t*)(hout + res_d);
-    hs.h_result = hout;
-    CLC_HIP(ctx, launch_pnp_ransac(dX, dx, N, dK, dSamples, S, thr2, dRt, dCount, dCost, dMask, dRes, ctx->stream, &ctx->prof, &hs));
+    hs.src = pin.in.pts;
+    hs.n_doubles = (int)(pin.in.bytes / sizeof(double));
+    hs.h_mask = pin.out.mask;
+    hs.h_result = pin.out.result;
+    CLC_HIP(ctx, launch_pnp_ransac(dX, dx, N, dK, dv.in.samples, S, thr2, dRt, dv.count, dv.cost, dMask, dv.out.result, ctx->stream, &ctx->prof, &hs));
     if (refine)
-        CLC_HIP(ctx, launch_pnp_refine(dRes /* PnpResult.Rt */, dX, dx, dMask, N, dK, refine_huber, 50, dRes + ref_off, ctx->stream,
-                                       &ctx->prof, &((const PnpResult*)dRes)->h, hout + ref_off));
+        CLC_HIP(ctx, launch_pnp_refine((const double*)dv.out.result /* PnpResult.Rt */, dX, dx, dMask, N, dK, refine_huber, 50, dv.out.ref, ctx->stream,
+                                       &ctx->prof, &((const PnpResult*)dv.out.result)->h, pin.out.ref));
     if (h_all_Rt) CLC_HIP(ctx, hipMemcpyAsync(h_all_Rt, dRt, sizeof(double) * 48 * S, hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const PnpResult& r = *(const PnpResult*)hout;
+    const PnpResult& r = *(const PnpResult*)pin.out.result;
     if (h_Rt) memcpy(h_Rt, r.Rt, sizeof r.Rt);
-    if (h_mask) memcpy(h_mask, (const uint8_t*)(hout + res_d), (size_t)N);
+    if (h_mask) memcpy(h_mask, pin.out.mask, (size_t)N);
     if (n_inliers) *n_inliers = r.h >= 0 ? r.count : 0;
     if (cost) *cost = r.cost;
     if (refine) {
-        const RefineOut& f = *(const RefineOut*)(hout + ref_off);
+        const RefineOut& f = *(const RefineOut*)pin.out.ref;
         if (h_Rt) memcpy(h_Rt, f.Rt, sizeof f.Rt);
         if (h_cov) memcpy(h_cov, f.cov, sizeof f.cov);
         if (rmse) *rmse = f.rmse;
@@ -216,42 +193,30 @@ static int essential_impl(clc_ctx* ctx, const double* h_x1, const double* h_x2, 
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     std::vector<int32_t> drawn;
     if (!h_samples) { draw_samples(seed, S, N, drawn, 5); h_samples = drawn.data(); }
-    // device workspace in doubles: [ x1 2N | x2 2N | K1 16 | K2 16 | samples (5S int32) ] in,
-    //                              [ FE 180 S | cost 10 S | count (10 S int32) ] scratch, [ result | mask ] out
-    const size_t in_d = (size_t)4 * N + 32 + ((size_t)5 * S + 1) / 2;
-    const size_t scr_d = (size_t)180 * S + (size_t)10 * S + ((size_t)10 * S + 1) / 2;
-    const size_t res_d = (sizeof(EpiResult) + 7) / 8;
-    const size_t out_d = res_d + ((size_t)N + 7) / 8;
-    int rc = ensure_pnp(ctx, in_d + scr_d + out_d + 8);
+    // RansacDev / RansacPin: [ x1 2N | x2 2N | K1 16 | K2 16 | samples ] in (one copy), 10 slots of { F, E } per sample,
+    // [ result | mask ] out (one copy, over the inputs in the pinned block)
+    const RansacDims dims{ (size_t)N, (size_t)S, 4, 2, 5, 10, 18, sizeof(EpiResult), 0 };
+    RansacDev dv; RansacPin pin;
+    int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, dims); });
+    if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, dims, true); });
     if (rc != CLC_OK) return rc;
-    rc = ensure_pinned(ctx, (in_d > out_d ? in_d : out_d) * sizeof(double) + 64);
-    if (rc != CLC_OK) return rc;
-    double* d1 = ctx->d_pnp.as<double>();
-    double* d2 = d1 + (size_t)2 * N;
-    double* dK1 = d2 + (size_t)2 * N;
-    double* dK2 = dK1 + 16;
-    int32_t* dSamples = (int32_t*)(dK2 + 16);
-    double* dFE = ctx->d_pnp.as<double>() + in_d;
-    double* dCost = dFE + (size_t)180 * S;
-    int32_t* dCount = (int32_t*)(dCost + (size_t)10 * S);
-    double* dRes = ctx->d_pnp.as<double>() + in_d + scr_d;
-    uint8_t* dMask = (uint8_t*)(dRes + res_d);
-    double* hp = ctx->h_pin.as<double>();
-    memcpy(hp, h_x1, sizeof(double) * 2 * N);
-    memcpy(hp + (size_t)2 * N, h_x2, sizeof(double) * 2 * N);
-    memcpy(hp + (size_t)4 * N, h_K1, sizeof(double) * 9);
-    memcpy(hp + (size_t)4 * N + 16, h_K2, sizeof(double) * 9);
-    memcpy(hp + (size_t)4 * N + 32, h_samples, sizeof(int32_t) * 5 * S);
-    CLC_HIP(ctx, hipMemcpyAsync(d1, hp, in_d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_essential_ransac(d1, d2, N, dK1, dK2, dSamples, S, thr2, dFE, dCount, dCost, dMask, dRes, ctx->stream, &ctx->prof));
-    CLC_HIP(ctx, hipMemcpyAsync(hp, dRes, out_d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    double *d1 = dv.in.pts, *d2 = d1 + (size_t)2 * N, *dFE = dv.models;
+    memcpy(pin.in.pts, h_x1, sizeof(double) * 2 * N);
+    memcpy(pin.in.pts + (size_t)2 * N, h_x2, sizeof(double) * 2 * N);
+    memcpy(pin.in.K, h_K1, sizeof(double) * 9);
+    memcpy(pin.in.K + 16, h_K2, sizeof(double) * 9);
+    memcpy(pin.in.samples, h_samples, sizeof(int32_t) * 5 * S);
+    CLC_HIP(ctx, hipMemcpyAsync(d1, pin.in.pts, pin.in.bytes, hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, launch_essential_ransac(d1, d2, N, dv.in.K, dv.in.K + 16, dv.in.samples, S, thr2, dFE, dv.count, dv.cost, dv.out.mask, dv.out.result, ctx->stream,
+                                         &ctx->prof));
+    CLC_HIP(ctx, hipMemcpyAsync(pin.out.result, dv.out.result, pin.out.bytes, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<double> fe;
     if (h_all_E) { fe.resize((size_t)180 * S); CLC_HIP(ctx, hipMemcpyAsync(fe.data(), dFE, sizeof(double) * 180 * S, hipMemcpyDeviceToHost, ctx->stream)); }
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const EpiResult& r = *(const EpiResult*)hp;
+    const EpiResult& r = *(const EpiResult*)pin.out.result;
     if (h_E) memcpy(h_E, r.E, sizeof r.E);
     if (h_F) memcpy(h_F, r.F, sizeof r.F);
-    if (h_mask) memcpy(h_mask, (const uint8_t*)(hp + res_d), (size_t)N);
+    if (h_mask) memcpy(h_mask, pin.out.mask, (size_t)N);
     if (n_inliers) *n_inliers = r.h >= 0 ? r.count : 0;
     if (h_all_E)
         for (size_t k = 0; k < (size_t)10 * S; ++k) memcpy(h_all_E + 9 * k, fe.data() + 18 * k + 9, sizeof(double) * 9);
@@ -287,31 +252,21 @@ int clc_pnp_refine(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
     if (!(huber_a > 0.0)) huber_a = 16.0;          // ceres::HuberLoss(Square(4.0)), Refiner.hpp:122
     if (max_iter <= 0) max_iter = 50;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    // workspace in doubles: [ X 3N | x 2N | K 16 | Rt_in 12 | mask (N bytes) ] in, [ RefineOut ] out
-    const size_t mask_d = ((size_t)N + 7) / 8;
-    const size_t in_d = (size_t)5 * N + 16 + 12 + mask_d;
-    const size_t out_d = (sizeof(RefineOut) + 7) / 8;
-    int rc = ensure_pnp(ctx, in_d + out_d + 8);
+    // RefineDev / RefinePin: [ X 3N | x 2N | K 16 | Rt_in 12 | mask (N bytes) ] in (one copy), the record out (over the inputs in the pinned block)
+    RefineDev dv; RefinePin pin;
+    int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, (size_t)N, true, sizeof(RefineOut)); });
+    if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, (size_t)N, true, sizeof(RefineOut), true); });
     if (rc != CLC_OK) return rc;
-    rc = ensure_pinned(ctx, (in_d > out_d ? in_d : out_d) * sizeof(double) + 64);
-    if (rc != CLC_OK) return rc;
-    double* dX = ctx->d_pnp.as<double>();
-    double* dx = dX + (size_t)3 * N;
-    double* dK = dx + (size_t)2 * N;
-    double* dRt = dK + 16;
-    uint8_t* dMask = (uint8_t*)(dRt + 12);
-    double* dOut = ctx->d_pnp.as<double>() + in_d;
-    double* hp = ctx->h_pin.as<double>();
-    memcpy(hp, h_X, sizeof(double) * 3 * N);
-    memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
-    memcpy(hp + (size_t)5 * N, h_K, sizeof(double) * 9);
-    memcpy(hp + (size_t)5 * N + 16, h_Rt_in, sizeof(double) * 12);
-    if (h_inlier_mask) memcpy(hp + (size_t)5 * N + 28, h_inlier_mask, (size_t)N);
-    CLC_HIP(ctx, hipMemcpyAsync(dX, hp, in_d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_pnp_refine(dRt, dX, dx, h_inlier_mask ? dMask : nullptr, N, dK, huber_a, max_iter, dOut, ctx->stream, &ctx->prof));
-    CLC_HIP(ctx, hipMemcpyAsync(hp, dOut, out_d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    memcpy(pin.in.X, h_X, sizeof(double) * 3 * N);
+    memcpy(pin.in.x, h_x, sizeof(double) * 2 * N);
+    memcpy(pin.in.K, h_K, sizeof(double) * 9);
+    memcpy(pin.in.Rt, h_Rt_in, sizeof(double) * 12);
+    if (h_inlier_mask) memcpy(pin.in.mask, h_inlier_mask, (size_t)N);
+    CLC_HIP(ctx, hipMemcpyAsync(dv.in.X, pin.in.X, pin.in.bytes, hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, launch_pnp_refine(dv.in.Rt, dv.in.X, dv.in.x, h_inlier_mask ? dv.in.mask : nullptr, N, dv.in.K, huber_a, max_iter, dv.out, ctx->stream, &ctx->prof));
+    CLC_HIP(ctx, hipMemcpyAsync(pin.out, dv.out, sizeof(RefineOut), hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const RefineOut& r = *(const RefineOut*)hp;
+    const RefineOut& r = *pin.out;
     if (h_Rt_out) memcpy(h_Rt_out, r.Rt, sizeof r.Rt);
     if (h_cov) memcpy(h_cov, r.cov, sizeof r.cov);
     if (rmse) *rmse = r.rmse;

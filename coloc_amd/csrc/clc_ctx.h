@@ -4,8 +4,10 @@
 
 #include "clc_buf.h"
 #include "clc_internal.h"
+#include "clc_layout.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -53,28 +55,8 @@ struct DescEntry;
 // context's own d_desc (own_rows); NONE = the last describing call wrote a caller buffer or failed, or nothing was described yet
 enum { ROWS_NONE = 0, ROWS_STAGED = 1, ROWS_OWN = 2 };
 
-// A context's block of gathered correspondences, device and pinned, for `cap` of them (ensure_gather):
-//   device [ a (a_width cap doubles) | b (2 cap) | q cap | t cap | n ]     tracks: X | x | query | map, pairs: x1 | x2 | q | t
-//   pinned [ count word (64 B, 0xFF.. = not out yet) | a | b (where the points are mirrored: pairs) | q | t ]
+// A context's block of gathered correspondences, device and pinned, for `cap` of them (ensure_gather; its arrays: GatherView, clc_layout.h)
 struct GatherBlock { DevBuf d; PinBuf h; size_t cap = 0; };
-struct GatherLayout {
-    int a_width; bool mirror_points;
-    size_t d_row() const { return (size_t)(a_width + 2) * sizeof(double) + 2 * sizeof(int32_t); }
-    size_t h_row() const { return (mirror_points ? (size_t)(a_width + 2) * sizeof(double) : 0) + 2 * sizeof(int32_t); }
-};
-constexpr GatherLayout kTrackLayout{ 3, false }, kPairLayout{ 2, true };
-// the block as its arrays (h_a / h_b: null where the points are not mirrored)
-struct GatherView {
-    double *a, *b; int32_t *q, *t, *n; uint32_t* h_n; double *h_a = nullptr, *h_b = nullptr; int32_t *h_q, *h_t;
-    GatherView(const GatherBlock& g, const GatherLayout& lay)
-    {
-        a = g.d.as<double>(); b = a + lay.a_width * g.cap; q = (int32_t*)(b + 2 * g.cap); t = q + g.cap; n = t + g.cap;
-        h_n = g.h.as<uint32_t>();
-        double* hp = (double*)(g.h.as<uint8_t>() + 64);
-        if (lay.mirror_points) { h_a = hp; h_b = hp + lay.a_width * g.cap; hp = h_b + 2 * g.cap; }
-        h_q = (int32_t*)hp; h_t = h_q + g.cap;
-    }
-};
 } // namespace clc
 
 struct clc_ctx {
@@ -111,7 +93,7 @@ struct clc_ctx {
     clc::DevBuf d_partial;           // uint2: the armed top-2 rows + arrival counters of the K2NN sweeps
     bool partial_dirty = false;      // armed (all-ones) state of the atomic top-2 rows was lost
     clc::DevBuf d_guided;            // float: the lines (3 per query row) and train points (2 per train row) of a guided match, or the query
-                                     // points (2) and the landmarks' projections (2 per map row) of a map match around a pose (k2nn_guided.hip)
+                                     // points (2) and the landmarks' projections (2 per map row) of a map match around a pose (GuidedDev)
     int formulation = clc::K2NN_MATRIX;   // K2NN sweep formulation (k2nn.hip): FP4 matrix pipe, or round 1's popcount kernel for A/B runs
     int target_blocks = 0;           // K2NN sweep workgroups aimed at per launch; 0 = the formulation's default
     int bias_a = 326, bias_b = 249;  // matrix sweep, one-round single-job plans: train share of a workgroup on wave slot 0 / 1 in 1/256 of the
@@ -131,27 +113,25 @@ struct clc_ctx {
     int map_X_n = -1;             // (-1: none set)
     clc::GatherBlock trk, pair;   // the tracks (clc_track_localize*_dev) / the pairs (clc_pair_filter*_dev) of this context's job
     clc::Event ev_track;             // orders the track / pair launch behind job.after_stream, and the contexts' streams behind the launch
-    // the inter-camera step from device memory (inter_dev.hip): temporary map, lists, the refinement's inputs / the pinned records
+    // the inter-camera step from device memory (inter_dev.hip; InterDev / InterPin, clc_layout.h)
     clc::DevBuf d_inter;
     clc::PinBuf h_inter;
-    // the map built on the device (map_build.hip): union-find words, track table and the staged map lists; the next map's points, which
-    // change places with d_map_X when a build succeeds; the pinned count and the mirrors of the host outputs
+    // the map built on the device (map_build.hip; MapStageDev / MapStagePin); the next map's points, which change places with d_map_X
+    // when a build succeeds
     clc::DevBuf d_mapb, d_map_X_next;
     clc::PinBuf h_mapb;
     // the map replaced at the old map's scale (map_update.hip): the NEXT map's descriptor rows, allocated on first use at d_m's size --
     // the sweep clamps its train reads to the last row (k2nn.hip), so nothing past the rows gathered is read and nothing is zeroed --
-    // which change places with d_m on install; the match and the common lists; the pinned record and the mirrors of the host outputs
+    // which change places with d_m on install; the match and the common lists and their pinned mirror (AlignDev / AlignPin)
     clc::DevBuf d_m_next, d_align;
     clc::PinBuf h_align;
-    // the map grown past the seed pair (map_grow.hip): device [ X per track | obs per track | the grown map's camera list ], pinned
-    // [ row count 64 B | camera list | masks ]; the per-track state of the last grown build, for clc_map_resect_build_dev -- the table
-    // lies in d_mapb, so whatever rewrites that block (a tracks / map build) ends it (grow_table = null)
+    // the map grown past the seed pair (map_grow.hip; GrowDev / GrowPin); the per-track state of the last grown build, for
+    // clc_map_resect_build_dev -- the table lies in d_mapb, so whatever rewrites that block (a tracks / map build) ends it (grow_table = null)
     clc::DevBuf d_growb;
     clc::PinBuf h_growb;
     const int32_t* grow_table = nullptr; const int32_t* grow_n_tracks = nullptr;
     int grow_n_cams = 0, grow_cap = 0;
-    // the bundle adjustment (map_ba.hip): device [ state | compaction lists | per-observation and per-point records | trial points |
-    // the workgroups' partial sums | the pixels of a composition ], pinned the record the host waits for
+    // the bundle adjustment (map_ba.hip; BaDev / BaPin)
     clc::DevBuf d_bab;
     clc::PinBuf h_bab;
     // host front end (clc_detect_and_describe*): ONE pinned block [ image | keypoints | descriptors | {written, found} ] the frame goes
@@ -198,13 +178,45 @@ template <class B> inline int grow(clc_ctx* ctx, B& b, size_t need, size_t num, 
     return e == hipSuccess ? CLC_OK : fail(ctx, CLC_ERR_HIP, what, e);
 }
 
+// THE way a block gets its arrays (clc_layout.h).  lay(Carve&): the block's layout -- a view's carve() with the block's dimensions.  It
+// is run on a measuring cursor, the block grown to what that took (grow's arguments as they are), then run on the block.  place_block:
+// the second half alone, for a consumer that places a view on a block an earlier call laid out; a view that runs past its block is
+// refused (CLC_ERR_STATE, `what`) instead of being handed to a kernel.
+template <class B, class F> inline int place_block(clc_ctx* ctx, const B& b, const char* what, F&& lay)
+{
+    Carve c(b.ptr);
+    lay(c);
+    return c.bytes() <= b.bytes ? CLC_OK : fail(ctx, CLC_ERR_STATE, what);
+}
+template <class B, class F> inline int carve_block(clc_ctx* ctx, B& b, size_t num, size_t den, bool sync_first, const char* what, F&& lay)
+{
+    Carve measure;
+    lay(measure);
+    const int rc = grow(ctx, b, measure.bytes(), num, den, sync_first, what);
+    return rc == CLC_OK ? place_block(ctx, b, what, lay) : rc;
+}
+
 // context-owned workspaces, grown on demand (capi_core.hip)
 int ensure_partial(clc_ctx* ctx, size_t elems);           // armed K2NN top-2 rows + arrival counters
-int ensure_pnp(clc_ctx* ctx, size_t doubles);             // pose scratch
-int ensure_pinned(clc_ctx* ctx, size_t bytes);            // pinned staging of the pose solves
 int ensure_slots(clc_ctx* ctx, int n, hipStream_t st);    // pyramids (+ detector maps) of n cameras
-int ensure_results(clc_ctx* ctx, size_t bytes);           // pinned mirror of match results
+// the pose scratch and the pinned staging of the pose solves -- ONE pinned buffer, one transfer in, one out --, both half as much again:
+// a stream of solves whose sizes creep upwards (map matches per frame) must not reallocate at every new maximum, and a pinned
+// allocation costs a millisecond; the pinned mirror of match results
+template <class F> inline int ensure_pnp(clc_ctx* ctx, F&& lay) { return carve_block(ctx, ctx->d_pnp, 1, 2, true, "growing d_pnp", lay); }
+template <class F> inline int ensure_pinned(clc_ctx* ctx, F&& lay) { return carve_block(ctx, ctx->h_pin, 1, 2, true, "growing h_pin", lay); }
+template <class F> inline int ensure_results(clc_ctx* ctx, F&& lay) { return carve_block(ctx, ctx->h_res, 0, 1, true, "growing h_res", lay); }
 int ensure_gather(clc_ctx* ctx, GatherBlock& g, size_t cap, const GatherLayout& lay);      // a gather block (gather.hip)
+
+// one 2-D side -- exactly one of kps / feat, the stride, the alignment, the focal length -- validated ONCE for whoever takes one, into
+// the kernels' view of it (gather.hip).  who: the entry point, for the failure's text (CLC_ERR_BAD_ARG)
+int gather_side(clc_ctx* ctx, const char* who, const uint32_t* count, const clc_keypoint* kps, const float* feat, int stride, const clc_camera_k3& cam,
+                GatherSide& out);
+// the pyramid levels' scales as clc_keypoints_to_features has them (GPUDetector.hpp:173): pow(float, integer) evaluated in double, rounded
+// to float -- on the host, once per launch record
+inline void level_scales(float out[CLC_MAX_LEVELS])
+{
+    for (int l = 0; l < CLC_MAX_LEVELS; ++l) out[l] = (float)std::pow((double)1.2f, (double)l);
+}
 
 // a describing call begins: the rows of the last one no longer stand (staged_n = -1, desc_pending abandoned, rows_at = NONE)
 // (desc_cache.hip)

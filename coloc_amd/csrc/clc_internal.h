@@ -340,7 +340,7 @@ struct PairJobDev : GatherJob {
 struct TrackJobs {
     TrackJobDev j[kMaxBatch];
     const double* map_X; int map_n;
-    float scale[CLC_MAX_LEVELS];      // (float) pow((double) 1.2f, level), from the host: clc_keypoints_to_features' values
+    float scale[CLC_MAX_LEVELS];      // the pyramid levels' scales, from the host (level_scales, clc_ctx.h)
 };
 struct PairJobs {
     PairJobDev j[kMaxBatch];

@@ -124,13 +124,13 @@ __global__ __launch_bounds__(256) void gather_rows_multi_kernel(const RowSources
 template <class Jobs> hipError_t launch(void (*kernel)(const Jobs), Jobs& jobs, const int n_jobs, hipStream_t stream)
 {
     if (n_jobs < 1 || n_jobs > kMaxBatch) return hipErrorInvalidValue;
-    // GPUDetector.hpp:173 through clc_keypoints_to_features: pow(float, integer) evaluated in double, rounded to float -- on the host
-    for (int l = 0; l < CLC_MAX_LEVELS; ++l) jobs.scale[l] = (float)std::pow((double)1.2f, (double)l);
+    level_scales(jobs.scale);
     hipLaunchKernelGGL(kernel, dim3(1, n_jobs), dim3(kGatherThreads), 0, stream, jobs);
     return hipGetLastError();
 }
 
-// one 2-D side, validated ONCE for the track's camera and both cameras of a pair, into the kernel's view of it.  who: "track" / "pair"
+} // namespace
+
 int gather_side(clc_ctx* ctx, const char* who, const uint32_t* count, const clc_keypoint* kps, const float* feat, const int stride,
                 const clc_camera_k3& cam, GatherSide& out)
 {
@@ -142,8 +142,6 @@ int gather_side(clc_ctx* ctx, const char* who, const uint32_t* count, const clc_
     out = GatherSide{ count, kps, feat, stride, UdCamera{ cam.focal, cam.ppx, cam.ppy, cam.k1, cam.k2, cam.k3 } };
     return CLC_OK;
 }
-
-} // namespace
 
 hipError_t launch_gather(TrackJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(track_build_kernel, jobs, n_jobs, stream); }
 hipError_t launch_gather(PairJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(pair_build_kernel, jobs, n_jobs, stream); }
@@ -189,13 +187,13 @@ int gather_inputs(clc_ctx* ctx, const clc_pair_job& job, PairJobDev& out, const 
 
 int ensure_gather(clc_ctx* ctx, GatherBlock& g, size_t cap, const GatherLayout& lay)
 {
-    cap = (cap + 63) & ~(size_t)63;
-    if (cap < 64) cap = 64;
+    cap = up64(cap < 64 ? 64 : cap);
     if (cap <= g.cap && g.d && g.h) return CLC_OK;
     // (no synchronisation: nothing of an earlier call is in flight, a solve returns after its staging launch has consumed the block)
     g.cap = 0;
-    int rc = grow(ctx, g.d, cap * lay.d_row() + 64, 0, 1, false, "growing a gather block");
-    if (rc == CLC_OK) rc = grow(ctx, g.h, 64 + cap * lay.h_row(), 0, 1, false, "growing a pinned gather block");
+    GatherView v;
+    int rc = carve_block(ctx, g.d, 0, 1, false, "growing a gather block", [&](Carve& c) { v.dev(c, lay, cap); });
+    if (rc == CLC_OK) rc = carve_block(ctx, g.h, 0, 1, false, "growing a pinned gather block", [&](Carve& c) { v.pin(c, lay, cap); });
     if (rc != CLC_OK) return rc;
     memset(g.h.ptr, 0xFF, 64);        // the count word: not out yet
     g.cap = cap;

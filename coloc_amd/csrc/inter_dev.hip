@@ -294,36 +294,15 @@ __global__ __launch_bounds__(kInterThreads) void inter_scale_kernel(const ScaleJ
     }
 }
 
-size_t dbl(size_t bytes) { return (bytes + 7) / 8; }
-
-// A context's blocks of this step (clc_ctx: d_inter / h_inter), for `cap` correspondences and `walk` = max(map rows, cap) list entries:
-//   device (doubles) [ Xt 3 cap | Xw 3 cap | x2f 2 cap | K 16 | Rt 12 | RefineOut | ratio walk | term walk | corr cap | first cap |
-//                      cg, ck, kg, kk walk each | valid | rows 64 B x cap (16-byte aligned) | match map_n ]
-//   pinned [ front record 64 B | scale record 64 B | RefineOut ]
-struct InterView {
-    double *Xt, *Xw, *x2f, *K, *Rt, *ref, *ratio, *term;
-    int32_t *corr, *first, *cg, *ck, *kg, *kk, *valid, *match;
-    uint4* rows;
-    int32_t* h_front; InterScaleRec* h_scale; RefineOut* h_ref;
-};
-int ensure_inter(clc_ctx* ctx, const size_t cap_in, const size_t map_n, InterView& v)
+// a context's blocks of this step, for `cap` correspondences against `map_n` map rows (InterDev / InterPin, clc_layout.h)
+struct InterView : InterDev, InterPin {};
+int ensure_inter(clc_ctx* ctx, const size_t cap, const size_t map_n, InterView& v)
 {
-    const size_t cap = (cap_in + 63) & ~(size_t)63, walk = ((map_n > cap ? map_n : cap) + 63) & ~(size_t)63;
-    const size_t ints = 2 * cap + 4 * walk + 64, ref_d = dbl(sizeof(RefineOut));
-    const size_t doubles = 8 * cap + 28 + ref_d + 2 * walk + dbl(ints * 4) + 2 /* alignment */ + 8 * cap + dbl((map_n + 64) * 4);
-    int rc = grow(ctx, ctx->d_inter, doubles * sizeof(double) + 64, 1, 4, true, "growing the inter-camera block");
-    if (rc == CLC_OK) rc = grow(ctx, ctx->h_inter, 128 + sizeof(RefineOut) + 64, 0, 1, true, "growing the pinned inter-camera records");
-    if (rc != CLC_OK) return rc;
-    double* d = ctx->d_inter.as<double>();
-    v.Xt = d; d += 3 * cap; v.Xw = d; d += 3 * cap; v.x2f = d; d += 2 * cap; v.K = d; d += 16; v.Rt = d; d += 12; v.ref = d; d += ref_d;
-    v.ratio = d; d += walk; v.term = d; d += walk;
-    int32_t* p = (int32_t*)d;
-    v.corr = p; p += cap; v.first = p; p += cap; v.cg = p; p += walk; v.ck = p; p += walk; v.kg = p; p += walk; v.kk = p; p += walk; v.valid = p; p += 64;
-    v.rows = (uint4*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-    v.match = (int32_t*)(v.rows + 4 * cap);
-    uint8_t* h = ctx->h_inter.as<uint8_t>();
-    v.h_front = (int32_t*)h; v.h_scale = (InterScaleRec*)(h + 64); v.h_ref = (RefineOut*)(h + 128);
-    return CLC_OK;
+    int rc = carve_block(ctx, ctx->d_inter, 1, 4, true, "growing the inter-camera block", [&](Carve& c) { v.InterDev::carve(c, cap, map_n, sizeof(RefineOut)); });
+    if (rc == CLC_OK)
+        rc = carve_block(ctx, ctx->h_inter, 0, 1, true, "growing the pinned inter-camera records",
+                         [&](Carve& c) { v.InterPin::carve(c, sizeof(InterScaleRec), sizeof(RefineOut)); });
+    return rc;
 }
 
 InterCam cam_of(const clc_camera_k3& c) { return InterCam{ c.focal, c.ppx, c.ppy }; }
@@ -434,7 +413,7 @@ int inter_batch(clc_ctx* const* ctxs, clc_inter_dev_job* jobs, const int n_jobs)
         //    (Q = global map, T = temporary map), on the job's own stream behind the front launch
         if (jb.d_first_desc) {
             hipStream_t sweep = ctxs[i]->stream;
-            const int rk = map_sweep_enqueue(ctxs[i], jb.d_first_desc, v.first, nf, jb.d_map_desc, map_n, v.rows, v.match, jb.match_threshold, sweep);
+            const int rk = map_sweep_enqueue(ctxs[i], jb.d_first_desc, v.first, nf, jb.d_map_desc, map_n, (uint4*)v.rows, v.match, jb.match_threshold, sweep);
             if (rk != CLC_OK) return abort_all(rk);
             e = sweep != st ? order_behind(ctxs[i]->ev_track, sweep, &st, 1) : hipSuccess;
             if (e != hipSuccess) return abort_all(fail(ctxs[i], CLC_ERR_HIP, "inter_pose_dev: ordering the scale launch behind the sweep", e));

@@ -21,29 +21,22 @@ int refine_enqueue(clc_ctx* ctx, const double* h_X, const double* h_x, int N, co
                    RefineOut** h_rec)
 {
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t in_d = (size_t)5 * N + 16 + 12;
-    const size_t out_d = (sizeof(RefineOut) + 7) / 8;
-    int rc = ensure_pnp(ctx, in_d + out_d + 8);
+    RefineDev dv; RefinePin pin;          // (the inputs lie alike in both: one staging launch carries them)
+    int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, (size_t)N, false, sizeof(RefineOut)); });
+    if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, (size_t)N, false, sizeof(RefineOut), false); });
     if (rc != CLC_OK) return rc;
-    rc = ensure_pinned(ctx, (in_d + out_d) * sizeof(double) + 64);
-    if (rc != CLC_OK) return rc;
-    double* dX = ctx->d_pnp.as<double>();
-    double* dx = dX + (size_t)3 * N;
-    double* dK = dx + (size_t)2 * N;
-    double* dRt = dK + 16;
-    double* hp = ctx->h_pin.as<double>();
-    memcpy(hp, h_X, sizeof(double) * 3 * N);
-    memcpy(hp + (size_t)3 * N, h_x, sizeof(double) * 2 * N);
-    memset(hp + (size_t)5 * N, 0, sizeof(double) * 16);
-    memcpy(hp + (size_t)5 * N, h_K, sizeof(double) * 9);
-    memcpy(hp + (size_t)5 * N + 16, h_Rt_in, sizeof(double) * 12);
-    *h_rec = (RefineOut*)(hp + in_d);
+    memcpy(pin.in.X, h_X, sizeof(double) * 3 * N);
+    memcpy(pin.in.x, h_x, sizeof(double) * 2 * N);
+    memset(pin.in.K, 0, sizeof(double) * 16);
+    memcpy(pin.in.K, h_K, sizeof(double) * 9);
+    memcpy(pin.in.Rt, h_Rt_in, sizeof(double) * 12);
+    *h_rec = pin.out;
     __atomic_store_n(&(*h_rec)->ready, 0, __ATOMIC_RELAXED);
-    const double* src = hp;
-    const size_t n_stage = (in_d + 1) & ~(size_t)1;
-    CLC_HIP(ctx, launch_acr_stage(&src, &dX, &n_stage, 1, ctx->stream));                 // inputs by a launch, not a copy command
-    CLC_HIP(ctx, launch_pnp_refine(dRt, dX, dx, nullptr, N, dK, huber_a > 0.0 ? huber_a : 16.0, 50, dX + in_d, ctx->stream, &ctx->prof, nullptr,
-                                   *h_rec));
+    const double* src = pin.in.X;
+    const size_t n_stage = (pin.in.bytes / sizeof(double) + 1) & ~(size_t)1;
+    CLC_HIP(ctx, launch_acr_stage(&src, &dv.in.X, &n_stage, 1, ctx->stream));            // inputs by a launch, not a copy command
+    CLC_HIP(ctx, launch_pnp_refine(dv.in.Rt, dv.in.X, dv.in.x, nullptr, N, dv.in.K, huber_a > 0.0 ? huber_a : 16.0, 50, dv.out, ctx->stream, &ctx->prof,
+                                   nullptr, *h_rec));
     return CLC_OK;
 }
 
@@ -54,18 +47,16 @@ int map_match_enqueue(clc_ctx* ctx, const clc_inter_pose_job& jb, const InterFro
 {
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nf = fr.corr.size(), nm = (size_t)jb.map_n;
-    // device: [ idx nf int32 | gathered nf x 64 B | match nm int32 ]   pinned: [ idx | match ]
-    const size_t idx_d = (nf * 4 + 15) / 16 * 2, rows_d = nf * 8, match_d = (nm * 4 + 15) / 16 * 2;
-    int rc = ensure_pnp(ctx, idx_d + rows_d + match_d + 8);
+    MapMatchDev dv; MapMatchPin pin;
+    int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, nf, nm); });
+    if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, nf, nm); });
     if (rc != CLC_OK) return rc;
-    rc = ensure_pinned(ctx, (idx_d + match_d) * sizeof(double) + 64);
-    if (rc != CLC_OK) return rc;
-    int32_t* h_idx = ctx->h_pin.as<int32_t>();
-    *h_match = (int32_t*)(ctx->h_pin.as<double>() + idx_d);
+    int32_t* h_idx = pin.idx;
+    *h_match = pin.match;
     for (size_t k = 0; k < nf; ++k) h_idx[k] = jb.first_feature[fr.corr[k]];
-    int32_t* d_idx = ctx->d_pnp.as<int32_t>();
-    uint4* d_rows = (uint4*)(ctx->d_pnp.as<double>() + idx_d);
-    int32_t* d_match = (int32_t*)(ctx->d_pnp.as<double>() + idx_d + rows_d);
+    int32_t* d_idx = dv.idx;
+    uint4* d_rows = (uint4*)dv.rows;
+    int32_t* d_match = dv.match;
     CLC_HIP(ctx, hipMemcpyAsync(d_idx, h_idx, nf * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     rc = map_sweep_enqueue(ctx, jb.d_first_desc, d_idx, (int)nf, jb.d_map_desc, jb.map_n, d_rows, d_match, jb.match_threshold, ctx->stream);
     if (rc != CLC_OK) return rc;

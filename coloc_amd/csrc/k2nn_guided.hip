@@ -345,13 +345,10 @@ int guided_plan(clc_ctx* ctx, const char* over_capacity, std::vector<K2nnJobDev>
     const K2nnPlan plan = k2nn_plan(kj.data(), n, target, ctx->xcd_map, K2NN_POPCOUNT, 0, 0, ctx->k2dev);
     if (!plan.atomic_merge) return fail(ctx, CLC_ERR_CAPACITY, over_capacity);
 
-    std::vector<size_t> off_L((size_t)n), off_P((size_t)n);
-    size_t floats = 0;
-    for (int k = 0; k < n; ++k) {
-        off_L[(size_t)k] = floats; floats += ((size_t)qf * (size_t)kj[(size_t)k].nq + 3) & ~(size_t)3;
-        off_P[(size_t)k] = floats; floats += (2 * (size_t)kj[(size_t)k].nt + 3) & ~(size_t)3;
-    }
-    int rc = grow(ctx, ctx->d_guided, floats * sizeof(float), 1, 4, true, "growing d_guided");
+    std::vector<GuidedDev> dv((size_t)n);
+    int rc = carve_block(ctx, ctx->d_guided, 1, 4, true, "growing d_guided", [&](Carve& c) {
+        for (int k = 0; k < n; ++k) dv[(size_t)k].carve(c, (size_t)qf, kj[(size_t)k].nq, kj[(size_t)k].nt);
+    });
     if (rc == CLC_OK) rc = ensure_partial(ctx, plan.partial_elems);
     if (rc != CLC_OK) return rc;
     if (ctx->partial_dirty) {
@@ -361,7 +358,7 @@ int guided_plan(clc_ctx* ctx, const char* over_capacity, std::vector<K2nnJobDev>
     for (int k = 0; k < n; ++k) {
         const K2nnJobDev& p = kj[(size_t)k];
         GuidedJobDev& g = list.j[k];
-        g.L = ctx->d_guided.as<float>() + off_L[(size_t)k]; g.pos = ctx->d_guided.as<float>() + off_P[(size_t)k];
+        g.L = dv[(size_t)k].L; g.pos = dv[(size_t)k].pos;
         g.nq = p.nq; g.nt = p.nt;
         g.qblocks = p.qblocks; g.splits = p.splits; g.t_per_split = p.t_per_split; g.partial_off = p.partial_off; g.cnt_off = p.cnt_off;
     }
@@ -398,13 +395,9 @@ int guided_inputs(clc_ctx* ctx, const clc_guided_job& job, PairJobDev& pd)
         ((uintptr_t)job.d_tpos & 3u))
         return bad("match_guided: misaligned device pointer");
     if (!(job.band > 0.f) || !std::isfinite(job.band)) return bad("match_guided: band must be finite and positive");
-    clc_pair_job pj{};
-    pj.d_match = job.d_match; pj.nq = job.nq; pj.nt = job.nt;
-    pj.d_count_a = job.d_count_a; pj.d_count_b = job.d_count_b;
-    pj.d_kps_a = job.d_kps_a; pj.d_feat_a = job.d_feat_a; pj.feat_stride_a = job.feat_stride_a;
-    pj.d_kps_b = job.d_kps_b; pj.d_feat_b = job.d_feat_b; pj.feat_stride_b = job.feat_stride_b;
-    pj.cam_a = job.cam_a; pj.cam_b = job.cam_b;
-    const int rc = gather_inputs(ctx, pj, pd, "match_guided: bad argument");           // the sides' rules are the pair kernel's
+    pd = PairJobDev{};                                                                  // the sides' rules are the pair kernel's
+    int rc = gather_side(ctx, "match_guided", job.d_count_a, job.d_kps_a, job.d_feat_a, job.feat_stride_a, job.cam_a, pd.a);
+    if (rc == CLC_OK) rc = gather_side(ctx, "match_guided", job.d_count_b, job.d_kps_b, job.d_feat_b, job.feat_stride_b, job.cam_b, pd.b);
     if (rc != CLC_OK) return rc;
     if ((uint32_t)job.nt > kIdxMask + 1u) return fail(ctx, CLC_ERR_CAPACITY, "match_guided: more than 2^22 train rows");
     return CLC_OK;
@@ -446,7 +439,7 @@ int guided_batch(clc_ctx* ctx, const clc_guided_job* jobs, const int n_jobs, voi
     for (int base = 0; base < n; base += kGuidedPrepJobs) {
         const int cnt = std::min(kGuidedPrepJobs, n - base);
         GuidedPrepList prep{};
-        for (int l = 0; l < CLC_MAX_LEVELS; ++l) prep.scale[l] = (float)std::pow((double)1.2f, (double)l);      // as launch_gather (gather.hip)
+        level_scales(prep.scale);
         uint32_t rows = 0;
         for (int k = 0; k < cnt; ++k) {
             const clc_guided_job& job = jobs[live[(size_t)(base + k)]];
@@ -478,14 +471,7 @@ int proj_inputs(clc_ctx* ctx, const clc_map_guided_job& job, GatherSide& side)
     if (!(job.radius > 0.f) || !std::isfinite(job.radius) || !(r2 > 0.f) || !std::isfinite(r2))
         return bad("match_map_guided: radius and its square must be finite and positive");
     for (int i = 0; i < 12; ++i) if (!std::isfinite(job.Rt[i])) return bad("match_map_guided: Rt is not finite");
-    clc_pair_job pj{};                                                                  // the side's rules are the gathers' (gather.hip)
-    pj.d_count_a = pj.d_count_b = job.d_count;
-    pj.d_kps_a = pj.d_kps_b = job.d_kps; pj.d_feat_a = pj.d_feat_b = job.d_feat; pj.feat_stride_a = pj.feat_stride_b = job.feat_stride;
-    pj.cam_a = pj.cam_b = job.cam;
-    PairJobDev pd;
-    const int rc = gather_inputs(ctx, pj, pd, "match_map_guided: bad argument");
-    side = pd.a;
-    return rc;
+    return gather_side(ctx, "match_map_guided", job.d_count, job.d_kps, job.d_feat, job.feat_stride, job.cam, side);      // the gathers' rules
 }
 
 int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, void* stream)
@@ -517,7 +503,7 @@ int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, v
     if (rc != CLC_OK) return rc;
 
     ProjPrepList prep{};
-    for (int l = 0; l < CLC_MAX_LEVELS; ++l) prep.scale[l] = (float)std::pow((double)1.2f, (double)l);          // as launch_gather (gather.hip)
+    level_scales(prep.scale);
     prep.map_X = ctx->d_map_X.as<double>(); prep.nm = nm;
     uint32_t rows = 0;
     for (int k = 0; k < n; ++k) {

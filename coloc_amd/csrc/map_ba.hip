@@ -317,8 +317,6 @@ __global__ __launch_bounds__(kOneGroup) void ba_accept_kernel(const BaJob job, c
     if (tid == 0) __hip_atomic_store(&r->ready, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-inline size_t up256(const size_t v) { return (v + 255) & ~(size_t)255; }
-
 } // namespace
 
 int ba_check(clc_ctx* ctx, clc_map_ba* ba, const char* who)
@@ -336,26 +334,20 @@ int ba_drive(clc_ctx* ctx, BaProblem& pb, clc_map_ba& ba)
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t P = (size_t)std::max(pb.n_points, 1), C = (size_t)pb.n_cams, chunks = (P + kBaChunk - 1) / kBaChunk;
-    // device [ state | idx | bits | rec | pt | flag | X_try | part | tpart | x (a composition's) ]
-    size_t off = 0;
-    const auto take = [&](const size_t bytes) { const size_t at = off; off = up256(off + bytes); return at; };
-    const size_t o_state = take(sizeof(BaState)), o_idx = take(P * sizeof(int32_t)), o_bits = take(P * sizeof(uint32_t)),
-                 o_rec = take(P * C * kBaRec * sizeof(double)), o_pt = take(P * kBaPoint * sizeof(double)), o_flag = take(2 * P * sizeof(double)),
-                 o_try = take(3 * P * sizeof(double)), o_part = take(chunks * kBaEntriesMax * sizeof(double)), o_tpart = take(4 * chunks * sizeof(double)),
-                 o_x = take(pb.x ? 0 : 2 * P * C * sizeof(double));
-    int rc = grow(ctx, ctx->d_bab, off, 1, 4, true, "growing the bundle adjustment block");
-    if (rc == CLC_OK) rc = grow(ctx, ctx->h_bab, up256(sizeof(BaRecord)), 0, 1, true, "allocating the bundle adjustment record");
+    const BaDims dims{ sizeof(BaState), P, C, chunks, (size_t)kBaRec, (size_t)kBaPoint, (size_t)kBaEntriesMax, pb.x == nullptr };
+    BaDev dv; BaPin pin;
+    int rc = carve_block(ctx, ctx->d_bab, 1, 4, true, "growing the bundle adjustment block", [&](Carve& c) { dv.carve(c, dims); });
+    if (rc == CLC_OK) rc = carve_block(ctx, ctx->h_bab, 0, 1, true, "allocating the bundle adjustment record", [&](Carve& c) { pin.carve(c, sizeof(BaRecord)); });
     if (rc != CLC_OK) return rc;
-    uint8_t* base = ctx->d_bab.as<uint8_t>();
     BaJob job{};
-    job.st = (BaState*)(base + o_state);
-    job.X = pb.X; job.obs = pb.obs; job.x = pb.x ? pb.x : (const double*)(base + o_x);
+    job.st = (BaState*)dv.state;
+    job.X = pb.X; job.obs = pb.obs; job.x = pb.x ? pb.x : dv.x;
     job.n_points = pb.n_points; job.n_cams = pb.n_cams;
-    job.idx = (int32_t*)(base + o_idx); job.bits = (uint32_t*)(base + o_bits);
-    job.rec = (double*)(base + o_rec); job.pt = (double*)(base + o_pt); job.flag = (double*)(base + o_flag);
-    job.X_try = (double*)(base + o_try); job.part = (double*)(base + o_part); job.tpart = (double*)(base + o_tpart);
+    job.idx = dv.idx; job.bits = dv.bits;
+    job.rec = dv.rec; job.pt = dv.pt; job.flag = dv.flag;
+    job.X_try = dv.X_try; job.part = dv.part; job.tpart = dv.tpart;
     job.a = ba.huber_a > 0.0 ? ba.huber_a : 16.0;
-    job.h_rec = ctx->h_bab.as<BaRecord>();
+    job.h_rec = (BaRecord*)pin.rec;
     BaInit in{};
     memcpy(in.K, pb.K, sizeof in.K); memcpy(in.Rt, pb.Rt, sizeof in.Rt);
     in.mask = pb.mask; in.max_it = ba.max_iterations > 0 ? ba.max_iterations : 500; in.ftol = ba.function_tolerance > 0.0 ? ba.function_tolerance : 1e-8;
@@ -365,7 +357,7 @@ int ba_drive(clc_ctx* ctx, BaProblem& pb, clc_map_ba& ba)
     if (!pb.x && pb.n_points > 0) {
         const unsigned cells = (unsigned)(P * C);
         hipLaunchKernelGGL(ba_pixels_kernel, dim3((cells + kWide - 1) / kWide), dim3(kWide), 0, st, *pb.cams, pb.table, (int32_t)pb.n_points, (int32_t)pb.n_cams,
-                           (double*)(base + o_x));
+                           dv.x);
     }
     // the start: init, try, accept -- and the first look at the record
     __atomic_store_n(&job.h_rec->ready, 0u, __ATOMIC_RELAXED);

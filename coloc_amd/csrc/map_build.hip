@@ -195,9 +195,7 @@ struct StageDetail {
     TrackGraph g;
     GatherSide side[kMaxBatch];
     int cam_i = 0, cam_j = 0;
-    size_t capr = 0;
-    int32_t* d_track = nullptr; int32_t* d_row = nullptr;
-    double* h_X = nullptr; int32_t* h_track = nullptr; int32_t* h_row = nullptr;
+    MapStageDev dev{}; MapStagePin pin{};
 };
 int map_stage_detail(clc_ctx* ctx, clc_map_job& job, MapStaged& out, StageDetail* detail);
 
@@ -234,19 +232,14 @@ int tracks_inputs(clc_ctx* ctx, const clc_tracks_job& job, TrackGraph& g, EdgePa
     return CLC_OK;
 }
 
-// the union-find words of `nodes` nodes (+ `ints` more int32 behind them) in the context's block
-int ensure_map_block(clc_ctx* ctx, const size_t nodes, const size_t ints, int32_t** rest)
+void graph_words(TrackGraph& g, const GraphWords& w) { g.parent = w.parent; g.word = w.word; g.track_id = w.track_id; }
+
+// the host copies of a staged map's lists, n rows, out of the pinned block
+void map_lists_out(clc_map_job& job, const MapStagePin& pin, const uint32_t n)
 {
-    const size_t n = (nodes + 63) & ~(size_t)63;
-    const int rc = grow(ctx, ctx->d_mapb, (3 * n + ints + 64) * sizeof(int32_t), 1, 4, true, "growing the map block");
-    if (rc != CLC_OK) return rc;
-    *rest = ctx->d_mapb.as<int32_t>() + 3 * n;
-    return CLC_OK;
-}
-void graph_words(clc_ctx* ctx, TrackGraph& g)
-{
-    const size_t n = ((size_t)g.n_nodes + 63) & ~(size_t)63;
-    g.parent = ctx->d_mapb.as<int32_t>(); g.word = (uint32_t*)(g.parent + n); g.track_id = g.parent + 2 * n;
+    if (job.map_track && n) memcpy(job.map_track, pin.track, sizeof(int32_t) * n);
+    if (job.map_row && n) memcpy(job.map_row, pin.row, sizeof(int32_t) * n);
+    if (job.X && n) memcpy(job.X, pin.X, sizeof(double) * 3 * n);
 }
 
 hipError_t launch_tracks(const TrackGraph& g, const EdgePairs& ep, const int n_pairs, const int edge_rows, hipStream_t st)
@@ -283,40 +276,35 @@ int map_stage_detail(clc_ctx* ctx, clc_map_job& job, MapStaged& out, StageDetail
     GatherSide side[kMaxBatch];
     for (int c = 0; c < job.tracks.n_cams; ++c) {
         const clc_map_camera& m = job.cams[c];
-        if ((m.d_kps != nullptr) == (m.d_feat != nullptr)) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_build: exactly one of d_kps / d_feat per camera");
-        if (m.d_feat && m.feat_stride < 2) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_build: feat_stride < 2");
-        if (((uintptr_t)m.d_kps & 3u) || ((uintptr_t)m.d_feat & 3u) || ((uintptr_t)m.d_desc & 15u)) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_build: misaligned device pointer");
-        if (!(m.cam.focal > 0.0)) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_build: focal must be positive");
-        side[c] = GatherSide{ nullptr, m.d_kps, m.d_feat, m.feat_stride, UdCamera{ m.cam.focal, m.cam.ppx, m.cam.ppy, m.cam.k1, m.cam.k2, m.cam.k3 } };
+        rc = gather_side(ctx, "map_build", nullptr, m.d_kps, m.d_feat, m.feat_stride, m.cam, side[c]);
+        if (rc != CLC_OK) return job.status = rc;
+        if ((uintptr_t)m.d_desc & 15u) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_build: misaligned device pointer");
     }
     const int cam_i = job.tracks.pairs[job.seed_pair].cam_a, cam_j = job.tracks.pairs[job.seed_pair].cam_b;
     if (!job.cams[cam_i].d_desc && job.tracks.rows[cam_i] > 0) return job.status = fail(ctx, CLC_ERR_BAD_ARG, "map_build: the lower seed camera needs its descriptor block");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // the block: [ union-find words | table | map_track | map_row | n_tracks ]; the next map's points apart; pinned
-    // [ words 64 B | X | map_track | map_row | table ]
-    const size_t cap = (size_t)g.cap_tracks, capr = (cap + 63) & ~(size_t)63, cells = cap * (size_t)g.n_cams;
-    int32_t* rest = nullptr;
-    rc = ensure_map_block(ctx, (size_t)g.n_nodes, cells + 2 * capr + 64, &rest);
-    if (rc == CLC_OK) rc = grow(ctx, ctx->d_map_X_next, (3 * capr + 8) * sizeof(double), 1, 4, true, "growing the next map's points");
-    if (rc == CLC_OK) rc = grow(ctx, ctx->h_mapb, 64 + 3 * capr * sizeof(double) + (2 * capr + cells + 64) * sizeof(int32_t), 1, 4, true, "growing the pinned map block");
+    // the map block and its pinned mirror (MapStageDev, MapStagePin); the next map's points apart
+    const size_t cap = (size_t)g.cap_tracks, n_cams = (size_t)g.n_cams;
+    MapStageDev dev; MapStagePin pin; MapPointsDev next;
+    rc = carve_block(ctx, ctx->d_mapb, 1, 4, true, "growing the map block", [&](Carve& c) { dev.carve(c, (size_t)g.n_nodes, cap, n_cams); });
+    if (rc == CLC_OK) rc = carve_block(ctx, ctx->d_map_X_next, 1, 4, true, "growing the next map's points", [&](Carve& c) { next.carve(c, up64(cap)); });
+    if (rc == CLC_OK) rc = carve_block(ctx, ctx->h_mapb, 1, 4, true, "growing the pinned map block", [&](Carve& c) { pin.carve(c, cap, n_cams); });
     if (rc != CLC_OK) return job.status = rc;
-    graph_words(ctx, g);
-    int32_t* d_track = rest; int32_t* d_row = d_track + capr;
-    g.n_tracks = d_row + capr; g.table = g.n_tracks + 64;
-    uint32_t* h_words = ctx->h_mapb.as<uint32_t>();
-    double* h_X = (double*)(ctx->h_mapb.as<uint8_t>() + 64);
-    int32_t* h_track = (int32_t*)(h_X + 3 * capr); int32_t* h_row = h_track + capr; int32_t* h_table = h_row + capr;
-    g.h_table = job.track_feat ? h_table : nullptr;
+    graph_words(g, dev.g);
+    int32_t* d_track = dev.track; int32_t* d_row = dev.row;
+    g.n_tracks = dev.n_tracks; g.table = dev.table;
+    uint32_t* h_words = pin.words;
+    g.h_table = job.track_feat ? pin.table : nullptr;
     SeedJob s{};
     s.table = g.table; s.n_tracks = g.n_tracks; s.n_cams = g.n_cams; s.cam_i = cam_i; s.cam_j = cam_j; s.cap = g.cap_tracks;
     s.a = side[cam_i]; s.b = side[cam_j];
-    for (int l = 0; l < CLC_MAX_LEVELS; ++l) s.scale[l] = (float)std::pow((double)1.2f, (double)l);      // clc_keypoints_to_features' values
+    level_scales(s.scale);
     memcpy(s.Rt_i, job.Rt_seed_a, sizeof s.Rt_i); memcpy(s.Rt_j, job.Rt_seed_b, sizeof s.Rt_j);
     projective_equivalent(side[cam_i].cam.focal, side[cam_i].cam.ppx, side[cam_i].cam.ppy, s.Rt_i, s.P_i);
     projective_equivalent(side[cam_j].cam.focal, side[cam_j].cam.ppx, side[cam_j].cam.ppy, s.Rt_j, s.P_j);
-    s.X = ctx->d_map_X_next.as<double>(); s.map_track = d_track; s.map_row = d_row;
-    s.h_X = job.X ? h_X : nullptr; s.h_track = job.map_track ? h_track : nullptr; s.h_row = job.map_row ? h_row : nullptr;
+    s.X = next.X; s.map_track = d_track; s.map_row = d_row;
+    s.h_X = job.X ? pin.X : nullptr; s.h_track = job.map_track ? pin.track : nullptr; s.h_row = job.map_row ? pin.row : nullptr;
     if (detail) { s.h_X = nullptr; s.h_track = nullptr; s.h_row = nullptr; }      // (the grown map's rows go out instead)
     s.h_words = h_words;
     __atomic_store_n(&h_words[0], 0xFFFFFFFFu, __ATOMIC_RELAXED);
@@ -331,18 +319,15 @@ int map_stage_detail(clc_ctx* ctx, clc_map_job& job, MapStaged& out, StageDetail
     if (rc != CLC_OK) return job.status = rc;
     const uint32_t n = __atomic_load_n(&h_words[0], __ATOMIC_ACQUIRE);
     job.n_tracks = (int)h_words[1];
-    if (job.track_feat && job.n_tracks > 0) memcpy(job.track_feat, h_table, sizeof(int32_t) * (size_t)job.n_tracks * (size_t)g.n_cams);
+    if (job.track_feat && job.n_tracks > 0) memcpy(job.track_feat, pin.table, sizeof(int32_t) * (size_t)job.n_tracks * (size_t)g.n_cams);
     if (detail) {
-        detail->g = g; detail->cam_i = cam_i; detail->cam_j = cam_j; detail->capr = capr;
+        detail->g = g; detail->cam_i = cam_i; detail->cam_j = cam_j; detail->dev = dev; detail->pin = pin;
         memcpy(detail->side, side, sizeof side);
-        detail->d_track = d_track; detail->d_row = d_row; detail->h_X = h_X; detail->h_track = h_track; detail->h_row = h_row;
         out.n = (int)std::min<uint32_t>(n, (uint32_t)g.cap_tracks); out.cam_i = cam_i; out.cam_j = cam_j; out.d_row = d_row;
         return CLC_OK;
     }
     if (n > ctx->mopts.maxkp) return job.status = fail(ctx, CLC_ERR_CAPACITY, "map_build: more map rows than MatcherOptions.maxkp (the previous map stays)");
-    if (job.map_track && n) memcpy(job.map_track, h_track, sizeof(int32_t) * n);
-    if (job.map_row && n) memcpy(job.map_row, h_row, sizeof(int32_t) * n);
-    if (job.X && n) memcpy(job.X, h_X, sizeof(double) * 3 * n);
+    map_lists_out(job, pin, n);
     job.map_n = (int)n;
     out.n = (int)n; out.cam_i = cam_i; out.cam_j = cam_j; out.d_row = d_row;
     return CLC_OK;
@@ -413,10 +398,10 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
     hipStream_t st = ctx->stream;
     gr.n_seed_rows = n_seed;
     memcpy(gr.Rt[d.cam_i], job.Rt_seed_a, sizeof gr.Rt[0]); memcpy(gr.Rt[d.cam_j], job.Rt_seed_b, sizeof gr.Rt[0]);
-    // device [ X per track 3 capr | obs capr | camera list capr ]; pinned [ row count 64 B | camera list capr | masks capr ]
-    const size_t capr = d.capr;
-    rc = grow(ctx, ctx->d_growb, 3 * capr * sizeof(double) + (2 * capr + 64) * sizeof(int32_t), 1, 4, true, "growing the map grow block");
-    if (rc == CLC_OK) rc = grow(ctx, ctx->h_growb, 64 + capr * sizeof(int32_t) + capr + 64, 1, 4, true, "growing the pinned map grow block");
+    // the per-track state and the grown map's camera list (GrowDev), their pinned mirror (GrowPin)
+    GrowDev gd; GrowPin gp;
+    rc = carve_block(ctx, ctx->d_growb, 1, 4, true, "growing the map grow block", [&](Carve& c) { gd.carve(c, (size_t)d.g.cap_tracks); });
+    if (rc == CLC_OK) rc = carve_block(ctx, ctx->h_growb, 1, 4, true, "growing the pinned map grow block", [&](Carve& c) { gp.carve(c, (size_t)d.g.cap_tracks); });
     // the resection lists: at most one entry per row of the camera, and the solve takes 16 384
     int widest = 1;
     for (int c = 0; c < n_cams; ++c) widest = std::max(widest, job.tracks.rows[c]);
@@ -424,14 +409,12 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
     if (rc != CLC_OK) return job.status = rc;
     GrowState s{};
     s.table = d.g.table; s.n_tracks = d.g.n_tracks; s.n_cams = n_cams; s.cap = d.g.cap_tracks;
-    s.X = ctx->d_growb.as<double>(); s.obs = (uint32_t*)(s.X + 3 * capr);
-    int32_t* d_cam = (int32_t*)(s.obs + capr);
-    uint32_t* h_n = ctx->h_growb.as<uint32_t>();
-    int32_t* h_cam = (int32_t*)(ctx->h_growb.as<uint8_t>() + 64);
-    uint8_t* h_obs = (uint8_t*)(h_cam + capr);
+    s.X = gd.X; s.obs = gd.obs;
+    int32_t* d_cam = gd.cam;
+    uint32_t* h_n = gp.n;
     GrowCams cams{};
     memcpy(cams.side, d.side, sizeof cams.side);
-    for (int l = 0; l < CLC_MAX_LEVELS; ++l) cams.scale[l] = (float)std::pow((double)1.2f, (double)l);      // clc_keypoints_to_features' values
+    level_scales(cams.scale);
     const auto set_pose = [&](const int c, const double* Rt) {
         memcpy(cams.Rt[c], Rt, sizeof cams.Rt[c]);
         projective_equivalent(cams.side[c].cam.focal, cams.side[c].cam.ppx, cams.side[c].cam.ppy, cams.Rt[c], cams.P[c]);
@@ -439,7 +422,7 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
     };
     set_pose(d.cam_i, job.Rt_seed_a);
     set_pose(d.cam_j, job.Rt_seed_b);
-    hipError_t e = launch_grow_scatter(s, d.d_track, ctx->d_map_X_next.as<double>(), n_seed, (1u << d.cam_i) | (1u << d.cam_j), st);
+    hipError_t e = launch_grow_scatter(s, d.dev.track, ctx->d_map_X_next.as<double>(), n_seed, (1u << d.cam_i) | (1u << d.cam_j), st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the scatter launch", e); }
     const GatherView v(ctx->trk, kTrackLayout);
     const int block_cap = (int)std::min<size_t>(ctx->trk.cap, (size_t)kAcrMaxN);
@@ -488,9 +471,9 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
     // setupMapDatabase over the landmarks: the rows in track-id order, over the staged seed map's lists
     __atomic_store_n(h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
     GrowMapOut mo{};
-    mo.X = ctx->d_map_X_next.as<double>(); mo.track = d.d_track; mo.cam = d_cam; mo.row = d.d_row;
-    mo.h_X = job.X ? d.h_X : nullptr; mo.h_track = job.map_track ? d.h_track : nullptr; mo.h_row = job.map_row ? d.h_row : nullptr;
-    mo.h_cam = gr.map_cam ? h_cam : nullptr; mo.h_obs = gr.map_obs ? h_obs : nullptr; mo.h_n = h_n;
+    mo.X = ctx->d_map_X_next.as<double>(); mo.track = d.dev.track; mo.cam = d_cam; mo.row = d.dev.row;
+    mo.h_X = job.X ? d.pin.X : nullptr; mo.h_track = job.map_track ? d.pin.track : nullptr; mo.h_row = job.map_row ? d.pin.row : nullptr;
+    mo.h_cam = gr.map_cam ? gp.cam : nullptr; mo.h_obs = gr.map_obs ? gp.obs : nullptr; mo.h_n = h_n;
     e = launch_grow_compact(s, mo, st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return job.status = fail(ctx, CLC_ERR_HIP, "map_grow: the compaction launch", e); }
     rc = wait_pinned(ctx, h_n, 0xFFFFFFFFu, st, std::chrono::steady_clock::now(), 2, "map_grow: the compaction left no count");
@@ -498,11 +481,9 @@ int map_stage_grown(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, MapStaged&
     const uint32_t n = __atomic_load_n(h_n, __ATOMIC_ACQUIRE);
     ctx->grow_table = s.table; ctx->grow_n_tracks = s.n_tracks; ctx->grow_n_cams = n_cams; ctx->grow_cap = s.cap;
     if (n > ctx->mopts.maxkp) return job.status = fail(ctx, CLC_ERR_CAPACITY, "map_grow: more map rows than MatcherOptions.maxkp (the previous map stays)");
-    if (job.map_track && n) memcpy(job.map_track, d.h_track, sizeof(int32_t) * n);
-    if (job.map_row && n) memcpy(job.map_row, d.h_row, sizeof(int32_t) * n);
-    if (job.X && n) memcpy(job.X, d.h_X, sizeof(double) * 3 * n);
-    if (gr.map_cam && n) memcpy(gr.map_cam, h_cam, sizeof(int32_t) * n);
-    if (gr.map_obs && n) memcpy(gr.map_obs, h_obs, n);
+    map_lists_out(job, d.pin, n);
+    if (gr.map_cam && n) memcpy(gr.map_cam, gp.cam, sizeof(int32_t) * n);
+    if (gr.map_obs && n) memcpy(gr.map_obs, gp.obs, n);
     job.map_n = (int)n;
     gr.n_added = (int)n - n_seed;
     out.n = (int)n; out.d_cam = d_cam;
@@ -602,10 +583,10 @@ int clc_tracks_build_dev(clc_ctx* ctx, const clc_tracks_job* job, int32_t* d_tra
     if (!d_n_tracks || (g.cap_tracks > 0 && !d_track_feat)) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: null output");
     if (((uintptr_t)d_track_feat | (uintptr_t)d_n_tracks) & 3u) return fail(ctx, CLC_ERR_BAD_ARG, "tracks_build: misaligned device pointer");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    int32_t* rest = nullptr;
-    rc = ensure_map_block(ctx, (size_t)g.n_nodes, 0, &rest);
+    TracksDev dev;
+    rc = carve_block(ctx, ctx->d_mapb, 1, 4, true, "growing the map block", [&](Carve& c) { dev.carve(c, (size_t)g.n_nodes); });
     if (rc != CLC_OK) return rc;
-    graph_words(ctx, g);
+    graph_words(g, dev.g);
     g.table = d_track_feat; g.h_table = nullptr; g.n_tracks = d_n_tracks;
     ctx->grow_table = nullptr;                           // (the block the last grown build's table lies in is rewritten)
     CLC_HIP(ctx, launch_tracks(g, ep, job->n_pairs, edge_rows, pick(ctx, stream)));
@@ -644,19 +625,21 @@ int clc_map_resect_build_dev(clc_ctx* ctx, const clc_map_job* job, int camera, d
     if (!ctx->grow_table || ctx->grow_n_cams != job->tracks.n_cams)
         return fail(ctx, CLC_ERR_STATE, "map_resect_build: the context holds no per-track state of a grown build with that many cameras");
     const clc_map_camera& m = job->cams[camera];
-    if ((m.d_kps != nullptr) == (m.d_feat != nullptr)) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: exactly one of d_kps / d_feat");
-    if (m.d_feat && m.feat_stride < 2) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: feat_stride < 2");
-    if (!(m.cam.focal > 0.0)) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: focal must be positive");
+    GatherSide side;
+    int rc = gather_side(ctx, "map_resect_build", nullptr, m.d_kps, m.d_feat, m.feat_stride, m.cam, side);
+    if (rc != CLC_OK) return rc;
     if (job->tracks.rows[camera] < 0 || !d_n || (job->tracks.rows[camera] > 0 && (!d_X || !d_x))) return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: null output");
-    if (((uintptr_t)m.d_kps & 3u) || ((uintptr_t)m.d_feat & 3u) || ((uintptr_t)d_X & 7u) || ((uintptr_t)d_x & 7u) || ((uintptr_t)d_track & 3u) ||
+    if (((uintptr_t)d_X & 7u) || ((uintptr_t)d_x & 7u) || ((uintptr_t)d_track & 3u) ||
         ((uintptr_t)d_row & 3u) || ((uintptr_t)d_n & 3u))
         return fail(ctx, CLC_ERR_BAD_ARG, "map_resect_build: misaligned device pointer");
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     GrowState s{};
     s.table = ctx->grow_table; s.n_tracks = ctx->grow_n_tracks; s.n_cams = ctx->grow_n_cams; s.cap = ctx->grow_cap;
-    const size_t capr = ((size_t)s.cap + 63) & ~(size_t)63;
-    s.X = ctx->d_growb.as<double>(); s.obs = (uint32_t*)(s.X + 3 * capr);
-    const GatherSide side{ nullptr, m.d_kps, m.d_feat, m.feat_stride, UdCamera{ m.cam.focal, m.cam.ppx, m.cam.ppy, m.cam.k1, m.cam.k2, m.cam.k3 } };
+    // the per-track state where the grown build left it: its view placed again, refused if the block no longer holds it
+    GrowDev gd;
+    rc = place_block(ctx, ctx->d_growb, "map_resect_build: the grow block does not hold the last grown build's state", [&](Carve& c) { gd.carve(c, (size_t)s.cap); });
+    if (rc != CLC_OK) return rc;
+    s.X = gd.X; s.obs = gd.obs;
     const ResectOut ro{ d_X, d_x, d_track, d_row, nullptr, nullptr, d_n, nullptr, job->tracks.rows[camera] };
     CLC_HIP(ctx, launch_resect_gather(s, side, camera, ro, pick(ctx, stream)));
     return CLC_OK;

@@ -174,7 +174,7 @@ hipError_t launch_resect_gather(const GrowState& s, const GatherSide& side, cons
 {
     if (camera < 0 || camera >= s.n_cams) return hipErrorInvalidValue;
     Scales sc;
-    for (int l = 0; l < CLC_MAX_LEVELS; ++l) sc.v[l] = (float)std::pow((double)1.2f, (double)l);      // clc_keypoints_to_features' values
+    level_scales(sc.v);
     hipLaunchKernelGGL(resect_gather_kernel, dim3(1), dim3(kOneGroup), 0, stream, s, side, sc, (int32_t)camera, out);
     return hipGetLastError();
 }

@@ -129,22 +129,24 @@ int map_align(clc_ctx* ctx, clc_map_align& job, const bool staged, const RowSour
     }
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // device [ match | cq | ct ] (n_old entries each); pinned [ record 64 B | X 3 n_new | match n_old ]
-    const size_t ro = ((size_t)n_old + 63) & ~(size_t)63;
+    // the match and the common lists, their pinned mirror (AlignDev, AlignPin)
+    AlignDev dev; AlignPin pin; MapPointsDev next;
     rc = grow(ctx, ctx->d_m_next, ctx->d_m.bytes, 0, 1, true, "allocating the next map's descriptor rows");
-    if (rc == CLC_OK && !staged) rc = grow(ctx, ctx->d_map_X_next, (3 * (size_t)n_new + 8) * sizeof(double), 1, 4, true, "growing the next map's points");
-    if (rc == CLC_OK) rc = grow(ctx, ctx->d_align, (3 * ro + 64) * sizeof(int32_t), 1, 4, true, "growing the map alignment block");
-    if (rc == CLC_OK) rc = grow(ctx, ctx->h_align, 64 + 3 * (size_t)n_new * sizeof(double) + (ro + 64) * sizeof(int32_t), 1, 4, true, "growing the pinned map alignment block");
+    if (rc == CLC_OK && !staged) rc = carve_block(ctx, ctx->d_map_X_next, 1, 4, true, "growing the next map's points", [&](Carve& c) { next.carve(c, (size_t)n_new); });
+    if (rc == CLC_OK) rc = carve_block(ctx, ctx->d_align, 1, 4, true, "growing the map alignment block", [&](Carve& c) { dev.carve(c, (size_t)n_old); });
+    if (rc == CLC_OK)
+        rc = carve_block(ctx, ctx->h_align, 1, 4, true, "growing the pinned map alignment block",
+                         [&](Carve& c) { pin.carve(c, (size_t)n_old, (size_t)n_new, sizeof(AlignRec), alignof(AlignRec)); });
     if (rc != CLC_OK) return rc;
     AlignJob a{};
-    int32_t* d_match = ctx->d_align.as<int32_t>();
+    int32_t* d_match = dev.match;
     a.match = n_old > 0 ? d_match : nullptr;
-    a.cq = d_match + ro; a.ct = a.cq + ro;
+    a.cq = dev.cq; a.ct = dev.ct;
     a.old_X = ctx->d_map_X.as<double>(); a.new_X = job.d_X; a.out_X = ctx->d_map_X_next.as<double>();
     a.n_old = n_old; a.n_new = n_new;
-    a.rec = ctx->h_align.as<AlignRec>();
-    double* h_X = (double*)(ctx->h_align.as<uint8_t>() + 64);
-    int32_t* h_match = (int32_t*)(h_X + 3 * (size_t)n_new);
+    a.rec = (AlignRec*)pin.rec;
+    double* h_X = pin.X;
+    int32_t* h_match = pin.match;
     a.h_X = job.X ? h_X : nullptr; a.h_match = job.match && n_old > 0 ? h_match : nullptr;
     __atomic_store_n(&a.rec->ready, 0, __ATOMIC_RELAXED);
     // behind whatever produced the new map: an event on the producer's stream, no host synchronisation

@@ -48,8 +48,6 @@ void acr_tables(int n, int m, float* logc_n, float* logc_k, std::vector<float>& 
     }
 }
 
-size_t dbl(size_t bytes) { return (bytes + 7) / 8; }
-
 // kind 0: a = X (3 N), b = x (2 N), K1 = intrinsics; kind 1: a = x1, b = x2 (2 N each), K1 / K2, image 2 of img_w x img_h;
 // kinds 2 / 3 (round 6: RobustMatcher's 'F' / 'H' models, RobustMatcher.hpp:128-151, :188-239): a = x1, b = x2 in pixels, both images
 // img_w x img_h -- the points are conditioned by the image size on their way into the pinned block (ACKernelAdaptor), the rounds are
@@ -133,66 +131,39 @@ struct AcrRun {
     {
         CLC_HIP(ctx, hipSetDevice(ctx->device));
         refine = kind == 0 && refine_huber > 0.0;
-        // device workspace (doubles): [ a | b | K1 16 | K2 16 | logc_n | logc_k | initial state ] staged by
-        // one launch, then scratch
-        const size_t state_d = 2 * dbl(sizeof(AcrState));                      // [ copy 0 | copy 1 = the state a run starts from ]
-        const size_t in_d = (size_t)(ad + 2) * N + 32 + 2 * dbl(sizeof(float) * ((size_t)N + 1)) + state_d;
-        // a round's launches read what the round before them wrote: two copies of state, models, slots and sorted lists, indexed by
-        // launch parity (acransac.hip: acr_round_kernel, acr_solve5_kernel)
-        const int copies = 2;
-        const int Ms = kind == 1 ? 10 : 4;                             // slots per iteration between the parity copies (the kernels' stride)
-        const size_t models_d = (size_t)copies * kAcrMaxBatch * Ms * md;
-        const size_t hyp_d = dbl(sizeof(AcrHyp) * copies * kAcrMaxBatch * Ms);
-        const size_t sorted_d = dbl(sizeof(uint32_t) * (size_t)copies * kAcrMaxBatch * Ms * N);
-        const size_t idx_d = dbl(sizeof(uint32_t) * (size_t)N);
-        const size_t res_d = dbl(sizeof(AcrResult)), mask_d = dbl((size_t)N);
-        const size_t ref_d = refine ? dbl(sizeof(RefineOut)) : 0;
-        int rc = ensure_pnp(ctx, in_d + models_d + hyp_d + sorted_d + 2 * idx_d + res_d + mask_d + ref_d + 16);
+        // the device workspace and the pinned block (AcrDev, AcrPin: the inputs, staged by one launch, lie alike in both).  A round's
+        // launches read what the round before them wrote: two copies of state, models, slots and sorted lists, indexed by launch parity
+        // (acransac.hip: acr_round_kernel, acr_solve5_kernel)
+        const AcrDims dims{ kind, (size_t)N, (size_t)md, sizeof(AcrState), sizeof(AcrHyp), sizeof(AcrResult), refine ? sizeof(RefineOut) : 0, (size_t)kAcrMaxBatch };
+        AcrDev dv; AcrPin pin;
+        int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, dims); });
+        if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, dims); });
         if (rc != CLC_OK) return rc;
-        // pinned: [ inputs | state mirror | sequence word | result | mask | inlier list | refine record ]
-        const size_t inl_d = dbl(sizeof(int32_t) * (size_t)N);
-        rc = ensure_pinned(ctx, (in_d + state_d + 1 + res_d + mask_d + inl_d + ref_d) * sizeof(double) + 64);   // (+1: the polled word)
-        if (rc != CLC_OK) return rc;
-        double* d = ctx->d_pnp.as<double>();
-        d_a = d;                               d += (size_t)ad * N;
-        d_b = d;                               d += (size_t)2 * N;
-        d_K1 = d;                              d += 16;
-        d_K2 = d;                              d += 16;
-        float* d_cn = (float*)d;               d += dbl(sizeof(float) * ((size_t)N + 1));
-        float* d_ck = (float*)d;               d += dbl(sizeof(float) * ((size_t)N + 1));
-        d_state = (AcrState*)d;                d += state_d;
-        d_models = d;                          d += models_d;
-        d_hyp = (AcrHyp*)d;                    d += hyp_d;
-        d_sorted = (uint32_t*)d;               d += sorted_d;
-        d_best = (uint32_t*)d;                 d += idx_d;
-        d_index = (uint32_t*)d;                d += idx_d;
-        d_res = (AcrResult*)d;                 d += res_d;
-        d_mask = (uint8_t*)d;                  d += mask_d;
-        d_ref = d;
-        double* hp = ctx->h_pin.as<double>();
+        d_a = dv.in.a; d_b = dv.in.b; d_K1 = dv.in.K1; d_K2 = dv.in.K2;
+        float* d_cn = dv.in.logc_n; float* d_ck = dv.in.logc_k;
+        d_state = (AcrState*)dv.in.state; d_models = dv.models; d_hyp = (AcrHyp*)dv.hyp; d_sorted = dv.sorted; d_best = dv.best; d_index = dv.index;
+        d_res = (AcrResult*)dv.result; d_mask = dv.mask; d_ref = dv.ref;
+        double* hp = pin.in.a;
         if (kind >= 2) {
             // ACKernelAdaptor: NormalizePoints(x, &x_, &N_, w, h) for both point sets (x_n = d x + t, oracle/clc_oracle_twoview.c orc_tv_normalize)
             // (points from device memory: the staging launch applies the same two operations, launch_acr_stage's cond)
             norm_t = tv::normalizer(img_w, img_h);
-            double* q1 = hp;
-            double* q2 = hp + (size_t)2 * N;
+            double* q1 = pin.in.a;
+            double* q2 = pin.in.b;
             for (int i = 0; i < N && !dev_a; ++i) {
                 q1[2 * i] = h_a[2 * i] * norm_t.d + norm_t.tx; q1[2 * i + 1] = h_a[2 * i + 1] * norm_t.d + norm_t.ty;
                 q2[2 * i] = h_b[2 * i] * norm_t.d + norm_t.tx; q2[2 * i + 1] = h_b[2 * i + 1] * norm_t.d + norm_t.ty;
             }
         } else if (!dev_a) {
-            memcpy(hp, h_a, sizeof(double) * ad * N);
-            memcpy(hp + (size_t)ad * N, h_b, sizeof(double) * 2 * N);
+            memcpy(pin.in.a, h_a, sizeof(double) * ad * N);
+            memcpy(pin.in.b, h_b, sizeof(double) * 2 * N);
         }
-        double* hK = hp + (size_t)(ad + 2) * N;
-        memset(hK, 0, sizeof(double) * 32);
-        if (h_K1) memcpy(hK, h_K1, sizeof(double) * 9);
-        if (h_K2) memcpy(hK + 16, h_K2, sizeof(double) * 9);
-        float* h_cn = (float*)(hK + 32);
-        float* h_ck = (float*)(hK + 32 + dbl(sizeof(float) * ((size_t)N + 1)));
-        acr_tables(N, m, h_cn, h_ck, ctx->acr_lg);
+        memset(pin.in.K1, 0, sizeof(double) * 32);                     // (K1 | K2)
+        if (h_K1) memcpy(pin.in.K1, h_K1, sizeof(double) * 9);
+        if (h_K2) memcpy(pin.in.K2, h_K2, sizeof(double) * 9);
+        acr_tables(N, m, pin.in.logc_n, pin.in.logc_k, ctx->acr_lg);
         // the state ACRANSAC starts from is part of the upload (every round draws its own samples on the device)
-        AcrState* h_states = (AcrState*)(hK + 32 + 2 * dbl(sizeof(float) * ((size_t)N + 1)));
+        AcrState* h_states = (AcrState*)pin.in.state;
         memset(h_states, 0, 2 * sizeof(AcrState));
         // launch 0 (parity 0) reads copy 1
         AcrState* h_init = h_states + 1;
@@ -204,10 +175,7 @@ struct AcrRun {
         h_init->ac_mode = std::isinf(precision) ? 1 : 0;
         h_init->grow = batch_cap < 32 ? batch_cap : 32;
         h_init->cur_batch = h_init->n_iter < h_init->grow ? h_init->n_iter : h_init->grow;
-        h_word = (unsigned long long*)(hp + in_d + state_d);
-        h_res = (AcrResult*)(hp + in_d + state_d + 1);
-        p_inl = (int32_t*)(hp + in_d + state_d + 1 + res_d + mask_d);
-        p_ref = (RefineOut*)(hp + in_d + state_d + 1 + res_d + mask_d + inl_d);
+        h_word = pin.word; h_res = (AcrResult*)pin.result; p_inl = pin.inliers; p_ref = pin.ref;
         __atomic_store_n(h_word, 0ull, __ATOMIC_RELAXED);
 
         pb = AcrProblem{};
@@ -237,7 +205,7 @@ struct AcrRun {
         pb.max_threshold = std::isinf(precision) ? INFINITY : precision * (pb.norm * pb.norm);
         pb.seed = seed;
 
-        stage_src = hp; stage_dst = ctx->d_pnp.as<double>(); stage_n = (in_d + 1) & ~(size_t)1;      // (both blocks are sized past in_d + 1)
+        stage_src = hp; stage_dst = dv.in.a; stage_n = (pin.in.bytes / sizeof(double) + 1) & ~(size_t)1;      // (both blocks go on past the inputs)
         // Upper bound of the batch a round can ask for, from what the host knows when it enqueues it (one or two rounds behind the
         // device): while the index set has not switched the batch doubles up to kAcrMaxBatch; afterwards it is what is left of the
         // reserve, remaining = n_iter - iter (+ a margin for the "no inliers: n_iter++" rule, once per round).
@@ -642,8 +610,9 @@ int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const doub
     if (S == 0) return CLC_OK;
     const int m = kind == 2 ? 7 : 4, M = kind == 2 ? 3 : 1;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t pts = (size_t)4 * N, smp = dbl(sizeof(int32_t) * (size_t)S * m), out = (size_t)S * M * 9;
-    int rc = ensure_pnp(ctx, pts + smp + out + 8);
+    const size_t pts = (size_t)4 * N, out = (size_t)S * M * 9;
+    TwoViewMinDev dv;
+    int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, (size_t)N, (size_t)S * m, out); });
     if (rc != CLC_OK) return rc;
     std::vector<double> q(pts);
     const tv::Normalizer t = tv::normalizer(img_w, img_h);
@@ -651,12 +620,12 @@ int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const doub
         q[2 * i] = h_x1[2 * i] * t.d + t.tx; q[2 * i + 1] = h_x1[2 * i + 1] * t.d + t.ty;
         q[(size_t)2 * N + 2 * i] = h_x2[2 * i] * t.d + t.tx; q[(size_t)2 * N + 2 * i + 1] = h_x2[2 * i + 1] * t.d + t.ty;
     }
-    double* d = ctx->d_pnp.as<double>();
-    int32_t* d_smp = (int32_t*)(d + pts);
-    double* d_out = d + pts + smp;
+    double* d = dv.x1;
+    int32_t* d_smp = dv.samples;
+    double* d_out = dv.out;
     CLC_HIP(ctx, hipMemcpyAsync(d, q.data(), sizeof(double) * pts, hipMemcpyHostToDevice, ctx->stream));
     CLC_HIP(ctx, hipMemcpyAsync(d_smp, h_samples, sizeof(int32_t) * (size_t)S * m, hipMemcpyHostToDevice, ctx->stream));
-    CLC_HIP(ctx, launch_twoview_minimal(kind, d, d + (size_t)2 * N, N, d_smp, S, d_out, ctx->stream));
+    CLC_HIP(ctx, launch_twoview_minimal(kind, dv.x1, dv.x2, N, d_smp, S, d_out, ctx->stream));
     CLC_HIP(ctx, hipMemcpyAsync(h_models, d_out, sizeof(double) * out, hipMemcpyDeviceToHost, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CLC_OK;

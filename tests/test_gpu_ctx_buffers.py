@@ -2,7 +2,8 @@
 driven small -> past its capacity -> small again on ONE context, and every output must equal, bit for bit, the same call on a fresh
 context; and creating, growing and destroying contexts over and over must not lose device memory.
 
-Shapes are chosen to cross a capacity, not to resemble the workload: a 128 x 96 detector, maxkp = 256."""
+Shapes are chosen to cross a capacity, not to resemble the workload: a 128 x 96 detector, maxkp = 256 (1 024 for the blocks of the map
+steps and of the inter-camera step, whose layouts are the views of coloc_amd/csrc/clc_layout.h)."""
 import numpy as np
 import pytest
 
@@ -139,6 +140,88 @@ def test_growth_keeps_results_map_points_and_tracks(grown):
             _same(got, want, (map_n, n))
         finally:
             fresh.close()
+
+
+# ---- the blocks of the map steps and of the inter-camera step: one context of maxkp = 1 024 per sequence ------------------------------------
+# (the scene builders are the ones of the tests that own these steps; every block below is laid out by a view of clc_layout.h, sized by
+# the call's counts and grown by a quarter)
+
+_GROW_JOBS = {}
+
+
+def _grow_job(big):
+    """3 cameras, every pair matched: 60 rows with 40 matches per pair give cap_tracks = min(120 edges, 180 nodes / 2) = 90, rounded to
+    128; 600 rows with 400 matches give 900, rounded to 960 -- past 1.25 x the small blocks (d_mapb, h_mapb, d_growb, h_growb, d_bab,
+    the track gather block)"""
+    import test_gpu_map_grow as mg
+    if big not in _GROW_JOBS:
+        n, m = (600, 400) if big else (60, 40)
+        sc = mg._scene(3, n, 4100 + n)
+        _GROW_JOBS[big] = dict(sc=sc, pairs=mg._scene_pairs(sc, m, 4200 + n, wrong=0.02), rows=[n] * 3,
+                               desc=mg._descriptors(n, sc["point_of"], 4300 + n, flips=6))
+    return _GROW_JOBS[big]
+
+
+def _grow_ba(ctx, big):
+    """the grown, bundle-adjusted build, then camera 2's resection list from the per-track state the build left in the context: the
+    consumer that places the grow block's view again"""
+    import test_gpu_map_grow as mg
+    j = _grow_job(big)
+    keep = []
+    pairs_dev, cams_dev = mg._dev_pairs(j["pairs"], keep), mg._dev_cams(j["sc"]["cams"], keep, j["desc"])
+    out = ctx.map_build_grow_ba_dev(j["rows"], pairs_dev, cams_dev, 0, j["sc"]["Rt"][0], j["sc"]["Rt"][1], seed=7)
+    assert out["map_n"] > (300 if big else 20) and out["grow"]["resected"][2], (out["map_n"], out["grow"]["status"])
+    return [out, mg._resect_on_device(ctx, j["rows"], cams_dev, 2)]
+
+
+_ALIGN_CASES = {}
+
+
+def _map_align(ctx, big):
+    """an old map of 50 / 700 rows replaced by one of 60 / 800: d_align and h_align hold the old rows rounded to 64 (64 -> 704), h_align
+    the new map's points as well"""
+    import test_gpu_map_update as up
+    if big not in _ALIGN_CASES:
+        n_old, n_new = (700, 800) if big else (50, 60)
+        q, t = up._spread_commons(n_old, n_new, n_old // 2, 4400 + n_old)
+        _ALIGN_CASES[big] = up._case(n_old, n_new, q, t, 4500 + n_old, block_rows=n_new + 100)
+    c = _ALIGN_CASES[big]
+    up._install_old(ctx, c)
+    got, keep = up._align(ctx, c)
+    assert got["status"] == 0 and got["n_common"] == c["n_old"] // 2
+    return got
+
+
+def _inter(ctx, big):
+    """one job of the inter-camera step from device memory through the reference's chain (the map sweep uses d_inter's rows and match
+    list): 40 pair correspondences against 300 map points, then 600 against 700"""
+    import test_gpu_inter_pose_dev as ip
+    from coloc_amd import abi
+    n, map_n = (600, 700) if big else (40, 300)
+    h, d = ip._world(9500 if big else 9040, n, map_n)
+    ctx.set_map_points(h["map_X"])
+    got = abi.inter_pose_batch_dev([ctx], [ip._dev_job(h, d, 51, chain=True, lower_is_b=0)])[0]
+    assert got["status"] == 0 and (not big or got["stage"] == 0)
+    return got
+
+
+def _ctx_1024():
+    from coloc_amd import Context
+    return Context(device=0, width=W, height=H, maxkp=1024, match_thresh=60)
+
+
+@pytest.mark.parametrize("driver", [_grow_ba, _map_align, _inter], ids=["grow_ba", "map_align", "inter_pose"])
+def test_growth_keeps_results_map_and_inter_blocks(driver):
+    grown = _ctx_1024()
+    try:
+        for big in (False, True, False):
+            fresh = _ctx_1024()
+            try:
+                _same(driver(grown, big), driver(fresh, big), (driver.__name__, big))
+            finally:
+                fresh.close()
+    finally:
+        grown.close()
 
 
 def _k2nn_jobs(ctx, oracle, ncam):
