@@ -130,6 +130,20 @@ class MapAlign(C.Structure):
 MAP_ALIGN_OK, MAP_ALIGN_NO_SCALE = 0, 1
 
 
+class MapAlignSim(C.Structure):
+    """clc_map_align_sim (include/coloc_hip.h)"""
+    _fields_ = [("d_desc", C.c_void_p), ("d_rows", C.c_void_p), ("d_X", C.c_void_p), ("n_new", C.c_int), ("threshold", C.c_int),
+                ("install", C.c_int), ("after_stream", C.c_void_p), ("apply", C.c_int), ("max_iteration", C.c_int), ("seed", C.c_uint64),
+                ("precision", C.c_double), ("match", C.c_void_p), ("X", C.c_void_p), ("inlier", C.c_void_p),
+                ("n_old", C.c_int), ("n_common", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int), ("refit", C.c_int),
+                ("status", C.c_int), ("s", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("error_max", C.c_double),
+                ("min_nfa", C.c_double)]
+
+
+MAP_SIM_OK, MAP_SIM_NO_MODEL = 0, 1
+SIM_APPLY_SCALE, SIM_APPLY_FULL = 0, 1
+
+
 class MapGrow(C.Structure):
     """clc_map_grow (include/coloc_hip.h)"""
     _fields_ = [("max_iteration", C.c_int), ("seed", C.c_uint64), ("precision", C.c_double), ("resected", C.c_int * MAX_BATCH),
@@ -213,6 +227,7 @@ EXPORTS = [
     "clc_ba_dev", "clc_map_build_grow_ba_dev", "clc_map_init_grow_ba_batch_dev", "clc_map_update_grow_ba_batch_dev",
     "clc_match_guided_dev", "clc_match_guided_batch_dev",
     "clc_match_map_guided_dev", "clc_match_map_guided_batch_dev",
+    "clc_sim3_acransac", "clc_sim3_minimal", "clc_map_align_sim_dev", "clc_map_update_sim_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
@@ -336,6 +351,10 @@ def load_library():
     lib.clc_two_view_acransac.argtypes = [vp, ci, vp, vp, ci, vp, vp, ci, ci, ci, C.c_uint64, C.c_double, vp, vp, vp, vp, ip, dp, dp, ip]
     lib.clc_two_view_acransac_batch.argtypes = [vp, ci, vp, ci]
     lib.clc_two_view_minimal.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, ci, vp]
+    lib.clc_sim3_acransac.argtypes = [vp, vp, vp, ci, ci, C.c_uint64, C.c_double, dp, vp, vp, vp, vp, vp, ip, dp, dp, ip, ip, ip]
+    lib.clc_sim3_minimal.argtypes = [vp, vp, vp, ci, vp, ci, vp]
+    lib.clc_map_align_sim_dev.argtypes = [vp, vp]
+    lib.clc_map_update_sim_batch_dev.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     lib.clc_mc_plan.argtypes = [vp, ci, ci, ci, ci, vp, ci, ip]
     lib.clc_mc_unique_id.argtypes = [vp]
     lib.clc_mc_create.argtypes = [vp, vp, ci, ci, ci, C.POINTER(vp)]
@@ -914,6 +933,53 @@ def map_update_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye
     return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
 
 
+def _sim_fill(a, maxkp, threshold=0, apply=SIM_APPLY_SCALE, sim_max_iteration=0, sim_seed=1, sim_precision=float("inf"), want_match=True):
+    """fills the in fields a composition reads of a MapAlignSim; -> (match, inlier) host arrays"""
+    a.threshold, a.apply, a.max_iteration, a.seed, a.precision = int(threshold), int(apply), int(sim_max_iteration), int(sim_seed), float(sim_precision)
+    match = np.full(max(int(maxkp), 1), -2, dtype=np.int32) if want_match else None
+    inlier = np.zeros(max(int(maxkp), 1), dtype=np.uint8)
+    a.match, a.inlier = (None if match is None else match.ctypes.data), inlier.ctypes.data
+    return match, inlier
+
+
+def _sim_result(a, match, inlier, X):
+    n_old, n_new, n_com = max(a.n_old, 0), max(a.n_new, 0), max(a.n_common, 0)
+    return dict(s=float(a.s), R=np.array(a.R).reshape(3, 3), t=np.array(a.t), n_old=a.n_old, n_common=a.n_common, n_inliers=a.n_inliers,
+                iterations=a.iterations, refit=a.refit, status=a.status, error_max=float(a.error_max), min_nfa=float(a.min_nfa),
+                match=None if match is None else match[:n_old].copy(), inlier=inlier[:n_com].astype(bool),
+                X=None if X is None else X[:n_new].copy())
+
+
+def map_update_sim_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, threshold=0,
+                             apply=SIM_APPLY_SCALE, sim_max_iteration=0, sim_seed=1, sim_precision=float("inf"), grow=False, ba=False,
+                             max_iteration=256, seed=0, precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
+    """clc_map_update_sim_batch_dev: map_update_batch_dev (grow=False), map_update_grow_batch_dev (grow=True) or
+    map_update_grow_ba_batch_dev (grow=True, ba=True) with the a-contrario similarity in place of the align step.  Returns (map result
+    dict -- X, Rt_seed_* and grow["Rt"] under the apply rule -- with a "sim" dict and, as asked, "grow" and "ba"; [pair filter results])."""
+    lib = load_library()
+    n = len(pair_jobs)
+    assert len(ctxs) == n == len(pair_cams)
+    arr = (PairJob * n)()
+    keep = []
+    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
+    j, g, b, a = MapJob(), MapGrow(), MapBa(), MapAlignSim()
+    out = _map_fill(j, keep, rows, [dict(cam_a=ca, cam_b=cb) for ca, cb in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision) if grow else None
+    _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
+    match, inlier = _sim_fill(a, ctxs[0].mopts.maxkp, threshold, apply, sim_max_iteration, sim_seed, sim_precision)
+    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
+    rc = lib.clc_map_update_sim_batch_dev(hs, arr, n, C.byref(j), C.byref(a), C.byref(g) if grow else None, C.byref(b) if ba else None)
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_map_update_sim_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    res = _map_result(j, *out)
+    res["sim"] = _sim_result(a, match, inlier, None)
+    if grow:
+        res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
+    if ba:
+        res["ba"] = _ba_result(b)
+    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+
+
 def _grow_fill(g, keep, rows, max_iteration=256, seed=0, precision=float("inf")):
     """fills a MapGrow; -> (map_cam, map_obs) host arrays with room as _map_fill's map_track"""
     g.max_iteration, g.seed, g.precision = int(max_iteration), int(seed), float(precision)
@@ -1462,6 +1528,19 @@ class Context:
         self._chk(self.lib.clc_map_align_dev(self.h, C.byref(a)))
         return _align_result(a, match, X)
 
+    def map_align_sim_dev(self, d_desc, d_X, n_new, d_rows=None, threshold=0, install=True, after_stream=None, apply=SIM_APPLY_SCALE,
+                          max_iteration=0, seed=1, precision=float("inf"), want_match=True, want_X=True):
+        """clc_map_align_sim_dev: clc_map_align_dev's step under the a-contrario similarity NEW -> OLD over the common features.  Returns a
+        dict: s, R, t, n_old, n_common, n_inliers, inlier (flags per common feature), iterations, refit, status, error_max, min_nfa,
+        match, X (the transformed points)."""
+        a = MapAlignSim()
+        a.d_desc, a.d_rows, a.d_X, a.n_new, a.install, a.after_stream = d_desc, d_rows, d_X, int(n_new), int(bool(install)), after_stream
+        match, inlier = _sim_fill(a, self.mopts.maxkp, threshold, apply, max_iteration, seed, precision, want_match)
+        X = np.zeros((max(int(n_new), 1), 3)) if want_X else None
+        a.X = None if X is None else X.ctypes.data
+        self._chk(self.lib.clc_map_align_sim_dev(self.h, C.byref(a)))
+        return _sim_result(a, match, inlier, X)
+
     def track_build_dev(self, d_X, d_x, d_query, d_map, d_n, stream=None, **job):
         """clc_track_build_dev: the track kernel alone, enqueue only; job keywords as track_localize_dev (d_match, nq, cam, d_kps | d_feat,
         feat_stride, d_count); outputs are device pointers with room for nq tracks"""
@@ -1711,6 +1790,34 @@ class Context:
         out = np.zeros((smp.shape[0], M, 9))
         self._chk(self.lib.clc_two_view_minimal(self.h, ord(model), _p(x1), _p(x2), x1.shape[0], int(img_wh[0]), int(img_wh[1]), _p(smp),
                                                 smp.shape[0], _p(out)))
+        return out
+
+    def sim3_acransac(self, x_new, x_old, max_iteration=256, seed=1, precision=float("inf")):
+        """clc_sim3_acransac: the a-contrario 3-D similarity NEW -> OLD, X_old ~ s R X_new + t.  Returns a dict: found, s, R (3,3), t (3),
+        A (3,4) = [sR | t], mask, inliers (ascending residual order), error_max (old-map units), min_nfa, iterations, valid, refit."""
+        x_new = np.ascontiguousarray(x_new, dtype=np.float64).reshape(-1, 3)
+        x_old = np.ascontiguousarray(x_old, dtype=np.float64).reshape(-1, 3)
+        n = x_new.shape[0]
+        assert x_old.shape[0] == n
+        R = np.zeros(9); t = np.zeros(3); A = np.zeros(12)
+        mask = np.zeros(max(n, 1), dtype=np.uint8); inl = np.zeros(max(n, 1), dtype=np.int32)
+        ni, its, valid, refit = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        s, emax, nfa = C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.lib.clc_sim3_acransac(self.h, _p(x_new), _p(x_old), n, int(max_iteration), int(seed), float(precision), C.byref(s),
+                                             _p(R), _p(t), _p(A), _p(mask), _p(inl), C.byref(ni), C.byref(emax), C.byref(nfa), C.byref(its),
+                                             C.byref(valid), C.byref(refit)))
+        return dict(found=valid.value >= 0, s=s.value, R=R.reshape(3, 3), t=t, A=A.reshape(3, 4), mask=mask[:n].astype(bool),
+                    inliers=inl[:ni.value].copy(), n_inliers=ni.value, error_max=emax.value, min_nfa=nfa.value, iterations=its.value,
+                    valid=valid.value, refit=refit.value)
+
+    def sim3_minimal(self, x_new, x_old, samples):
+        """clc_sim3_minimal: the minimal similarities [sR | t] of the given samples (S x 3 indices): array (S, 12), NaN rows where a
+        sample is degenerate or names no correspondence."""
+        x_new = np.ascontiguousarray(x_new, dtype=np.float64).reshape(-1, 3)
+        x_old = np.ascontiguousarray(x_old, dtype=np.float64).reshape(-1, 3)
+        smp = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((smp.shape[0], 12))
+        self._chk(self.lib.clc_sim3_minimal(self.h, _p(x_new), _p(x_old), x_new.shape[0], _p(smp), smp.shape[0], _p(out)))
         return out
 
     def pnp_refine(self, X, x, K, Rt0, mask=None, huber_a=16.0, max_iter=50):

@@ -32,6 +32,7 @@
 #include "p3p.h"
 #include "fivept_wave.h"
 #include "twoview_min.h"
+#include "sim3_math.h"
 
 namespace clc {
 
@@ -421,7 +422,8 @@ __device__ __forceinline__ void acr_best_bcast(double& v, double& e, int& k, int
 }
 
 // One model slot, one workgroup of T threads: `model` (global memory or LDS) -> *hyp_slot and the sorted index list out_idx[0..n).
-template <int E, bool PRE = false>
+// KIND: the residual is chosen at compile time where the round names its kind (4: the 3-D similarity); -1: by pb.kind, as kinds 0-3 are
+template <int E, bool PRE = false, int KIND = -1>
 __device__ __forceinline__ void acr_nfa_body(const AcrProblem& pb, const int P /* = T * E, power of two >= n */, const double* model,
                                              AcrHyp* __restrict__ hyp_slot, uint32_t* __restrict__ out_idx, const int tid, const int T,
                                              uint64_t* lkey /* [e][tid] staging of the cross-wave exchanges (one word per element) */,
@@ -444,6 +446,7 @@ __device__ __forceinline__ void acr_nfa_body(const AcrProblem& pb, const int P /
         return;
     }
     auto residual = [&](const int i) -> double {
+        if constexpr (KIND == 4) return sim3_residual(model, pb.a + 3 * i, pb.b + 3 * i);
         if (pb.kind == 0) return acr_err_resection(model, pb.K1v, pb.norm, pb.a[3 * i], pb.a[3 * i + 1], pb.a[3 * i + 2], pb.b[2 * i], pb.b[2 * i + 1]);
         const double u1 = pb.a[2 * i], v1 = pb.a[2 * i + 1], u2 = pb.b[2 * i], v2 = pb.b[2 * i + 1];
         return pb.kind == 1 ? acr_err_epipolar(model, u1, v1, u2, v2) : (pb.kind == 2 ? acr_err_line(model, u1, v1, u2, v2) : acr_err_transfer(model, u1, v1, u2, v2));
@@ -774,12 +777,37 @@ __device__ __forceinline__ void acr_keep(const AcrProblem& pb, const AcrCore& c,
 // the host has launch r + 2 enqueued long before r + 1 ends, and the launch that reports "done" is the last one in the stream.
 // The same one-launch round serves the two cheap two-view solvers (round 6: 'F' seven points, 'H' four points -- twoview_min.h): a
 // slot workgroup solves its iteration's sample on thread 0 (all the slots of an iteration solve the same sample and keep their own
-// root), everything else is the resection round.  KIND = AcrProblem::kind; slots and models keep the resection's strides (4 slots per
+// root), everything else is the resection round.  So does the 3-D similarity (kind 4: three points, one model, sim3_math.h; the project's
+// own statement, clc_sim3_acransac), whose residual acr_nfa_body takes at compile time.  KIND = AcrProblem::kind; slots and models keep the resection's strides (4 slots per
 // iteration between the parity copies, 12 doubles per model) so that the host lays one workspace out for all three.
 template <int KIND> struct AcrKind;
 template <> struct AcrKind<0> { static constexpr int m = 3, M = 4; };
 template <> struct AcrKind<2> { static constexpr int m = 7, M = 3; };
 template <> struct AcrKind<3> { static constexpr int m = 4, M = 1; };
+template <> struct AcrKind<4> { static constexpr int m = 3, M = 1; };
+
+// the similarity of the sample {id[0..3)} of a kind-4 problem (x = X_new, y = X_old, 3 N each) -> out[0..12) (NaN: degenerate sample, an
+// index outside [0, N) or root != 0): sim3_minimal, the body sim3_minimal_kernel runs
+__device__ __forceinline__ void acr_sim3_sample_root(const double* __restrict__ x, const double* __restrict__ y, const int (&id)[3], const int N,
+                                                     const int root, double* out)
+{
+    bool ok = root == 0;
+    int i[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+        i[p] = id[p];
+        if (i[p] < 0 || i[p] >= N) { ok = false; i[p] = 0; }
+    }
+    double px[3][3], py[3][3], A[12];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) { px[p][q] = x[3 * i[p] + q]; py[p][q] = y[3 * i[p] + q]; }
+    sim3_minimal(px[0], px[1], px[2], py[0], py[1], py[2], A);
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+    for (int e = 0; e < 12; ++e) out[e] = ok ? A[e] : qnan;
+}
 
 // the model of root `root` of the sample {id[0..m)} of a seven-point / four-point problem -> out[0..12) (9 used; NaN: no such root)
 template <int KIND>
@@ -876,6 +904,7 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
 #endif
         ACR_STAMP(3);
         if constexpr (KIND == 0) p3p_sample_root(pb.a, pb.b, pb.K1v, id[0], id[1], id[2], pb.n, slot & 3, s_model);
+        else if constexpr (KIND == 4) acr_sim3_sample_root(pb.a, pb.b, id, pb.n, slot % M, s_model);
         else acr_twoview_sample_root<KIND>(pb.a, pb.b, id, pb.n, slot % M, s_model);
         ACR_STAMP(4);
         double* mo = models + ((size_t)par * kSlots + slot) * 12;
@@ -884,7 +913,7 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
     }
     __syncthreads();
     ACR_STAMP(5);
-    acr_nfa_body<E, kPre>(pb, P, s_model, hyps + (size_t)par * kSlots + slot, sorted + ((size_t)par * kSlots + slot) * pb.n, tid, T,
+    acr_nfa_body<E, kPre, KIND == 4 ? 4 : -1>(pb, P, s_model, hyps + (size_t)par * kSlots + slot, sorted + ((size_t)par * kSlots + slot) * pb.n, tid, T,
                           reinterpret_cast<uint64_t*>(acr_lds), &pre);
 }
 
@@ -919,6 +948,109 @@ hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_
     if (kind == 2) hipLaunchKernelGGL(twoview_minimal_kernel<2>, dim3((S * 3 + 63) / 64), dim3(64), 0, stream, d_x1, d_x2, N, d_samples, S, d_out);
     else if (kind == 3) hipLaunchKernelGGL(twoview_minimal_kernel<3>, dim3((S + 63) / 64), dim3(64), 0, stream, d_x1, d_x2, N, d_samples, S, d_out);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ---- the 3-D similarity behind the rounds (kind 4) ----------------------------------------------------------------------------------
+// The minimal models of caller-chosen samples (clc_sim3_minimal): one thread per sample, the body the round runs.
+__global__ __launch_bounds__(64) void sim3_minimal_kernel(const double* __restrict__ x, const double* __restrict__ y, const int N,
+                                                          const int32_t* __restrict__ samples, const int S, double* __restrict__ out /* S x 12 */)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= S) return;
+    const int id[3] = { samples[3 * t], samples[3 * t + 1], samples[3 * t + 2] };
+    double mo[12];
+    acr_sim3_sample_root(x, y, id, N, 0, mo);
+#pragma unroll
+    for (int e = 0; e < 12; ++e) out[(size_t)t * 12 + e] = mo[e];
+}
+hipError_t launch_sim3_minimal(const double* d_x, const double* d_y, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream)
+{
+    if (S <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sim3_minimal_kernel, dim3((S + 63) / 64), dim3(64), 0, stream, d_x, d_y, N, d_samples, S, d_out);
+    return hipGetLastError();
+}
+
+// The refit, ONE workgroup of kSim3Threads behind the round that completed the run (its result record and mask are in device memory).
+// Thread t counts the mask bytes of its kSim3Span consecutive correspondences, thread 0 turns the counts into offsets, every thread
+// writes its inliers -- the list in ascending index; then thread c sums partial c (kSim3Chunk consecutive inliers, left to right) of the
+// two passes of sim3_refit and thread 0 adds the partials left to right: the statement's additions in the statement's order, no atomics.
+// The record goes out last, `ready` behind a system-scope fence.
+static constexpr int kSim3Threads = 256, kSim3Span = kAcrMaxN / kSim3Threads, kSim3Parts = kAcrMaxN / kSim3Chunk;
+static_assert(kSim3Parts <= kSim3Threads && kSim3Span * kSim3Threads == kAcrMaxN, "one thread per partial sum, every correspondence counted");
+__global__ __launch_bounds__(kSim3Threads) void sim3_refit_kernel(const AcrResult* __restrict__ d_res, const uint8_t* __restrict__ d_mask,
+                                                                  const double* __restrict__ x, const double* __restrict__ y, const int N,
+                                                                  int32_t* __restrict__ list, Sim3Out* __restrict__ d_out, Sim3Out* h_out)
+{
+    __shared__ int s_off[kSim3Threads + 1];
+    __shared__ double s_part[kSim3Parts][10];
+    __shared__ double s_mean[6];
+    const int tid = threadIdx.x;
+    const int valid = d_res->valid, n_res = d_res->n_inliers;
+    const bool found = sim3_accepted(valid, n_res) && n_res <= N;
+    int n = 0;
+    if (found) {
+        const int b = tid * kSim3Span, e = b + kSim3Span < N ? b + kSim3Span : N;
+        int cnt = 0;
+        for (int i = b; i < e; ++i) cnt += d_mask[i] ? 1 : 0;
+        s_off[tid + 1] = cnt;
+        __syncthreads();
+        if (tid == 0) {
+            s_off[0] = 0;
+            for (int k = 1; k <= kSim3Threads; ++k) s_off[k] += s_off[k - 1];
+        }
+        __syncthreads();
+        int at = s_off[tid];
+        for (int i = b; i < e; ++i) if (d_mask[i]) list[at++] = i;
+        n = s_off[kSim3Threads];
+        __syncthreads();                                                // (the list is written: same workgroup, global memory)
+        const int parts = (n + kSim3Chunk - 1) / kSim3Chunk;
+        if (tid < parts) sim3_sum_points(x, y, list, tid * kSim3Chunk, (tid + 1) * kSim3Chunk < n ? (tid + 1) * kSim3Chunk : n, s_part[tid]);
+        __syncthreads();
+        if (tid == 0 && n > 0) {
+            double sum6[6];
+            for (int c = 0; c < parts; ++c) sim3_add(sum6, s_part[c], 6, c == 0);
+            for (int q = 0; q < 6; ++q) s_mean[q] = sum6[q] / (double)n;
+        }
+        __syncthreads();
+        if (tid < parts) {
+            double xbar[3] = { s_mean[0], s_mean[1], s_mean[2] }, ybar[3] = { s_mean[3], s_mean[4], s_mean[5] };
+            sim3_sum_cov(x, y, list, tid * kSim3Chunk, (tid + 1) * kSim3Chunk < n ? (tid + 1) * kSim3Chunk : n, xbar, ybar, s_part[tid]);
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    Sim3Out o;
+    o.s = 1.0;
+    for (int q = 0; q < 9; ++q) o.R[q] = (q % 4 == 0) ? 1.0 : 0.0;
+    for (int q = 0; q < 3; ++q) o.t[q] = 0.0;
+    for (int q = 0; q < 12; ++q) o.A[q] = (q % 5 == 0) ? 1.0 : 0.0;
+    o.found = found && n == n_res ? 1 : 0; o.refit = 0; o.n_inliers = o.found ? n : 0; o.ready = 0;
+    if (o.found) {
+        for (int q = 0; q < 12; ++q) o.A[q] = d_res->model[q];
+        sim3_from_model(o.A, &o.s, o.R, o.t);
+        const int parts = (n + kSim3Chunk - 1) / kSim3Chunk;
+        double cov10[10];
+        for (int c = 0; c < parts; ++c) sim3_add(cov10, s_part[c], 10, c == 0);
+        const double xbar[3] = { s_mean[0], s_mean[1], s_mean[2] }, ybar[3] = { s_mean[3], s_mean[4], s_mean[5] };
+        o.refit = sim3_umeyama(n, xbar, ybar, cov10, &o.s, o.R, o.t, o.A) ? 1 : 0;
+    }
+    *d_out = o;
+    if (h_out) {
+        h_out->s = o.s;
+        for (int q = 0; q < 9; ++q) h_out->R[q] = o.R[q];
+        for (int q = 0; q < 3; ++q) h_out->t[q] = o.t[q];
+        for (int q = 0; q < 12; ++q) h_out->A[q] = o.A[q];
+        h_out->found = o.found; h_out->refit = o.refit; h_out->n_inliers = o.n_inliers;
+        __threadfence_system();
+        __hip_atomic_store(&h_out->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+hipError_t launch_sim3_refit(const AcrResult* d_res, const uint8_t* d_mask, const double* d_x, const double* d_y, int N, int32_t* d_list,
+                             Sim3Out* d_out, Sim3Out* h_out, hipStream_t stream)
+{
+    if (N < 1 || N > kAcrMaxN) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sim3_refit_kernel, dim3(1), dim3(kSim3Threads), 0, stream, d_res, d_mask, d_x, d_y, N, d_list, d_out, h_out);
     return hipGetLastError();
 }
 
@@ -1028,6 +1160,7 @@ static hipError_t acr_launch_kind(const int kind, const AcrChains& chains, int n
     if (kind == 1) return acr_launch_round5<E>(chains, n_chains, B, P, par, stream);
     if (kind == 2) return acr_launch_round<E, 2>(chains, n_chains, B, P, par, stream);
     if (kind == 3) return acr_launch_round<E, 3>(chains, n_chains, B, P, par, stream);
+    if (kind == 4) return acr_launch_round<E, 4>(chains, n_chains, B, P, par, stream);
     return hipErrorInvalidValue;
 }
 hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream)

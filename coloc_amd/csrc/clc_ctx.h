@@ -230,6 +230,10 @@ void k2nn_probe_bias(clc_ctx* ctx);                       // once per process an
 // all two-view a-contrario filters of a batch (pose_batch.hip); jobs[i] on ctxs[i]
 int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind /* 1 'E', 2 'F', 3 'H' */);
 int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what);
+// clc_sim3_acransac on N 3-D / 3-D pairs that lie in DEVICE memory (d_x_new | d_x_old, 3 N each; read in place, they must stand until the
+// call returns) with the box { min, max } of d_x_old from whoever gathered them (pose_batch.hip).  out: identity where there is no model
+int sim3_solve_dev(clc_ctx* ctx, const double* d_x_new, const double* d_x_old, int N, const double* box, int max_iteration, uint64_t seed,
+                   double precision, Sim3Out* out, uint8_t* h_mask, int* n_inliers, double* error_max, double* min_nfa, int* iterations);
 // clc_pair_filter_batch_dev under model 'E' (pose_batch.hip), which also says where each job's inlier list lies for the DEVICE:
 // inliers[i] = the list in job i's context's pinned block, in the filter's order, written by the round that completed the run before
 // its word (null: the job's solve did not start); it stands until the context's next solve
@@ -292,8 +296,9 @@ int resect_solve(clc_ctx* ctx, int N, const clc_camera_k3& cam, int max_iteratio
                  double* error_max);
 // clc_map_init_batch_dev (align == null: map_install) / clc_map_update_batch_dev (map_align_staged) behind their extern "C" names
 // (gr != null: the grown stage, clc_map_init_grow_batch_dev; ba != null: the grown stage bundle-adjusted, the _grow_ba_ entries)
+// (sim != null, align == null: the similarity step in place of the align step, clc_map_update_sim_batch_dev)
 int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr = nullptr,
-                   clc_map_ba* ba = nullptr);
+                   clc_map_ba* ba = nullptr, clc_map_align_sim* sim = nullptr);
 int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, clc_map_ba* ba);
 // ---- the bundle adjustment (map_ba.hip) ---------------------------------------------------------------------------------------------
 // ba's in fields checked (CLC_ERR_BAD_ARG on `who`) and its out fields cleared
@@ -313,6 +318,8 @@ int ba_drive(clc_ctx* ctx, BaProblem& pb, clc_map_ba& ba);
 int map_align_state(clc_ctx* ctx, const char* who);
 // (gr != null: a grown stage -- the rows gathered by the stage's camera list, the resected cameras' poses rescaled as well)
 int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align, clc_map_grow* gr = nullptr);
+// the same under the a-contrario similarity (clc_map_align_sim_dev's step): points and poses under sim.apply
+int map_align_sim_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align_sim& sim, clc_map_grow* gr = nullptr);
 
 // Every consumer stream behind what `producer` holds now (pose_batch.hip): ONE event (ev: its owner's, created on first use), no host
 // synchronisation; where an event call fails the host waits for the producer instead, and what that synchronisation reports is returned.

@@ -242,6 +242,7 @@ static constexpr size_t kAcrMaxLds = (size_t)kAcrMaxN * 8;
 struct AcrProblem {        // passed by value to every kernel of a solve
     int kind;              // 0: resection (P3P, [R|t] models of 12 doubles), 1: essential (five-point, {F, E} models of 18),
                            // 2: fundamental (seven-point), 3: homography (four-point): 9 doubles in a stride of 12, normalised coordinates
+                           // 4: 3-D similarity (three points, sim3_math.h): A = [sR | t], 12 doubles; a = X_new (3 n), b = X_old (3 n)
     int n, m, max_models, model_doubles;
     int batch_cap;         // most iterations a round evaluates (<= kAcrMaxBatch): the schedule, not the result, depends on it
     const double* a;       // X (3 n)  | x1 (2 n; kinds 2, 3: conditioned by the image size)
@@ -346,6 +347,16 @@ struct PairJobs {
     PairJobDev j[kMaxBatch];
     float scale[CLC_MAX_LEVELS];      // as TrackJobs::scale
 };
+// The common features of two maps as 3-D / 3-D pairs (clc_map_align_sim_dev): query = old map row q, match[q] = new map row.  Pair i
+// writes X_new | X_old into the solve's point blocks and (q, m) into the common lists; the bounding box of the X_old written and then the
+// count (GatherJob::n / h_n; all of them, also past cap) come out in the same launch, the box in front of the count.  a: unused but count.
+struct MapPairJobDev : GatherJob {
+    const double* old_X; const double* new_X; int n_new;               // in: the installed map's points, the new map's, its rows
+    double* xn; double* xo; int32_t* cq; int32_t* ct;                   // out, device (cap pairs)
+    double* h_box;                                                      // out, pinned: { min x, y, z, max x, y, z } of xo (6 doubles)
+};
+struct MapPairJobs { MapPairJobDev j[1]; };
+hipError_t launch_gather(MapPairJobs& jobs, hipStream_t stream);
 // ONE launch for n_jobs <= kMaxBatch cameras / pairs (blockIdx.y = job); scale[] is filled in here
 hipError_t launch_gather(TrackJobs& jobs, int n_jobs, hipStream_t stream);
 hipError_t launch_gather(PairJobs& jobs, int n_jobs, hipStream_t stream);
@@ -355,6 +366,22 @@ int gather_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, 
 int gather_inputs(clc_ctx* ctx, const clc_pair_job& job, PairJobDev& out, const char* who);
 // the seven-point / four-point models (kind 2: <= 3 per sample, kind 3: 1) of S samples of normalised correspondences: d_out S x M x 9, NaN = no model
 hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_x2, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
+
+// ---- the 3-D similarity (kind 4 of the a-contrario path; sim3_math.h) -------------------------------------------------------------------
+// What the refit launch behind the last round leaves (device and pinned): the similarity NEW -> OLD that is reported.
+struct Sim3Out {
+    double s, R[9], t[3], A[12];      // found: the refit's (refit = 1) or the minimal model's; else s = 1, R = I, t = 0, A = [I | 0]
+    int32_t found;          // sim3_accepted(valid, n_inliers)
+    int32_t refit;
+    int32_t n_inliers;      // 0 where not found
+    int32_t ready;          // written LAST (system-scope release)
+};
+// the minimal models of S samples of three correspondences each: d_out S x 12, NaN = degenerate sample or an index outside [0, N)
+hipError_t launch_sim3_minimal(const double* d_x, const double* d_y, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
+// ONE workgroup behind the round that completed a kind-4 run: acceptance rule, the inliers of d_mask in ascending index (d_list: N words
+// of scratch), Umeyama's refit by partial sums of kSim3Chunk inliers, the record to d_out and (nullable) the pinned h_out, `ready` last
+hipError_t launch_sim3_refit(const AcrResult* d_res, const uint8_t* d_mask, const double* d_x, const double* d_y, int N, int32_t* d_list,
+                             Sim3Out* d_out, Sim3Out* h_out, hipStream_t stream);
 
 } // namespace clc
 #endif

@@ -89,6 +89,26 @@ struct AlignPin {
     }
 };
 
+// The same two blocks of the similarity step (clc_map_align_sim_dev), for `cap` common features at most (min(n_old, the solve's capacity)):
+// d_align: [ match | cq | ct as above | X_new 3 cap | X_old 3 cap of the common features: the solve's points | the transform's counter 64 B ]
+struct AlignSimDev {
+    AlignDev lists; double *xn, *xo; unsigned int* done;
+    void carve(Carve& c, size_t n_old, size_t cap)
+    {
+        lists.carve(c, n_old); xn = c.take<double>(3 * cap); xo = c.take<double>(3 * cap + 8); done = c.take<unsigned int>(16, 64);
+    }
+};
+// h_align: [ the gather's record 128 B: count word (0xFF.. = not out yet) at 0, the box of X_old at 64 | the transform's record (64 B or
+//            its size) | X 3 n_new | match up64(n_old) + 64 ]
+struct AlignSimPin {
+    uint32_t* h_n; double* box; void* rec; double* X; int32_t* match;
+    void carve(Carve& c, size_t n_old, size_t n_new, size_t rec_bytes, size_t rec_align)
+    {
+        h_n = c.take<uint32_t>(16, 64); box = c.take<double>(8); rec = c.take_bytes(rec_bytes > 64 ? rec_bytes : 64, rec_align);
+        X = c.take<double>(3 * n_new); match = c.take<int32_t>(up64(n_old) + 64);
+    }
+};
+
 // ---- the inter-camera step from device memory (inter_dev.hip) ---------------------------------------------------------------------------
 // d_inter, for cap = up64(correspondences) and walk = up64(max(map rows, cap)) list entries:
 //   [ Xt 3 cap | Xw 3 cap | x2f 2 cap | K 16 | Rt 12 | the refinement's record | ratio walk | term walk | corr cap | first cap |
@@ -149,18 +169,20 @@ struct GatherView {
 // ---- the pose scratch d_pnp and its pinned staging h_pin: one layout per solve ----------------------------------------------------------
 // Every array starts on 8 bytes (the blocks were laid out in doubles); what a staging launch or ONE copy carries is a sub-layout.
 
-// The a-contrario solve (pose_batch.hip).  kind 0: resection (a = X, 3 per row), 1-3: E, F, H (a = x1); N correspondences; the records'
+// The a-contrario solve (pose_batch.hip).  kind 0: resection (a = X, 3 per row), 1-3: E, F, H (a = x1), 4: similarity (a = X_new, b = X_old,
+// 3 per row each; ref_bytes: the refit's record); N correspondences; the records'
 // sizes (ref_bytes 0: no refinement); md: doubles per model slot; batch: most iterations a round evaluates.
-struct AcrDims { int kind; size_t N, md, state_bytes, hyp_bytes, result_bytes, ref_bytes, batch; };
-// the inputs, staged by one launch: [ a | b 2 N | K1 16 | K2 16 | logc_n N + 1 floats | logc_k | state copy 0 | copy 1 = a run's start ]
+struct AcrDims { int kind; size_t N, md, state_bytes, hyp_bytes, result_bytes, ref_bytes, batch; bool points_elsewhere = false; };
+// (points_elsewhere: a | b are read where the gather left them -- the similarity from device points --, the blocks hold none)
+// the inputs, staged by one launch: [ a | b 2 N (kind 4: 3 N) | K1 16 | K2 16 | logc_n N + 1 floats | logc_k | state copy 0 | copy 1 = a run's start ]
 struct AcrIn {
     double *a, *b, *K1, *K2; float *logc_n, *logc_k; void* state; size_t bytes;
     void carve(Carve& c, const AcrDims& d)
     {
         c.take<double>(0);
         const size_t at = c.bytes();
-        a = c.take<double>((size_t)(d.kind == 0 ? 3 : 2) * d.N);
-        b = c.take<double>(2 * d.N); K1 = c.take<double>(16); K2 = c.take<double>(16);
+        a = c.take<double>(d.points_elsewhere ? 0 : (size_t)(d.kind == 0 || d.kind == 4 ? 3 : 2) * d.N);
+        b = c.take<double>(d.points_elsewhere ? 0 : (size_t)(d.kind == 4 ? 3 : 2) * d.N); K1 = c.take<double>(16); K2 = c.take<double>(16);
         logc_n = c.take<float>(d.N + 1, 8); logc_k = c.take<float>(d.N + 1, 8); state = c.take_bytes(2 * d.state_bytes, 8);
         c.take<double>(0);
         bytes = c.bytes() - at;
@@ -200,6 +222,15 @@ struct TwoViewMinDev {
     void carve(Carve& c, size_t N, size_t sample_ints, size_t out_doubles)
     {
         x1 = c.take<double>(2 * N); x2 = c.take<double>(2 * N); samples = c.take<int32_t>(sample_ints, 8); out = c.take<double>(out_doubles + 8, 8);
+    }
+};
+
+// clc_sim3_minimal: [ x 3 N | y 3 N | samples 3 S | models out 12 S | 8 doubles ]
+struct Sim3MinDev {
+    double *x, *y; int32_t* samples; double* out;
+    void carve(Carve& c, size_t N, size_t S)
+    {
+        x = c.take<double>(3 * N); y = c.take<double>(3 * N); samples = c.take<int32_t>(3 * S, 8); out = c.take<double>(12 * S + 8, 8);
     }
 };
 

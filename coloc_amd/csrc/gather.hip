@@ -7,6 +7,9 @@
 //           (acransac.hip: acr_stage_kernel), so the block and its pinned mirrors serve all three models.
 // Both are ONE ordered compaction (gather below, over wg_compact.h) that differs only in what an accepted query writes.  gather_rows_kernel:
 // rows of a descriptor block picked by an index list (the temporary map's descriptors of the inter-camera step, inter_pose.hip).
+//   map pairs  the common features of two maps as 3-D / 3-D pairs X_new | X_old with their common lists, the bounding box of the X_old
+//           and the count in one launch (map_update.hip: clc_map_align_sim_dev) -- a third emit, and the one gather that adds something
+//           (gather_finish) between its last correspondence and its count.
 //
 // One launch for a batch of jobs, blockIdx.y = job, ONE workgroup per job: nq <= maxkp is 5-10 k (the solve takes at most 16 384
 // correspondences), a few KB in and a few tens of KB out -- the launch is latency-bound, and one workgroup keeps the ordered compaction a
@@ -68,6 +71,48 @@ __device__ __forceinline__ void emit(const PairJobs& jobs, const PairJobDev& jb,
     if (jb.h_x2) { jb.h_x2[2 * i] = u2[0]; jb.h_x2[2 * i + 1] = u2[1]; }
 }
 
+// the common features of two maps: a match names a row of the new map; pair i = the landmark of new row m | the landmark of old row q
+__device__ __forceinline__ int32_t train_rows(const MapPairJobs&, const MapPairJobDev& jb) { return jb.n_new > 0 ? jb.n_new : 0; }
+__device__ __forceinline__ void emit(const MapPairJobs&, const MapPairJobDev& jb, const uint32_t q, const int32_t m, const size_t i)
+{
+    const double* xn = jb.new_X + 3 * (size_t)m;
+    const double* xo = jb.old_X + 3 * (size_t)q;
+    jb.xn[3 * i] = xn[0]; jb.xn[3 * i + 1] = xn[1]; jb.xn[3 * i + 2] = xn[2];
+    jb.xo[3 * i] = xo[0]; jb.xo[3 * i + 1] = xo[1]; jb.xo[3 * i + 2] = xo[2];
+    jb.cq[i] = (int32_t)q; jb.ct[i] = m;
+}
+
+// What a gather adds once its correspondences are written and before the count goes out: nothing for tracks and pairs; the map pairs'
+// bounding box of the old points written (minima and maxima: exact whatever the order), into the pinned record
+template <class Jobs, class Job> __device__ __forceinline__ void gather_finish(const Jobs&, const Job&, const uint32_t) {}
+__device__ __forceinline__ void gather_finish(const MapPairJobs&, const MapPairJobDev& jb, const uint32_t count)
+{
+    __shared__ double s_box[kGatherThreads / 64][6];
+    const uint32_t tid = threadIdx.x, n = count < (uint32_t)jb.cap ? count : (uint32_t)jb.cap;
+    const double inf = __longlong_as_double(0x7ff0000000000000LL);
+    double bx[6] = { inf, inf, inf, -inf, -inf, -inf };
+    __syncthreads();                                     // the pairs of this workgroup are read back (global memory, one workgroup)
+    for (uint32_t i = tid; i < n; i += kGatherThreads)
+        for (int c = 0; c < 3; ++c) {
+            const double v = jb.xo[3 * (size_t)i + c];
+            bx[c] = v < bx[c] ? v : bx[c];
+            bx[3 + c] = v > bx[3 + c] ? v : bx[3 + c];
+        }
+    for (int c = 0; c < 6; ++c)
+        for (int d = 32; d > 0; d >>= 1) {
+            const double o = __shfl_xor(bx[c], d);
+            bx[c] = c < 3 ? (o < bx[c] ? o : bx[c]) : (o > bx[c] ? o : bx[c]);
+        }
+    if ((tid & 63u) == 0) for (int c = 0; c < 6; ++c) s_box[tid >> 6][c] = bx[c];
+    __syncthreads();
+    if (tid == 0 && jb.h_box)
+        for (int c = 0; c < 6; ++c) {
+            double v = s_box[0][c];
+            for (int w = 1; w < kGatherThreads / 64; ++w) { const double o = s_box[w][c]; v = c < 3 ? (o < v ? o : v) : (o > v ? o : v); }
+            jb.h_box[c] = v;
+        }
+}
+
 // The gather as an ordered compaction (wg_compact.h, which states the two rules it keeps): correspondence i is the i-th accepted query in
 // ascending query order, and the count comes out last, behind a system-scope fence.
 template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
@@ -88,6 +133,7 @@ template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
         if (ok && i < (uint32_t)jb.cap) emit(jobs, jb, q, m, (size_t)i);
         base += total;
     }
+    gather_finish(jobs, jb, base);
     // the count comes out last: every wave's stores (device blocks and pinned mirrors) are complete and visible system-wide before the
     // word the host polls changes
     __threadfence_system();
@@ -101,6 +147,7 @@ template <class Jobs> __device__ __forceinline__ void gather(const Jobs& jobs)
 // two instantiations, two kernels: each carries only its own emit
 __global__ __launch_bounds__(kGatherThreads) void track_build_kernel(const TrackJobs jobs) { gather(jobs); }
 __global__ __launch_bounds__(kGatherThreads) void pair_build_kernel(const PairJobs jobs) { gather(jobs); }
+__global__ __launch_bounds__(kGatherThreads) void map_pair_build_kernel(const MapPairJobs jobs) { gather(jobs); }
 
 // rows idx[0 .. n) of a descriptor block, 16 bytes per thread
 __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restrict__ src, const int32_t* __restrict__ idx, uint4* __restrict__ dst, const uint32_t n)
@@ -145,6 +192,11 @@ int gather_side(clc_ctx* ctx, const char* who, const uint32_t* count, const clc_
 
 hipError_t launch_gather(TrackJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(track_build_kernel, jobs, n_jobs, stream); }
 hipError_t launch_gather(PairJobs& jobs, const int n_jobs, hipStream_t stream) { return launch(pair_build_kernel, jobs, n_jobs, stream); }
+hipError_t launch_gather(MapPairJobs& jobs, hipStream_t stream)
+{
+    hipLaunchKernelGGL(map_pair_build_kernel, dim3(1, 1), dim3(kGatherThreads), 0, stream, jobs);
+    return hipGetLastError();
+}
 
 hipError_t launch_gather_rows(const uint4* src, const int32_t* d_idx, uint4* dst, const uint32_t n, hipStream_t stream)
 {

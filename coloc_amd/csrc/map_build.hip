@@ -501,15 +501,22 @@ int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, clc_map_ba*
 
 // clc_map_init_batch_dev (align == null) and clc_map_update_batch_dev (map_update.hip): the filters, the selection, the seed poses and the
 // stage half are ONE path; what follows the stage half differs -- the install above, or the align step at the old map's scale.
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr, clc_map_ba* ba)
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr, clc_map_ba* ba,
+                   clc_map_align_sim* sim)
 {
     if (gr) grow_outputs_none(*gr);
+    if (sim) {
+        sim->n_old = 0; sim->n_common = 0; sim->n_inliers = 0; sim->iterations = 0; sim->refit = 0; sim->status = CLC_MAP_SIM_NO_MODEL;
+        sim->s = 1.0; sim->error_max = 0.0; sim->min_nfa = INFINITY;
+        for (int q = 0; q < 9; ++q) sim->R[q] = q % 4 == 0 ? 1.0 : 0.0;
+        for (int q = 0; q < 3; ++q) sim->t[q] = 0.0;
+    }
     if (align) { align->n_old = 0; align->n_common = 0; align->n_terms = 0; align->status = CLC_MAP_ALIGN_NO_SCALE; align->scale = 1.0; }
     if (n_pairs < 1 || n_pairs > kMaxPairs || !ctxs || !pair_jobs || !job) return CLC_ERR_BAD_ARG;
     const int rc0 = check_batch_contexts(ctxs, n_pairs, "map_init_batch: every pair needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
     clc_ctx* c0 = ctxs[0];
-    if (align) { const int rs = map_align_state(c0, "map_update_batch"); if (rs != CLC_OK) return job->status = rs; }
+    if (align || sim) { const int rs = map_align_state(c0, "map_update_batch"); if (rs != CLC_OK) return job->status = rs; }
     job->seed_pair = -1; job->n_tracks = 0; job->map_n = -1; job->status = CLC_OK;
     memset(job->entered, 0, sizeof job->entered);
     if (job->tracks.n_pairs != n_pairs || !job->tracks.pairs) return job->status = fail(c0, CLC_ERR_BAD_ARG, "map_init_batch: tracks.pairs must name the cameras of every pair job");
@@ -562,7 +569,7 @@ int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, c
     job->tracks.pairs = tp.data(); job->seed_pair = seed; job->after_stream = nullptr;
     MapStaged staged;
     int rc = gr ? map_stage_grown(c0, *job, *gr, staged, ba) : map_stage(c0, *job, staged);
-    if (rc == CLC_OK) rc = align ? map_align_staged(c0, *job, staged, *align, gr) : map_install(c0, *job, staged);
+    if (rc == CLC_OK) rc = sim ? map_align_sim_staged(c0, *job, staged, *sim, gr) : (align ? map_align_staged(c0, *job, staged, *align, gr) : map_install(c0, *job, staged));
     job->tracks.pairs = callers; job->after_stream = after;
     // (the union launch read the other contexts' blocks and pinned lists; it ran before the count the build waited for came out)
     return rc;

@@ -14,6 +14,7 @@
 #include "clc_ctx.h"
 #include "inter_math.h"
 #include "map_math.h"
+#include "sim3_math.h"
 #include "wg_compact.h"
 
 #include <chrono>
@@ -182,6 +183,158 @@ int map_align(clc_ctx* ctx, clc_map_align& job, const bool staged, const RowSour
     return CLC_OK;
 }
 
+// ---- the same step under an a-contrario similarity (clc_map_align_sim_dev) -------------------------------------------------------------
+// Launches on the context's stream: the gather of the rows and the sweep exactly as above; the ordered gather's map-pair form (gather.hip)
+// -> the common lists, X_new | X_old of every common feature, the box of those X_old and the count, for which the host waits; the solve
+// (pose_batch.hip: sim3_solve_dev, the rounds and the refit on the points where the gather left them); sim_transform_kernel over all
+// n_new points, the pinned mirrors and the record the host waits for last.  The install is the two swaps of map_align.
+struct SimRec { int32_t ready, pad_; };
+struct SimApply {
+    const double* new_X; double* out_X; double* h_X;       // (new_X may BE out_X: every thread reads its point before it writes it)
+    const int32_t* match; int32_t* h_match;                // the sweep's matches -> the cleaned mirror (nullable)
+    int32_t n_old, n_new, mode, found;
+    double s, A[12];
+    SimRec* rec;
+};
+constexpr int kSimThreads = 256;
+__global__ __launch_bounds__(kSimThreads) void sim_transform_kernel(const SimApply a, unsigned int* done /* device: workgroups that have finished */)
+{
+    const uint32_t i = blockIdx.x * kSimThreads + threadIdx.x;
+    if (i < (uint32_t)a.n_new) {
+        const double X[3] = { a.new_X[3 * (size_t)i], a.new_X[3 * (size_t)i + 1], a.new_X[3 * (size_t)i + 2] };
+        double o[3] = { X[0], X[1], X[2] };                    // no model: the bits as they are
+        if (a.found) {
+            if (a.mode == CLC_SIM_APPLY_FULL) sim3_apply_point(a.A, X, o);
+            else { o[0] = X[0] * a.s; o[1] = X[1] * a.s; o[2] = X[2] * a.s; }
+        }
+        for (int c = 0; c < 3; ++c) {
+            a.out_X[3 * (size_t)i + c] = o[c];
+            if (a.h_X) a.h_X[3 * (size_t)i + c] = o[c];
+        }
+    }
+    if (a.h_match && i < (uint32_t)a.n_old) {
+        int32_t t = a.match[i];
+        if (t < 0 || t >= a.n_new) t = -1;
+        a.h_match[i] = t;
+    }
+    // the record comes out last: the workgroup that finishes last (a counter in device memory, cleared in front of the launch) publishes it
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int before = atomicAdd(done, 1u);
+        if (before + 1u == gridDim.x) {
+            __threadfence_system();
+            __hip_atomic_store(&a.rec->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+void sim_outputs_none(clc_map_align_sim& job)
+{
+    job.n_old = 0; job.n_common = 0; job.n_inliers = 0; job.iterations = 0; job.refit = 0; job.status = CLC_MAP_SIM_NO_MODEL;
+    job.s = 1.0; job.error_max = 0.0; job.min_nfa = INFINITY;
+    for (int q = 0; q < 9; ++q) job.R[q] = q % 4 == 0 ? 1.0 : 0.0;
+    for (int q = 0; q < 3; ++q) job.t[q] = 0.0;
+}
+
+int map_align_sim(clc_ctx* ctx, clc_map_align_sim& job, const bool staged, const RowSources* srcs = nullptr, const int32_t* d_cam = nullptr)
+{
+    sim_outputs_none(job);
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "map_align_sim: context created without matcher options");
+    if (job.n_new < 0 || (job.n_new > 0 && (!job.d_desc || !job.d_X))) return fail(ctx, CLC_ERR_BAD_ARG, "map_align_sim: negative count / null block");
+    if (((uintptr_t)job.d_desc & 15u) || ((uintptr_t)job.d_rows & 3u) || ((uintptr_t)job.d_X & 7u)) return fail(ctx, CLC_ERR_BAD_ARG, "map_align_sim: misaligned device pointer");
+    if (job.apply != CLC_SIM_APPLY_SCALE && job.apply != CLC_SIM_APPLY_FULL) return fail(ctx, CLC_ERR_BAD_ARG, "map_align_sim: apply must be CLC_SIM_APPLY_SCALE or CLC_SIM_APPLY_FULL");
+    if (job.max_iteration < 0) return fail(ctx, CLC_ERR_BAD_ARG, "map_align_sim: negative max_iteration");
+    int rc = map_align_state(ctx, "map_align_sim");
+    if (rc != CLC_OK) return rc;
+    if ((uint32_t)job.n_new > ctx->mopts.maxkp) return fail(ctx, CLC_ERR_CAPACITY, "map_align_sim: more map rows than MatcherOptions.maxkp (the previous map stays)");
+    const int n_old = ctx->map_n, n_new = job.n_new;
+    job.n_old = n_old;
+    if (n_new == 0) {
+        if (job.match) for (int q = 0; q < n_old; ++q) job.match[q] = -1;
+        if (job.install) { ctx->map_n = 0; ctx->map_X_n = -1; }
+        return CLC_OK;
+    }
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t cap = (size_t)(n_old < kAcrMaxN ? n_old : kAcrMaxN);
+    AlignSimDev dev; AlignSimPin pin; MapPointsDev next;
+    rc = grow(ctx, ctx->d_m_next, ctx->d_m.bytes, 0, 1, true, "allocating the next map's descriptor rows");
+    if (rc == CLC_OK && !staged) rc = carve_block(ctx, ctx->d_map_X_next, 1, 4, true, "growing the next map's points", [&](Carve& c) { next.carve(c, (size_t)n_new); });
+    if (rc == CLC_OK) rc = carve_block(ctx, ctx->d_align, 1, 4, true, "growing the map alignment block", [&](Carve& c) { dev.carve(c, (size_t)n_old, cap); });
+    if (rc == CLC_OK)
+        rc = carve_block(ctx, ctx->h_align, 1, 4, true, "growing the pinned map alignment block",
+                         [&](Carve& c) { pin.carve(c, (size_t)n_old, (size_t)n_new, sizeof(SimRec), alignof(SimRec)); });
+    if (rc != CLC_OK) return rc;
+    unsigned int* d_done = dev.done;
+    int32_t* d_match = dev.lists.match;
+    SimRec* rec = (SimRec*)pin.rec;
+    __atomic_store_n(pin.h_n, 0xFFFFFFFFu, __ATOMIC_RELAXED);
+    __atomic_store_n(&rec->ready, 0, __ATOMIC_RELAXED);
+    hipStream_t prod = (hipStream_t)job.after_stream;
+    if (prod && prod != st) CLC_HIP(ctx, order_behind(ctx->ev_track, prod, &st, 1));
+    CLC_HIP(ctx, hipMemsetAsync(d_done, 0, sizeof(unsigned int), st));
+    // the new rows into the NEXT map's buffer and the sweep: map_align's, launch for launch
+    if (srcs) {
+        CLC_HIP(ctx, launch_gather_rows_multi(*srcs, d_cam, job.d_rows, ctx->d_m_next.as<uint4>(), (uint32_t)n_new, st));
+        if (n_old > 0) {
+            rc = map_sweep_rows_enqueue(ctx, n_new, ctx->d_m.ptr, n_old, ctx->d_m_next.as<uint4>(), d_match, job.threshold, st);
+            if (rc != CLC_OK) { (void)hipStreamSynchronize(st); return rc; }
+        }
+    } else if (n_old > 0) {
+        rc = map_sweep_enqueue(ctx, job.d_desc, job.d_rows, n_new, ctx->d_m.ptr, n_old, ctx->d_m_next.as<uint4>(), d_match, job.threshold, st);
+        if (rc != CLC_OK) { (void)hipStreamSynchronize(st); return rc; }
+    } else if (job.install) {
+        CLC_HIP(ctx, launch_gather_rows((const uint4*)job.d_desc, job.d_rows, ctx->d_m_next.as<uint4>(), (uint32_t)n_new, st));
+    }
+    // the common features as 3-D / 3-D pairs, their box and their count
+    MapPairJobs pj{};
+    MapPairJobDev& g = pj.j[0];
+    g.match = d_match; g.nq = n_old; g.cap = (int)cap; g.n = nullptr; g.h_n = pin.h_n;
+    g.old_X = ctx->d_map_X.as<double>(); g.new_X = job.d_X; g.n_new = n_new;
+    g.xn = dev.xn; g.xo = dev.xo; g.cq = dev.lists.cq; g.ct = dev.lists.ct; g.h_box = pin.box;
+    hipError_t e = launch_gather(pj, st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(ctx, CLC_ERR_HIP, "map_align_sim: the gather launch", e); }
+    rc = wait_pinned(ctx, pin.h_n, 0xFFFFFFFFu, st, std::chrono::steady_clock::now(), 5, "map_align_sim: the gather launch left no count");
+    if (rc != CLC_OK) return rc;
+    const uint32_t n_common = __atomic_load_n(pin.h_n, __ATOMIC_ACQUIRE);
+    job.n_common = (int)n_common;
+    if (n_common > (uint32_t)kAcrMaxN) return fail(ctx, CLC_ERR_CAPACITY, "map_align_sim: more than 16384 common features (the previous map stays)");
+    // the solve on the pairs where they lie
+    Sim3Out o{};
+    int n_inl = 0, its = 0;
+    double emax = 0.0, nfa = INFINITY;
+    double box[6];
+    memcpy(box, pin.box, sizeof box);
+    rc = sim3_solve_dev(ctx, dev.xn, dev.xo, (int)n_common, box, job.max_iteration > 0 ? job.max_iteration : 256, job.seed, job.precision, &o,
+                        job.inlier, &n_inl, &emax, &nfa, &its);
+    if (rc != CLC_OK) return rc;
+    // every point of the new map
+    SimApply a{};
+    a.new_X = job.d_X; a.out_X = ctx->d_map_X_next.as<double>(); a.h_X = job.X ? pin.X : nullptr;
+    a.match = d_match; a.h_match = job.match && n_old > 0 ? pin.match : nullptr;
+    a.n_old = n_old; a.n_new = n_new; a.mode = job.apply; a.found = o.found; a.s = o.s;
+    memcpy(a.A, o.A, sizeof a.A);
+    a.rec = rec;
+    const int most = n_new > n_old ? n_new : n_old;
+    hipLaunchKernelGGL(sim_transform_kernel, dim3((unsigned)((most + kSimThreads - 1) / kSimThreads)), dim3(kSimThreads), 0, st, a, d_done);
+    e = hipGetLastError();
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(ctx, CLC_ERR_HIP, "map_align_sim: the transform launch", e); }
+    rc = wait_pinned(ctx, &rec->ready, 0, st, std::chrono::steady_clock::now(), 5, "map_align_sim: the transform launch left no record");
+    if (rc != CLC_OK) return rc;
+    job.n_inliers = n_inl; job.iterations = its; job.refit = o.refit; job.status = o.found ? CLC_MAP_SIM_OK : CLC_MAP_SIM_NO_MODEL;
+    job.s = o.s; memcpy(job.R, o.R, sizeof job.R); memcpy(job.t, o.t, sizeof job.t);
+    job.error_max = emax; job.min_nfa = nfa;
+    if (a.h_match) memcpy(job.match, pin.match, sizeof(int32_t) * (size_t)n_old);
+    if (a.h_X) memcpy(job.X, pin.X, sizeof(double) * 3 * (size_t)n_new);
+    if (job.install) {
+        std::swap(ctx->d_m, ctx->d_m_next);
+        std::swap(ctx->d_map_X, ctx->d_map_X_next);
+        ctx->map_n = n_new; ctx->map_X_n = n_new;
+    }
+    return CLC_OK;
+}
+
 } // namespace
 
 int map_align_state(clc_ctx* ctx, const char* who)
@@ -211,6 +364,31 @@ int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, cl
     return CLC_OK;
 }
 
+// the similarity step on a staged map, installing it, with the job's host points, seed poses and (gr) resected poses under the apply rule
+int map_align_sim_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align_sim& sim, clc_map_grow* gr)
+{
+    RowSources srcs{};
+    for (int c = 0; c < job.tracks.n_cams && c < kMaxBatch; ++c) srcs.src[c] = (const uint4*)job.cams[c].d_desc;
+    clc_map_align_sim a{};
+    a.d_desc = job.cams[staged.cam_i].d_desc; a.d_rows = staged.d_row; a.d_X = ctx->d_map_X_next.as<double>(); a.n_new = staged.n;
+    a.threshold = sim.threshold; a.install = 1; a.after_stream = nullptr;
+    a.apply = sim.apply; a.max_iteration = sim.max_iteration; a.seed = sim.seed; a.precision = sim.precision;
+    a.match = sim.match; a.X = job.X; a.inlier = sim.inlier;
+    const int rc = staged.d_cam ? map_align_sim(ctx, a, true, &srcs, staged.d_cam) : map_align_sim(ctx, a, true);
+    sim.n_old = a.n_old; sim.n_common = a.n_common; sim.n_inliers = a.n_inliers; sim.iterations = a.iterations; sim.refit = a.refit;
+    sim.status = a.status; sim.s = a.s; sim.error_max = a.error_max; sim.min_nfa = a.min_nfa;
+    memcpy(sim.R, a.R, sizeof sim.R); memcpy(sim.t, a.t, sizeof sim.t);
+    if (rc != CLC_OK) return job.status = rc;
+    if (a.status != CLC_MAP_SIM_OK) return CLC_OK;               // no model: the poses as they are
+    const auto pose = [&](double* Rt) { if (a.apply == CLC_SIM_APPLY_FULL) sim3_apply_pose(a.s, a.R, a.t, Rt); else rescale_pose(Rt, a.s); };
+    pose(job.Rt_seed_a);
+    pose(job.Rt_seed_b);
+    if (gr)
+        for (int c = 0; c < job.tracks.n_cams; ++c)
+            if (gr->resected[c] || c == staged.cam_i || c == staged.cam_j) pose(gr->Rt[c]);
+    return CLC_OK;
+}
+
 } // namespace clc
 
 using namespace clc;
@@ -221,6 +399,20 @@ int clc_map_align_dev(clc_ctx* ctx, clc_map_align* job)
 {
     if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "map_align: null context / job");
     return map_align(ctx, *job, false);
+}
+
+int clc_map_align_sim_dev(clc_ctx* ctx, clc_map_align_sim* job)
+{
+    if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "map_align_sim: null context / job");
+    return map_align_sim(ctx, *job, false);
+}
+
+int clc_map_update_sim_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align_sim* sim,
+                                 clc_map_grow* grow, clc_map_ba* ba)
+{
+    if (!sim || (ba && !grow)) return CLC_ERR_BAD_ARG;
+    if (ba && ba_check(nullptr, ba, "map_update_sim_batch") != CLC_OK) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr, grow, ba, sim);
 }
 
 int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align)

@@ -5,6 +5,7 @@
 #include "clc_ctx.h"
 #include "clc_acr.h"
 #include "twoview_min.h"
+#include "sim3_math.h"
 
 #include <algorithm>
 #include <chrono>
@@ -52,7 +53,10 @@ void acr_tables(int n, int m, float* logc_n, float* logc_k, std::vector<float>& 
 // kinds 2 / 3 (round 6: RobustMatcher's 'F' / 'H' models, RobustMatcher.hpp:128-151, :188-239): a = x1, b = x2 in pixels, both images
 // img_w x img_h -- the points are conditioned by the image size on their way into the pinned block (ACKernelAdaptor), the rounds are
 // the resection's one-launch rounds with the seven-point / four-point solve in place of P3P, the model is brought back to pixels in finish().
-// h_model: 12 doubles [R|t] (kind 0), {E (9), F (9)} (kind 1), F or H (9, pixels; kinds 2 / 3).
+// kind 4 (the 3-D similarity NEW -> OLD of sim3_math.h, the project's own statement): a = X_new, b = X_old (3 N each), no camera, no image;
+// residuals in old-map units, alpha = the unit ball over the bounding box of b (box: from the caller where the points are on the device),
+// exponent 1.5; behind the rounds ONE launch applies the acceptance rule and refits (launch_sim3_refit), its record is `sim`.
+// h_model: 12 doubles [R|t] (kind 0), {E (9), F (9)} (kind 1), F or H (9, pixels; kinds 2 / 3), [sR|t] (kind 4).
 //
 // One a-contrario solve as a small state machine (round 4): begin() validates and prepares the inputs and the problem, poll() looks at the
 // pinned progress word ONCE and reports whether the run needs another round -- or moves on to the refinement, whose record it then polls
@@ -70,6 +74,9 @@ struct AcrRun {
     double* h_model = nullptr; uint8_t* h_mask = nullptr; int32_t* h_inliers = nullptr;
     int *n_inliers = nullptr, *iterations = nullptr, *rounds = nullptr;
     double *error_max = nullptr, *min_nfa = nullptr, *h_cov = nullptr, *rmse = nullptr;
+    Sim3Out* sim = nullptr;           // kind 4: the reported similarity (out); box: { min, max } of b where the points are the device's
+    const double* box = nullptr;      // (dev_a / dev_b: read in place by the rounds and the refit, not staged)
+    int* valid = nullptr;
     // state
     enum Phase { IDLE, ROUNDS, REFINE, DONE } phase = IDLE;
     int status = CLC_OK;
@@ -88,6 +95,8 @@ struct AcrRun {
     AcrResult* h_res = nullptr;
     int32_t* p_inl = nullptr;
     RefineOut* p_ref = nullptr;
+    Sim3Out* p_sim = nullptr; Sim3Out* d_sim = nullptr;
+    int32_t* ready = nullptr;         // what the REFINE phase polls: the refinement's / the refit's flag
     double *d_a = nullptr, *d_b = nullptr, *d_K1 = nullptr, *d_K2 = nullptr, *d_models = nullptr, *d_ref = nullptr;
     AcrState* d_state = nullptr; AcrHyp* d_hyp = nullptr;
     uint32_t *d_sorted = nullptr, *d_best = nullptr, *d_index = nullptr;
@@ -102,12 +111,12 @@ struct AcrRun {
     // evaluates.  Returns a status; phase == DONE afterwards means there is nothing to wait for.
     int begin(const int cap)
     {
-        static const int k_m[4] = { 3, 5, 7, 4 }, k_M[4] = { 4, 10, 3, 1 }, k_md[4] = { 12, 18, 12, 12 };
-        if (kind < 0 || kind > 3) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: unknown model"));
+        static const int k_m[5] = { 3, 5, 7, 4, 3 }, k_M[5] = { 4, 10, 3, 1, 1 }, k_md[5] = { 12, 18, 12, 12, 12 };
+        if (kind < 0 || kind > 4) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: unknown model"));
         m = k_m[kind]; M = k_M[kind]; md = k_md[kind];
-        const int ad = kind == 0 ? 3 : 2;
+        const int ad = kind == 0 || kind == 4 ? 3 : 2;
         if (!ctx || N < 0 || max_iteration < 0 || (kind <= 1 && !h_K1) || (kind == 1 && !h_K2) || (N > 0 && !(dev_a && dev_b) && (!h_a || !h_b)) ||
-            ((dev_a || dev_b) && (!dev_a || !dev_b)))
+            ((dev_a || dev_b) && (!dev_a || !dev_b)) || (kind == 4 && dev_a && !box))
             return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: bad argument"));
         if (kind == 0 && !pose_K_ok(h_K1)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }"));
         if (n_inliers) *n_inliers = 0;
@@ -115,11 +124,16 @@ struct AcrRun {
         if (min_nfa) *min_nfa = INFINITY;
         if (iterations) *iterations = 0;
         if (rounds) *rounds = 0;
+        if (valid) *valid = -1;
+        if (sim) {
+            *sim = Sim3Out{};
+            sim->s = 1.0; sim->R[0] = sim->R[4] = sim->R[8] = 1.0; sim->A[0] = sim->A[5] = sim->A[10] = 1.0;
+        }
         if (h_mask && N > 0) memset(h_mask, 0, (size_t)N);
         if (N <= m || max_iteration == 0) return stop(CLC_OK);                 // ACRANSAC: nData <= sizeSample -> (0, 0), no model
         if (N > kAcrMaxN) return stop(fail(ctx, CLC_ERR_CAPACITY, "acransac: more than 16384 correspondences per solve"));
         if (max_iteration > 500000) return stop(fail(ctx, CLC_ERR_CAPACITY, "acransac: more than 500000 iterations"));
-        if (kind >= 1 && (img_w <= 0 || img_h <= 0)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: image size needed for the two-view models"));
+        if (kind >= 1 && kind <= 3 && (img_w <= 0 || img_h <= 0)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: image size needed for the two-view models"));
         phase = DONE; status = CLC_ERR_HIP;                                     // (what an early CLC_HIP return leaves behind)
         batch_cap = cap;
         const int rc0 = begin_body(ad);
@@ -134,17 +148,31 @@ struct AcrRun {
         // the device workspace and the pinned block (AcrDev, AcrPin: the inputs, staged by one launch, lie alike in both).  A round's
         // launches read what the round before them wrote: two copies of state, models, slots and sorted lists, indexed by launch parity
         // (acransac.hip: acr_round_kernel, acr_solve5_kernel)
-        const AcrDims dims{ kind, (size_t)N, (size_t)md, sizeof(AcrState), sizeof(AcrHyp), sizeof(AcrResult), refine ? sizeof(RefineOut) : 0, (size_t)kAcrMaxBatch };
+        double V = 0.0;
+        if (kind == 4) {
+            // the box of the old points: a flat or unbounded one admits no alpha, hence no model
+            double bx[6];
+            if (dev_a) memcpy(bx, box, sizeof bx);
+            for (int q = 0; q < 3 && !dev_a; ++q) {
+                bx[q] = bx[3 + q] = h_b[q];
+                for (int i = 1; i < N; ++i) { const double v = h_b[3 * i + q]; bx[q] = v < bx[q] ? v : bx[q]; bx[3 + q] = v > bx[3 + q] ? v : bx[3 + q]; }
+            }
+            V = sim3_box_volume(bx);
+            if (!sim3_volume_ok(V)) return stop(CLC_OK);
+        }
+        const AcrDims dims{ kind, (size_t)N, (size_t)md, sizeof(AcrState), sizeof(AcrHyp), sizeof(AcrResult),
+                            kind == 4 ? sizeof(Sim3Out) : (refine ? sizeof(RefineOut) : 0), (size_t)kAcrMaxBatch, kind == 4 && dev_a != nullptr };
         AcrDev dv; AcrPin pin;
         int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, dims); });
         if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, dims); });
         if (rc != CLC_OK) return rc;
         d_a = dv.in.a; d_b = dv.in.b; d_K1 = dv.in.K1; d_K2 = dv.in.K2;
+        if (dims.points_elsewhere) { d_a = const_cast<double*>(dev_a); d_b = const_cast<double*>(dev_b); }
         float* d_cn = dv.in.logc_n; float* d_ck = dv.in.logc_k;
         d_state = (AcrState*)dv.in.state; d_models = dv.models; d_hyp = (AcrHyp*)dv.hyp; d_sorted = dv.sorted; d_best = dv.best; d_index = dv.index;
         d_res = (AcrResult*)dv.result; d_mask = dv.mask; d_ref = dv.ref;
         double* hp = pin.in.a;
-        if (kind >= 2) {
+        if (kind == 2 || kind == 3) {
             // ACKernelAdaptor: NormalizePoints(x, &x_, &N_, w, h) for both point sets (x_n = d x + t, oracle/clc_oracle_twoview.c orc_tv_normalize)
             // (points from device memory: the staging launch applies the same two operations, launch_acr_stage's cond)
             norm_t = tv::normalizer(img_w, img_h);
@@ -156,7 +184,7 @@ struct AcrRun {
             }
         } else if (!dev_a) {
             memcpy(pin.in.a, h_a, sizeof(double) * ad * N);
-            memcpy(pin.in.b, h_b, sizeof(double) * 2 * N);
+            memcpy(pin.in.b, h_b, sizeof(double) * (kind == 4 ? 3 : 2) * N);
         }
         memset(pin.in.K1, 0, sizeof(double) * 32);                     // (K1 | K2)
         if (h_K1) memcpy(pin.in.K1, h_K1, sizeof(double) * 9);
@@ -176,6 +204,7 @@ struct AcrRun {
         h_init->grow = batch_cap < 32 ? batch_cap : 32;
         h_init->cur_batch = h_init->n_iter < h_init->grow ? h_init->n_iter : h_init->grow;
         h_word = pin.word; h_res = (AcrResult*)pin.result; p_inl = pin.inliers; p_ref = pin.ref;
+        p_sim = (Sim3Out*)pin.ref; d_sim = (Sim3Out*)dv.ref;
         __atomic_store_n(h_word, 0ull, __ATOMIC_RELAXED);
 
         pb = AcrProblem{};
@@ -193,6 +222,11 @@ struct AcrRun {
             const double D = sqrt((double)img_w * (double)img_w + (double)img_h * (double)img_h), A = (double)img_w * (double)img_h;
             pb.logalpha0 = clc_acr_log10(2.0 * D / A * .5);
             pb.mult = 0.5;
+            pb.norm = 1.0;
+        } else if (kind == 4) {
+            // a squared distance in old-map units against the box of the old points: log10(((4 / 3) pi) / V), error^(3/2)
+            pb.logalpha0 = clc_acr_log10(sim3_alpha0(V));
+            pb.mult = 1.5;
             pb.norm = 1.0;
         } else {
             // ACKernelAdaptor on conditioned points: 'F' point-to-line, log10(2 D / A / N2(0,0)), error^(1/2); 'H' point-to-point,
@@ -267,6 +301,19 @@ struct AcrRun {
             // The result record, mask and inlier list were written by the round that completed the run BEFORE its word (system-scope
             // release / acquire): no finish launch, and without refinement no stream synchronisation either -- the round enqueued ahead is
             // still in the stream, evaluates nothing and touches no host memory; anything enqueued later on this stream is ordered behind it.
+            if (kind == 4) {
+                // the acceptance rule and the refit: one single-workgroup launch on the rounds' stream, behind the round enqueued ahead
+                // (it reads the result record and the mask of the completing round, and uses the index set as its list); its pinned
+                // record is polled like the refinement's
+                __atomic_store_n(&p_sim->ready, 0, __ATOMIC_RELAXED);
+                const hipError_t e = launch_sim3_refit(d_res, d_mask, d_a, d_b, N, (int32_t*)d_index, d_sim, p_sim, st);
+                if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "launch_sim3_refit", e));
+                ready = &p_sim->ready;
+                spins = 0;
+                wait_start = std::chrono::steady_clock::now();
+                phase = REFINE;
+                return CLC_OK;
+            }
             if (!refine) { phase = DONE; return CLC_OK; }
             // On the run's own context's stream: behind the launch that completed the run when the rounds ran there (nothing is queued
             // behind that launch any more: the word of the last round comes out of the last launch); a shared group's stream still carries
@@ -278,17 +325,18 @@ struct AcrRun {
             const hipError_t e = launch_pnp_refine((const double*)d_res /* AcrResult.model = [R|t] */, d_a, d_b, d_mask, N, d_K1, refine_huber, 50,
                                                    d_ref, ctx->stream, &ctx->prof, &d_res->valid, p_ref);
             if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "launch_pnp_refine", e));
+            ready = &p_ref->ready;
             spins = 0;
             wait_start = std::chrono::steady_clock::now();
             phase = REFINE;
             return CLC_OK;
         }
         if (phase == REFINE) {
-            if (__atomic_load_n(&p_ref->ready, __ATOMIC_ACQUIRE) == 0) {
+            if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == 0) {
                 if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - wait_start > std::chrono::milliseconds(5)) {
-                    const hipError_t e = hipStreamSynchronize(ctx->stream);
+                    const hipError_t e = hipStreamSynchronize(kind == 4 ? st : ctx->stream);
                     if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "hipStreamSynchronize(refine stream)", e));
-                    if (__atomic_load_n(&p_ref->ready, __ATOMIC_ACQUIRE) == 0) return drained(fail(ctx, CLC_ERR_HIP, "acransac: refinement did not complete"));
+                    if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == 0) return drained(fail(ctx, CLC_ERR_HIP, "acransac: refinement did not complete"));
                 } else return CLC_OK;
             }
             phase = DONE;
@@ -300,8 +348,15 @@ struct AcrRun {
     void finish()
     {
         if (status != CLC_OK || !h_res) return;
-        const AcrResult r = *h_res;
-        if (h_model) {
+        AcrResult r = *h_res;
+        if (kind == 4) {
+            // what the refit launch decided: not accepted = no model, no inliers (min_nfa and the iterations stay the run's)
+            const Sim3Out o = *p_sim;
+            if (!o.found) { r.n_inliers = 0; r.error_max = 0.0; r.valid = -1; }
+            if (sim) { *sim = o; sim->ready = 0; }
+            if (h_model) memcpy(h_model, o.A, sizeof(double) * 12);
+            if (valid) *valid = r.valid;
+        } else if (h_model) {
             if (kind == 0) memcpy(h_model, r.model, sizeof(double) * 12);
             else if (kind >= 2) {
                 // Unnormalize(&model): F = N2^T Fn N1, H = N2^-1 Hn N1 (no model: zeros stay zeros)
@@ -368,7 +423,8 @@ struct AcrGroup {
             for (int i = 0; i < n; ++i) {
                 const AcrRun* r = live[k + i];
                 src[i] = r->stage_src; dst[i] = r->stage_dst; cnt[i] = r->stage_n;
-                da[i] = r->dev_a; db[i] = r->dev_b; nc[i] = r->N;
+                const bool in_place = r->kind == 4;                  // (the similarity's device points are not staged)
+                da[i] = in_place ? nullptr : r->dev_a; db[i] = in_place ? nullptr : r->dev_b; nc[i] = r->N;
                 aw[i] = r->kind == 0 ? 3 : 2;
                 const bool cnd = r->kind >= 2 && r->dev_a;
                 cond[i][0] = cnd ? r->norm_t.d : 0.0; cond[i][1] = cnd ? r->norm_t.tx : 0.0; cond[i][2] = cnd ? r->norm_t.ty : 0.0;
@@ -631,6 +687,45 @@ int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const doub
     return CLC_OK;
 }
 
+// The 3-D similarity NEW -> OLD between two landmark sets (sim3_math.h; the project's own statement, include/coloc_hip.h)
+int clc_sim3_acransac(clc_ctx* ctx, const double* h_x_new, const double* h_x_old, int N, int max_iteration, uint64_t seed, double precision,
+                      double* s, double* h_R, double* h_t, double* h_A, uint8_t* h_inlier_mask, int32_t* h_inliers, int* n_inliers,
+                      double* error_max, double* min_nfa, int* iterations, int* valid, int* refit)
+{
+    Sim3Out o{};
+    AcrRun run;
+    run.ctx = ctx; run.kind = 4; run.h_a = h_x_new; run.h_b = h_x_old; run.N = N;
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
+    run.sim = &o; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
+    run.min_nfa = min_nfa; run.iterations = iterations; run.valid = valid;
+    const int rc = solve_one(run);
+    if (!run.sim || o.s == 0.0) { o = Sim3Out{}; o.s = 1.0; o.R[0] = o.R[4] = o.R[8] = 1.0; o.A[0] = o.A[5] = o.A[10] = 1.0; }   // (refused before begin())
+    if (s) *s = o.s;
+    if (h_R) memcpy(h_R, o.R, sizeof o.R);
+    if (h_t) memcpy(h_t, o.t, sizeof o.t);
+    if (h_A) memcpy(h_A, o.A, sizeof o.A);
+    if (refit) *refit = o.refit;
+    return rc;
+}
+
+int clc_sim3_minimal(clc_ctx* ctx, const double* h_x_new, const double* h_x_old, int N, const int32_t* h_samples, int S, double* h_models)
+{
+    if (!ctx || N <= 0 || S < 0 || !h_x_new || !h_x_old || (S > 0 && (!h_samples || !h_models)))
+        return fail(ctx, CLC_ERR_BAD_ARG, "sim3_minimal: bad argument");
+    if (S == 0) return CLC_OK;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    Sim3MinDev dv;
+    const int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, (size_t)N, (size_t)S); });
+    if (rc != CLC_OK) return rc;
+    CLC_HIP(ctx, hipMemcpyAsync(dv.x, h_x_new, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, hipMemcpyAsync(dv.y, h_x_old, sizeof(double) * 3 * (size_t)N, hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, hipMemcpyAsync(dv.samples, h_samples, sizeof(int32_t) * 3 * (size_t)S, hipMemcpyHostToDevice, ctx->stream));
+    CLC_HIP(ctx, launch_sim3_minimal(dv.x, dv.y, N, dv.samples, S, dv.out, ctx->stream));
+    CLC_HIP(ctx, hipMemcpyAsync(h_models, dv.out, sizeof(double) * 12 * (size_t)S, hipMemcpyDeviceToHost, ctx->stream));
+    CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CLC_OK;
+}
+
 } // extern "C"
 
 namespace {
@@ -673,6 +768,16 @@ int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what)
 
 // kind 1: E -> job.E, F -> job.F; kinds 2 / 3: the model matrix -> job.E (RelativePose_Info::essential_matrix receives it, whatever the
 // model: RobustMatcher.hpp:141, :207), and job.F = F for kind 2, zeros for kind 3
+int sim3_solve_dev(clc_ctx* ctx, const double* d_x_new, const double* d_x_old, int N, const double* box, int max_iteration, uint64_t seed,
+                   double precision, Sim3Out* out, uint8_t* h_mask, int* n_inliers, double* error_max, double* min_nfa, int* iterations)
+{
+    AcrRun run;
+    run.ctx = ctx; run.kind = 4; run.dev_a = d_x_new; run.dev_b = d_x_old; run.box = box; run.N = N;
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
+    run.sim = out; run.h_mask = h_mask; run.n_inliers = n_inliers; run.error_max = error_max; run.min_nfa = min_nfa; run.iterations = iterations;
+    return solve_one(run);
+}
+
 int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind)
 {
     std::vector<AcrRun> runs((size_t)n_jobs);

@@ -19,6 +19,10 @@
 //        as the reference's live code does: every putative map-to-map match is kept, in order (:346, :359-360); the fundamental
 //        matrix predicted from the known displacement, F = Kinv^T rotDiff^T K^T [K rotDiff poseDiff / |poseDiff|]_x (:317-327), is
 //        only used to log f1^T F f2 per match to "guidedmatches2.txt" (:334-349).  Host arithmetic, no GPU work.
+//   bool matchMapsSimilarity(landmarksOld, landmarksNew, commonFeatures, scale, R, t)                  OUR OWN STATEMENT, an addition
+//        what matchMaps set out to do -- filter the map-to-map matches geometrically --, by the a-contrario 3-D similarity NEW -> OLD
+//        over the landmarks of the common features (clc_sim3_acransac): only the inliers stay in commonFeatures,
+//        X_old ~ scale R X_new + t comes back.  OpenMVG parity unpinned; matchMaps itself is as it was.
 // x1 / x2 are 2 x N UNDISTORTED pixel coordinates (computeRelativePose undistorts with get_ud_pixel, :391-397).
 // Status convention as the reference: EXIT_SUCCESS / EXIT_FAILURE through bool, FALSE MEANS SUCCESS.
 //   bool filterFundamental(...)  :128-151   ('F': seven points, distance to the epipolar line)     -> clc_two_view_acransac
@@ -329,6 +333,31 @@ inline int decompose_homography_mat(const openMVG::Mat3& H, const openMVG::Mat3&
     motions->push_back(HomographyMotion{ Rb, tb, nb });
     motions->push_back(HomographyMotion{ Rb, neg(tb), neg(nb) });
     return 4;
+}
+
+// matchMapsSimilarity's host-side conversions.  The common features (i_ = row of the OLD map, j_ = row of the NEW one, as
+// matchMapFeatures(old, new) emits them) and the two maps' landmarks by row -> the flat N x 3 blocks clc_sim3_acransac takes; a match that
+// names no landmark of either set is left out.  kept[k] = the common feature behind pair k.
+inline void sim3_pairs(const std::vector<openMVG::Vec3>& landmarksOld, const std::vector<openMVG::Vec3>& landmarksNew,
+                       const std::vector<openMVG::matching::IndMatch>& commonFeatures, std::vector<double>& x_new, std::vector<double>& x_old,
+                       std::vector<size_t>& kept)
+{
+    x_new.clear(); x_old.clear(); kept.clear();
+    for (size_t k = 0; k < commonFeatures.size(); ++k) {
+        const size_t i = commonFeatures[k].i_, j = commonFeatures[k].j_;
+        if (i >= landmarksOld.size() || j >= landmarksNew.size()) continue;
+        for (int c = 0; c < 3; ++c) { x_old.push_back(landmarksOld[i][c]); x_new.push_back(landmarksNew[j][c]); }
+        kept.push_back(k);
+    }
+}
+// the common features whose pair the model keeps (mask: one byte per pair), in their order
+inline std::vector<openMVG::matching::IndMatch> sim3_inlier_features(const std::vector<openMVG::matching::IndMatch>& commonFeatures,
+                                                                     const std::vector<size_t>& kept, const std::vector<uint8_t>& mask)
+{
+    std::vector<openMVG::matching::IndMatch> out;
+    for (size_t k = 0; k < kept.size() && k < mask.size(); ++k)
+        if (mask[k] && kept[k] < commonFeatures.size()) out.push_back(commonFeatures[kept[k]]);
+    return out;
 }
 
 } // namespace hipgeom
@@ -720,6 +749,36 @@ public:
         }
         myfile.close();
         return EXIT_SUCCESS;
+    }
+
+    // OUR OWN STATEMENT (no counterpart in the reference; OpenMVG parity unpinned): the geometric filter matchMaps was meant to be.
+    // landmarksOld / landmarksNew: the landmark of every descriptor row of the old / new map (the scene's GetLandmarks() in mapRegionIdx
+    // order); commonFeatures: matchMapFeatures(old, new), i_ = old row, j_ = new row.  The a-contrario similarity NEW -> OLD of
+    // clc_sim3_acransac over their landmarks: on return only the inliers are left in commonFeatures and X_old ~ scale R X_new + t.
+    // EXIT_SUCCESS (false): a model was found.  EXIT_FAILURE: none (commonFeatures empty, scale 1, R = I, t = 0) or the call failed.
+    bool matchMapsSimilarity(const std::vector<openMVG::Vec3>& landmarksOld, const std::vector<openMVG::Vec3>& landmarksNew,
+                             std::vector<openMVG::matching::IndMatch>& commonFeatures, double& scale, openMVG::Mat3& rotation,
+                             openMVG::Vec3& translation, const double precision = std::numeric_limits<double>::infinity())
+    {
+        std::vector<double> x_new, x_old;
+        std::vector<size_t> kept;
+        hipgeom::sim3_pairs(landmarksOld, landmarksNew, commonFeatures, x_new, x_old, kept);
+        const int n = static_cast<int>(kept.size());
+        std::vector<uint8_t> mask(static_cast<size_t>(n > 0 ? n : 1), 0);
+        double s = 1.0, R[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, t[3] = { 0, 0, 0 };
+        int n_inl = 0, valid = -1;
+        const int rc = ctx_ ? clc_sim3_acransac(ctx_, x_new.data(), x_old.data(), n, iterationCount, seed++, precision, &s, R, t, nullptr, mask.data(),
+                                                nullptr, &n_inl, nullptr, nullptr, nullptr, &valid, nullptr)
+                            : CLC_ERR_STATE;
+        if (rc != CLC_OK) std::cerr << "HIPRobustMatcher: clc_sim3_acransac: " << (ctx_ ? clc_last_error_string(ctx_) : "no context") << std::endl;
+        const bool found = rc == CLC_OK && valid >= 0;
+        commonFeatures = found ? hipgeom::sim3_inlier_features(commonFeatures, kept, mask) : std::vector<openMVG::matching::IndMatch>();
+        scale = found ? s : 1.0;
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) rotation(i, j) = found ? R[3 * i + j] : (i == j ? 1.0 : 0.0);
+            translation[i] = found ? t[i] : 0.0;
+        }
+        return found ? EXIT_SUCCESS : EXIT_FAILURE;
     }
 
 private:

@@ -48,7 +48,8 @@ extern "C" {
  * (clc_set_map_points, clc_track_build_dev, clc_track_localize_dev, clc_track_localize_batch_dev) and two-view correspondences
  * (clc_pair_build_dev, clc_pair_filter_dev, clc_pair_filter_batch_dev), the inter-camera step from device memory (clc_inter_*_dev) and
  * the map built on the device (clc_tracks_build_dev, clc_map_build_dev, clc_map_init_batch_dev) and replaced at the old map's scale
- * (clc_map_align_dev, clc_map_update_batch_dev).
+ * (clc_map_align_dev, clc_map_update_batch_dev), and the a-contrario 3-D similarity that aligns a replaced map to the old one
+ * (clc_sim3_acransac, clc_sim3_minimal, clc_map_align_sim_dev, clc_map_update_sim_batch_dev).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -657,6 +658,39 @@ int clc_two_view_acransac_batch(clc_ctx* const* ctxs, int model, clc_two_view_jo
 int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const double* h_x2, int N, int img_w, int img_h,
                          const int32_t* h_samples, int S, double* h_models);
 
+/* The 3-D similarity between two landmark sets by a-contrario RANSAC (a new entry under ABI 4).  OUR OWN STATEMENT, an addition with
+ * OpenMVG parity unpinned: the reference's matchMaps was meant to filter the matches between the old and the new map geometrically, its
+ * homography filter is commented out (RobustMatcher.hpp:247-293) and the live code keeps every match (:348-362); the scale rule behind it
+ * (colocUtils.hpp:184-211, clc_map_align_dev) averages distance ratios over all of them.  Convention: the similarity maps NEW to OLD,
+ * X_old ~ s R X_new + t; a model is A = [sR | t], 12 doubles, 3 x 4 row-major.  The arithmetic is coloc_amd/csrc/sim3_math.h, one
+ * statement for host and device (IEEE +, -, *, /, sqrt in a written order, no contraction):
+ *   minimal solver  three correspondences.  In each cloud an orthonormal triad from p1 - p0 and (p1 - p0) x (p2 - p0); R = F_old F_new^T;
+ *                   s = sqrt(S_old / S_new), S = sum |p_i - mean|^2 over the three points; t = mean_old - s R mean_new.  A sample is
+ *                   degenerate when, in either cloud, |e1 x e2|^2 <= 1e-12 |e1|^2 |e2|^2: its slot is NaN-filled (an empty root).
+ *   residual        |X_old - (A [X_new; 1])|^2 in old-map units, every row ((A0 X + A1 Y) + A2 Z) + A3.
+ *   a-contrario     the fifth kind of the one multi-solve launch path (one launch per round, as resection): samples of 3, one model per
+ *                   sample, alpha0 = ((4 / 3) pi) / V with V = (ex ey) ez the volume of the axis-aligned bounding box of the OLD points,
+ *                   exponent 1.5, loge0 as for the other kinds.  A V that is not positive and finite admits no model.
+ *   acceptance      a meaningful model (NFA < 0) with more than 2.5 x 3 inliers -- the rule of HIP_SfM_Localizer::Localize.
+ *   refit           Umeyama's least-squares similarity over the inliers in ascending index: centroids and the 3 x 3 cross-covariance as
+ *                   partial sums of 128 consecutive inliers, each left to right, the partials left to right; 3 x 3 SVD by one-sided
+ *                   Jacobi (<= 30 sweeps); R = U diag(1, 1, d) V^T, d = sign(det U det V); s = (sigma1 + sigma2 + d sigma3) / (S_new / n);
+ *                   t = mean_old - s R mean_new.  Refused -- the minimal model is kept, *refit = 0 -- when sigma2 <= 1e-12 sigma1 or an
+ *                   output is not finite.  One single-workgroup launch behind the last round, no floating-point atomics.
+ *   reported        after a refit its own s, R, t with A = [sR | t]; else s = sqrt((A00^2 + A10^2) + A20^2), R = A[:, :3] / s, t = A[:, 3].
+ * h_x_new / h_x_old: N x 3.  precision: upper bound of the residual (squared old-map units), +inf: none.  Outputs (all nullable): *s,
+ * h_R (9), h_t (3), h_A (12), h_inlier_mask (N), h_inliers (N, ascending residual), *n_inliers, *error_max (sqrt of the threshold
+ * residual: old-map units), *min_nfa, *iterations, *valid (the iteration that gave the model, -1: none), *refit.  Not found -- N <= 3
+ * (no solve runs), a degenerate box, no meaningful model or the acceptance rule failing --: s = 1, R = I, t = 0, A = [I | 0], no inliers,
+ * *valid = -1; *min_nfa and *iterations are the run's.  N > 16 384: CLC_ERR_CAPACITY. */
+int clc_sim3_acransac(clc_ctx* ctx, const double* h_x_new, const double* h_x_old, int N, int max_iteration, uint64_t seed,
+                      double precision, double* s, double* h_R, double* h_t, double* h_A, uint8_t* h_inlier_mask, int32_t* h_inliers,
+                      int* n_inliers, double* error_max, double* min_nfa, int* iterations, int* valid, int* refit);
+/* The minimal solver above on caller-chosen samples (the hypothesis generator, as clc_two_view_minimal is for 'F' / 'H'): h_samples
+ * S x 3 indices into the N correspondences; h_models S x 12, NaN-filled for a degenerate sample or an index outside [0, N). */
+int clc_sim3_minimal(clc_ctx* ctx, const double* h_x_new, const double* h_x_old, int N, const int32_t* h_samples, int S,
+                     double* h_models);
+
 /* The inter-camera step of ColoC::interPoseEstimator(source, dest) between the pair's putative matches and the covariance intersection
  * (coloc.hpp:296-340), for several camera pairs at once: a-contrario five-point filter (filterMatchesPair, :296) -> relative pose from
  * E with the chirality vote (RobustMatcher.hpp:176-183) -> the pair's temporary map triangulated in the source camera's frame (:306) ->
@@ -1201,6 +1235,60 @@ typedef struct clc_map_align {
 int clc_map_align_dev(clc_ctx* ctx, clc_map_align* job);
 int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align);
 
+/* ---- the same step under an a-contrario similarity (new entries under ABI 4) ----------------------------------------------------------
+ * OUR OWN STATEMENT, an addition with OpenMVG parity unpinned: it finishes what matchMaps set out to do (its geometric filter is
+ * commented out, RobustMatcher.hpp:247-293) and replaces the mean of distance ratios, into which one wrong common feature puts an
+ * arbitrary ratio, by the similarity NEW -> OLD of clc_sim3_acransac over the common features.  clc_map_align_dev, the
+ * clc_map_update_*_batch_dev entries and matchMaps are unchanged.
+ *
+ * clc_map_align_sim_dev: the inputs of clc_map_align_dev plus apply, max_iteration (0: 256), seed and precision (as clc_sim3_acransac).
+ *   COMMON FEATURES: found exactly as clc_map_align_dev finds them -- the same gather, the same sweep, the same list in ascending old row.
+ *   GATHER: one launch of the ordered gather writes X_new | X_old of every common feature into the solve's blocks and leaves the
+ *     bounding box of those X_old and then the count in a pinned record.  FIRST HOST WAIT: that record (the NFA tables need the count,
+ *     alpha0 the box).  More than 16 384 common features: CLC_ERR_CAPACITY before anything is installed.
+ *   SOLVE: the rounds and the refit of clc_sim3_acransac on those pairs, read where the gather left them.
+ *   TRANSFORM: one launch over all n_new points into the context's staging buffer and -- where X was asked for -- a pinned mirror:
+ *     CLC_SIM_APPLY_SCALE  X' = X * s, one multiply per component; poses go through rescale_pose(s) (the old behaviour, the robust s);
+ *     CLC_SIM_APPLY_FULL   X' = s R X + t, every row ((A0 X + A1 Y) + A2 Z) + A3 with A = [sR | t] (sim3_apply_point); a camera
+ *                          [R_c | t_c] becomes R_c' = R_c R^T, t_c' = s t_c - R_c' t (sim3_apply_pose), its centre moves to s R C + t.
+ *     SECOND HOST WAIT: the transform's record, released last.
+ *   NO MODEL (fewer than 4 common features, the acceptance rule failing, a degenerate box): status = CLC_MAP_SIM_NO_MODEL, s = 1, R = I,
+ *     t = 0 and the points are installed with their bits unchanged -- the counterpart of CLC_MAP_ALIGN_NO_SCALE.
+ *   OUTPUTS: n_old, n_common, n_inliers, inlier (nullable host, n_old bytes of room: 1 for every common feature the model keeps, in list
+ *     order), match, X, s, R, t, error_max, min_nfa, iterations, refit, status.  INSTALL, ORDERING, ERRORS and capacity as
+ *     clc_map_align_dev (apply outside the two values: CLC_ERR_BAD_ARG); on every error the previous map serves exactly as before.  The
+ *     scratch lies in the alignment blocks and the solve's own workspace; no descriptor, point or match is copied in either direction.
+ *
+ * clc_map_update_sim_batch_dev: the composition.  It is clc_map_update_batch_dev (grow == ba == NULL), clc_map_update_grow_batch_dev
+ * (grow given) or clc_map_update_grow_ba_batch_dev (grow and ba given; ba needs grow: CLC_ERR_BAD_ARG otherwise) with the step above
+ * in place of the align step: of `sim` threshold, apply, max_iteration, seed, precision, match and inlier are read, its out fields
+ * written.  job->X holds the transformed landmarks; the seed poses -- and with grow the resected cameras' -- are transformed under the
+ * same apply rule.  No entering pair, no previous map: as in those calls, with status CLC_MAP_SIM_NO_MODEL, s = 1. */
+enum { CLC_MAP_SIM_OK = 0, CLC_MAP_SIM_NO_MODEL = 1 };
+enum { CLC_SIM_APPLY_SCALE = 0, CLC_SIM_APPLY_FULL = 1 };
+typedef struct clc_map_align_sim {
+    /* in */
+    const void*    d_desc;       /* descriptor block, rows of 64 B, 16-byte aligned */
+    const int32_t* d_rows;       /* nullable: new map row i = row d_rows[i] of d_desc; NULL: row i */
+    const double*  d_X;          /* n_new x 3, NOT written */
+    int            n_new;
+    int            threshold;    /* <= 0: 60 (GPUMatcher.hpp:162) */
+    int            install;      /* 0: report only, the context's map is left exactly as it was */
+    void*          after_stream; /* nullable, as clc_map_job */
+    int            apply;        /* CLC_SIM_APPLY_SCALE / CLC_SIM_APPLY_FULL */
+    int            max_iteration;/* 0: 256 */
+    uint64_t       seed;
+    double         precision;    /* +inf: a-contrario threshold */
+    /* out */
+    int32_t*       match;        /* nullable host, n_old entries: new row matched by old row q, or -1 */
+    double*        X;            /* nullable host, n_new x 3: the transformed points */
+    uint8_t*       inlier;       /* nullable host, n_old bytes of room: the flags of the n_common common features, in list order */
+    int            n_old, n_common, n_inliers, iterations, refit, status;
+    double         s, R[9], t[3], error_max, min_nfa;
+} clc_map_align_sim;
+int clc_map_align_sim_dev(clc_ctx* ctx, clc_map_align_sim* job);
+/* (clc_map_update_sim_batch_dev is declared behind clc_map_grow and clc_map_ba, below) */
+
 /* ---- the map grown past the seed pair: resect the other cameras, add their tracks ---------------------------------------------------
  * What Reconstructor::reconstructScene runs after the seed triangulation: `for (auto resectionId : resectionList)
  * resectionCamera(resectionId)` (Reconstructor.hpp:153-154, 259-415), and setupMapDatabase (colocData.hpp:89-121) over the landmarks
@@ -1354,6 +1442,9 @@ int clc_map_init_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs
                                    clc_map_ba* ba);
 int clc_map_update_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align,
                                      clc_map_grow* grow, clc_map_ba* ba);
+/* the composition under the a-contrario similarity (clc_map_align_sim above) */
+int clc_map_update_sim_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align_sim* sim,
+                                 clc_map_grow* grow /* nullable */, clc_map_ba* ba /* nullable, needs grow */);
 
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses

@@ -1,0 +1,17 @@
+"""coloc_amd/csrc/sim3_math.h and the host-side conversions of HIPRobustMatcher::matchMapsSimilarity under AddressSanitizer and
+UndefinedBehaviorSanitizer, as a stand-alone program (tests/host/sim3_asan_main.cpp, its own main): host code only, nothing loaded into
+Python, no GPU."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_sim3_math_and_the_policy_conversions_are_clean_under_the_sanitizers(tmp_path):
+    exe = tmp_path / "sim3_asan_main"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "coloc_amd", "host"),
+                           os.path.join(ROOT, "tests", "host", "sim3_asan_main.cpp"), "-o", str(exe)])
+    r = subprocess.run([str(exe)], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "sim3_asan_main: ok" in r.stdout
