@@ -34,6 +34,9 @@
 #include "twoview_min.h"
 #include "sim3_math.h"
 
+// a switch over AcrKindId that lacks a kind does not compile (acr_launch_model)
+#pragma clang diagnostic error "-Wswitch"
+
 namespace clc {
 
 // -DCLC_ACR_STAMP (experiments only, tools/archive/acr_stamps.py): thread 0 of slot workgroup 0 leaves s_memtime at the phase boundaries of
@@ -45,6 +48,9 @@ __device__ unsigned long long g_acr_stamp[16];
 #define ACR_STAMP(i) do { } while (0)
 #endif
 
+// acr_finish_block compares a run-time kind: the essential is the one kind whose error is reported as it is (acr_kind()'s error_in_units)
+static_assert(!acr_kind(kAcrEssential).error_in_units && acr_kind(kAcrResection).error_in_units && acr_kind(kAcrFundamental).error_in_units &&
+              acr_kind(kAcrHomography).error_in_units && acr_kind(kAcrSimilarity).error_in_units, "acr_finish_block: error_in_units");
 __device__ __forceinline__ void acr_finish_block(const AcrProblem& pb, const AcrState& s, const uint32_t* __restrict__ best_inliers,
                                                  const AcrFinish& fin, const int tid, const int T)
 {
@@ -64,7 +70,7 @@ __device__ __forceinline__ void acr_finish_block(const AcrProblem& pb, const Acr
         r.min_nfa = s.min_nfa;
         // unormalizeError: resection sqrt(e) / N1(0,0), fundamental / homography sqrt(e) / N2(0,0) -> pixels; essential: the squared
         // pixel distance as it is
-        r.error_max = !ok ? 0.0 : (pb.kind != 1 ? sqrt(s.error_max) / pb.norm : s.error_max);
+        r.error_max = !ok ? 0.0 : (pb.kind != kAcrEssential ? sqrt(s.error_max) / pb.norm : s.error_max);
         r.n_inliers = n_inl;
         r.valid = ok ? s.best_iter : -1;
         r.iterations = s.iter;
@@ -422,7 +428,7 @@ __device__ __forceinline__ void acr_best_bcast(double& v, double& e, int& k, int
 }
 
 // One model slot, one workgroup of T threads: `model` (global memory or LDS) -> *hyp_slot and the sorted index list out_idx[0..n).
-// KIND: the residual is chosen at compile time where the round names its kind (4: the 3-D similarity); -1: by pb.kind, as kinds 0-3 are
+// KIND: the residual is chosen at compile time where the round names its kind (the 3-D similarity); -1: by pb.kind, as the other four are
 template <int E, bool PRE = false, int KIND = -1>
 __device__ __forceinline__ void acr_nfa_body(const AcrProblem& pb, const int P /* = T * E, power of two >= n */, const double* model,
                                              AcrHyp* __restrict__ hyp_slot, uint32_t* __restrict__ out_idx, const int tid, const int T,
@@ -446,10 +452,10 @@ __device__ __forceinline__ void acr_nfa_body(const AcrProblem& pb, const int P /
         return;
     }
     auto residual = [&](const int i) -> double {
-        if constexpr (KIND == 4) return sim3_residual(model, pb.a + 3 * i, pb.b + 3 * i);
-        if (pb.kind == 0) return acr_err_resection(model, pb.K1v, pb.norm, pb.a[3 * i], pb.a[3 * i + 1], pb.a[3 * i + 2], pb.b[2 * i], pb.b[2 * i + 1]);
+        if constexpr (KIND == kAcrSimilarity) return sim3_residual(model, pb.a + 3 * i, pb.b + 3 * i);
+        if (pb.kind == kAcrResection) return acr_err_resection(model, pb.K1v, pb.norm, pb.a[3 * i], pb.a[3 * i + 1], pb.a[3 * i + 2], pb.b[2 * i], pb.b[2 * i + 1]);
         const double u1 = pb.a[2 * i], v1 = pb.a[2 * i + 1], u2 = pb.b[2 * i], v2 = pb.b[2 * i + 1];
-        return pb.kind == 1 ? acr_err_epipolar(model, u1, v1, u2, v2) : (pb.kind == 2 ? acr_err_line(model, u1, v1, u2, v2) : acr_err_transfer(model, u1, v1, u2, v2));
+        return pb.kind == kAcrEssential ? acr_err_epipolar(model, u1, v1, u2, v2) : (pb.kind == kAcrFundamental ? acr_err_line(model, u1, v1, u2, v2) : acr_err_transfer(model, u1, v1, u2, v2));
     };
     uint64_t key[E];
     uint32_t idx[E];
@@ -554,7 +560,7 @@ template <int E>
 __global__ __launch_bounds__(1024) void acr_nfa_kernel(const AcrChains chains, const int par, const int P)
 {
     extern __shared__ unsigned char acr_lds[];
-    constexpr int kSlots = kAcrMaxBatch * 10;
+    constexpr int kSlots = kAcrMaxBatch * acr_kind(kAcrEssential).slots;
     const AcrChain& ch = chains.c[blockIdx.y];
     const AcrProblem& pb = ch.pb;
     const int slot = blockIdx.x;
@@ -777,16 +783,13 @@ __device__ __forceinline__ void acr_keep(const AcrProblem& pb, const AcrCore& c,
 // the host has launch r + 2 enqueued long before r + 1 ends, and the launch that reports "done" is the last one in the stream.
 // The same one-launch round serves the two cheap two-view solvers (round 6: 'F' seven points, 'H' four points -- twoview_min.h): a
 // slot workgroup solves its iteration's sample on thread 0 (all the slots of an iteration solve the same sample and keep their own
-// root), everything else is the resection round.  So does the 3-D similarity (kind 4: three points, one model, sim3_math.h; the project's
-// own statement, clc_sim3_acransac), whose residual acr_nfa_body takes at compile time.  KIND = AcrProblem::kind; slots and models keep the resection's strides (4 slots per
-// iteration between the parity copies, 12 doubles per model) so that the host lays one workspace out for all three.
-template <int KIND> struct AcrKind;
-template <> struct AcrKind<0> { static constexpr int m = 3, M = 4; };
-template <> struct AcrKind<2> { static constexpr int m = 7, M = 3; };
-template <> struct AcrKind<3> { static constexpr int m = 4, M = 1; };
-template <> struct AcrKind<4> { static constexpr int m = 3, M = 1; };
+// root), everything else is the resection round.  So does the 3-D similarity (three points, one model, sim3_math.h; the project's
+// own statement, clc_sim3_acransac), whose residual acr_nfa_body takes at compile time.  KIND = AcrProblem::kind, an AcrKindId: sample size,
+// models per sample and slots per iteration are its row of acr_kind() (acr_kind.h); slots and models keep the resection's strides (4 slots
+// per iteration between the parity copies, 12 doubles per model: asserted beside the table) so that the host lays one workspace out for
+// all four.
 
-// the similarity of the sample {id[0..3)} of a kind-4 problem (x = X_new, y = X_old, 3 N each) -> out[0..12) (NaN: degenerate sample, an
+// the similarity of the sample {id[0..3)} of a similarity problem (x = X_new, y = X_old, 3 N each) -> out[0..12) (NaN: degenerate sample, an
 // index outside [0, N) or root != 0): sim3_minimal, the body sim3_minimal_kernel runs
 __device__ __forceinline__ void acr_sim3_sample_root(const double* __restrict__ x, const double* __restrict__ y, const int (&id)[3], const int N,
                                                      const int root, double* out)
@@ -811,10 +814,10 @@ __device__ __forceinline__ void acr_sim3_sample_root(const double* __restrict__ 
 
 // the model of root `root` of the sample {id[0..m)} of a seven-point / four-point problem -> out[0..12) (9 used; NaN: no such root)
 template <int KIND>
-__device__ __forceinline__ void acr_twoview_sample_root(const double* __restrict__ x1, const double* __restrict__ x2, const int (&id)[AcrKind<KIND>::m],
+__device__ __forceinline__ void acr_twoview_sample_root(const double* __restrict__ x1, const double* __restrict__ x2, const int (&id)[acr_kind(KIND).m],
                                                         const int N, const int root, double* out)
 {
-    constexpr int m = AcrKind<KIND>::m;
+    constexpr int m = acr_kind(KIND).m;
     double a[m][2], b[m][2];
     bool ok = true;
 #pragma unroll
@@ -827,7 +830,7 @@ __device__ __forceinline__ void acr_twoview_sample_root(const double* __restrict
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     double M9[9];
     bool have;
-    if constexpr (KIND == 2) {
+    if constexpr (KIND == kAcrFundamental) {
         double F[3][9];
         const int nr = tv::seven_point(a, b, F);
         have = ok && root < nr;
@@ -850,7 +853,7 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
                                                unsigned long long* __restrict__ h_word, const AcrFinish& fin)
 {
     extern __shared__ unsigned char acr_lds[];
-    constexpr int kSlots = kAcrMaxBatch * 4;
+    constexpr int kSlots = kAcrMaxBatch * acr_kind(KIND).slots;
     __shared__ AcrCore s_core;
     __shared__ AcrPick s_pick;
     __shared__ AcrState s_full;
@@ -861,8 +864,8 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
     const unsigned long long t_start = __builtin_amdgcn_s_memtime();
     unsigned long long t_replay = 0;
 #endif
-    constexpr int m = AcrKind<KIND>::m, M = AcrKind<KIND>::M;
-    constexpr bool kPre = KIND == 0 && E <= 2;                      // (more elements per thread: the registers are worth more than the latency)
+    constexpr int m = acr_kind(KIND).m, M = acr_kind(KIND).M;
+    constexpr bool kPre = KIND == kAcrResection && E <= 2;                      // (more elements per thread: the registers are worth more than the latency)
     AcrPre<kPre ? E : 1> pre;
     if (kPre && !keeper) acr_prefetch<kPre ? E : 1>(pb, tid, pre);
     const AcrState* st_in = states + (par ^ 1);
@@ -903,8 +906,8 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
         ACR_STAMP(3);
-        if constexpr (KIND == 0) p3p_sample_root(pb.a, pb.b, pb.K1v, id[0], id[1], id[2], pb.n, slot & 3, s_model);
-        else if constexpr (KIND == 4) acr_sim3_sample_root(pb.a, pb.b, id, pb.n, slot % M, s_model);
+        if constexpr (KIND == kAcrResection) p3p_sample_root(pb.a, pb.b, pb.K1v, id[0], id[1], id[2], pb.n, slot & 3, s_model);
+        else if constexpr (KIND == kAcrSimilarity) acr_sim3_sample_root(pb.a, pb.b, id, pb.n, slot % M, s_model);
         else acr_twoview_sample_root<KIND>(pb.a, pb.b, id, pb.n, slot % M, s_model);
         ACR_STAMP(4);
         double* mo = models + ((size_t)par * kSlots + slot) * 12;
@@ -913,7 +916,7 @@ __device__ __forceinline__ void acr_round_body(AcrState* __restrict__ states /* 
     }
     __syncthreads();
     ACR_STAMP(5);
-    acr_nfa_body<E, kPre, KIND == 4 ? 4 : -1>(pb, P, s_model, hyps + (size_t)par * kSlots + slot, sorted + ((size_t)par * kSlots + slot) * pb.n, tid, T,
+    acr_nfa_body<E, kPre, KIND == kAcrSimilarity ? KIND : -1>(pb, P, s_model, hyps + (size_t)par * kSlots + slot, sorted + ((size_t)par * kSlots + slot) * pb.n, tid, T,
                           reinterpret_cast<uint64_t*>(acr_lds), &pre);
 }
 
@@ -930,7 +933,7 @@ template <int KIND>
 __global__ __launch_bounds__(64) void twoview_minimal_kernel(const double* __restrict__ x1, const double* __restrict__ x2, const int N,
                                                              const int32_t* __restrict__ samples, const int S, double* __restrict__ out /* S x M x 9 */)
 {
-    constexpr int m = AcrKind<KIND>::m, M = AcrKind<KIND>::M;
+    constexpr int m = acr_kind(KIND).m, M = acr_kind(KIND).M;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= S * M) return;
     const int sidx = t / M, root = t % M;
@@ -945,13 +948,14 @@ __global__ __launch_bounds__(64) void twoview_minimal_kernel(const double* __res
 hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_x2, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream)
 {
     if (S <= 0) return hipSuccess;
-    if (kind == 2) hipLaunchKernelGGL(twoview_minimal_kernel<2>, dim3((S * 3 + 63) / 64), dim3(64), 0, stream, d_x1, d_x2, N, d_samples, S, d_out);
-    else if (kind == 3) hipLaunchKernelGGL(twoview_minimal_kernel<3>, dim3((S + 63) / 64), dim3(64), 0, stream, d_x1, d_x2, N, d_samples, S, d_out);
+    const dim3 grid((S * acr_kind(kind).M + 63) / 64);                // one thread per (sample, root)
+    if (kind == kAcrFundamental) hipLaunchKernelGGL(twoview_minimal_kernel<kAcrFundamental>, grid, dim3(64), 0, stream, d_x1, d_x2, N, d_samples, S, d_out);
+    else if (kind == kAcrHomography) hipLaunchKernelGGL(twoview_minimal_kernel<kAcrHomography>, grid, dim3(64), 0, stream, d_x1, d_x2, N, d_samples, S, d_out);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-// ---- the 3-D similarity behind the rounds (kind 4) ----------------------------------------------------------------------------------
+// ---- the 3-D similarity behind the rounds (kAcrSimilarity) ----------------------------------------------------------------------------------
 // The minimal models of caller-chosen samples (clc_sim3_minimal): one thread per sample, the body the round runs.
 __global__ __launch_bounds__(64) void sim3_minimal_kernel(const double* __restrict__ x, const double* __restrict__ y, const int N,
                                                           const int32_t* __restrict__ samples, const int S, double* __restrict__ out /* S x 12 */)
@@ -1069,7 +1073,7 @@ __device__ __forceinline__ void acr_solve5_body(AcrState* __restrict__ states /*
                                                 uint32_t* __restrict__ best_inliers, uint32_t* __restrict__ index_set,
                                                 unsigned long long* __restrict__ h_word, const AcrFinish& fin)
 {
-    constexpr int kSlots = kAcrMaxBatch * 10;
+    constexpr int kSlots = kAcrMaxBatch * acr_kind(kAcrEssential).slots;
     __shared__ AcrCore s_core;
     __shared__ AcrPick s_pick;
     __shared__ AcrState s_full;
@@ -1135,7 +1139,7 @@ static hipError_t acr_launch_round(const AcrChains& chains, int n_chains, int B,
     static bool attr_set[64] = {};
     const hipError_t e = acr_dyn_lds(acr_round_kernel<E, KIND>, attr_set);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((acr_round_kernel<E, KIND>), dim3(B * AcrKind<KIND>::M + 1 /* the keeper */, n_chains), dim3(P / E), acr_lds_bytes<E>(P),
+    hipLaunchKernelGGL((acr_round_kernel<E, KIND>), dim3(B * acr_kind(KIND).M + 1 /* the keeper */, n_chains), dim3(P / E), acr_lds_bytes<E>(P),
                        stream, chains, par, P);
     return hipGetLastError();
 }
@@ -1150,17 +1154,20 @@ static hipError_t acr_launch_round5(const AcrChains& chains, int n_chains, int B
     static bool attr_set[64] = {};
     e = acr_dyn_lds(acr_nfa_kernel<E>, attr_set);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(acr_nfa_kernel<E>, dim3(B * 10, n_chains), dim3(P / E), acr_lds_bytes<E>(P), stream, chains, par, P);
+    hipLaunchKernelGGL(acr_nfa_kernel<E>, dim3(B * acr_kind(kAcrEssential).M, n_chains), dim3(P / E), acr_lds_bytes<E>(P), stream, chains, par, P);
     return hipGetLastError();
 }
 template <int E>
-static hipError_t acr_launch_kind(const int kind, const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
+static hipError_t acr_launch_model(const int kind, const AcrChains& chains, int n_chains, int B, int P, int par, hipStream_t stream)
 {
-    if (kind == 0) return acr_launch_round<E, 0>(chains, n_chains, B, P, par, stream);
-    if (kind == 1) return acr_launch_round5<E>(chains, n_chains, B, P, par, stream);
-    if (kind == 2) return acr_launch_round<E, 2>(chains, n_chains, B, P, par, stream);
-    if (kind == 3) return acr_launch_round<E, 3>(chains, n_chains, B, P, par, stream);
-    if (kind == 4) return acr_launch_round<E, 4>(chains, n_chains, B, P, par, stream);
+    switch ((AcrKindId)kind) {
+    case kAcrResection:   return acr_launch_round<E, kAcrResection>(chains, n_chains, B, P, par, stream);
+    case kAcrEssential:   return acr_launch_round5<E>(chains, n_chains, B, P, par, stream);
+    case kAcrFundamental: return acr_launch_round<E, kAcrFundamental>(chains, n_chains, B, P, par, stream);
+    case kAcrHomography:  return acr_launch_round<E, kAcrHomography>(chains, n_chains, B, P, par, stream);
+    case kAcrSimilarity:  return acr_launch_round<E, kAcrSimilarity>(chains, n_chains, B, P, par, stream);
+    case kAcrKindCount:   break;
+    }
     return hipErrorInvalidValue;
 }
 hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int batch_bound, hipStream_t stream)
@@ -1171,11 +1178,11 @@ hipError_t launch_acr_round(const AcrChains& chains, int n_chains, int par, int 
     const int B = batch_bound < 1 ? 1 : (batch_bound > kAcrMaxBatch ? kAcrMaxBatch : batch_bound);
     int P = 64;                                                      // every chain sorts at the widest chain's width: the order of its n real
     for (int c = 0; c < n_chains; ++c) while (P < chains.c[c].pb.n) P <<= 1;   // elements is the same
-    if (P <= 1024) return acr_launch_kind<1>(kind, chains, n_chains, B, P, par, stream);
-    if (P == 2048) return acr_launch_kind<2>(kind, chains, n_chains, B, P, par, stream);
-    if (P == 4096) return acr_launch_kind<4>(kind, chains, n_chains, B, P, par, stream);
-    if (P == 8192) return acr_launch_kind<8>(kind, chains, n_chains, B, P, par, stream);
-    return acr_launch_kind<16>(kind, chains, n_chains, B, P, par, stream);
+    if (P <= 1024) return acr_launch_model<1>(kind, chains, n_chains, B, P, par, stream);
+    if (P == 2048) return acr_launch_model<2>(kind, chains, n_chains, B, P, par, stream);
+    if (P == 4096) return acr_launch_model<4>(kind, chains, n_chains, B, P, par, stream);
+    if (P == 8192) return acr_launch_model<8>(kind, chains, n_chains, B, P, par, stream);
+    return acr_launch_model<16>(kind, chains, n_chains, B, P, par, stream);
 }
 
 // inputs of the solves: pinned host blocks -> device workspaces, by ONE launch (blockIdx.y = solve) instead of copy commands (a copy

@@ -228,7 +228,7 @@ int run_jobs(clc_ctx* ctx, std::vector<K2nnJobDev>& jobs, hipStream_t st, bool p
 void k2nn_probe_bias(clc_ctx* ctx);                       // once per process and device: which unequal shares suit this device
 
 // all two-view a-contrario filters of a batch (pose_batch.hip); jobs[i] on ctxs[i]
-int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind /* 1 'E', 2 'F', 3 'H' */);
+int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind /* kAcrEssential, kAcrFundamental or kAcrHomography */);
 int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what);
 // clc_sim3_acransac on N 3-D / 3-D pairs that lie in DEVICE memory (d_x_new | d_x_old, 3 N each; read in place, they must stand until the
 // call returns) with the box { min, max } of d_x_old from whoever gathered them (pose_batch.hip).  out: identity where there is no model

@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include "../../include/coloc_hip.h"
+#include "acr_kind.h"
 
 namespace clc {
 
@@ -240,19 +241,18 @@ static constexpr int kAcrMaxBatch = 128;           // iterations evaluated per r
 static constexpr int kAcrMaxN = 16384;             // correspondences per solve: 8 B x 16 384 = 128 KB of LDS per model slot (16 elements per thread)
 static constexpr size_t kAcrMaxLds = (size_t)kAcrMaxN * 8;
 struct AcrProblem {        // passed by value to every kernel of a solve
-    int kind;              // 0: resection (P3P, [R|t] models of 12 doubles), 1: essential (five-point, {F, E} models of 18),
-                           // 2: fundamental (seven-point), 3: homography (four-point): 9 doubles in a stride of 12, normalised coordinates
-                           // 4: 3-D similarity (three points, sim3_math.h): A = [sR | t], 12 doubles; a = X_new (3 n), b = X_old (3 n)
-    int n, m, max_models, model_doubles;
+    int kind;              // an AcrKindId (acr_kind.h).  Models: [R|t], 12 doubles (resection); {F, E}, 18 (essential); F / H in normalised
+                           // coordinates, 9 in a stride of 12 (fundamental, homography); A = [sR | t], 12 (similarity)
+    int n, m, max_models, model_doubles;   // m, max_models, model_doubles: acr_kind(kind)'s m, M, md, filled in by the host
     int batch_cap;         // most iterations a round evaluates (<= kAcrMaxBatch): the schedule, not the result, depends on it
-    const double* a;       // X (3 n)  | x1 (2 n; kinds 2, 3: conditioned by the image size)
-    const double* b;       // x (2 n)  | x2 (2 n)
+    const double* a;       // X (3 n)  | x1 (2 n; fundamental, homography: conditioned by the image size) | X_new (3 n)
+    const double* b;       // x (2 n)  | x2 (2 n)                                                              | X_old (3 n)
     const double* K1;      // 9 doubles row-major (+ padding)
     const double* K2;
     const float* logc_n;   // log10 C(n, k), k = 0..n
     const float* logc_k;   // log10 C(k, m)
     double loge0, logalpha0, mult, max_threshold;
-    double norm;           // resection: 1 / focal (residuals are scaled to the normalised camera plane); essential: 1; kinds 2, 3: N2(0,0)
+    double norm;           // resection: 1 / focal (residuals are scaled to the normalised camera plane); essential, similarity: 1; fundamental, homography: N2(0,0)
     uint64_t seed;
     double K1v[9];         // resection: K1 by value -- kernel arguments sit in scalar registers, a load of K1 is a ~1 us round trip
 };
@@ -299,8 +299,9 @@ struct AcrChain {
     AcrFinish fin;
 };
 struct AcrChains { AcrChain c[kMaxBatch]; };
-// One round of n_chains solves of one kind (a single solve: n_chains = 1): ONE launch for kinds 0 / 2 / 3 (replay of the previous round +
-// samples + P3P / seven-point / four-point + residuals / sort / NFA), TWO for kind 1 (replay + samples + five-point; nfa).  The states,
+// One round of n_chains solves of one kind (a single solve: n_chains = 1): ONE launch for every kind (replay of the previous round +
+// samples + P3P / seven-point / four-point / similarity + residuals / sort / NFA) but the essential, which takes TWO (replay + samples +
+// five-point; nfa).  The states,
 // slots, sorted lists and models of a chain hold two copies: this launch reads copy par ^ 1 and writes copy par; the initial state goes
 // into copy 1 and the first launch has par 0.  batch_bound (iterations the grids cover, >= the batch the device states ask for) and the
 // sort width cover the largest chain; chain.fin: where the round that completes a run leaves mask / inlier list / result record.
@@ -364,10 +365,10 @@ hipError_t launch_gather(PairJobs& jobs, int n_jobs, hipStream_t stream);
 // and cap are the caller's.  who: the text of a refused nq / nt / d_match
 int gather_inputs(clc_ctx* ctx_map, const clc_track_job& job, TrackJobDev& out, const char* who);
 int gather_inputs(clc_ctx* ctx, const clc_pair_job& job, PairJobDev& out, const char* who);
-// the seven-point / four-point models (kind 2: <= 3 per sample, kind 3: 1) of S samples of normalised correspondences: d_out S x M x 9, NaN = no model
+// the seven-point / four-point models (kAcrFundamental: <= 3 per sample, kAcrHomography: 1) of S samples of normalised correspondences: d_out S x M x 9, NaN = no model
 hipError_t launch_twoview_minimal(int kind, const double* d_x1, const double* d_x2, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
 
-// ---- the 3-D similarity (kind 4 of the a-contrario path; sim3_math.h) -------------------------------------------------------------------
+// ---- the 3-D similarity (kAcrSimilarity of the a-contrario path; sim3_math.h) -------------------------------------------------------------------
 // What the refit launch behind the last round leaves (device and pinned): the similarity NEW -> OLD that is reported.
 struct Sim3Out {
     double s, R[9], t[3], A[12];      // found: the refit's (refit = 1) or the minimal model's; else s = 1, R = I, t = 0, A = [I | 0]
@@ -378,7 +379,7 @@ struct Sim3Out {
 };
 // the minimal models of S samples of three correspondences each: d_out S x 12, NaN = degenerate sample or an index outside [0, N)
 hipError_t launch_sim3_minimal(const double* d_x, const double* d_y, int N, const int32_t* d_samples, int S, double* d_out, hipStream_t stream);
-// ONE workgroup behind the round that completed a kind-4 run: acceptance rule, the inliers of d_mask in ascending index (d_list: N words
+// ONE workgroup behind the round that completed a similarity run: acceptance rule, the inliers of d_mask in ascending index (d_list: N words
 // of scratch), Umeyama's refit by partial sums of kSim3Chunk inliers, the record to d_out and (nullable) the pinned h_out, `ready` last
 hipError_t launch_sim3_refit(const AcrResult* d_res, const uint8_t* d_mask, const double* d_x, const double* d_y, int N, int32_t* d_list,
                              Sim3Out* d_out, Sim3Out* h_out, hipStream_t stream);

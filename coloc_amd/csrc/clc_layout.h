@@ -8,6 +8,7 @@
 #define CLC_LAYOUT_H
 
 #include "clc_carve.h"
+#include "acr_kind.h"
 
 namespace clc {
 
@@ -169,20 +170,21 @@ struct GatherView {
 // ---- the pose scratch d_pnp and its pinned staging h_pin: one layout per solve ----------------------------------------------------------
 // Every array starts on 8 bytes (the blocks were laid out in doubles); what a staging launch or ONE copy carries is a sub-layout.
 
-// The a-contrario solve (pose_batch.hip).  kind 0: resection (a = X, 3 per row), 1-3: E, F, H (a = x1), 4: similarity (a = X_new, b = X_old,
-// 3 per row each; ref_bytes: the refit's record); N correspondences; the records'
-// sizes (ref_bytes 0: no refinement); md: doubles per model slot; batch: most iterations a round evaluates.
-struct AcrDims { int kind; size_t N, md, state_bytes, hyp_bytes, result_bytes, ref_bytes, batch; bool points_elsewhere = false; };
+// The a-contrario solve (pose_batch.hip).  kind: an AcrKindId, whose row of acr_kind() gives the widths of a | b, the slots per iteration
+// and the doubles per model slot; N correspondences; the records' sizes (ref_bytes: the record of what runs behind the rounds, 0:
+// nothing does); batch: most iterations a round evaluates.
+struct AcrDims { int kind; size_t N, state_bytes, hyp_bytes, result_bytes, ref_bytes, batch; bool points_elsewhere = false; };
 // (points_elsewhere: a | b are read where the gather left them -- the similarity from device points --, the blocks hold none)
-// the inputs, staged by one launch: [ a | b 2 N (kind 4: 3 N) | K1 16 | K2 16 | logc_n N + 1 floats | logc_k | state copy 0 | copy 1 = a run's start ]
+// the inputs, staged by one launch: [ a | b (a_width N | b_width N) | K1 16 | K2 16 | logc_n N + 1 floats | logc_k | state copy 0 | copy 1 = a run's start ]
 struct AcrIn {
     double *a, *b, *K1, *K2; float *logc_n, *logc_k; void* state; size_t bytes;
     void carve(Carve& c, const AcrDims& d)
     {
         c.take<double>(0);
         const size_t at = c.bytes();
-        a = c.take<double>(d.points_elsewhere ? 0 : (size_t)(d.kind == 0 || d.kind == 4 ? 3 : 2) * d.N);
-        b = c.take<double>(d.points_elsewhere ? 0 : (size_t)(d.kind == 4 ? 3 : 2) * d.N); K1 = c.take<double>(16); K2 = c.take<double>(16);
+        const AcrKindInfo k = acr_kind(d.kind);
+        a = c.take<double>(d.points_elsewhere ? 0 : (size_t)k.a_width * d.N);
+        b = c.take<double>(d.points_elsewhere ? 0 : (size_t)k.b_width * d.N); K1 = c.take<double>(16); K2 = c.take<double>(16);
         logc_n = c.take<float>(d.N + 1, 8); logc_k = c.take<float>(d.N + 1, 8); state = c.take_bytes(2 * d.state_bytes, 8);
         c.take<double>(0);
         bytes = c.bytes() - at;
@@ -195,9 +197,10 @@ struct AcrDev {
     double* models; void* hyp; uint32_t *sorted, *best, *index; void* result; uint8_t* mask; double* ref;
     void carve(Carve& c, const AcrDims& d)
     {
-        const size_t slots = 2 * d.batch * (size_t)(d.kind == 1 ? 10 : 4);      // per iteration 10 (E) or 4 model slots between the parity copies
+        const AcrKindInfo k = acr_kind(d.kind);
+        const size_t slots = 2 * d.batch * (size_t)k.slots;                    // (the parity copies)
         in.carve(c, d);
-        models = c.take<double>(slots * d.md); hyp = c.take_bytes(d.hyp_bytes * slots, 8);
+        models = c.take<double>(slots * (size_t)k.md); hyp = c.take_bytes(d.hyp_bytes * slots, 8);
         sorted = c.take<uint32_t>(slots * d.N, 8); best = c.take<uint32_t>(d.N, 8); index = c.take<uint32_t>(d.N, 8);
         result = c.take_bytes(d.result_bytes, 8); mask = c.take<uint8_t>(d.N, 8); ref = (double*)c.take_bytes(d.ref_bytes, 8);
         c.take<double>(16);

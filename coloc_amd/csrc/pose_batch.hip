@@ -16,6 +16,9 @@
 
 using namespace clc;
 
+// a switch over AcrKindId that lacks a kind does not compile (set_problem, after_rounds, model_out)
+#pragma clang diagnostic error "-Wswitch"
+
 namespace {
 
 // log10 C(n, k) and log10 C(k, m), k = 0..n, as OpenMVG tabulates them: a FLOAT log10 table, float accumulation
@@ -49,42 +52,49 @@ void acr_tables(int n, int m, float* logc_n, float* logc_k, std::vector<float>& 
     }
 }
 
-// kind 0: a = X (3 N), b = x (2 N), K1 = intrinsics; kind 1: a = x1, b = x2 (2 N each), K1 / K2, image 2 of img_w x img_h;
-// kinds 2 / 3 (round 6: RobustMatcher's 'F' / 'H' models, RobustMatcher.hpp:128-151, :188-239): a = x1, b = x2 in pixels, both images
-// img_w x img_h -- the points are conditioned by the image size on their way into the pinned block (ACKernelAdaptor), the rounds are
-// the resection's one-launch rounds with the seven-point / four-point solve in place of P3P, the model is brought back to pixels in finish().
-// kind 4 (the 3-D similarity NEW -> OLD of sim3_math.h, the project's own statement): a = X_new, b = X_old (3 N each), no camera, no image;
-// residuals in old-map units, alpha = the unit ball over the bounding box of b (box: from the caller where the points are on the device),
-// exponent 1.5; behind the rounds ONE launch applies the acceptance rule and refits (launch_sim3_refit), its record is `sim`.
-// h_model: 12 doubles [R|t] (kind 0), {E (9), F (9)} (kind 1), F or H (9, pixels; kinds 2 / 3), [sR|t] (kind 4).
-//
-// One a-contrario solve as a small state machine (round 4): begin() validates and prepares the inputs and the problem, poll() looks at the
-// pinned progress word ONCE and reports whether the run needs another round -- or moves on to the refinement, whose record it then polls
-// the same way --, finish() copies the result out.  What goes into the stream of the solve's rounds is acr_drive's.
+// The identity a similarity solve reports where it finds no model: s = 1, R = I, t = 0, A = [I | 0]
+Sim3Out sim3_identity()
+{
+    Sim3Out o{};
+    o.s = 1.0; o.R[0] = o.R[4] = o.R[8] = 1.0; o.A[0] = o.A[5] = o.A[10] = 1.0;
+    return o;
+}
+
+// The Huber constant of the refinement behind a pose: the caller's, 16 where it names none; -1: no refinement
+double refine_huber_of(const bool refine, const double huber_a) { return refine ? (huber_a > 0.0 ? huber_a : 16.0) : -1.0; }
+
+// One a-contrario solve as a small state machine: begin() validates and prepares the inputs and the problem, poll() looks at the pinned
+// progress word ONCE and reports whether the run needs another round -- or moves on to what runs behind the rounds, whose record it then
+// polls the same way --, finish() copies the result out.  What goes into the stream of the solve's rounds is acr_drive's.
+// kind: an AcrKindId.  What a | b hold and what the solve needs is its row of acr_kind() (acr_kind.h); begin / poll / finish hold what is
+// the same for every kind, and what differs is ONE switch each, a case per kind and no default: set_problem() (alpha, norm, what the
+// problem carries by value), after_rounds() (nothing, the pose refinement, the similarity's refit), model_out() (how the model leaves).
+// h_model: 12 doubles [R|t] (resection), [sR|t] (similarity); 18 for the two-view kinds, the model matrix and then the fundamental matrix
+// that goes with it: { E, F }, { F, F }, { H, zeros }, in pixels.
 struct AcrRun {
     // arguments
     clc_ctx* ctx = nullptr;
-    int kind = 0, N = 0, img_w = 0, img_h = 0, max_iteration = 0;
+    int kind = kAcrResection, N = 0, img_w = 0, img_h = 0, max_iteration = 0;
     const double *h_a = nullptr, *h_b = nullptr, *h_K1 = nullptr, *h_K2 = nullptr;
-    // a | b from device memory: X | x of the track block (kind 0) or x1 | x2 in pixels of the pair block (kinds 1-3) of gather.hip;
-    // they are staged from these blocks -- kinds 2 / 3 conditioned by the staging launch --, h_a / h_b unused
+    // a | b from device memory: X | x of the track block (resection) or x1 | x2 in pixels of the pair block (two-view kinds) of gather.hip;
+    // they are staged from these blocks -- conditioned by the staging launch where the kind is --, h_a / h_b unused
     const double *dev_a = nullptr, *dev_b = nullptr;
     uint64_t seed = 0;
     double precision = 0.0, refine_huber = -1.0;
     double* h_model = nullptr; uint8_t* h_mask = nullptr; int32_t* h_inliers = nullptr;
     int *n_inliers = nullptr, *iterations = nullptr, *rounds = nullptr;
     double *error_max = nullptr, *min_nfa = nullptr, *h_cov = nullptr, *rmse = nullptr;
-    Sim3Out* sim = nullptr;           // kind 4: the reported similarity (out); box: { min, max } of b where the points are the device's
+    Sim3Out* sim = nullptr;           // similarity: the reported one (out); box: { min, max } of b where the points are the device's
     const double* box = nullptr;      // (dev_a / dev_b: read in place by the rounds and the refit, not staged)
     int* valid = nullptr;
     // state
     enum Phase { IDLE, ROUNDS, REFINE, DONE } phase = IDLE;
     int status = CLC_OK;
-    int m = 0, M = 0, md = 0;
     bool refine = false;
     AcrProblem pb{};
-    tv::Normalizer norm_t{};          // kinds 2, 3: the conditioning of both point sets
+    tv::Normalizer norm_t{};          // the conditioned kinds: the conditioning of both point sets
     hipStream_t st = nullptr;         // the stream of the solve's rounds (its group's: acr_drive)
+    hipStream_t after_st = nullptr;   // the stream of what runs behind the rounds (after_rounds)
     int bound = 0, first_bound = 0, reserve0 = 0;
     uint32_t round = 0, spins = 0;
     std::chrono::steady_clock::time_point wait_start;
@@ -96,7 +106,7 @@ struct AcrRun {
     int32_t* p_inl = nullptr;
     RefineOut* p_ref = nullptr;
     Sim3Out* p_sim = nullptr; Sim3Out* d_sim = nullptr;
-    int32_t* ready = nullptr;         // what the REFINE phase polls: the refinement's / the refit's flag
+    int32_t* ready = nullptr;         // what the REFINE phase polls: the flag of the record of what runs behind the rounds
     double *d_a = nullptr, *d_b = nullptr, *d_K1 = nullptr, *d_K2 = nullptr, *d_models = nullptr, *d_ref = nullptr;
     AcrState* d_state = nullptr; AcrHyp* d_hyp = nullptr;
     uint32_t *d_sorted = nullptr, *d_best = nullptr, *d_index = nullptr;
@@ -111,57 +121,92 @@ struct AcrRun {
     // evaluates.  Returns a status; phase == DONE afterwards means there is nothing to wait for.
     int begin(const int cap)
     {
-        static const int k_m[5] = { 3, 5, 7, 4, 3 }, k_M[5] = { 4, 10, 3, 1, 1 }, k_md[5] = { 12, 18, 12, 12, 12 };
-        if (kind < 0 || kind > 4) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: unknown model"));
-        m = k_m[kind]; M = k_M[kind]; md = k_md[kind];
-        const int ad = kind == 0 || kind == 4 ? 3 : 2;
-        if (!ctx || N < 0 || max_iteration < 0 || (kind <= 1 && !h_K1) || (kind == 1 && !h_K2) || (N > 0 && !(dev_a && dev_b) && (!h_a || !h_b)) ||
-            ((dev_a || dev_b) && (!dev_a || !dev_b)) || (kind == 4 && dev_a && !box))
+        if (!acr_is_kind(kind)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: unknown model"));
+        const AcrKindInfo k = acr_kind(kind);
+        if (!ctx || N < 0 || max_iteration < 0 || (k.needs_K1 && !h_K1) || (k.needs_K2 && !h_K2) || (N > 0 && !(dev_a && dev_b) && (!h_a || !h_b)) ||
+            ((dev_a || dev_b) && (!dev_a || !dev_b)) || (k.in_place && dev_a && !box))
             return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: bad argument"));
-        if (kind == 0 && !pose_K_ok(h_K1)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }"));
+        if (kind == kAcrResection && !pose_K_ok(h_K1)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: K must be { fx, skew, cx; 0, fy, cy; 0, 0, 1 }"));
         if (n_inliers) *n_inliers = 0;
         if (error_max) *error_max = 0.0;
         if (min_nfa) *min_nfa = INFINITY;
         if (iterations) *iterations = 0;
         if (rounds) *rounds = 0;
         if (valid) *valid = -1;
-        if (sim) {
-            *sim = Sim3Out{};
-            sim->s = 1.0; sim->R[0] = sim->R[4] = sim->R[8] = 1.0; sim->A[0] = sim->A[5] = sim->A[10] = 1.0;
-        }
+        if (sim) *sim = sim3_identity();
         if (h_mask && N > 0) memset(h_mask, 0, (size_t)N);
-        if (N <= m || max_iteration == 0) return stop(CLC_OK);                 // ACRANSAC: nData <= sizeSample -> (0, 0), no model
+        if (N <= k.m || max_iteration == 0) return stop(CLC_OK);                 // ACRANSAC: nData <= sizeSample -> (0, 0), no model
         if (N > kAcrMaxN) return stop(fail(ctx, CLC_ERR_CAPACITY, "acransac: more than 16384 correspondences per solve"));
         if (max_iteration > 500000) return stop(fail(ctx, CLC_ERR_CAPACITY, "acransac: more than 500000 iterations"));
-        if (kind >= 1 && kind <= 3 && (img_w <= 0 || img_h <= 0)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: image size needed for the two-view models"));
+        if (k.needs_image && (img_w <= 0 || img_h <= 0)) return stop(fail(ctx, CLC_ERR_BAD_ARG, "acransac: image size needed for the two-view models"));
         phase = DONE; status = CLC_ERR_HIP;                                     // (what an early CLC_HIP return leaves behind)
         batch_cap = cap;
-        const int rc0 = begin_body(ad);
+        const int rc0 = begin_body(k);
         if (rc0 != CLC_OK) { phase = DONE; status = rc0; }
         return rc0;
     }
 
-    int begin_body(const int ad)
+    // The part of the problem that differs by kind: logalpha0 and norm (mult is the table's), what the problem carries by value, the
+    // conditioning.  From the image size, K1 and the box.  False: the kind admits no alpha here, hence no model.
+    bool set_problem()
     {
-        CLC_HIP(ctx, hipSetDevice(ctx->device));
-        refine = kind == 0 && refine_huber > 0.0;
-        // the device workspace and the pinned block (AcrDev, AcrPin: the inputs, staged by one launch, lie alike in both).  A round's
-        // launches read what the round before them wrote: two copies of state, models, slots and sorted lists, indexed by launch parity
-        // (acransac.hip: acr_round_kernel, acr_solve5_kernel)
-        double V = 0.0;
-        if (kind == 4) {
-            // the box of the old points: a flat or unbounded one admits no alpha, hence no model
+        const double D = sqrt((double)img_w * (double)img_w + (double)img_h * (double)img_h), A = (double)img_w * (double)img_h;
+        pb.mult = acr_kind(kind).mult;
+        pb.norm = 1.0;
+        switch ((AcrKindId)kind) {
+        case kAcrResection:
+            // ACKernelAdaptorResection_Intrinsics: residuals on the normalised camera plane (x 1 / focal), logalpha0 = log10(pi)
+            pb.logalpha0 = clc_acr_log10(M_PI);
+            pb.norm = 1.0 / h_K1[0];
+            for (int e = 0; e < 9; ++e) pb.K1v[e] = h_K1[e];
+            return true;
+        case kAcrEssential:
+            // ACKernelAdaptorEssential: point-to-line, logalpha0 = log10(2 D / A * 0.5) of image 2, error^(1/2)
+            pb.logalpha0 = clc_acr_log10(2.0 * D / A * .5);
+            return true;
+        case kAcrFundamental:
+            // ACKernelAdaptor on conditioned points (NormalizePoints(x, &x_, &N_, w, h), x_n = d x + t, for both point sets): point-to-line,
+            // log10(2 D / A / N2(0,0)), error^(1/2); thresholds and the reported precision scale with N2(0,0) = d
+            norm_t = tv::normalizer(img_w, img_h);
+            pb.norm = norm_t.d;
+            pb.logalpha0 = clc_acr_log10(2.0 * D / A / pb.norm);
+            return true;
+        case kAcrHomography:
+            // as the fundamental, point-to-point: log10(pi / A / N2(0,0)^2)
+            norm_t = tv::normalizer(img_w, img_h);
+            pb.norm = norm_t.d;
+            pb.logalpha0 = clc_acr_log10(M_PI / A / (pb.norm * pb.norm));
+            return true;
+        case kAcrSimilarity: {
+            // a squared distance in old-map units against the box of the old points: log10(((4 / 3) pi) / V), error^(3/2); a flat or
+            // unbounded box admits no alpha
             double bx[6];
             if (dev_a) memcpy(bx, box, sizeof bx);
             for (int q = 0; q < 3 && !dev_a; ++q) {
                 bx[q] = bx[3 + q] = h_b[q];
                 for (int i = 1; i < N; ++i) { const double v = h_b[3 * i + q]; bx[q] = v < bx[q] ? v : bx[q]; bx[3 + q] = v > bx[3 + q] ? v : bx[3 + q]; }
             }
-            V = sim3_box_volume(bx);
-            if (!sim3_volume_ok(V)) return stop(CLC_OK);
+            const double V = sim3_box_volume(bx);
+            if (!sim3_volume_ok(V)) return false;
+            pb.logalpha0 = clc_acr_log10(sim3_alpha0(V));
+            return true;
         }
-        const AcrDims dims{ kind, (size_t)N, (size_t)md, sizeof(AcrState), sizeof(AcrHyp), sizeof(AcrResult),
-                            kind == 4 ? sizeof(Sim3Out) : (refine ? sizeof(RefineOut) : 0), (size_t)kAcrMaxBatch, kind == 4 && dev_a != nullptr };
+        case kAcrKindCount: break;
+        }
+        return false;
+    }
+
+    int begin_body(const AcrKindInfo& k)
+    {
+        CLC_HIP(ctx, hipSetDevice(ctx->device));
+        refine = kind == kAcrResection && refine_huber > 0.0;
+        pb = AcrProblem{};
+        if (!set_problem()) return stop(CLC_OK);
+        // the device workspace and the pinned block (AcrDev, AcrPin: the inputs, staged by one launch, lie alike in both).  A round's
+        // launches read what the round before them wrote: two copies of state, models, slots and sorted lists, indexed by launch parity
+        // (acransac.hip: acr_round_kernel, acr_solve5_kernel).  ref: the record of what after_rounds() launches
+        const AcrDims dims{ kind, (size_t)N, sizeof(AcrState), sizeof(AcrHyp), sizeof(AcrResult),
+                            kind == kAcrSimilarity ? sizeof(Sim3Out) : (refine ? sizeof(RefineOut) : 0), (size_t)kAcrMaxBatch, k.in_place && dev_a != nullptr };
         AcrDev dv; AcrPin pin;
         int rc = ensure_pnp(ctx, [&](Carve& c) { dv.carve(c, dims); });
         if (rc == CLC_OK) rc = ensure_pinned(ctx, [&](Carve& c) { pin.carve(c, dims); });
@@ -172,24 +217,18 @@ struct AcrRun {
         d_state = (AcrState*)dv.in.state; d_models = dv.models; d_hyp = (AcrHyp*)dv.hyp; d_sorted = dv.sorted; d_best = dv.best; d_index = dv.index;
         d_res = (AcrResult*)dv.result; d_mask = dv.mask; d_ref = dv.ref;
         double* hp = pin.in.a;
-        if (kind == 2 || kind == 3) {
-            // ACKernelAdaptor: NormalizePoints(x, &x_, &N_, w, h) for both point sets (x_n = d x + t, oracle/clc_oracle_twoview.c orc_tv_normalize)
+        if (!dev_a && k.conditioned) {
             // (points from device memory: the staging launch applies the same two operations, launch_acr_stage's cond)
-            norm_t = tv::normalizer(img_w, img_h);
-            double* q1 = pin.in.a;
-            double* q2 = pin.in.b;
-            for (int i = 0; i < N && !dev_a; ++i) {
-                q1[2 * i] = h_a[2 * i] * norm_t.d + norm_t.tx; q1[2 * i + 1] = h_a[2 * i + 1] * norm_t.d + norm_t.ty;
-                q2[2 * i] = h_b[2 * i] * norm_t.d + norm_t.tx; q2[2 * i + 1] = h_b[2 * i + 1] * norm_t.d + norm_t.ty;
-            }
+            tv::condition(norm_t, h_a, N, pin.in.a);
+            tv::condition(norm_t, h_b, N, pin.in.b);
         } else if (!dev_a) {
-            memcpy(pin.in.a, h_a, sizeof(double) * ad * N);
-            memcpy(pin.in.b, h_b, sizeof(double) * (kind == 4 ? 3 : 2) * N);
+            memcpy(pin.in.a, h_a, sizeof(double) * k.a_width * N);
+            memcpy(pin.in.b, h_b, sizeof(double) * k.b_width * N);
         }
         memset(pin.in.K1, 0, sizeof(double) * 32);                     // (K1 | K2)
         if (h_K1) memcpy(pin.in.K1, h_K1, sizeof(double) * 9);
         if (h_K2) memcpy(pin.in.K2, h_K2, sizeof(double) * 9);
-        acr_tables(N, m, pin.in.logc_n, pin.in.logc_k, ctx->acr_lg);
+        acr_tables(N, k.m, pin.in.logc_n, pin.in.logc_k, ctx->acr_lg);
         // the state ACRANSAC starts from is part of the upload (every round draws its own samples on the device)
         AcrState* h_states = (AcrState*)pin.in.state;
         memset(h_states, 0, 2 * sizeof(AcrState));
@@ -207,35 +246,9 @@ struct AcrRun {
         p_sim = (Sim3Out*)pin.ref; d_sim = (Sim3Out*)dv.ref;
         __atomic_store_n(h_word, 0ull, __ATOMIC_RELAXED);
 
-        pb = AcrProblem{};
-        pb.kind = kind; pb.n = N; pb.m = m; pb.max_models = M; pb.model_doubles = md; pb.batch_cap = batch_cap;
+        pb.kind = kind; pb.n = N; pb.m = k.m; pb.max_models = k.M; pb.model_doubles = k.md; pb.batch_cap = batch_cap;
         pb.a = d_a; pb.b = d_b; pb.K1 = d_K1; pb.K2 = d_K2; pb.logc_n = d_cn; pb.logc_k = d_ck;
-        pb.loge0 = clc_acr_log10((double)M * (double)(N - m));
-        if (kind == 0) {
-            // ACKernelAdaptorResection_Intrinsics: residuals on the normalised camera plane (x 1 / focal), logalpha0 = log10(pi)
-            pb.logalpha0 = clc_acr_log10(M_PI);
-            pb.mult = 1.0;
-            pb.norm = 1.0 / h_K1[0];
-            for (int e = 0; e < 9; ++e) pb.K1v[e] = h_K1[e];
-        } else if (kind == 1) {
-            // ACKernelAdaptorEssential: point-to-line, logalpha0 = log10(2 D / A * 0.5) of image 2, error^(1/2)
-            const double D = sqrt((double)img_w * (double)img_w + (double)img_h * (double)img_h), A = (double)img_w * (double)img_h;
-            pb.logalpha0 = clc_acr_log10(2.0 * D / A * .5);
-            pb.mult = 0.5;
-            pb.norm = 1.0;
-        } else if (kind == 4) {
-            // a squared distance in old-map units against the box of the old points: log10(((4 / 3) pi) / V), error^(3/2)
-            pb.logalpha0 = clc_acr_log10(sim3_alpha0(V));
-            pb.mult = 1.5;
-            pb.norm = 1.0;
-        } else {
-            // ACKernelAdaptor on conditioned points: 'F' point-to-line, log10(2 D / A / N2(0,0)), error^(1/2); 'H' point-to-point,
-            // log10(pi / A / N2(0,0)^2); thresholds and the reported precision scale with N2(0,0) = d
-            const double D = sqrt((double)img_w * (double)img_w + (double)img_h * (double)img_h), A = (double)img_w * (double)img_h;
-            pb.norm = norm_t.d;
-            if (kind == 2) { pb.logalpha0 = clc_acr_log10(2.0 * D / A / pb.norm); pb.mult = 0.5; }
-            else { pb.logalpha0 = clc_acr_log10(M_PI / A / (pb.norm * pb.norm)); pb.mult = 1.0; }
-        }
+        pb.loge0 = clc_acr_log10((double)k.M * (double)(N - k.m));
         pb.max_threshold = std::isinf(precision) ? INFINITY : precision * (pb.norm * pb.norm);
         pb.seed = seed;
 
@@ -270,8 +283,47 @@ struct AcrRun {
         wait_start = std::chrono::steady_clock::now();
     }
 
-    // One look at the progress word / the refinement's ready flag; enqueues no round.  prof: where the end of the rounds is marked (null:
-    // nowhere).  Returns the status; phase == DONE when the solve has ended.
+    // What runs behind the rounds, behind the word that said "done": nothing (the solve has ended), or ONE launch whose pinned record sets
+    // `ready` last -- the host polls that instead of synchronising after_st (~5 us), with the synchronisation as the fallback after 5 ms.
+    int after_rounds()
+    {
+        hipError_t e = hipSuccess;
+        const char* what = "";
+        switch ((AcrKindId)kind) {
+        case kAcrResection:
+            if (!refine) { phase = DONE; return CLC_OK; }
+            // The pose refinement, on the run's own context's stream: behind the launch that completed the run when the rounds ran there
+            // (nothing is queued behind that launch any more: the word of the last round comes out of the last launch); a shared group's
+            // stream still carries the other solves' rounds, and what the refinement reads was written before the word the host has just
+            // seen -- system-scope release / acquire --, so the launch needs no ordering against it.
+            ready = &p_ref->ready; after_st = ctx->stream; what = "launch_pnp_refine";
+            __atomic_store_n(ready, 0, __ATOMIC_RELAXED);
+            e = launch_pnp_refine((const double*)d_res /* AcrResult.model = [R|t] */, d_a, d_b, d_mask, N, d_K1, refine_huber, 50, d_ref, after_st,
+                                  &ctx->prof, &d_res->valid, p_ref);
+            break;
+        case kAcrEssential:
+        case kAcrFundamental:
+        case kAcrHomography:
+        case kAcrKindCount:             // (no kind: begin() has refused it)
+            phase = DONE;
+            return CLC_OK;
+        case kAcrSimilarity:
+            // the acceptance rule and the refit: one single-workgroup launch on the rounds' stream, behind the round enqueued ahead (it
+            // reads the result record and the mask of the completing round, and uses the index set as its list)
+            ready = &p_sim->ready; after_st = st; what = "launch_sim3_refit";
+            __atomic_store_n(ready, 0, __ATOMIC_RELAXED);
+            e = launch_sim3_refit(d_res, d_mask, d_a, d_b, N, (int32_t*)d_index, d_sim, p_sim, after_st);
+            break;
+        }
+        if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, what, e));
+        spins = 0;
+        wait_start = std::chrono::steady_clock::now();
+        phase = REFINE;
+        return CLC_OK;
+    }
+
+    // One look at the progress word / the ready flag of what runs behind the rounds; enqueues no round.  prof: where the end of the rounds
+    // is marked (null: nowhere).  Returns the status; phase == DONE when the solve has ended.
     int poll(Profiler* prof)
     {
         if (phase == ROUNDS) {
@@ -301,40 +353,12 @@ struct AcrRun {
             // The result record, mask and inlier list were written by the round that completed the run BEFORE its word (system-scope
             // release / acquire): no finish launch, and without refinement no stream synchronisation either -- the round enqueued ahead is
             // still in the stream, evaluates nothing and touches no host memory; anything enqueued later on this stream is ordered behind it.
-            if (kind == 4) {
-                // the acceptance rule and the refit: one single-workgroup launch on the rounds' stream, behind the round enqueued ahead
-                // (it reads the result record and the mask of the completing round, and uses the index set as its list); its pinned
-                // record is polled like the refinement's
-                __atomic_store_n(&p_sim->ready, 0, __ATOMIC_RELAXED);
-                const hipError_t e = launch_sim3_refit(d_res, d_mask, d_a, d_b, N, (int32_t*)d_index, d_sim, p_sim, st);
-                if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "launch_sim3_refit", e));
-                ready = &p_sim->ready;
-                spins = 0;
-                wait_start = std::chrono::steady_clock::now();
-                phase = REFINE;
-                return CLC_OK;
-            }
-            if (!refine) { phase = DONE; return CLC_OK; }
-            // On the run's own context's stream: behind the launch that completed the run when the rounds ran there (nothing is queued
-            // behind that launch any more: the word of the last round comes out of the last launch); a shared group's stream still carries
-            // the other solves' rounds, and what the refinement reads was written before the word the host has just seen -- system-scope
-            // release / acquire --, so the launch needs no ordering against it.  The refinement writes its record into pinned memory and
-            // sets `ready` last; the host polls that instead of synchronising the stream (~5 us), with the synchronisation as the fallback
-            // after 5 ms.
-            __atomic_store_n(&p_ref->ready, 0, __ATOMIC_RELAXED);
-            const hipError_t e = launch_pnp_refine((const double*)d_res /* AcrResult.model = [R|t] */, d_a, d_b, d_mask, N, d_K1, refine_huber, 50,
-                                                   d_ref, ctx->stream, &ctx->prof, &d_res->valid, p_ref);
-            if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "launch_pnp_refine", e));
-            ready = &p_ref->ready;
-            spins = 0;
-            wait_start = std::chrono::steady_clock::now();
-            phase = REFINE;
-            return CLC_OK;
+            return after_rounds();
         }
         if (phase == REFINE) {
             if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == 0) {
                 if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - wait_start > std::chrono::milliseconds(5)) {
-                    const hipError_t e = hipStreamSynchronize(kind == 4 ? st : ctx->stream);
+                    const hipError_t e = hipStreamSynchronize(after_st);
                     if (e != hipSuccess) return drained(fail(ctx, CLC_ERR_HIP, "hipStreamSynchronize(refine stream)", e));
                     if (__atomic_load_n(ready, __ATOMIC_ACQUIRE) == 0) return drained(fail(ctx, CLC_ERR_HIP, "acransac: refinement did not complete"));
                 } else return CLC_OK;
@@ -344,26 +368,51 @@ struct AcrRun {
         return status;
     }
 
+    // The model as the run leaves it, into h_model (nullable; AcrRun's head says what each kind leaves); r: the run's record, which a
+    // kind may still amend
+    void model_out(AcrResult& r)
+    {
+        const size_t m9 = sizeof(double) * 9;
+        switch ((AcrKindId)kind) {
+        case kAcrResection:
+            if (h_model) memcpy(h_model, r.model, sizeof(double) * 12);
+            return;
+        case kAcrEssential:
+            if (h_model) { memcpy(h_model, r.model + 9, m9); memcpy(h_model + 9, r.model, m9); }      // the slots hold { F, E }
+            return;
+        case kAcrFundamental:
+            // Unnormalize(&model): F = N2^T Fn N1 (no model: zeros); it is its own fundamental matrix
+            if (!h_model) return;
+            if (r.n_inliers > 0) tv::unnormalize(false, norm_t, r.model, h_model);
+            else memset(h_model, 0, m9);
+            memcpy(h_model + 9, h_model, m9);
+            return;
+        case kAcrHomography:
+            // Unnormalize(&model): H = N2^-1 Hn N1 (no model: zeros); no fundamental matrix goes with it
+            if (!h_model) return;
+            if (r.n_inliers > 0) tv::unnormalize(true, norm_t, r.model, h_model);
+            else memset(h_model, 0, m9);
+            memset(h_model + 9, 0, m9);
+            return;
+        case kAcrSimilarity: {
+            // what the refit launch decided: not accepted = no model, no inliers (min_nfa and the iterations stay the run's)
+            const Sim3Out o = *p_sim;
+            if (!o.found) { r.n_inliers = 0; r.error_max = 0.0; r.valid = -1; }
+            if (sim) { *sim = o; sim->ready = 0; }
+            if (h_model) memcpy(h_model, o.A, sizeof o.A);
+            return;
+        }
+        case kAcrKindCount: return;
+        }
+    }
+
     // after phase == DONE with status CLC_OK and a run that was started: the result into the caller's buffers
     void finish()
     {
         if (status != CLC_OK || !h_res) return;
         AcrResult r = *h_res;
-        if (kind == 4) {
-            // what the refit launch decided: not accepted = no model, no inliers (min_nfa and the iterations stay the run's)
-            const Sim3Out o = *p_sim;
-            if (!o.found) { r.n_inliers = 0; r.error_max = 0.0; r.valid = -1; }
-            if (sim) { *sim = o; sim->ready = 0; }
-            if (h_model) memcpy(h_model, o.A, sizeof(double) * 12);
-            if (valid) *valid = r.valid;
-        } else if (h_model) {
-            if (kind == 0) memcpy(h_model, r.model, sizeof(double) * 12);
-            else if (kind >= 2) {
-                // Unnormalize(&model): F = N2^T Fn N1, H = N2^-1 Hn N1 (no model: zeros stay zeros)
-                if (r.n_inliers > 0) tv::unnormalize(kind == 3, norm_t, r.model, h_model);
-                else memset(h_model, 0, sizeof(double) * 9);
-            } else { memcpy(h_model, r.model + 9, sizeof(double) * 9); memcpy(h_model + 9, r.model, sizeof(double) * 9); }   // slots hold {F, E}
-        }
+        model_out(r);
+        if (valid) *valid = r.valid;
         // the mask is rebuilt from the inlier list here (h_mask was cleared above): the device does not push N bytes + one scattered byte
         // per inlier over PCIe for it
         if (h_mask) for (int i = 0; i < r.n_inliers; ++i) h_mask[p_inl[i]] = 1;
@@ -423,10 +472,10 @@ struct AcrGroup {
             for (int i = 0; i < n; ++i) {
                 const AcrRun* r = live[k + i];
                 src[i] = r->stage_src; dst[i] = r->stage_dst; cnt[i] = r->stage_n;
-                const bool in_place = r->kind == 4;                  // (the similarity's device points are not staged)
-                da[i] = in_place ? nullptr : r->dev_a; db[i] = in_place ? nullptr : r->dev_b; nc[i] = r->N;
-                aw[i] = r->kind == 0 ? 3 : 2;
-                const bool cnd = r->kind >= 2 && r->dev_a;
+                const AcrKindInfo kd = acr_kind(r->kind);
+                da[i] = kd.in_place ? nullptr : r->dev_a; db[i] = kd.in_place ? nullptr : r->dev_b; nc[i] = r->N;      // (in place: not staged)
+                aw[i] = kd.a_width;
+                const bool cnd = kd.conditioned && r->dev_a;
                 cond[i][0] = cnd ? r->norm_t.d : 0.0; cond[i][1] = cnd ? r->norm_t.tx : 0.0; cond[i][2] = cnd ? r->norm_t.ty : 0.0;
             }
             const hipError_t e = launch_acr_stage(src, dst, cnt, n, st, da, db, nc, aw, cond);
@@ -513,14 +562,15 @@ struct AcrGroup {
 // the device at a time); in lockstep eight poses are ~12 launches, but each carries every solve's speculative slots -- 8 x 32 iterations x 4
 // models of 1 024 threads do not fit the chip at once (33 us per round against 17.5) -- hence the cap on a round's iterations, which costs
 // rounds.  The two-view round is a 44 us chain of dependent fp64 steps in ONE wave per iteration: eight chains' solves in one launch cost
-// what one costs.  Default: lockstep for two-view batches of four or more (rounds of <= 12 iterations) and resection batches of eight or
-// more (<= 8); CLC_ACR_LOCKSTEP=1 / =0 forces it on (any batch of two or more) / off for both kinds, CLC_ACR_BATCH_CAP the iterations.
+// what one costs.  Default (acr_kind()'s lockstep_from / lockstep_cap): lockstep for essential batches of four or more (rounds of <= 12
+// iterations) and batches of eight or more of the one-launch kinds (<= 8); CLC_ACR_LOCKSTEP=1 / =0 forces it on (any batch of two or
+// more) / off for every kind, CLC_ACR_BATCH_CAP the iterations.
 bool acr_lockstep(const int kind, const int n_jobs)
 {
     static const int mode = [] { const char* e = getenv("CLC_ACR_LOCKSTEP"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
     if (n_jobs < 2 || mode == 0) return false;
     if (mode == 1) return true;
-    return kind == 1 ? n_jobs >= 4 : n_jobs >= 8;      // (kinds 2, 3 run the resection's one-launch rounds: its break-even)
+    return n_jobs >= acr_kind(kind).lockstep_from;     // (the one-launch rounds share the resection's break-even)
 }
 
 // Every run to its end from ONE host thread.  shared: the runs are ONE group on the first run's context's stream (a lockstep batch);
@@ -537,7 +587,7 @@ void acr_drive(AcrRun* runs, const int n, const bool shared)
         AcrRun& r = runs[i];
         AcrGroup& g = groups[shared ? 0 : (size_t)i];
         g.shared = shared;
-        int cap = shared ? (r.kind == 1 ? 12 : 8) : kAcrMaxBatch;      // (a shared launch carries every chain's speculative slots: shorter rounds)
+        int cap = shared ? acr_kind(r.kind).lockstep_cap : kAcrMaxBatch;      // (a shared launch carries every chain's speculative slots: shorter rounds)
         if (const char* e = getenv("CLC_ACR_BATCH_CAP")) { const int v = atoi(e); if (v >= 1 && v <= kAcrMaxBatch) cap = v; }
         (void)r.begin(cap);
         if (r.phase == AcrRun::ROUNDS) g.live.push_back(&r);
@@ -581,7 +631,7 @@ int clc_pnp_acransac(clc_ctx* ctx, const double* h_X, const double* h_x, int N, 
 {
     if (h_Rt) memset(h_Rt, 0, sizeof(double) * 12);
     AcrRun run;
-    run.ctx = ctx; run.kind = 0; run.h_a = h_X; run.h_b = h_x; run.N = N; run.h_K1 = h_K;
+    run.ctx = ctx; run.kind = kAcrResection; run.h_a = h_X; run.h_b = h_x; run.N = N; run.h_K1 = h_K;
     run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
     run.h_model = h_Rt; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
     run.min_nfa = min_nfa; run.iterations = iterations;
@@ -596,8 +646,8 @@ int clc_pnp_localize_ac(clc_ctx* ctx, const double* h_X, const double* h_x, int 
     if (h_cov) memset(h_cov, 0, sizeof(double) * 36);
     if (rmse) *rmse = 0.0;
     AcrRun run;
-    run.ctx = ctx; run.kind = 0; run.h_a = h_X; run.h_b = h_x; run.N = N; run.h_K1 = h_K;
-    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision; run.refine_huber = huber_a > 0.0 ? huber_a : 16.0;
+    run.ctx = ctx; run.kind = kAcrResection; run.h_a = h_X; run.h_b = h_x; run.N = N; run.h_K1 = h_K;
+    run.max_iteration = max_iteration; run.seed = seed; run.precision = precision; run.refine_huber = refine_huber_of(true, huber_a);
     run.h_model = h_Rt; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
     run.h_cov = h_cov; run.rmse = rmse;
     return solve_one(run);
@@ -616,13 +666,13 @@ int clc_pnp_localize_ac_batch(clc_ctx* const* ctxs, clc_pose_job* jobs, int n_jo
         if (jb.Rt) memset(jb.Rt, 0, sizeof(double) * 12);
         if (jb.cov) memset(jb.cov, 0, sizeof(double) * 36);
         jb.n_inliers = 0; jb.error_max = 0.0; jb.rmse = 0.0; jb.iterations = 0;
-        r.ctx = ctxs[i]; r.kind = 0; r.h_a = jb.X; r.h_b = jb.x; r.N = jb.n; r.h_K1 = jb.K;
+        r.ctx = ctxs[i]; r.kind = kAcrResection; r.h_a = jb.X; r.h_b = jb.x; r.N = jb.n; r.h_K1 = jb.K;
         r.max_iteration = jb.max_iteration; r.seed = jb.seed; r.precision = jb.precision;
-        r.refine_huber = jb.refine ? (jb.huber_a > 0.0 ? jb.huber_a : 16.0) : -1.0;
+        r.refine_huber = refine_huber_of(jb.refine, jb.huber_a);
         r.h_model = jb.Rt; r.h_mask = jb.inlier_mask; r.h_inliers = jb.inliers; r.n_inliers = &jb.n_inliers; r.error_max = &jb.error_max;
         r.iterations = &jb.iterations; r.h_cov = jb.cov; r.rmse = &jb.rmse;
     }
-    acr_drive(runs.data(), n_jobs, acr_lockstep(0, n_jobs));
+    acr_drive(runs.data(), n_jobs, acr_lockstep(kAcrResection, n_jobs));
     return finish_all(runs, [&](const size_t i, const int status) { jobs[i].status = status; });
 }
 
@@ -634,37 +684,35 @@ int clc_essential_acransac(clc_ctx* ctx, const double* h_x1, const double* h_x2,
                                  h_inlier_mask, h_inliers, n_inliers, error_max, min_nfa, iterations);
 }
 
-// RobustMatcher's model letter -> the solve kind (colocParams::model, RobustMatcher.hpp:399-405)
-static int two_view_kind(const int model) { return model == CLC_MODEL_ESSENTIAL ? 1 : (model == CLC_MODEL_FUNDAMENTAL ? 2 : (model == CLC_MODEL_HOMOGRAPHY ? 3 : -1)); }
-
 int clc_two_view_acransac(clc_ctx* ctx, int model, const double* h_x1, const double* h_x2, int N, const double* h_K1, const double* h_K2,
                           int img_w, int img_h, int max_iteration, uint64_t seed, double precision, double* h_M, double* h_F,
                           uint8_t* h_inlier_mask, int32_t* h_inliers, int* n_inliers, double* error_max, double* min_nfa, int* iterations)
 {
-    const int kind = two_view_kind(model);
-    if (kind < 0) return fail(ctx, CLC_ERR_BAD_ARG, "two_view_acransac: model must be 'E', 'F' or 'H'");
-    // the model as the solve leaves it: { E, F } (kind 1), F or H (kinds 2 / 3: F = the model for 'F', zeros for 'H')
+    const int kind = acr_kind_of_model(model);
+    if (!acr_is_kind(kind)) return fail(ctx, CLC_ERR_BAD_ARG, "two_view_acransac: model must be 'E', 'F' or 'H'");
+    // the model as the solve leaves it (AcrRun::model_out): the model matrix, then the fundamental matrix that goes with it
     double EF[18] = {};
     AcrRun run;
     run.ctx = ctx; run.kind = kind; run.h_a = h_x1; run.h_b = h_x2; run.N = N; run.img_w = img_w; run.img_h = img_h;
-    if (kind == 1) { run.h_K1 = h_K1; run.h_K2 = h_K2; }
+    if (acr_kind(kind).needs_K1) run.h_K1 = h_K1;
+    if (acr_kind(kind).needs_K2) run.h_K2 = h_K2;
     run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
     run.h_model = EF; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
     run.min_nfa = min_nfa; run.iterations = iterations;
     const int rc = solve_one(run);
     if (h_M) memcpy(h_M, EF, sizeof(double) * 9);
-    if (h_F) memcpy(h_F, kind == 2 ? EF : EF + 9, sizeof(double) * 9);
+    if (h_F) memcpy(h_F, EF + 9, sizeof(double) * 9);
     return rc;
 }
 
 int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const double* h_x2, int N, int img_w, int img_h, const int32_t* h_samples,
                          int S, double* h_models)
 {
-    const int kind = two_view_kind(model);
-    if (!ctx || kind < 2 || N <= 0 || S < 0 || !h_x1 || !h_x2 || img_w <= 0 || img_h <= 0 || (S > 0 && (!h_samples || !h_models)))
+    const int kind = acr_kind_of_model(model);
+    if (!ctx || (kind != kAcrFundamental && kind != kAcrHomography) || N <= 0 || S < 0 || !h_x1 || !h_x2 || img_w <= 0 || img_h <= 0 || (S > 0 && (!h_samples || !h_models)))
         return fail(ctx, CLC_ERR_BAD_ARG, "two_view_minimal: bad argument (models 'F' and 'H')");
     if (S == 0) return CLC_OK;
-    const int m = kind == 2 ? 7 : 4, M = kind == 2 ? 3 : 1;
+    const int m = acr_kind(kind).m, M = acr_kind(kind).M;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t pts = (size_t)4 * N, out = (size_t)S * M * 9;
     TwoViewMinDev dv;
@@ -672,10 +720,8 @@ int clc_two_view_minimal(clc_ctx* ctx, int model, const double* h_x1, const doub
     if (rc != CLC_OK) return rc;
     std::vector<double> q(pts);
     const tv::Normalizer t = tv::normalizer(img_w, img_h);
-    for (int i = 0; i < N; ++i) {
-        q[2 * i] = h_x1[2 * i] * t.d + t.tx; q[2 * i + 1] = h_x1[2 * i + 1] * t.d + t.ty;
-        q[(size_t)2 * N + 2 * i] = h_x2[2 * i] * t.d + t.tx; q[(size_t)2 * N + 2 * i + 1] = h_x2[2 * i + 1] * t.d + t.ty;
-    }
+    tv::condition(t, h_x1, N, q.data());
+    tv::condition(t, h_x2, N, q.data() + (size_t)2 * N);
     double* d = dv.x1;
     int32_t* d_smp = dv.samples;
     double* d_out = dv.out;
@@ -694,12 +740,12 @@ int clc_sim3_acransac(clc_ctx* ctx, const double* h_x_new, const double* h_x_old
 {
     Sim3Out o{};
     AcrRun run;
-    run.ctx = ctx; run.kind = 4; run.h_a = h_x_new; run.h_b = h_x_old; run.N = N;
+    run.ctx = ctx; run.kind = kAcrSimilarity; run.h_a = h_x_new; run.h_b = h_x_old; run.N = N;
     run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
     run.sim = &o; run.h_mask = h_inlier_mask; run.h_inliers = h_inliers; run.n_inliers = n_inliers; run.error_max = error_max;
     run.min_nfa = min_nfa; run.iterations = iterations; run.valid = valid;
     const int rc = solve_one(run);
-    if (!run.sim || o.s == 0.0) { o = Sim3Out{}; o.s = 1.0; o.R[0] = o.R[4] = o.R[8] = 1.0; o.A[0] = o.A[5] = o.A[10] = 1.0; }   // (refused before begin())
+    if (o.s == 0.0) o = sim3_identity();      // (refused before begin() reached the record)
     if (s) *s = o.s;
     if (h_R) memcpy(h_R, o.R, sizeof o.R);
     if (h_t) memcpy(h_t, o.t, sizeof o.t);
@@ -766,18 +812,18 @@ int check_batch_contexts(clc_ctx* const* ctxs, int n_jobs, const char* what)
 }
 
 
-// kind 1: E -> job.E, F -> job.F; kinds 2 / 3: the model matrix -> job.E (RelativePose_Info::essential_matrix receives it, whatever the
-// model: RobustMatcher.hpp:141, :207), and job.F = F for kind 2, zeros for kind 3
 int sim3_solve_dev(clc_ctx* ctx, const double* d_x_new, const double* d_x_old, int N, const double* box, int max_iteration, uint64_t seed,
                    double precision, Sim3Out* out, uint8_t* h_mask, int* n_inliers, double* error_max, double* min_nfa, int* iterations)
 {
     AcrRun run;
-    run.ctx = ctx; run.kind = 4; run.dev_a = d_x_new; run.dev_b = d_x_old; run.box = box; run.N = N;
+    run.ctx = ctx; run.kind = kAcrSimilarity; run.dev_a = d_x_new; run.dev_b = d_x_old; run.box = box; run.N = N;
     run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
     run.sim = out; run.h_mask = h_mask; run.n_inliers = n_inliers; run.error_max = error_max; run.min_nfa = min_nfa; run.iterations = iterations;
     return solve_one(run);
 }
 
+// The model matrix -> job.E (RelativePose_Info::essential_matrix receives it, whatever the model: RobustMatcher.hpp:141, :207), the
+// fundamental matrix that goes with it -> job.F (AcrRun::model_out)
 int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind)
 {
     std::vector<AcrRun> runs((size_t)n_jobs);
@@ -787,7 +833,7 @@ int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int 
     return finish_all(runs, [&](const size_t i, const int status) {
         jobs[i]->status = status;
         if (jobs[i]->E) memcpy(jobs[i]->E, &EF[18 * i], sizeof(double) * 9);
-        if (jobs[i]->F) memcpy(jobs[i]->F, &EF[18 * i + (kind == 2 ? 0 : 9)], sizeof(double) * 9);
+        if (jobs[i]->F) memcpy(jobs[i]->F, &EF[18 * i + 9], sizeof(double) * 9);
     });
 }
 
@@ -795,27 +841,27 @@ int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int 
 
 extern "C" {
 
-int clc_essential_acransac_batch(clc_ctx* const* ctxs, clc_two_view_job* jobs, int n_jobs)
+// who: the entry point's name, as its error text carries it
+static int two_view_batch_entry(const char* who, clc_ctx* const* ctxs, int model, clc_two_view_job* jobs, int n_jobs)
 {
-    if (n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
+    const int kind = acr_kind_of_model(model);
+    if (!acr_is_kind(kind) || n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
     if (n_jobs == 0) return CLC_OK;
-    const int rc0 = check_batch_contexts(ctxs, n_jobs, "essential_acransac_batch: every job needs a context of its own");
-    if (rc0 != CLC_OK) return rc0;
-    std::vector<clc_two_view_job*> ptr((size_t)n_jobs);
-    for (int i = 0; i < n_jobs; ++i) ptr[(size_t)i] = &jobs[i];
-    return acr_two_view_batch(ctxs, ptr.data(), n_jobs, 1);
-}
-
-int clc_two_view_acransac_batch(clc_ctx* const* ctxs, int model, clc_two_view_job* jobs, int n_jobs)
-{
-    const int kind = two_view_kind(model);
-    if (kind < 0 || n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
-    if (n_jobs == 0) return CLC_OK;
-    const int rc0 = check_batch_contexts(ctxs, n_jobs, "two_view_acransac_batch: every job needs a context of its own");
+    const int rc0 = check_batch_contexts(ctxs, n_jobs, (std::string(who) + ": every job needs a context of its own").c_str());
     if (rc0 != CLC_OK) return rc0;
     std::vector<clc_two_view_job*> ptr((size_t)n_jobs);
     for (int i = 0; i < n_jobs; ++i) ptr[(size_t)i] = &jobs[i];
     return acr_two_view_batch(ctxs, ptr.data(), n_jobs, kind);
+}
+
+int clc_essential_acransac_batch(clc_ctx* const* ctxs, clc_two_view_job* jobs, int n_jobs)
+{
+    return two_view_batch_entry("essential_acransac_batch", ctxs, CLC_MODEL_ESSENTIAL, jobs, n_jobs);
+}
+
+int clc_two_view_acransac_batch(clc_ctx* const* ctxs, int model, clc_two_view_job* jobs, int n_jobs)
+{
+    return two_view_batch_entry("two_view_acransac_batch", ctxs, model, jobs, n_jobs);
 }
 
 } // extern "C"
@@ -854,11 +900,11 @@ struct TrackPath {
     {
         K[0] = jb.cam.focal; K[2] = jb.cam.ppx; K[4] = jb.cam.focal; K[5] = jb.cam.ppy; K[8] = 1.0;      // Pinhole_Intrinsic_Radial_K3::K()
         r.h_K1 = K;
-        r.refine_huber = jb.refine ? (jb.huber_a > 0.0 ? jb.huber_a : 16.0) : -1.0;
+        r.refine_huber = refine_huber_of(jb.refine, jb.huber_a);
         r.h_model = jb.Rt; r.h_cov = jb.cov; r.rmse = &jb.rmse;
     }
     // trackedFeatures
-    static void results(Job& jb, const GatherView& v, const size_t n, int, const double*)
+    static void results(Job& jb, const GatherView& v, const size_t n, const double*)
     {
         if (jb.track_query && n) memcpy(jb.track_query, v.h_q, sizeof(int32_t) * n);
         if (jb.track_map && n) memcpy(jb.track_map, v.h_t, sizeof(int32_t) * n);
@@ -890,15 +936,16 @@ struct PairPath {
     {
         K[0] = jb.cam_a.focal; K[2] = jb.cam_a.ppx; K[4] = jb.cam_a.focal; K[5] = jb.cam_a.ppy; K[8] = 1.0;      // Pinhole_Intrinsic_Radial_K3::K()
         K[9] = jb.cam_b.focal; K[11] = jb.cam_b.ppx; K[13] = jb.cam_b.focal; K[14] = jb.cam_b.ppy; K[17] = 1.0;  // of the two cameras
-        if (kind == 1) { r.h_K1 = K; r.h_K2 = K + 9; }
+        if (acr_kind(kind).needs_K1) r.h_K1 = K;
+        if (acr_kind(kind).needs_K2) r.h_K2 = K + 9;
         r.img_w = jb.img_w; r.img_h = jb.img_h;
         r.h_model = model; r.min_nfa = &jb.min_nfa;
     }
-    // kind 1: the slots hold { E, F }; kinds 2 / 3: the model matrix, F = it ('F') or zeros ('H') -- as clc_two_view_acransac
-    static void results(Job& jb, const GatherView& v, const size_t n, const int kind, const double* model)
+    // model: the model matrix, then the fundamental matrix that goes with it (AcrRun::model_out) -- as clc_two_view_acransac
+    static void results(Job& jb, const GatherView& v, const size_t n, const double* model)
     {
         if (jb.M) memcpy(jb.M, model, sizeof(double) * 9);
-        if (jb.F && kind != 3) memcpy(jb.F, kind == 1 ? model + 9 : model, sizeof(double) * 9);
+        if (jb.F) memcpy(jb.F, model + 9, sizeof(double) * 9);
         if (jb.pair_q && n) memcpy(jb.pair_q, v.h_q, sizeof(int32_t) * n);
         if (jb.pair_t && n) memcpy(jb.pair_t, v.h_t, sizeof(int32_t) * n);
         if (jb.x1 && n) memcpy(jb.x1, v.h_a, sizeof(double) * 2 * n);
@@ -978,7 +1025,7 @@ template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typ
         jb.status = status;
         // the kernel wrote the pinned mirrors before the count came out
         const GatherView v(Path::block(ctxs[i]), Path::layout);
-        Path::results(jb, v, (size_t)std::min(Path::count(jb), std::min(jb.nq, kAcrMaxN)), kind, &models[18 * i]);
+        Path::results(jb, v, (size_t)std::min(Path::count(jb), std::min(jb.nq, kAcrMaxN)), &models[18 * i]);
     });
 }
 
@@ -987,10 +1034,10 @@ template <class Path> int gather_solve(clc_ctx* const* ctxs, const int kind, typ
 int clc::pair_filter_essential(clc_ctx* const* ctxs, clc_pair_job* jobs, const int n_jobs, const int32_t** inliers)
 {
     for (int i = 0; i < n_jobs; ++i) inliers[i] = nullptr;
-    return gather_solve<PairPath>(ctxs, 1, jobs, n_jobs, inliers);
+    return gather_solve<PairPath>(ctxs, kAcrEssential, jobs, n_jobs, inliers);
 }
 
-// The resection of the grow step (map_build.hip): ONE AcrRun filled from the context's track block as gather_solve fills it -- kind 0, no
+// The resection of the grow step (map_build.hip): ONE AcrRun filled from the context's track block as gather_solve fills it -- no
 // refinement -- and driven like every other solve.
 int clc::resect_solve(clc_ctx* ctx, const int N, const clc_camera_k3& cam, const int max_iteration, const uint64_t seed, const double precision,
                       double* Rt, int* n_inliers, double* error_max)
@@ -999,7 +1046,7 @@ int clc::resect_solve(clc_ctx* ctx, const int N, const clc_camera_k3& cam, const
     memset(Rt, 0, sizeof(double) * 12);
     const GatherView v(ctx->trk, kTrackLayout);
     AcrRun run;
-    run.ctx = ctx; run.kind = 0; run.N = N; run.dev_a = v.a; run.dev_b = v.b; run.h_K1 = K;
+    run.ctx = ctx; run.kind = kAcrResection; run.N = N; run.dev_a = v.a; run.dev_b = v.b; run.h_K1 = K;
     run.max_iteration = max_iteration; run.seed = seed; run.precision = precision;
     run.h_model = Rt; run.n_inliers = n_inliers; run.error_max = error_max;
     return solve_one(run);
@@ -1013,31 +1060,31 @@ int clc_track_localize_batch_dev(clc_ctx* const* ctxs, clc_track_job* jobs, int 
     if (n_jobs == 0) return CLC_OK;
     const int rc0 = check_batch_contexts(ctxs, n_jobs, "track_localize_batch: every job needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
-    return gather_solve<TrackPath>(ctxs, 0, jobs, n_jobs);
+    return gather_solve<TrackPath>(ctxs, kAcrResection, jobs, n_jobs);
 }
 
 int clc_track_localize_dev(clc_ctx* ctx, clc_track_job* job)
 {
     if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "track_localize: null context / job");
-    return gather_solve<TrackPath>(&ctx, 0, job, 1);
+    return gather_solve<TrackPath>(&ctx, kAcrResection, job, 1);
 }
 
 int clc_pair_filter_batch_dev(clc_ctx* const* ctxs, int model, clc_pair_job* jobs, int n_jobs)
 {
-    const int kind = two_view_kind(model);
+    const int kind = acr_kind_of_model(model);
     if (n_jobs < 0 || (n_jobs > 0 && (!ctxs || !jobs))) return CLC_ERR_BAD_ARG;
-    if (n_jobs == 0) return kind < 0 ? CLC_ERR_BAD_ARG : CLC_OK;
+    if (n_jobs == 0) return acr_is_kind(kind) ? CLC_OK : CLC_ERR_BAD_ARG;
     const int rc0 = check_batch_contexts(ctxs, n_jobs, "pair_filter_batch: every job needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
-    if (kind < 0) return fail(ctxs[0], CLC_ERR_BAD_ARG, "pair_filter_batch: model must be 'E', 'F' or 'H'");
+    if (!acr_is_kind(kind)) return fail(ctxs[0], CLC_ERR_BAD_ARG, "pair_filter_batch: model must be 'E', 'F' or 'H'");
     return gather_solve<PairPath>(ctxs, kind, jobs, n_jobs);
 }
 
 int clc_pair_filter_dev(clc_ctx* ctx, int model, clc_pair_job* job)
 {
     if (!ctx || !job) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: null context / job");
-    const int kind = two_view_kind(model);
-    if (kind < 0) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: model must be 'E', 'F' or 'H'");
+    const int kind = acr_kind_of_model(model);
+    if (!acr_is_kind(kind)) return fail(ctx, CLC_ERR_BAD_ARG, "pair_filter: model must be 'E', 'F' or 'H'");
     return gather_solve<PairPath>(&ctx, kind, job, 1);
 }
 

@@ -1,5 +1,5 @@
 // sim3_math.h -- the fp64 statements of the 3-D similarity that aligns a replaced map to the old one, host + device inline and written
-// ONCE, as map_math.h and guided_math.h are: the a-contrario round (acransac.hip, kind 4), the refit launch behind it and the host build
+// ONCE, as map_math.h and guided_math.h are: the a-contrario round (acransac.hip, kAcrSimilarity), the refit launch behind it and the host build
 // the tests hold them to (tests/host/sim3_host_lib.cpp) run the very same statements, so the device has the host's bits by construction.
 // IEEE +, -, *, / and sqrt only, contraction off: an expression is the operations written here, in this order.
 //

@@ -260,6 +260,12 @@ CLC_TV_HD void mul3(const double* A, const double* B, double* C)
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) C[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
 }
+// NormalizePoints: n points x (2 n doubles) -> out = (x * d + tx, y * d + ty), one multiplication and one addition each (the host's form;
+// acr_stage_kernel applies the same two operations to points that are the device's)
+CLC_TV_HD void condition(const Normalizer& t, const double* x, const int n, double* out)
+{
+    for (int i = 0; i < n; ++i) { out[2 * i] = x[2 * i] * t.d + t.tx; out[2 * i + 1] = x[2 * i + 1] * t.d + t.ty; }
+}
 // UnnormalizerT: F = T2^T Fn T1 (fundamental);  UnnormalizerI: H = T2^-1 Hn T1 (homography).  Both images have the same size here
 // (the reference hands params.imageSize for both, RobustMatcher.hpp:138-139, :199-201).
 CLC_TV_HD void unnormalize(const bool homography, const Normalizer& t, const double* Mn, double* M)

@@ -153,22 +153,30 @@ void gather_views()
     }
 }
 
+// the five kinds of the a-contrario solve as the kernels and copies use them (resection, E, F, H, similarity): doubles per correspondence
+// in a | b, model slots per iteration, doubles per model slot -- written out here, not read from acr_kind()
+const size_t kAcrA[5] = { 3, 2, 2, 2, 3 }, kAcrB[5] = { 2, 2, 2, 2, 3 }, kAcrSlots[5] = { 4, 10, 4, 4, 4 }, kAcrMd[5] = { 12, 18, 12, 12, 12 };
+
 void acr_in_arrays(const AcrIn& in, const AcrDims& d, Arrs& a)
 {
-    a = { arr("a", in.a, (size_t)(d.kind == 0 ? 3 : 2) * d.N), arr("b", in.b, 2 * d.N), arr("K1", in.K1, 16), arr("K2", in.K2, 16),
+    const size_t n_pts = d.points_elsewhere ? 0 : d.N;              // (points read where they lie: zero-length a | b)
+    a = { arr("a", in.a, kAcrA[d.kind] * n_pts), arr("b", in.b, kAcrB[d.kind] * n_pts), arr("K1", in.K1, 16), arr("K2", in.K2, 16),
           arr("logc_n", in.logc_n, d.N + 1, 8), arr("logc_k", in.logc_k, d.N + 1, 8), raw("state", in.state, 2 * d.state_bytes, 8) };
 }
 
 void pose_views()
 {
-    static const size_t md[4] = { 12, 18, 12, 12 };
-    for (int kind = 0; kind < 4; ++kind) for (int refine = 0; refine < 2; ++refine) for (size_t N : kCounts) for (size_t rec : kRecs) {
-        const AcrDims d{ kind, N, md[kind], rec, rec, rec, refine ? rec : 0, 128 };
-        const size_t slots = 2 * 128 * (size_t)(kind == 1 ? 10 : 4);
+    // (only the similarity reads device points in place)
+    for (int kind = 0; kind < 5; ++kind) for (int elsewhere = 0; elsewhere < (kind == 4 ? 2 : 1); ++elsewhere)
+    for (int refine = 0; refine < 2; ++refine) for (size_t N : kCounts) for (size_t rec : kRecs) {
+        const AcrDims d{ kind, N, rec, rec, rec, refine ? rec : 0, 128, elsewhere != 0 };
+        const size_t slots = 2 * 128 * kAcrSlots[kind];
+        const size_t* md = kAcrMd;
         AcrDev dv{}; AcrPin pv{};
         check("AcrDev", [&](Carve& c, Arrs& a) {
             dv.carve(c, d);
             acr_in_arrays(dv.in, d, a);
+            if (elsewhere && c.base && (dv.in.a != dv.in.b || (void*)dv.in.b != (void*)dv.in.K1)) die("AcrDev", "points elsewhere, yet a | b take room");
             for (const Arr& x : Arrs{ arr("models", dv.models, slots * md[kind]), raw("hyp", dv.hyp, rec * slots, 8), arr("sorted", dv.sorted, slots * N, 8),
                                       arr("best", dv.best, N, 8), arr("index", dv.index, N, 8), raw("result", dv.result, rec, 8), arr("mask", dv.mask, N, 8),
                                       raw("ref", dv.ref, refine ? rec : 0, 8) })
