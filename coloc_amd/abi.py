@@ -227,10 +227,13 @@ EXPORTS = [
     "clc_ba_dev", "clc_map_build_grow_ba_dev", "clc_map_init_grow_ba_batch_dev", "clc_map_update_grow_ba_batch_dev",
     "clc_match_guided_dev", "clc_match_guided_batch_dev",
     "clc_match_map_guided_dev", "clc_match_map_guided_batch_dev",
+    "clc_match_map_binned_dev", "clc_match_map_binned_batch_dev", "clc_map_bin_build_dev", "clc_map_binned_plan",
     "clc_sim3_acransac", "clc_sim3_minimal", "clc_map_align_sim_dev", "clc_map_update_sim_batch_dev",
 ]
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
+# clc_map_binned_plan: what clc_match_map_binned_dev runs for a job
+BIN_PLAN_SWEEP, BIN_PLAN_BINNED = 0, 1
 KERNELS = ["pyramid_kernel", "clatch_kernel", "k2nn_sweep_kernel", "k2nn_merge_kernel", "pnp_residual_kernel",
            "pnp_score_kernel", "detect_kernels"]
 
@@ -404,6 +407,10 @@ def load_library():
     lib.clc_match_guided_batch_dev.argtypes = [vp, vp, ci, vp]
     lib.clc_match_map_guided_dev.argtypes = [vp, vp, vp]
     lib.clc_match_map_guided_batch_dev.argtypes = [vp, vp, ci, vp]
+    lib.clc_match_map_binned_dev.argtypes = [vp, vp, vp]
+    lib.clc_match_map_binned_batch_dev.argtypes = [vp, vp, ci, vp]
+    lib.clc_map_bin_build_dev.argtypes = [vp, vp, vp, vp, vp]
+    lib.clc_map_binned_plan.argtypes = [vp, vp, C.c_float, vp, vp]
     _lib = lib
     return lib
 
@@ -1597,6 +1604,38 @@ class Context:
         for i in range(n):
             _map_guided_fill(arr[i], **jobs[i])
         self._chk(self.lib.clc_match_map_guided_batch_dev(self.h, arr, n, stream))
+
+    def match_map_binned_dev(self, stream=None, **job):
+        """clc_match_map_binned_dev: match_map_guided_dev's job, outputs and bits through a cell grid of the projections instead of the
+        whole-map sweep (map_binned_plan tells which of the two a job runs), enqueue only.  The keywords of match_map_guided_dev."""
+        j = MapGuidedJob()
+        _map_guided_fill(j, **job)
+        self._chk(self.lib.clc_match_map_binned_dev(self.h, C.byref(j), stream))
+
+    def match_map_binned_batch_dev(self, jobs, stream=None):
+        """clc_match_map_binned_batch_dev: jobs = [dict(the keywords of match_map_guided_dev), ...], at most MAX_BATCH; the BINNED jobs
+        share one prep, one bin and one match launch, the SWEEP jobs go through the guided path together."""
+        n = len(jobs)
+        arr = (MapGuidedJob * max(n, 1))()
+        for i in range(n):
+            _map_guided_fill(arr[i], **jobs[i])
+        self._chk(self.lib.clc_match_map_binned_batch_dev(self.h, arr, n, stream))
+
+    def map_bin_build_dev(self, d_cell_start, d_cell_row, stream=None, **job):
+        """clc_map_bin_build_dev: the prep and bin launches of match_map_binned_dev alone, the table copied out: d_cell_start (4357 int32,
+        device), d_cell_row (map_n int32, device: the map rows in cell order).  The keywords of match_map_guided_dev."""
+        j = MapGuidedJob()
+        _map_guided_fill(j, **job)
+        self._chk(self.lib.clc_map_bin_build_dev(self.h, C.byref(j), d_cell_start, d_cell_row, stream))
+
+    def map_binned_plan(self, cam, radius):
+        """clc_map_binned_plan: dict(plan = BIN_PLAN_SWEEP | BIN_PLAN_BINNED, cells_per_axis, lanes_per_query, cell_side) of
+        match_map_binned_dev for cam = (focal, ppx, ppy, k1, k2, k3) and `radius` on this context's map."""
+        info = (C.c_int32 * 4)()
+        side = C.c_double(0.0)
+        c = CameraK3(*[float(v) for v in cam])
+        self._chk(self.lib.clc_map_binned_plan(self.h, C.byref(c), C.c_float(radius), info, C.byref(side)))
+        return dict(plan=info[0], cells_per_axis=info[1], lanes_per_query=info[2], cell_side=side.value)
 
     def pair_filter_dev(self, model, **job):
         """clc_pair_filter_dev: computeRelativePose's gather + the a-contrario filter of model 'E' | 'F' | 'H' from device memory.  Keywords:

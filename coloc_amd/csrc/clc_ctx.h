@@ -94,6 +94,7 @@ struct clc_ctx {
     bool partial_dirty = false;      // armed (all-ones) state of the atomic top-2 rows was lost
     clc::DevBuf d_guided;            // float: the lines (3 per query row) and train points (2 per train row) of a guided match, or the query
                                      // points (2) and the landmarks' projections (2 per map row) of a map match around a pose (GuidedDev)
+    clc::DevBuf d_binned;            // the binned map match's query points, projections, cell table and records (BinnedDev)
     int formulation = clc::K2NN_MATRIX;   // K2NN sweep formulation (k2nn.hip): FP4 matrix pipe, or round 1's popcount kernel for A/B runs
     int target_blocks = 0;           // K2NN sweep workgroups aimed at per launch; 0 = the formulation's default
     int bias_a = 326, bias_b = 249;  // matrix sweep, one-round single-job plans: train share of a workgroup on wave slot 0 / 1 in 1/256 of the

@@ -383,6 +383,18 @@ struct GuidedDev {
     }
 };
 
+// ---- the binned map match's scratch d_binned (k2nn_binned.hip) --------------------------------------------------------------------------
+// per job [ query points 2 nq floats | projections 2 nm floats | records nm x 16 B { xt, yt, row, 0 } in cell order | cell_start cells + 1 |
+//           the cell of every map row nm x 2 B ], each starting on 16 bytes
+struct BinnedDev {
+    float *qpos, *proj; void* rec; int32_t* cell_start; uint16_t* cell_of;
+    void carve(Carve& c, size_t nq, size_t nm, size_t cells)
+    {
+        qpos = c.take<float>((2 * nq + 3) & ~(size_t)3, 16); proj = c.take<float>((2 * nm + 3) & ~(size_t)3, 16);
+        rec = c.take_bytes(16 * nm, 16); cell_start = c.take<int32_t>(cells + 1, 16); cell_of = c.take<uint16_t>(nm, 16);
+    }
+};
+
 // ---- the host-pointer K2NN entries' pinned mirror h_res (capi_match.hip): [ match nq | best nq | second nq | 64 B ] --------------------
 struct MatchPin {
     int32_t* match; uint16_t *best, *second;

@@ -29,6 +29,7 @@
 #include "clc_ctx.h"
 #include "guided_math.h"
 #include "proj_math.h"
+#include "k2nn_proj.h"
 #include "k2nn_sweep.h"
 #include "k2nn_top2.h"
 #include "ud_pixel.h"
@@ -71,20 +72,7 @@ struct GuidedJobDev {
 struct GuidedJobList { GuidedJobDev j[kGuidedMaxJobs]; };
 static_assert(sizeof(GuidedJobList) <= 4096, "GuidedJobList is passed as a kernel argument: it must stay within the 4 KB kernarg segment");
 
-// The map match's prep records: the frame's rows and camera, the predicted [R|t]; the landmarks are the context's, the same for every job.
-struct ProjPrepJob {
-    GatherSide a;
-    double Rt[12];
-    uint32_t nq, pad_;
-    float* qpos; float* proj;         // the context's scratch: 2 nq / 2 nm floats
-    float* qpos_out; float* proj_out; // the caller's copies, nullable
-};
-struct ProjPrepList {
-    ProjPrepJob j[kMaxBatch];
-    const double* map_X; uint32_t nm; // the landmarks of the map rows (d_map_X), nm = the context's map rows
-    float scale[CLC_MAX_LEVELS];      // as PairJobs::scale
-};
-static_assert(sizeof(ProjPrepList) <= 4096, "ProjPrepList is passed as a kernel argument: a batch of CLC_MAX_BATCH cameras is ONE prep launch");
+// (the map match's prep records, ProjPrepJob / ProjPrepList: k2nn_proj.h, shared with k2nn_binned.hip)
 
 // The two gates.  kF floats of a query stay in the lane's registers; pass() is the ONE statement of the gate (guided_math.h / proj_math.h).
 struct LineGate {
@@ -457,9 +445,11 @@ int guided_batch(clc_ctx* ctx, const clc_guided_job* jobs, const int n_jobs, voi
     return guided_sweep<LineGate>(ctx, "match_guided: launch", hipGetLastError(), list, n, st);
 }
 
-// ---- the map match guided by a predicted pose --------------------------------------------------------------------------------------------
+} // namespace
+
+// ---- the map match guided by a predicted pose (declared in k2nn_proj.h: k2nn_binned.hip runs the same checks and the same prep) ----------
 // the arguments of one job, checked; its 2-D side into `side`
-int proj_inputs(clc_ctx* ctx, const clc_map_guided_job& job, GatherSide& side)
+static int proj_inputs(clc_ctx* ctx, const clc_map_guided_job& job, GatherSide& side)
 {
     const auto bad = [&](const char* what) { return fail(ctx, CLC_ERR_BAD_ARG, what); };
     if (job.nq < 0 || (job.nq > 0 && (!job.d_q || !job.d_match))) return bad("match_map_guided: negative count / null block");
@@ -474,7 +464,7 @@ int proj_inputs(clc_ctx* ctx, const clc_map_guided_job& job, GatherSide& side)
     return gather_side(ctx, "match_map_guided", job.d_count, job.d_kps, job.d_feat, job.feat_stride, job.cam, side);      // the gathers' rules
 }
 
-int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, void* stream)
+int proj_checks(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, std::vector<GatherSide>& sides)
 {
     if (!ctx || n_jobs < 0 || n_jobs > kMaxBatch || (n_jobs > 0 && !jobs)) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_guided: null context / jobs, or a job count outside 0 .. CLC_MAX_BATCH");
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_guided: context created without matcher options");
@@ -482,13 +472,27 @@ int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, v
     if (ctx->map_n > 0 && ctx->map_X_n < ctx->map_n)
         return fail(ctx, CLC_ERR_STATE, "match_map_guided: fewer map points (set_map_points) than map descriptors (set_map)");
     // everything is checked before anything is enqueued
-    std::vector<GatherSide> sides((size_t)n_jobs);
+    sides.assign((size_t)n_jobs, GatherSide{});
     for (int j = 0; j < n_jobs; ++j) {
         const int rc = proj_inputs(ctx, jobs[j], sides[(size_t)j]);
         if (rc != CLC_OK) return rc;
     }
     if ((uint32_t)ctx->map_n > kIdxMask + 1u) return fail(ctx, CLC_ERR_CAPACITY, "match_map_guided: more than 2^22 map rows");
-    std::vector<int> live;                                                   // a job without query rows has nothing to answer
+    return CLC_OK;
+}
+
+hipError_t proj_prep_launch(const ProjPrepList& prep, const uint32_t rows, const int n, hipStream_t st)
+{
+    hipLaunchKernelGGL(proj_prep_kernel, dim3((rows + 255u) / 256u, (unsigned)n), dim3(256), 0, st, prep);
+    return hipGetLastError();
+}
+
+int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, void* stream)
+{
+    std::vector<GatherSide> sides;
+    const int checked = proj_checks(ctx, jobs, n_jobs, sides);
+    if (checked != CLC_OK) return checked;
+    std::vector<int> live;                                                  // a job without query rows has nothing to answer
     for (int j = 0; j < n_jobs; ++j) if (jobs[j].nq > 0) live.push_back(j);
     if (live.empty()) return CLC_OK;
     const int n = (int)live.size();
@@ -522,11 +526,8 @@ int proj_batch(clc_ctx* ctx, const clc_map_guided_job* jobs, const int n_jobs, v
         pj.qpos_out = job.d_qpos; pj.proj_out = job.d_proj;
         rows = std::max(rows, pj.nq + nm);
     }
-    hipLaunchKernelGGL(proj_prep_kernel, dim3((rows + 255u) / 256u, (unsigned)n), dim3(256), 0, st, prep);
-    return guided_sweep<PointGate>(ctx, "match_map_guided: launch", hipGetLastError(), list, n, st);
+    return guided_sweep<PointGate>(ctx, "match_map_guided: launch", proj_prep_launch(prep, rows, n, st), list, n, st);
 }
-
-} // namespace
 
 } // namespace clc
 

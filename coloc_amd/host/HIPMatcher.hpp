@@ -188,6 +188,22 @@ public:
         return !check(clc_match_map_guided_dev(ctx_, &jb, after_stream), "matchSceneWithMapGuidedDev");
     }
 
+    // matchSceneWithMapGuidedDev through a cell grid of the projections (clc_match_map_binned_dev): the same arguments, the same d_match
+    // bit for bit, without the whole-map sweep -- a keypoint meets only the map rows binned into the at most 3 x 3 cells around it.  Jobs
+    // the grid does not suit (clc_map_binned_plan: SWEEP) run the guided path inside the entry.  false = enqueued.
+    bool matchSceneWithMapBinnedDev(const openMVG::geometry::Pose3& predictedPose, const clc_camera_k3& intrinsics, const void* d_desc, int nq,
+                                    const clc_keypoint* d_kps, const uint32_t* d_count, float radius, int32_t* d_match_out, void* after_stream)
+    {
+        clc_map_guided_job jb{};
+        jb.d_q = d_desc; jb.nq = nq; jb.d_count = d_count; jb.d_kps = d_kps;
+        jb.cam = intrinsics;
+        const openMVG::Vec3 t = predictedPose.translation();                     // t = -R C
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) jb.Rt[4 * i + j] = predictedPose.rotation()(i, j); jb.Rt[4 * i + 3] = t[i]; }
+        jb.radius = radius; jb.threshold = matchThreshold_;
+        jb.d_match = d_match_out;
+        return !check(clc_match_map_binned_dev(ctx_, &jb, after_stream), "matchSceneWithMapBinnedDev");
+    }
+
     // GPUMatcher.hpp:180-226: IndMatch(i_ = query index, j_ = train index); dmatches(train, query, 0)
     openMVG::matching::IndMatches computeMatches(void* h_descriptorsQuery, void* h_descriptorsTraining, int numKPQuery,
                                                  int numKPTraining, uint8_t threshold = 40)

@@ -1009,6 +1009,49 @@ typedef struct clc_map_guided_job {
 int clc_match_map_guided_dev(clc_ctx* ctx, const clc_map_guided_job* job, void* stream);
 int clc_match_map_guided_batch_dev(clc_ctx* ctx, const clc_map_guided_job* jobs, int n_jobs, void* stream);
 
+/* ---- tracking by projection through a cell grid: the same match without the whole-map sweep --------------------------------------------
+ * clc_match_map_binned_dev takes clc_match_map_guided_dev's job and leaves clc_match_map_guided_dev's outputs, bit for bit: the rule
+ * above is THE rule (query point, train point, gate, top-2, outputs, Rt).  What differs is which map rows a query meets.  The
+ * projections are binned into a grid of cells and a query visits only the cells its window covers; every row it visits goes through
+ * the unchanged gate, the window holds every row that can pass it, and the top-2 is a fold of keys
+ * (distance << 22) + row by min / med3, which does not depend on the order the rows are met in.  (Later under ABI 4: new entry points
+ * only; the guided entries keep their code.)
+ *
+ * THE CELL RULE, in fp64 with + - * /, floor, min, max in source order (coloc_amd/csrc/bin_math.h, host and device):
+ *   rw    = (double)radius * (1.0 + 0x1p-10)               the window's half-width
+ *   W     = 2.0 * max(cam.ppx, cam.ppy)                    the grid's extent on both axes, origin (0, 0)
+ *   c     = max(rw, W / 64.0)                              the cell's side: never below rw
+ *   k(v)  = (int)min(max(floor(v / c), -1.0), 64.0) + 1    1 .. 64 inside, 0 and 65 the ring; clamped BEFORE the conversion
+ *   cell(x, y) = k(y) * 66 + k(x)                          66 * 66 = 4356 cells, row-major
+ *   binned rows   map row i is binned iff it has a projection; its cell is cell((double)x_t, (double)y_t) of the floats the prep wrote.
+ *   query window  kx in [k((double)x_q - rw), k((double)x_q + rw)], ky likewise: at most 3 x 3 cells, at most three contiguous runs of
+ *                 the table sorted by cell.  A query whose point is NaN has no window and is answered -1.
+ *   THE PLAN      host-side, from the job and the map's size alone.  BINNED iff radius >= 2^-10, 8 rw <= W, 0 < map_n <= 65 536 and
+ *                 ppx, ppy finite and positive; otherwise SWEEP: the entry runs clc_match_map_guided_dev's path for that job, with the
+ *                 same bits.
+ *
+ * clc_match_map_binned_dev / _batch_dev: outputs, errors and limits are clc_match_map_guided_dev's -- the same argument checks before
+ * anything is enqueued, CLC_ERR_STATE / CLC_ERR_CAPACITY as there, an empty map gives every query -1, nq == 0 writes nothing.  Enqueue
+ * only on `stream` (0: the context's), capturable once the context's scratch has its size, no host wait: the prep launch of the guided
+ * entry, one workgroup per job that builds the table (histogram, scan, scatter), one match launch with 16 lanes per query.  Batch: n_jobs
+ * in [0, CLC_MAX_BATCH], every job's result the single call's; the BINNED jobs share one prep, one bin and one match launch, the SWEEP
+ * jobs go through the guided path together.
+ *
+ * clc_map_bin_build_dev: the inner step alone -- prep and bin for `job` -- with the table copied out: d_cell_start[4357] (device; entry
+ * i = the rows in cells below i, entry 4356 = the binned rows) and d_cell_row[map_n] (device; the map rows in cell order, the order
+ * inside a cell unspecified; entries at or past d_cell_start[4356] are not written).  Rows without a projection appear in no cell.  It
+ * builds the table whatever the plan says of the radius; the job's checks are the match's, and further: a null or misaligned table or a
+ * principal point that is not finite and positive: CLC_ERR_BAD_ARG; more than 65 536 map rows: CLC_ERR_CAPACITY.
+ *
+ * clc_map_binned_plan: what the entry would do for (cam, radius) on this context's map: info = { plan (0 SWEEP, 1 BINNED), cells per
+ * axis (66), lanes per query (16), 0 }, *cell_side (nullable) = c.  A null context, camera or info: CLC_ERR_BAD_ARG. */
+#define CLC_BIN_PLAN_SWEEP  0
+#define CLC_BIN_PLAN_BINNED 1
+int clc_match_map_binned_dev(clc_ctx* ctx, const clc_map_guided_job* job, void* stream);
+int clc_match_map_binned_batch_dev(clc_ctx* ctx, const clc_map_guided_job* jobs, int n_jobs, void* stream);
+int clc_map_bin_build_dev(clc_ctx* ctx, const clc_map_guided_job* job, int32_t* d_cell_start, int32_t* d_cell_row, void* stream);
+int clc_map_binned_plan(const clc_ctx* ctx, const clc_camera_k3* cam, float radius, int32_t* info, double* cell_side);
+
 /* ---- the inter-camera step from device memory: ColoC::interPoseEstimator (coloc.hpp:296-340) without a host trip --------------------
  * What clc_inter_pose_batch computes, fed from the pair's d_match instead of host correspondences: the pair gather and the 'E' filter of
  * clc_pair_filter_dev, then -- on the device, in the operation order of the host path, so with its bits -- the chirality vote over the
