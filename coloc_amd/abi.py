@@ -64,6 +64,17 @@ class TrackJob(C.Structure):
                 ("error_max", C.c_double), ("rmse", C.c_double)]
 
 
+class TrackPriorJob(C.Structure):
+    """clc_track_prior_job (include/coloc_hip.h)"""
+    _fields_ = [("d_match", C.c_void_p), ("nq", C.c_int), ("d_count", C.c_void_p), ("d_kps", C.c_void_p), ("d_feat", C.c_void_p),
+                ("feat_stride", C.c_int), ("cam", CameraK3), ("after_stream", C.c_void_p),
+                ("Rt_prior", C.c_double * 12), ("gate", C.c_double), ("huber_a", C.c_double), ("rounds", C.c_int), ("max_iter", C.c_int),
+                ("min_inliers", C.c_int),
+                ("Rt", C.c_void_p), ("cov", C.c_void_p), ("track_query", C.c_void_p), ("track_map", C.c_void_p), ("inlier_mask", C.c_void_p),
+                ("n_tracks", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int), ("rounds_run", C.c_int), ("converged", C.c_int),
+                ("result", C.c_int), ("status", C.c_int), ("rmse", C.c_double)]
+
+
 class PairJob(C.Structure):
     """clc_pair_job (include/coloc_hip.h)"""
     _fields_ = [("d_match", C.c_void_p), ("nq", C.c_int), ("nt", C.c_int), ("d_count_a", C.c_void_p), ("d_count_b", C.c_void_p),
@@ -229,7 +240,10 @@ EXPORTS = [
     "clc_match_map_guided_dev", "clc_match_map_guided_batch_dev",
     "clc_match_map_binned_dev", "clc_match_map_binned_batch_dev", "clc_map_bin_build_dev", "clc_map_binned_plan",
     "clc_sim3_acransac", "clc_sim3_minimal", "clc_map_align_sim_dev", "clc_map_update_sim_batch_dev",
+    "clc_track_prior_dev", "clc_track_prior_batch_dev", "clc_pnp_refine_prior",
 ]
+# clc_track_prior_job.result
+TRACK_PRIOR_OK, TRACK_PRIOR_FEW = 0, 1
 # clc_detect_set_selection: which keypoints a frame with more than maxkp keeps
 SELECT_FIRST, SELECT_STRONGEST = 0, 1
 # clc_map_binned_plan: what clc_match_map_binned_dev runs for a job
@@ -384,6 +398,9 @@ def load_library():
     lib.clc_track_build_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.clc_track_localize_dev.argtypes = [vp, vp]
     lib.clc_track_localize_batch_dev.argtypes = [vp, vp, ci]
+    lib.clc_track_prior_dev.argtypes = [vp, vp]
+    lib.clc_track_prior_batch_dev.argtypes = [vp, vp, ci]
+    lib.clc_pnp_refine_prior.argtypes = [vp, vp, vp, ci, vp, vp, C.c_double, C.c_double, ci, ci, ci, vp, vp, vp] + [vp] * 6
     lib.clc_pair_build_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.clc_pair_filter_dev.argtypes = [vp, ci, vp]
     lib.clc_pair_filter_batch_dev.argtypes = [vp, ci, vp, ci]
@@ -717,6 +734,45 @@ def track_localize_batch_dev(ctxs, jobs):
     if rc != CLC_OK:
         raise CLCError(rc, "clc_track_localize_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
     return [_track_result(arr[i], *outs[i]) for i in range(n)]
+
+
+def _track_prior_fill(j, keep, d_match, nq, cam, Rt_prior, gate, d_kps=None, d_feat=None, feat_stride=4, d_count=None, after_stream=None,
+                      huber_a=16.0, rounds=0, max_iter=0, min_inliers=0):
+    """fills a TrackPriorJob; cam = (focal, ppx, ppy, k1, k2, k3); device pointers as integers; Rt_prior (3, 4)"""
+    j.d_match, j.nq, j.d_count, j.d_kps, j.d_feat, j.feat_stride = d_match, int(nq), d_count, d_kps, d_feat, int(feat_stride)
+    j.cam = CameraK3(*[float(v) for v in cam])
+    j.after_stream = after_stream
+    j.Rt_prior = (C.c_double * 12)(*[float(v) for v in np.asarray(Rt_prior, dtype=np.float64).reshape(12)])
+    j.gate, j.huber_a, j.rounds, j.max_iter, j.min_inliers = float(gate), float(huber_a), int(rounds), int(max_iter), int(min_inliers)
+    n = max(int(nq), 1)
+    Rt, cov = np.zeros(12), np.zeros(36)
+    tq, tm, mask = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint8)
+    keep.append((Rt, cov, tq, tm, mask))
+    j.Rt, j.cov, j.track_query, j.track_map, j.inlier_mask = (a.ctypes.data for a in (Rt, cov, tq, tm, mask))
+    return Rt, cov, tq, tm, mask
+
+
+def _track_prior_result(j, Rt, cov, tq, tm, mask):
+    nt = max(min(j.n_tracks, len(tq)), 0)
+    return dict(Rt=Rt.reshape(3, 4).copy(), cov=cov.reshape(6, 6).copy(), n_tracks=j.n_tracks, track_query=tq[:nt].copy(),
+                track_map=tm[:nt].copy(), mask=mask[:nt].astype(bool), n_inliers=j.n_inliers, iterations=j.iterations,
+                rounds_run=j.rounds_run, converged=j.converged, result=j.result, rmse=j.rmse, status=j.status)
+
+
+def track_prior_batch_dev(ctxs, jobs):
+    """clc_track_prior_batch_dev: jobs = [dict(d_match=, nq=, cam=, Rt_prior=, gate=, d_kps= | d_feat=, ...), ...] (the keywords of
+    Context.track_prior_dev), job i on ctxs[i], the map points from ctxs[0].  Returns a list of result dicts."""
+    lib = load_library()
+    n = len(jobs)
+    assert len(ctxs) == n
+    arr = (TrackPriorJob * max(n, 1))()
+    keep = []
+    outs = [_track_prior_fill(arr[i], keep, **jobs[i]) for i in range(n)]
+    hs = (C.c_void_p * max(n, 1))(*[c.h for c in ctxs])
+    rc = lib.clc_track_prior_batch_dev(hs, arr, n)
+    if rc != CLC_OK:
+        raise CLCError(rc, "clc_track_prior_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    return [_track_prior_result(arr[i], *outs[i]) for i in range(n)]
 
 
 def _pair_fill(j, keep, d_match, nq, nt, cam_a, cam_b, d_kps_a=None, d_feat_a=None, feat_stride_a=4, d_kps_b=None, d_feat_b=None,
@@ -1564,6 +1620,35 @@ class Context:
         out = _track_fill(j, keep, **job)
         self._chk(self.lib.clc_track_localize_dev(self.h, C.byref(j)))
         return _track_result(j, *out)
+
+    def track_prior_dev(self, **job):
+        """clc_track_prior_dev: the tracks of the frame, then the pose from the PREDICTED pose without a minimal sample.  Keywords: d_match,
+        nq, cam = (focal, ppx, ppy, k1, k2, k3), d_kps or d_feat (+ feat_stride), d_count, after_stream, Rt_prior (3, 4), gate (pixels: the
+        error_max of the camera's last a-contrario solve), huber_a, rounds, max_iter, min_inliers.  Returns a dict: Rt, cov, n_tracks,
+        track_query, track_map, mask, n_inliers, iterations, rounds_run, converged, result (TRACK_PRIOR_OK / TRACK_PRIOR_FEW: run
+        match_map_dev + track_localize_dev for the frame), rmse."""
+        j = TrackPriorJob()
+        keep = []
+        out = _track_prior_fill(j, keep, **job)
+        self._chk(self.lib.clc_track_prior_dev(self.h, C.byref(j)))
+        return _track_prior_result(j, *out)
+
+    def pnp_refine_prior(self, X, x, K, Rt_prior, gate, huber_a=16.0, rounds=0, max_iter=0, min_inliers=0):
+        """clc_pnp_refine_prior: the same solve on host arrays.  Returns a dict: Rt (3, 4), cov (6, 6), mask, n_inliers, rmse, iterations,
+        rounds_run, converged, result."""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 2)
+        K = np.ascontiguousarray(K, dtype=np.float64).reshape(9)
+        Rt0 = np.ascontiguousarray(Rt_prior, dtype=np.float64).reshape(12)
+        n = X.shape[0]
+        Rt, cov, mask = np.zeros(12), np.zeros(36), np.zeros(max(n, 1), dtype=np.uint8)
+        ni, it, rr, cv, res = (C.c_int() for _ in range(5))
+        rmse = C.c_double()
+        self._chk(self.lib.clc_pnp_refine_prior(self.h, _p(X) if n else None, _p(x) if n else None, n, _p(K), _p(Rt0), float(gate), float(huber_a),
+                                                int(rounds), int(max_iter), int(min_inliers), _p(Rt), _p(cov), _p(mask), C.addressof(ni),
+                                                C.addressof(rmse), C.addressof(it), C.addressof(rr), C.addressof(cv), C.addressof(res)))
+        return dict(Rt=Rt.reshape(3, 4), cov=cov.reshape(6, 6), mask=mask[:n].astype(bool), n_inliers=ni.value, rmse=rmse.value,
+                    iterations=it.value, rounds_run=rr.value, converged=cv.value, result=res.value)
 
     def pair_build_dev(self, d_x1, d_x2, d_pair_q, d_pair_t, d_n, stream=None, **job):
         """clc_pair_build_dev: the pair kernel alone, enqueue only; job keywords as pair_filter_dev (d_match, nq, nt, cam_a, cam_b,

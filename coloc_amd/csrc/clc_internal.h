@@ -384,5 +384,30 @@ hipError_t launch_sim3_minimal(const double* d_x, const double* d_y, int N, cons
 hipError_t launch_sim3_refit(const AcrResult* d_res, const uint8_t* d_mask, const double* d_x, const double* d_y, int N, int32_t* d_list,
                              Sim3Out* d_out, Sim3Out* h_out, hipStream_t stream);
 
+// ---- the pose from a prediction (pose_prior.hip; include/coloc_hip.h: clc_track_prior_dev, THE RULE) -----------------------------------------
+// What the kernel leaves in PINNED memory, one per job
+struct PriorOut {
+    double Rt[12];
+    double cov[36];         // zeros: CLC_TRACK_PRIOR_FEW, or the 6 x 6 is not positive definite
+    double cost, rmse;      // 1/2 sum rho and sqrt(cost / (2 n_inliers)) at the pose over the mask
+    int32_t n_tracks;       // the count as read (all tracks, also past the capacity)
+    int32_t n_inliers, iterations, rounds_run, converged, result;
+    int32_t capacity;       // 1: more tracks than the block holds, the kernel worked on the first `cap`
+    int32_t ready;          // written LAST (system-scope release)
+};
+struct PriorJobDev {
+    const double* X; const double* x;          // the tracks: 3 N | 2 N (a context's track block, or an upload)
+    const int32_t* n_dev; int n;               // N: the device word where given (the gather's count), else n
+    int cap;                                   // most tracks X | x hold (<= 16 384)
+    double fx, sk, cx, fy, cy;                 // K = { fx, sk, cx; 0, fy, cy; 0, 0, 1 }
+    double Rt[12];                             // the prior
+    double g2, huber_a;
+    int rounds, max_iter, min_inliers;
+    uint8_t* h_mask; PriorOut* out;            // pinned: cap bytes, the record
+};
+struct PriorJobs { PriorJobDev j[kMaxBatch]; };
+// ONE launch for n_jobs <= kMaxBatch poses (blockIdx.x = job, one workgroup each)
+hipError_t launch_pose_prior(const PriorJobs& jobs, int n_jobs, hipStream_t stream);
+
 } // namespace clc
 #endif

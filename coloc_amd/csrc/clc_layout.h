@@ -269,6 +269,37 @@ struct RefinePin {
     }
 };
 
+// The pose from a prediction (pose_prior.hip).  What the kernel writes is pinned: [ record (64 B or its size) | mask up64(cap) bytes | 64 B ];
+// the tracks are read where the gather left them (clc_track_prior_dev) or, for clc_pnp_refine_prior, come in by ONE copy:
+// pinned [ X 3 N | x 2 N | record | mask | 64 B ] -> device [ X 3 N | x 2 N | 8 doubles ]
+struct PriorPin {
+    void* rec; uint8_t* mask;
+    void carve(Carve& c, size_t cap, size_t rec_bytes)
+    {
+        rec = c.take_bytes(rec_bytes > 64 ? rec_bytes : 64, 8); mask = c.take<uint8_t>(up64(cap), 8);
+        c.take_bytes(64, 8);
+    }
+};
+struct PriorIn {
+    double *X, *x; size_t bytes;
+    void carve(Carve& c, size_t N)
+    {
+        c.take<double>(0);
+        const size_t at = c.bytes();
+        X = c.take<double>(3 * N); x = c.take<double>(2 * N);
+        c.take<double>(0);
+        bytes = c.bytes() - at;
+    }
+};
+struct PriorHostDev {
+    PriorIn in;
+    void carve(Carve& c, size_t N) { in.carve(c, N); c.take<double>(8); }
+};
+struct PriorHostPin {
+    PriorIn in; PriorPin out;
+    void carve(Carve& c, size_t N, size_t rec_bytes) { in.carve(c, N); out.carve(c, N, rec_bytes); }
+};
+
 // The host-geometry inter-camera step's map match (inter_pose.hip): device [ idx nf | gathered rows nf x 64 B | match nm | 8 doubles ],
 // pinned [ idx | match | 64 B ]; every array starts on 16 bytes
 struct MapMatchDev {

@@ -174,6 +174,67 @@ public:
         return EXIT_SUCCESS;
     }
 
+    // A TRACKED frame's pose from the prediction (clc_track_prior_dev; an ADDITION, INTEGRATION.md 3n: the reference's
+    // intraPoseEstimator always calls Localize).  `pose` comes in as the PREDICTED pose -- the previous frame's, or the filter's --,
+    // `gate` (pixels) is naturally the error_max the camera's last a-contrario solve returned; d_match is what the match by projection
+    // under that prediction left on the GPU (HIPMatcher::matchSceneWithMapGuidedDev), the rest as localizeImageDev.  No minimal sample
+    // and no seed is drawn: the pose is a few robust Gauss-Newton rounds from the prediction, one launch behind the track launch, one
+    // host wait.  Leaves pose, covariance, rmse (the reference's mean pixel distance of the reprojected inliers), trackedFeatures
+    // (IndMatch(map, query), ascending query) and inliers (ascending track index) and returns the members' convention, false = success.
+    // CLC_TRACK_PRIOR_FEW is reported as FAILURE with `pose` left as it came in: the caller then runs matchSceneWithMap +
+    // localizeImageDev for that frame, as it does for the first frame.
+    bool localizeImagePriorDev(int& idx, openMVG::geometry::Pose3& pose, double gate, colocData& data, Cov6& covariance, float& rmse,
+                               openMVG::matching::IndMatches& trackedFeatures, std::vector<uint32_t>& inliers, const int32_t* d_match, int nq,
+                               const uint32_t* d_count, const clc_keypoint* d_kps, const float* d_feat = nullptr, int feat_stride = 4,
+                               void* after_stream = nullptr)
+    {
+        openMVG::cameras::Pinhole_Intrinsic_Radial_K3 cam = camera(idx);
+        trackedFeatures.clear();
+        inliers.clear();
+        if (!ctx_ || nq <= 0) { std::cout << "Localization unsuccessful" << std::endl; return EXIT_FAILURE; }
+        std::vector<int32_t> tq(static_cast<size_t>(nq)), tm(static_cast<size_t>(nq));
+        std::vector<uint8_t> mask(static_cast<size_t>(nq), 0);
+        double Rt[12], cov[36];
+        clc_track_prior_job jb{};
+        jb.d_match = d_match; jb.nq = nq; jb.d_count = d_count; jb.d_kps = d_kps; jb.d_feat = d_feat; jb.feat_stride = feat_stride;
+        jb.cam = clc_camera_k3{ cam.focal(), cam.principal_point()[0], cam.principal_point()[1], (*dist)[idx](0), (*dist)[idx](1), (*dist)[idx](2) };
+        jb.after_stream = after_stream;
+        const openMVG::Vec3 t0 = pose.translation();
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) jb.Rt_prior[4 * i + j] = pose.rotation()(i, j); jb.Rt_prior[4 * i + 3] = t0[i]; }
+        jb.gate = gate; jb.huber_a = 16.0; jb.rounds = 0; jb.max_iter = 0; jb.min_inliers = 0;      // the entry's defaults: 4 rounds of <= 50, 8 inliers
+        jb.Rt = Rt; jb.cov = cov; jb.track_query = tq.data(); jb.track_map = tm.data(); jb.inlier_mask = mask.data();
+        const int rc = clc_track_prior_dev(ctx_, &jb);
+        if (rc != CLC_OK) {
+            std::cerr << "HIPLocalizer: clc_track_prior_dev: " << clc_last_error_string(ctx_) << std::endl;
+            std::cout << "Localization unsuccessful" << std::endl;
+            return EXIT_FAILURE;
+        }
+        for (int i = 0; i < jb.n_tracks; ++i)
+            trackedFeatures.emplace_back(static_cast<openMVG::IndexT>(tm[static_cast<size_t>(i)]), static_cast<openMVG::IndexT>(tq[static_cast<size_t>(i)]));
+        if (jb.result != CLC_TRACK_PRIOR_OK) { std::cout << "Localization unsuccessful" << std::endl; return EXIT_FAILURE; }
+        pose = pose_from_Rt(Rt);
+        for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) covariance(i, j) = cov[6 * i + j];
+        openMVG::sfm::Image_Localizer_Match_Data md;
+        md.pt3D.resize(3, static_cast<size_t>(jb.n_tracks));
+        md.pt2D.resize(2, static_cast<size_t>(jb.n_tracks));
+        for (int i = 0; i < jb.n_tracks; ++i) if (mask[static_cast<size_t>(i)]) md.vec_inliers.push_back(static_cast<uint32_t>(i));
+        const auto& regions = *data.regions.at(idx).get();
+        for (uint32_t c : md.vec_inliers) {
+            const auto& X = data.scene.GetLandmarks().at(data.mapRegionIdx[trackedFeatures[c].i_]).X;
+            for (int r = 0; r < 3; ++r) md.pt3D(r, c) = X[r];
+            const auto p = regions.GetRegionPosition(trackedFeatures[c].j_);
+            const openMVG::Vec2 px = cam.get_ud_pixel(openMVG::Vec2(static_cast<double>(p[0]), static_cast<double>(p[1])));
+            md.pt2D(0, c) = px[0];
+            md.pt2D(1, c) = px[1];
+        }
+        double Kd[9];
+        intrinsics(cam, Kd);
+        rmse = mean_reprojection(pose, Kd, md);
+        std::cout << "Localization successful" << std::endl;
+        inliers = md.vec_inliers;
+        return EXIT_SUCCESS;
+    }
+
     // localizeImage for SEVERAL cameras at once (not in the reference, whose loop calls localizeImage camera by camera, coloc.hpp:129-137;
     // BASELINE config[2]: "batched PnP/RANSAC pose").  The cameras' a-contrario solves -- chains of short launches with the host in the
     // loop -- run through clc_pnp_localize_ac_batch, each on a light context of its own, and interleave on the device; every camera's

@@ -49,7 +49,8 @@ extern "C" {
  * (clc_pair_build_dev, clc_pair_filter_dev, clc_pair_filter_batch_dev), the inter-camera step from device memory (clc_inter_*_dev) and
  * the map built on the device (clc_tracks_build_dev, clc_map_build_dev, clc_map_init_batch_dev) and replaced at the old map's scale
  * (clc_map_align_dev, clc_map_update_batch_dev), and the a-contrario 3-D similarity that aligns a replaced map to the old one
- * (clc_sim3_acransac, clc_sim3_minimal, clc_map_align_sim_dev, clc_map_update_sim_batch_dev).
+ * (clc_sim3_acransac, clc_sim3_minimal, clc_map_align_sim_dev, clc_map_update_sim_batch_dev), and a tracked frame's pose from the
+ * prediction (clc_track_prior_dev, clc_track_prior_batch_dev, clc_pnp_refine_prior).
  * Bindings check clc_abi_version() BEFORE resolving symbols an older library does not export. */
 #define CLC_ABI_VERSION 4
 #define CLC_DESC_BYTES 64
@@ -1051,6 +1052,90 @@ int clc_match_map_binned_dev(clc_ctx* ctx, const clc_map_guided_job* job, void* 
 int clc_match_map_binned_batch_dev(clc_ctx* ctx, const clc_map_guided_job* jobs, int n_jobs, void* stream);
 int clc_map_bin_build_dev(clc_ctx* ctx, const clc_map_guided_job* job, int32_t* d_cell_start, int32_t* d_cell_row, void* stream);
 int clc_map_binned_plan(const clc_ctx* ctx, const clc_camera_k3* cam, float radius, int32_t* info, double* cell_side);
+
+/* ---- a tracked frame's pose from the prediction: the solve behind the match by projection -----------------------------------------------
+ * clc_track_localize_dev runs Localize for every frame: the host waits for the track count, drives the a-contrario P3P solve round by
+ * round, then refines.  With a predicted pose and tracks that all lie within `radius` of where that pose puts them (the guided / binned
+ * match above), sampling has nothing left to find: the pose is a few robust Gauss-Newton steps from the prediction.  These entries
+ * give pose, inliers and covariance from the prediction and the tracks in ONE solve launch behind the track gather, with no minimal
+ * sample; the host waits for one record at the end and for nothing in between, the track count included.  The reference has no
+ * counterpart -- intraPoseEstimator always calls Localize (coloc.hpp:223, Localizer.hpp:77-108) --: like the matches by projection this
+ * is THIS library's statement, parity with nothing is pinned, and no existing entry changes.  (Later under ABI 4: new entry points
+ * only.)
+ *
+ * THE RULE.
+ *   inputs       N tracks (X_i, x_i) in the track list's order -- accepted queries ascending, x_i through get_ud_pixel: exactly what
+ *                clc_track_build_dev writes --, K = { focal, 0, ppx; 0, focal, ppy; 0, 0, 1 }, the prior [R0|t0] (HOST, 12 doubles, the
+ *                layout clc_track_job.Rt returns and clc_map_guided_job.Rt takes), gate (pixels; g2 = gate * gate is formed once on the
+ *                host), huber_a (<= 0: 16), rounds (0: 4; legal 1 .. 8), max_iter per round (0: 50, as clc_pnp_refine), min_inliers
+ *                (<= 0: 8, Localize's "more than 2.5 x 3" rule, as CLC_MAP_SIM_NO_MODEL).
+ *   classify(p)  track i is IN iff zc_i > 0 and sq_i <= g2, with zc and sq = r0^2 + r1^2 exactly as the Levenberg-Marquardt pass computes
+ *                them at the parameters p.  Any NaN gives "out"; a squared residual of exactly g2 is in.
+ *   m_0          the tracks with zc_i > 0 under the prior: NO residual gate on the first round (a guided caller's tracks are within its
+ *                radius by construction; for others the Huber tail bounds what an outlier can pull).
+ *   round k      for k = 0 .. rounds - 1: if |m_k| < 4, stop.  p_{k+1} = the Levenberg-Marquardt of clc_pnp_refine from p_k over m_k:
+ *                cost 1/2 sum rho, parameters [angle-axis | t], lambda reset to 1e-4 at the start of every round, steps x 0.1 (floor 1e-12)
+ *                and x 10, the stop above 1e10, the function / gradient / parameter tests and "a failed 6 x 6 solve is a rejected step"
+ *                all unchanged.  m_{k+1} = classify(p_{k+1}); if m_{k+1} == m_k, stop with converged = 1.
+ *   outputs      Rt = the last p (the prior's own bits where no step was accepted); inlier_mask = classify of that pose over ALL tracks
+ *                (a track dropped in one round can return in a later one); n_inliers = |mask|; cov = (J^T W J)^-1 and
+ *                rmse = sqrt(cost / (2 n_inliers)) from the sums at that pose over that mask (cov zero where the 6 x 6 is not positive
+ *                definite, as clc_pnp_refine); iterations summed over the rounds; rounds_run; converged;
+ *                result = CLC_TRACK_PRIOR_OK when n_inliers >= max(min_inliers, 4), else CLC_TRACK_PRIOR_FEW: the pose is then the last p
+ *                -- the prior itself when |m_0| < 4 or N < 4 --, cov is zero, and the call still returns CLC_OK.
+ *   determinism  no floating-point atomics, sums reduced in a fixed order: two runs on the same inputs give the same bits.
+ * FEW is the caller's signal to run clc_match_map_dev + clc_track_localize_dev for that frame: the library does not fall back on its own
+ * (INTEGRATION.md 3n).  The first frame, and any frame after FEW, goes through clc_track_localize_dev.  The natural gate is the
+ * error_max the camera's last a-contrario solve returned: the precision AC-RANSAC found, in pixels.
+ *
+ * clc_track_prior_dev: the frame exactly as clc_track_job names it, then the step.  The track launch of clc_track_localize_dev, then ONE
+ * solve launch (one workgroup of 512 threads) on the context's stream, which reads the track count from DEVICE memory; one host wait,
+ * on the pinned record the solve writes last.  Host outputs (nullable): Rt 12, cov 36, track_query / track_map / inlier_mask with room
+ * for nq entries (n_tracks are written).  ORDERING: after_stream as clc_track_job.
+ * clc_track_prior_batch_dev: n_jobs in [0, CLC_MAX_BATCH], job i on ctxs[i] (a context of its own each, one device), the map points
+ * ctxs[0]'s; ONE track launch and ONE solve launch (a workgroup per job) on ctxs[0]'s stream; every job's result is the single call's,
+ * bit for bit; jobs[i].status per job, the return value the first failure.
+ * clc_pnp_refine_prior: the same solve on host arrays (one upload, one launch, the record); K as clc_pnp_refine reads it
+ * ({ fx, skew, cx; 0, fy, cy; 0, 0, 1 }, anything else CLC_ERR_BAD_ARG); h_inlier_mask N bytes; every output pointer nullable.
+ * Errors, all checked before anything is enqueued: a non-finite prior, gate or gate * gate not finite and positive, rounds outside
+ * 0 .. 8, a negative max_iter, both or neither of d_kps / d_feat, a misaligned pointer, a non-positive focal, a null context or job,
+ * n_jobs out of range: CLC_ERR_BAD_ARG; no map points, or fewer map points than map rows (clc_track_localize_dev's rule):
+ * CLC_ERR_STATE.  More than 16 384 tracks: the solve works on none of the surplus and the entry returns CLC_ERR_CAPACITY after its wait
+ * (clc_pnp_refine_prior: before anything is enqueued).  nq == 0 or no accepted query: CLC_OK, result = FEW, Rt = the prior. */
+#define CLC_TRACK_PRIOR_OK  0
+#define CLC_TRACK_PRIOR_FEW 1
+typedef struct clc_track_prior_job {
+    /* in: the frame, exactly clc_track_job's */
+    const int32_t*      d_match;
+    int                 nq;
+    const uint32_t*     d_count;      /* nullable */
+    const clc_keypoint* d_kps;        /* or */
+    const float*        d_feat;
+    int                 feat_stride;
+    clc_camera_k3       cam;
+    void*               after_stream; /* nullable */
+    /* in: the step */
+    double              Rt_prior[12];
+    double              gate;         /* pixels */
+    double              huber_a;      /* <= 0: 16 */
+    int                 rounds;       /* 0: 4 */
+    int                 max_iter;     /* per round; 0: 50 */
+    int                 min_inliers;  /* <= 0: 8 */
+    /* out (pointers nullable, host memory) */
+    double*             Rt;
+    double*             cov;
+    int32_t*            track_query;
+    int32_t*            track_map;
+    uint8_t*            inlier_mask;
+    int                 n_tracks, n_inliers, iterations, rounds_run, converged, result, status;
+    double              rmse;
+} clc_track_prior_job;
+int clc_track_prior_dev(clc_ctx* ctx, clc_track_prior_job* job);
+int clc_track_prior_batch_dev(clc_ctx* const* ctxs, clc_track_prior_job* jobs, int n_jobs);
+int clc_pnp_refine_prior(clc_ctx* ctx, const double* h_X, const double* h_x, int N, const double* h_K, const double* h_Rt_prior,
+                         double gate, double huber_a, int rounds, int max_iter, int min_inliers, double* h_Rt, double* h_cov,
+                         uint8_t* h_inlier_mask, int* n_inliers, double* rmse, int* iterations, int* rounds_run, int* converged,
+                         int* result);
 
 /* ---- the inter-camera step from device memory: ColoC::interPoseEstimator (coloc.hpp:296-340) without a host trip --------------------
  * What clc_inter_pose_batch computes, fed from the pair's d_match instead of host correspondences: the pair gather and the 'E' filter of
