@@ -22,7 +22,8 @@
 //   a wave expands its 64 queries into B operands once (registers), the workgroup expands each 32-train tile into
 //   LDS (coalesced 8-byte loads, 7 VALU ops per 16 bytes of FP4) for its four waves.
 //
-// (B) popcount -- k2nn_sweep_kernel (round 1's kernel, kept as the measured A/B reference):
+// (B) popcount -- k2nn_sweep_kernel (round 1's kernel, kept as the measured A/B reference; its body is k2nn_sweep.h, which the gated
+//   sweeps of k2nn_guided.hip run as well):
 //
 //   * lane = query.  Each lane keeps R complete 512-bit queries in VGPRs (16 dwords each), so a
 //     distance needs NO cross-lane traffic at all.
@@ -45,7 +46,7 @@
 //     writes the int32 results and re-arms rows and counter -- no second launch, no spinning.
 //     Train sets beyond 2^22 vectors fall back to per-split slabs + an ordered merge kernel.
 #include "clc_internal.h"
-#include "k2nn_sweep.h"      // the workgroup's shape, the key layout, the pointer types, accept / emit_result (shared with k2nn_guided.hip)
+#include "k2nn_sweep.h"      // the popcount sweep's body, the key layout, the pointer types, accept / emit_result
 #include "k2nn_top2.h"
 #include <algorithm>
 
@@ -72,189 +73,25 @@ static_assert(((kIdxMask + 1u) >> 5) <= kBiasBeginMask + 1u, "every tile of an a
 
 int k2nn_queries_per_block(int formulation) { return formulation == K2NN_POPCOUNT ? kQPerBlock : kMxQPerBlock; }
 
-// One train vector (16 wave-uniform dwords in SGPRs) against the R queries of this lane.
-//
-// Per query: 16 x (v_xor_b32 with the scalar train word, immediately consumed by v_bcnt_u32_b32 with accumulate), then
-// key = (distance << 22) + index; second = med3(best, second, key); best = min(best, key).
-// The exact instruction pattern is measured, not guessed (20k x 20k sweep, same device):
-//     v_xor ; v_bcnt ; s_nop 0     311-313 us   <- this file
-//     v_xor ; v_bcnt               368 us       (back to back: the SGPR-operand v_xor after a v_bcnt costs a full 4 cycles)
-//     v_xor ; s_nop 0 ; v_bcnt     324 us       v_xor ; s_nop ; v_bcnt ; s_nop   377 us
-//     ... ; s_nop 1 / two s_nop 0 / s_nop 3 after the pair   316 / 317 / 314 us
-// i.e. the v_bcnt must directly follow the v_xor that feeds it and ONE idle issue slot must follow the pair: then a
-// pair issues in ~6.3 cycles instead of 8 (profiles/r01_valu_issue_rates.txt).  The compiler used to supply that
-// s_nop by accident (it pads every asm statement with a hazard nop); it is spelled out here so that the pattern does
-// not depend on it (an s_nop inside the three top-2 instructions, or the VOP3 encoding of the v_xor, changed nothing or
-// cost 1-2 %).  The first v_bcnt accumulates onto the literal 0 (no v_mov to clear the accumulator).
-template <int R>
-__device__ __forceinline__ void sweep_one(const uint32_t (&q)[R][16], const u32x4 a, const u32x4 b,
-                                          const u32x4 c, const u32x4 d, const uint32_t t_rel,
-                                          uint32_t (&best)[R], uint32_t (&second)[R])
-{
-#define K2NN_PAIR(t, q, accin) "v_xor_b32 %1, " t ", " q "\n\tv_bcnt_u32_b32 %0, %1, " accin "\n\ts_nop 0\n\t"
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        uint32_t acc, tmp;
-        asm volatile(K2NN_PAIR("%10", "%2", "0") K2NN_PAIR("%11", "%3", "%0") K2NN_PAIR("%12", "%4", "%0") K2NN_PAIR("%13", "%5", "%0")
-                     K2NN_PAIR("%14", "%6", "%0") K2NN_PAIR("%15", "%7", "%0") K2NN_PAIR("%16", "%8", "%0") K2NN_PAIR("%17", "%9", "%0")
-                     : "=&v"(acc), "=&v"(tmp)
-                     : "v"(q[r][0]), "v"(q[r][1]), "v"(q[r][2]), "v"(q[r][3]), "v"(q[r][4]), "v"(q[r][5]), "v"(q[r][6]), "v"(q[r][7]),
-                       "s"(a.x), "s"(a.y), "s"(a.z), "s"(a.w), "s"(b.x), "s"(b.y), "s"(b.z), "s"(b.w));
-        asm volatile(K2NN_PAIR("%12", "%4", "%0") K2NN_PAIR("%13", "%5", "%0") K2NN_PAIR("%14", "%6", "%0") K2NN_PAIR("%15", "%7", "%0")
-                     K2NN_PAIR("%16", "%8", "%0") K2NN_PAIR("%17", "%9", "%0") K2NN_PAIR("%18", "%10", "%0") K2NN_PAIR("%19", "%11", "%0")
-                     "v_lshl_add_u32 %1, %0, 22, %20\n\tv_med3_u32 %3, %2, %3, %1\n\tv_min_u32 %2, %2, %1"
-                     : "+v"(acc), "=&v"(tmp), "+v"(best[r]), "+v"(second[r])
-                     : "v"(q[r][8]), "v"(q[r][9]), "v"(q[r][10]), "v"(q[r][11]), "v"(q[r][12]), "v"(q[r][13]), "v"(q[r][14]), "v"(q[r][15]),
-                       "s"(c.x), "s"(c.y), "s"(c.z), "s"(c.w), "s"(d.x), "s"(d.y), "s"(d.z), "s"(d.w), "s"(t_rel));
-    }
-#undef K2NN_PAIR
-}
-
-// (accept / emit_result, the acceptance rule and the finalize of a folded row: k2nn_sweep.h)
-
+// The plain popcount sweep: the one body of k2nn_sweep.h without a gate.  The kernel's own: K2nnJobDev and its live counts (k2nn_job_nq
+// with q_row0, k2nn_job_nt), the acceptance rule it is compiled for, and the slab rows of a plan without the atomic fold.
 template <int R, bool RATIO = false>
 __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_kernel(const K2nnJobList jobs,
                                                                   uint2* __restrict__ partial)
 {
-    __shared__ uint32_t s_best[kWaves - 1][R][64], s_second[kWaves - 1][R][64];
     const K2nnJobDev& job = jobs.j[blockIdx.y];
     const uint32_t job_nq = k2nn_job_nq(job), job_nt = k2nn_job_nt(job);     // == job.nq / job.nt unless the counts live on the device
-    // XCD-aware tile order.  Workgroups go to the 8 XCDs round-robin by linear id and every XCD has its own L2.
-    // The planner makes `splits` a multiple of 8 (and with it gridDim.x), so XCD x only ever sees the train splits
-    // with (split & 7) == x: each L2 holds an eighth of T plus the queries, the 8 L2s together pull 8 Q + T from HBM
-    // instead of 8 (Q + T), and every XCD gets exactly the same number of workgroups.  (A 2 x 4 arrangement -- half
-    // of Q, a quarter of T per XCD -- fetches less still but leaves the XCDs 8 % out of balance at 79 query blocks
-    // x 78 splits: measured 2 % slower.)
-    const uint32_t nblk = job.qblocks * job.splits;
-    if (blockIdx.x >= nblk) return;
-    const uint32_t qblock = blockIdx.x / job.splits;
-    const uint32_t split = blockIdx.x - qblock * job.splits;
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t qbase = qblock * (64u * R) + lane;
-
-    uint32_t q[R][16];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        uint32_t qi = qbase + 64u * r;
-        if (qi >= job_nq) qi = job_nq ? job_nq - 1u : 0u;   // clamp: duplicate work, never stored (row 0 of the block always exists)
-        const global_cu4_ptr qp = (global_cu4_ptr)(uintptr_t)job.q + (size_t)qi * 4u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const u32x4 v = qp[k];
-            q[r][4 * k + 0] = v.x; q[r][4 * k + 1] = v.y; q[r][4 * k + 2] = v.z; q[r][4 * k + 3] = v.w;
-        }
-    }
-    uint32_t best[R], second[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) { best[r] = kEmpty; second[r] = kEmpty; }
-
-    // this wave's quarter [t0, t1) of the workgroup's split [s0, s1)
-    const uint32_t s0 = min(split * job.t_per_split, job_nt);
-    const uint32_t s1 = min(s0 + job.t_per_split, job_nt);
-    const uint32_t per_wave = (s1 - s0 + kWaves - 1) / kWaves;
-    const uint32_t t0 = min(s0 + wave * per_wave, s1);
-    const uint32_t t1 = min(t0 + per_wave, s1);
-
-    // Software-pipelined scalar loads: wait for the CURRENT train vector, immediately issue the
-    // s_load_dwordx16 of the NEXT one, then run the 70 VALU ops of the current one while it is in
-    // flight.  (Left to itself the compiler issues the load and waits for it at the loop top; the
-    // explicit order is worth ~11 % at 8 waves/SIMD.)  The prefetch never reads past the slice.
-    // Keys carry the index relative to s0 (the workgroup's split), so the waves' results merge by key.
-    const_u4_ptr tp = (const_u4_ptr)(uintptr_t)job.t + (size_t)t0 * 4u;   // wave-uniform -> s_load_dwordx16
-    if (t0 < t1) {
-        // two SGPR buffers used alternately (no register copies: the scalar ALU is shared by the CU and
-        // 16 s_mov per train vector made it the bottleneck); an odd tail vector is handled after the loop
-        const uint32_t n = t1 - t0;
-        u32x4 a0 = tp[0], b0 = tp[1], c0 = tp[2], d0 = tp[3];
-        uint32_t t = t0;
-        for (uint32_t pair = 0; pair < (n >> 1); ++pair, t += 2) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);                 // lgkmcnt(0): buffer 0 (vector t) has landed
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 a1 = tp[4], b1 = tp[5], c1 = tp[6], d1 = tp[7];          // vector t+1 -> buffer 1
-            __builtin_amdgcn_sched_barrier(0);
-            sweep_one<R>(q, a0, b0, c0, d0, t - s0, best, second);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);                 // buffer 1 has landed
-            __builtin_amdgcn_sched_barrier(0);
-            const_u4_ptr np = (t + 2 < t1) ? tp + 8 : tp;       // vector t+2 -> buffer 0 (never past the slice)
-            a0 = np[0]; b0 = np[1]; c0 = np[2]; d0 = np[3];
-            __builtin_amdgcn_sched_barrier(0);
-            sweep_one<R>(q, a1, b1, c1, d1, t + 1 - s0, best, second);
-            __builtin_amdgcn_sched_barrier(0);
-            tp += 8;
-        }
-        if (n & 1u) sweep_one<R>(q, a0, b0, c0, d0, t - s0, best, second);
-    }
-
-    // fold the kWaves waves through LDS: keys are unique and totally ordered, so
-    // (b, s) (+) (b', s') = (min(b, b'), min(max(b, b'), s, s')) in any order
-    if (wave != 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) { s_best[wave - 1][r][lane] = best[r]; s_second[wave - 1][r][lane] = second[r]; }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int w = 0; w < kWaves - 1; ++w) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const uint32_t ob = s_best[w][r][lane], os = s_second[w][r][lane];
-            second[r] = min(min(second[r], os), max(best[r], ob));
-            best[r] = min(best[r], ob);
-        }
-    }
-
+    SweepSplit<R> sp;
+    if (!sweep_split<R, NoGate>(job, job_nq, job_nt, sp)) return;
     if (job.atomic_merge) {
-        // Fold this split into the query's global top-2 with two 32-bit atomicMin.  Keys carry the
-        // GLOBAL train index here (s0 + index in split < 2^22), so unsigned order on keys is the total
-        // order (distance, index) and the fold is commutative: whichever value leaves the `best` slot
-        // (because a smaller key arrived) is offered to `second` by the arrival that displaced it.
-        unsigned int* top = reinterpret_cast<unsigned int*>(partial + job.partial_off);
-        uint32_t seen = 0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const uint32_t qi = qbase + 64u * r;
-            if (qi < job_nq && best[r] != kEmpty) {
-                const uint32_t bkey = best[r] + s0;
-                const uint32_t skey = second[r] == kEmpty ? kEmpty : second[r] + s0;
-                const uint32_t old = atomicMin(top + 2u * qi, bkey);
-                const uint32_t cand = bkey < old ? min(old, skey) : bkey;
-                seen |= old;
-                if (cand != kEmpty) seen |= atomicMin(top + 2u * qi + 1u, cand);
-            }
-        }
-        // Arrival counter of this query block (armed at all-ones like the rows, so the n-th arrival reads n - 2).
-        // Every atomic above RETURNS a value and the wave waits for all of them (vmcnt(0)), i.e. they have been
-        // performed at the memory side -- agent-scope atomics bypass the XCD-local L2 -- before lane 0 counts this
-        // workgroup in.  Whoever arrives last therefore knows every split has been folded and turns the rows into
-        // results; rows and counter are read AND re-armed by atomic exchange, so no cached copy is ever consulted.
-        // (A __threadfence() here would be the textbook release, but its L2 write-back + invalidate per workgroup
-        // evicts the train slices the other workgroups are streaming: measured +50 % on the whole sweep.)
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(seen) : : "memory");
-        unsigned int* cnt = reinterpret_cast<unsigned int*>(partial) + job.cnt_off + qblock;
-        uint32_t arrival = 0;
-        if (lane == 0) arrival = atomicAdd(cnt, 1u) + 1u;
-        arrival = __builtin_amdgcn_readfirstlane(arrival);
-        if (arrival != job.splits - 1u) return;
-        if (lane == 0) atomicExch(cnt, kEmpty);
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const uint32_t qi = qbase + 64u * r;
-            if (qi < job.nq) {          // every PLANNED row gets an answer; rows past a device-side count hold no key -> -1
-                const uint32_t bkey = atomicExch(top + 2u * qi, kEmpty);
-                const uint32_t skey = atomicExch(top + 2u * qi + 1u, kEmpty);
-                emit_result<RATIO>(job, qi, bkey, skey);
-            }
-        }
+        sweep_fold_finalize<R, RATIO>(job, job_nq, partial, sp);
         return;
     }
-    const global_u2_ptr prow = (global_u2_ptr)(uintptr_t)partial + job.partial_off + (size_t)split * job.nq_pad;
+    const global_u2_ptr prow = (global_u2_ptr)(uintptr_t)partial + job.partial_off + (size_t)sp.split * job.nq_pad;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const uint32_t qi = qbase + 64u * r;
-        if (qi < job.nq) prow[qi] = qi < job_nq ? u32x2{ best[r], second[r] } : u32x2{ kEmpty, kEmpty };
+        const uint32_t qi = sp.qbase + 64u * r;
+        if (qi < job.nq) prow[qi] = qi < job_nq ? u32x2{ sp.best[r], sp.second[r] } : u32x2{ kEmpty, kEmpty };
     }
 }
 
@@ -547,17 +384,14 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
         if (qi < job.nq) prow[qi] = qi < job_nq ? u32x2{ bkey_l, skey_l } : u32x2{ kEmpty, kEmpty };
         return;
     }
-    // same fold / arrival / finalize protocol as the popcount kernel (see there for why no fence is needed): every
+    // same fold / arrival / finalize protocol as the popcount sweep (k2nn_sweep.h, sweep_fold_finalize: why no fence is needed).  The fold of
+    // a row is shared (top2_row_fold); the arrival and the last arrival's exchanges are this kernel's own per-thread statement (behind
+    // a shared function the instructions of this finalize changed order, and the kernel's text is held as it was): every
     // thread's atomics RETURN, every wave waits for them, the workgroup barrier joins the four waves, then one lane
     // counts the workgroup in; the last arrival of a query block turns the rows into results and re-arms them.
     unsigned int* top = reinterpret_cast<unsigned int*>(partial + job.partial_off);
     uint32_t seen = 0;
-    if (qi < job_nq && bkey_l != kEmpty) {
-        const uint32_t old = atomicMin(top + 2u * qi, bkey_l);
-        const uint32_t cand = bkey_l < old ? min(old, skey_l) : bkey_l;
-        seen |= old;
-        if (cand != kEmpty) seen |= atomicMin(top + 2u * qi + 1u, cand);
-    }
+    if (qi < job_nq && bkey_l != kEmpty) seen = top2_row_fold(top, qi, bkey_l, skey_l);
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(seen) : : "memory");
     __syncthreads();
     unsigned int* cnt = reinterpret_cast<unsigned int*>(partial) + job.cnt_off + qblock;
@@ -580,15 +414,8 @@ __global__ __launch_bounds__(64 * kMxWaves) void k2nn_sweep_mx_kernel(const K2nn
     }
 }
 
-// Atomic mode, jobs with an EMPTY train set only (no sweep workgroup exists that could finalize them):
-// the reference leaves best_i uninitialised there (CUDAK2NN.cu:54,75); defined here as "no match".
-__global__ __launch_bounds__(256) void k2nn_nomatch_kernel(const K2nnJobList jobs)
-{
-    const K2nnJobDev& job = jobs.j[blockIdx.y];
-    const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
-    if (job.nt != 0u || qi >= job.nq) return;
-    emit_result<false>(job, qi, kEmpty, kEmpty);                      // no best row: -1 under either rule
-}
+// jobs with an EMPTY train set, atomic mode (nomatch_rows, k2nn_sweep.h)
+__global__ __launch_bounds__(256) void k2nn_nomatch_kernel(const K2nnJobList jobs) { nomatch_rows(jobs); }
 
 // Fold the per-split partials of one query and threshold.
 // The merge of two partial results is associative as long as the left operand holds the lower
@@ -661,6 +488,31 @@ __global__ __launch_bounds__(kMergeQ * kMergeGroups) void k2nn_merge_kernel(cons
     job.out[qi] = ok ? a.best_i : -1;
     if (job.best_out) job.best_out[qi] = (uint16_t)min(a.best_v, 65535);
     if (job.second_out) job.second_out[qi] = (uint16_t)min(a.second_v, 65535);
+}
+
+// Unequal shares by wave slot (K2nnJobDev.bias_a), the arithmetic of one query block, stated once for the plan's checks and the launch's
+// tables.  Query block q of nq_blocks interleaved ones has its split k on workgroup k nq_blocks + q of the id space, and slot_wgs ids
+// make a wave slot: n0 of its splits sit on slot 0 (a tiles each), n1 on slot 1 (b tiles), and the n2 on slot 2 share the rest of the
+// nt_tiles, c tiles each, the first `extra` of them one more (c = extra = 0 where nothing is left or n2 == 0).
+struct SlotShares { uint32_t n0, n1, n2, used, c, extra; };
+static SlotShares slot_shares(const uint32_t slot_wgs, const uint32_t q, const uint32_t nq_blocks, const uint32_t splits, const uint32_t a, const uint32_t b,
+                              const uint32_t nt_tiles)
+{
+    SlotShares s;
+    s.n0 = std::min((slot_wgs - q + nq_blocks - 1u) / nq_blocks, splits);
+    s.n1 = std::min((2u * slot_wgs - q + nq_blocks - 1u) / nq_blocks, splits) - s.n0;
+    s.n2 = splits - s.n0 - s.n1;
+    s.used = s.n0 * a + s.n1 * b;
+    const uint32_t rest = nt_tiles > s.used ? nt_tiles - s.used : 0u;
+    s.c = s.n2 ? rest / s.n2 : 0u;
+    s.extra = s.n2 ? rest - s.c * s.n2 : 0u;
+    return s;
+}
+// what k2nn_plan asks of every query block: a slot-2 split exists, the slot-0 and slot-1 splits lie inside the train set, every slot-2 split
+// is within the 13-bit index field (256 tiles) and none is below the two tiles the equal plan guarantees (min_per)
+static bool slot_shares_fit(const SlotShares& s, const uint32_t nt_tiles)
+{
+    return s.n2 >= 1u && s.used < nt_tiles && s.c + (s.extra ? 1u : 0u) <= 255u && s.c >= 2u;
 }
 
 K2nnPlan k2nn_plan(K2nnJobDev* jobs, int njobs, int target_blocks, bool xcd_map, int formulation, int bias_a, int bias_b, K2nnDevice dev)
@@ -749,19 +601,11 @@ K2nnPlan k2nn_plan(K2nnJobDev* jobs, int njobs, int target_blocks, bool xcd_map,
             const uint32_t den = jb.splits * 256u;
             const uint32_t a = bias_a < 64 ? (uint32_t)bias_a : (nt_tiles * (uint32_t)bias_a + den / 2u) / den;
             const uint32_t b = bias_b < 64 ? (uint32_t)bias_b : (nt_tiles * (uint32_t)bias_b + den / 2u) / den;
-            // every query block's split sizes as the kernel derives them: all within the 13-bit index field (256 tiles), the slot-0 and
-            // slot-1 splits inside the train set
+            // every query block's split sizes as the kernel derives them (slot_shares_fit) ... and everything the 32-bit table entry
+            // carries inside its field (a 12-bit begin field silently clamped train sets beyond 4096 tiles)
             const uint32_t nqx = jb.qblocks >> 3;
-            // ... and everything the 32-bit table entry carries inside its field (a 12-bit begin field silently clamped train
-            // sets beyond 4096 tiles), no slot-2 split below the two tiles the equal plan guarantees (min_per)
             bool ok = a >= 1u && b >= 1u && a <= 255u && b <= 255u && nqx <= kBiasQlMask + 1u && nt_tiles <= kBiasBeginMask;
-            for (uint32_t ql = 0; ok && ql < nqx; ++ql) {
-                const uint32_t n0 = std::min((cu_x - ql + nqx - 1u) / nqx, jb.splits);
-                const uint32_t n1 = std::min((2u * cu_x - ql + nqx - 1u) / nqx, jb.splits) - n0;
-                const uint32_t n2 = jb.splits - n0 - n1;
-                const uint32_t used = n0 * a + n1 * b;
-                ok = n2 >= 1u && used < nt_tiles && (nt_tiles - used + n2 - 1u) / n2 <= 255u && (nt_tiles - used) / n2 >= 2u;
-            }
+            for (uint32_t ql = 0; ok && ql < nqx; ++ql) ok = slot_shares_fit(slot_shares(cu_x, ql, nqx, jb.splits, a, b, nt_tiles), nt_tiles);
             if (ok) { jb.bias_a = a; jb.bias_b = b; jb.bias_magic = 0u; jb.slot_wgs = cu_x; }
         }
         // the same for query-block counts that are NOT whole eights: interleaved over all workgroup ids (K2nnJobDev.bias_magic), the split
@@ -775,13 +619,7 @@ K2nnPlan k2nn_plan(K2nnJobDev* jobs, int njobs, int target_blocks, bool xcd_map,
             const uint32_t a = bias_a < 64 ? (uint32_t)bias_a : (nt_tiles * (uint32_t)bias_a + den / 2u) / den;
             const uint32_t b = bias_b < 64 ? (uint32_t)bias_b : (nt_tiles * (uint32_t)bias_b + den / 2u) / den;
             bool ok = a >= 1u && b >= 1u && a <= 255u && b <= 255u;
-            for (uint32_t q = 0; ok && q < QB; ++q) {
-                const uint32_t n0 = std::min((dev.n_cu - q + QB - 1u) / QB, sp);
-                const uint32_t n1 = std::min((2u * dev.n_cu - q + QB - 1u) / QB, sp) - n0;
-                const uint32_t n2 = sp - n0 - n1;
-                const uint32_t used = n0 * a + n1 * b;
-                ok = n2 >= 1u && used < nt_tiles && (nt_tiles - used + n2 - 1u) / n2 <= 255u && (nt_tiles - used) / n2 >= 2u;
-            }
+            for (uint32_t q = 0; ok && q < QB; ++q) ok = slot_shares_fit(slot_shares(dev.n_cu, q, QB, sp, a, b, nt_tiles), nt_tiles);
             if (ok) {
                 jb.bias_a = a; jb.bias_b = b;
                 jb.bias_magic = (uint32_t)((0x100000000ull + QB - 1u) / QB);
@@ -822,13 +660,8 @@ hipError_t launch_k2nn(const K2nnJobDev* jobs, int njobs, uint2* d_partial, hipS
             const K2nnJobDev& jb = list.j[0];
             const uint32_t QB = jb.qblocks, nt_tiles = (jb.nt + 31u) >> 5;
             for (uint32_t q = 0; q < QB && q < 128u; ++q) {
-                const uint32_t n0 = std::min((jb.slot_wgs - q + QB - 1u) / QB, jb.splits);
-                const uint32_t n1 = std::min((2u * jb.slot_wgs - q + QB - 1u) / QB, jb.splits) - n0;
-                const uint32_t n2 = jb.splits - n0 - n1;
-                const uint32_t used = n0 * jb.bias_a + n1 * jb.bias_b;
-                const uint32_t rest = nt_tiles > used ? nt_tiles - used : 0u;
-                const uint32_t c = n2 ? rest / n2 : 0u, extra = n2 ? rest - c * n2 : 0u;
-                list.bias_tab[q] = n0 | (n1 << 8) | (std::min(c, 255u) << 16) | (std::min(extra, 255u) << 24);
+                const SlotShares s = slot_shares(jb.slot_wgs, q, QB, jb.splits, jb.bias_a, jb.bias_b, nt_tiles);
+                list.bias_tab[q] = s.n0 | (s.n1 << 8) | (std::min(s.c, 255u) << 16) | (std::min(s.extra, 255u) << 24);
             }
             grid_x = QB * jb.splits;                                          // nothing padded
         } else
@@ -840,15 +673,10 @@ hipError_t launch_k2nn(const K2nnJobDev* jobs, int njobs, uint2* d_partial, hipS
             const uint32_t nqx = jb.qblocks >> 3, nt_tiles = (jb.nt + 31u) >> 5;
             for (uint32_t w = 0; w < nqx * jb.splits && w < 96u; ++w) {
                 const uint32_t ql = w % nqx, k = w / nqx;
-                const uint32_t n0 = std::min((jb.slot_wgs - ql + nqx - 1u) / nqx, jb.splits);
-                const uint32_t n1 = std::min((2u * jb.slot_wgs - ql + nqx - 1u) / nqx, jb.splits) - n0;
-                const uint32_t n2 = jb.splits - n0 - n1;
-                const uint32_t used = n0 * jb.bias_a + n1 * jb.bias_b;
-                const uint32_t rest = nt_tiles > used ? nt_tiles - used : 0u;
-                const uint32_t c = n2 ? rest / n2 : 0u, extra = n2 ? rest - c * n2 : 0u;
-                const uint32_t k0 = std::min(k, n0), k1 = std::min(k - k0, n1), k2 = k - k0 - k1;
-                const uint32_t begin = k0 * jb.bias_a + k1 * jb.bias_b + k2 * c + std::min(k2, extra);
-                uint32_t size = k < n0 ? jb.bias_a : (k < n0 + n1 ? jb.bias_b : c + (k2 < extra ? 1u : 0u));
+                const SlotShares s = slot_shares(jb.slot_wgs, ql, nqx, jb.splits, jb.bias_a, jb.bias_b, nt_tiles);
+                const uint32_t k0 = std::min(k, s.n0), k1 = std::min(k - k0, s.n1), k2 = k - k0 - k1;
+                const uint32_t begin = k0 * jb.bias_a + k1 * jb.bias_b + k2 * s.c + std::min(k2, s.extra);
+                uint32_t size = k < s.n0 ? jb.bias_a : (k < s.n0 + s.n1 ? jb.bias_b : s.c + (k2 < s.extra ? 1u : 0u));
                 if (k + 1u == jb.splits) size = nt_tiles > begin ? nt_tiles - begin : 0u;      // the last split takes what is left
                 // (k2nn_plan has checked that every field holds its value; the clamps only keep a corrupted job record from aliasing)
                 list.bias_tab[w] = (ql & kBiasQlMask) | (std::min(begin, kBiasBeginMask) << kBiasBeginShift) | (std::min(size, kBiasSizeMax) << kBiasSizeShift);

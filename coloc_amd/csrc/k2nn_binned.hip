@@ -229,9 +229,7 @@ __global__ __launch_bounds__(kMatchThreads) void k2nn_binned_kernel(const BinJob
         best = top2_min(best, ob);
     }
     if (sub != 0u) return;
-    K2nnJobDev fin{};                                     // what emit_result reads of a job
-    fin.out = jb.out; fin.best_out = jb.best_out; fin.second_out = jb.second_out; fin.thr = jb.thr;
-    emit_result<false>(fin, qi, best, second);            // every PLANNED row gets an answer; rows past a device-side count hold no key -> -1
+    emit_result<false>(jb, qi, best, second);             // every PLANNED row gets an answer; rows past a device-side count hold no key -> -1
 }
 
 // The jobs `pick` of a checked batch through prep, bin and (match: not the table alone) the match launch.  cell_start_out / cell_row_out:

@@ -6,19 +6,20 @@
 //                             kernel runs), then guided_line (guided_math.h) for a query row -> L, 3 floats; the pixel rounded to float for a
 //                             train row -> (x, y), 2 floats.  Rows past a device-side count, and queries without a line, carry NaNs: they
 //                             can never pass the gate.
-//   k2nn_sweep_guided_kernel  the popcount sweep of k2nn.hip (lane = query, the train row wave-uniform in SGPRs, the same 2-D
-//                             decomposition, plan, atomic fold and arrival-counter finalize) with the gate: the lane keeps the lines of its
+//   k2nn_sweep_guided_kernel  the popcount sweep (k2nn_sweep.h: the ONE body behind this kernel and k2nn.hip's k2nn_sweep_kernel -- lane =
+//                             query, the train row wave-uniform in SGPRs, the 2-D decomposition, the pipelined loop, the LDS fold, the
+//                             atomic fold and the arrival-counter finalize) with a gate: the lane keeps the lines of its
 //                             kR queries in six VGPRs, the train point arrives as the train row does -- one s_load_dwordx2 beside the
 //                             s_load_dwordx16, a vector ahead --, and a non-candidate's key becomes kEmpty in front of the med3 / min pair
 //                             (v_fma, v_fma, v_cmp, v_cndmask per pair: no branch).  Each v_fma reads ONE scalar operand (the train
 //                             coordinate) next to two vector operands, the v_cmp one (the band): within the one-SGPR-per-instruction rule
 //                             of the gfx9 vector ALU, so no v_mov copies a scalar into the loop.
 // It runs whatever formulation the context is set to: a per-pair gate has no place in the matrix sweep, whose C operand is per tile.
-// The jobs travel in records of their own (GuidedJobList), not in K2nnJobDev: the existing sweep kernels are compiled as they were.
+// The jobs travel in records of their own (GuidedJobList), not in K2nnJobDev, whose layout the matrix sweep is compiled against.  This
+// file owns the gates, the record, how its live counts are read (counted) and the kernel's entry; everything behind that is the body's.
 //
-// The same sweep serves the map match guided by a predicted pose (clc_match_map_guided_dev / clc_match_map_guided_batch_dev): the GATE is a
-// template parameter of k2nn_sweep_guided_kernel / sweep_one_guided, so ONE pipelined loop, one LDS fold, one atomic fold and one finalize
-// stand behind both.
+// The same sweep serves the map match guided by a predicted pose (clc_match_map_guided_dev / clc_match_map_guided_batch_dev): the GATE is
+// the body's template parameter (sweep_one, sweep_rows).
 //   LineGate   3 floats per query (the line), limit = band:  v_fma, v_fma, v_cmp, v_cndmask per pair
 //   PointGate  2 floats per query (the undistorted pixel), limit = r2 = radius^2; the train point is the landmark's projection under the
 //              predicted [R|t]:  v_sub, v_sub, v_mul, v_fma, v_cmp, v_cndmask per pair (proj_in_radius, proj_math.h) -- each still reads at
@@ -84,9 +85,6 @@ struct PointGate {
     static __device__ __forceinline__ bool pass(const float (&g)[2], const float x, const float y, const float lim) { return proj_in_radius(g[0], g[1], x, y, lim); }
 };
 
-typedef const u32x2 __attribute__((address_space(4)))* const_u2_ptr;
-typedef const float __attribute__((address_space(1)))* global_cf_ptr;
-
 __device__ __forceinline__ uint32_t counted(const uint32_t planned, const uint32_t* count)
 {
     if (!count) return planned;
@@ -150,177 +148,20 @@ __global__ __launch_bounds__(256) void proj_prep_kernel(const ProjPrepList jobs)
     }
 }
 
-// One train vector (16 wave-uniform dwords in SGPRs) and its point (2 more) against the R queries of this lane: sweep_one of k2nn.hip --
-// the same xor / popcount pairs, in its measured issue pattern (see there) -- with the key formed and gated in C++ behind them:
-// key = (distance << 22) + index, or kEmpty where the gate says no (Gate::pass, the one statement of each gate); then the med3 / min pair.
-template <int R, class Gate>
-__device__ __forceinline__ void sweep_one_guided(const uint32_t (&q)[R][16], const float (&L)[R][Gate::kF], const u32x4 a, const u32x4 b, const u32x4 c,
-                                                 const u32x4 d, const u32x2 p, const float band, const uint32_t t_rel, uint32_t (&best)[R],
-                                                 uint32_t (&second)[R])
-{
-    const float x = __uint_as_float(p.x), y = __uint_as_float(p.y);
-#define K2NN_PAIR(t, q, accin) "v_xor_b32 %1, " t ", " q "\n\tv_bcnt_u32_b32 %0, %1, " accin "\n\ts_nop 0\n\t"
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        uint32_t acc, tmp;
-        asm volatile(K2NN_PAIR("%10", "%2", "0") K2NN_PAIR("%11", "%3", "%0") K2NN_PAIR("%12", "%4", "%0") K2NN_PAIR("%13", "%5", "%0")
-                     K2NN_PAIR("%14", "%6", "%0") K2NN_PAIR("%15", "%7", "%0") K2NN_PAIR("%16", "%8", "%0") K2NN_PAIR("%17", "%9", "%0")
-                     : "=&v"(acc), "=&v"(tmp)
-                     : "v"(q[r][0]), "v"(q[r][1]), "v"(q[r][2]), "v"(q[r][3]), "v"(q[r][4]), "v"(q[r][5]), "v"(q[r][6]), "v"(q[r][7]),
-                       "s"(a.x), "s"(a.y), "s"(a.z), "s"(a.w), "s"(b.x), "s"(b.y), "s"(b.z), "s"(b.w));
-        asm volatile(K2NN_PAIR("%10", "%2", "%0") K2NN_PAIR("%11", "%3", "%0") K2NN_PAIR("%12", "%4", "%0") K2NN_PAIR("%13", "%5", "%0")
-                     K2NN_PAIR("%14", "%6", "%0") K2NN_PAIR("%15", "%7", "%0") K2NN_PAIR("%16", "%8", "%0") K2NN_PAIR("%17", "%9", "%0")
-                     : "+v"(acc), "=&v"(tmp)
-                     : "v"(q[r][8]), "v"(q[r][9]), "v"(q[r][10]), "v"(q[r][11]), "v"(q[r][12]), "v"(q[r][13]), "v"(q[r][14]), "v"(q[r][15]),
-                       "s"(c.x), "s"(c.y), "s"(c.z), "s"(c.w), "s"(d.x), "s"(d.y), "s"(d.z), "s"(d.w));
-        uint32_t key = (acc << kKeyShift) + t_rel;
-        key = Gate::pass(L[r], x, y, band) ? key : kEmpty;
-        second[r] = top2_med3(best[r], second[r], key);
-        best[r] = top2_min(best[r], key);
-    }
-#undef K2NN_PAIR
-}
-
+// The gated popcount sweep: the one body of k2nn_sweep.h with the gate.  The kernel's own: GuidedJobDev and its live counts (counted),
+// the return when nothing is planned to sweep, the K2NN rule, always the atomic fold (guided_plan refuses every other plan).
 template <int R, class Gate>
 __global__ __launch_bounds__(64 * kWaves) void k2nn_sweep_guided_kernel(const GuidedJobList jobs, uint2* __restrict__ partial)
 {
-    __shared__ uint32_t s_best[kWaves - 1][R][64], s_second[kWaves - 1][R][64];
     const GuidedJobDev& job = jobs.j[blockIdx.y];
     if (job.nt == 0u) return;                                             // nothing planned to sweep: guided_nomatch_kernel answers
     const uint32_t job_nq = counted(job.nq, job.cnt_q), job_nt = counted(job.nt, job.cnt_t);
-    const uint32_t nblk = job.qblocks * job.splits;
-    if (blockIdx.x >= nblk) return;
-    const uint32_t qblock = blockIdx.x / job.splits;                      // (a multiple of 8 splits pins a train split to an XCD: k2nn.hip)
-    const uint32_t split = blockIdx.x - qblock * job.splits;
-
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t qbase = qblock * (64u * R) + lane;
-
-    uint32_t q[R][16];
-    float L[R][Gate::kF];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        uint32_t qi = qbase + 64u * r;
-        if (qi >= job_nq) qi = job_nq ? job_nq - 1u : 0u;   // clamp: duplicate work, never stored (row 0 of the block always exists)
-        const global_cu4_ptr qp = (global_cu4_ptr)(uintptr_t)job.q + (size_t)qi * 4u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const u32x4 v = qp[k];
-            q[r][4 * k + 0] = v.x; q[r][4 * k + 1] = v.y; q[r][4 * k + 2] = v.z; q[r][4 * k + 3] = v.w;
-        }
-        const global_cf_ptr lp = (global_cf_ptr)(uintptr_t)job.L + (size_t)qi * (size_t)Gate::kF;
-#pragma unroll
-        for (int k = 0; k < Gate::kF; ++k) L[r][k] = lp[k];
-    }
-    uint32_t best[R], second[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) { best[r] = kEmpty; second[r] = kEmpty; }
-    const float band = job.band;
-
-    // this wave's share [t0, t1) of the workgroup's split [s0, s1)
-    const uint32_t s0 = min(split * job.t_per_split, job_nt);
-    const uint32_t s1 = min(s0 + job.t_per_split, job_nt);
-    const uint32_t per_wave = (s1 - s0 + kWaves - 1) / kWaves;
-    const uint32_t t0 = min(s0 + wave * per_wave, s1);
-    const uint32_t t1 = min(t0 + per_wave, s1);
-
-    // the software-pipelined scalar loads of k2nn_sweep_kernel, the train point riding beside the train row in both buffers; neither
-    // prefetch reads past the slice
-    const_u4_ptr tp = (const_u4_ptr)(uintptr_t)job.t + (size_t)t0 * 4u;   // wave-uniform -> s_load_dwordx16
-    const_u2_ptr pp = (const_u2_ptr)(uintptr_t)job.pos + (size_t)t0;      // wave-uniform -> s_load_dwordx2
-    if (t0 < t1) {
-        const uint32_t n = t1 - t0;
-        u32x4 a0 = tp[0], b0 = tp[1], c0 = tp[2], d0 = tp[3];
-        u32x2 p0 = pp[0];
-        uint32_t t = t0;
-        for (uint32_t pair = 0; pair < (n >> 1); ++pair, t += 2) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);                 // lgkmcnt(0): buffer 0 (vector t) has landed
-            __builtin_amdgcn_sched_barrier(0);
-            const u32x4 a1 = tp[4], b1 = tp[5], c1 = tp[6], d1 = tp[7];          // vector t+1 -> buffer 1
-            const u32x2 p1 = pp[1];
-            __builtin_amdgcn_sched_barrier(0);
-            sweep_one_guided<R, Gate>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);                 // buffer 1 has landed
-            __builtin_amdgcn_sched_barrier(0);
-            const bool more = t + 2 < t1;                       // vector t+2 -> buffer 0 (never past the slice)
-            const_u4_ptr np = more ? tp + 8 : tp;
-            const_u2_ptr npp = more ? pp + 2 : pp;
-            a0 = np[0]; b0 = np[1]; c0 = np[2]; d0 = np[3];
-            p0 = npp[0];
-            __builtin_amdgcn_sched_barrier(0);
-            sweep_one_guided<R, Gate>(q, L, a1, b1, c1, d1, p1, band, t + 1 - s0, best, second);
-            __builtin_amdgcn_sched_barrier(0);
-            tp += 8;
-            pp += 2;
-        }
-        if (n & 1u) sweep_one_guided<R, Gate>(q, L, a0, b0, c0, d0, p0, band, t - s0, best, second);
-    }
-
-    // fold the kWaves waves through LDS (k2nn_sweep_kernel)
-    if (wave != 0) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) { s_best[wave - 1][r][lane] = best[r]; s_second[wave - 1][r][lane] = second[r]; }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int w = 0; w < kWaves - 1; ++w) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const uint32_t ob = s_best[w][r][lane], os = s_second[w][r][lane];
-            second[r] = min(min(second[r], os), max(best[r], ob));
-            best[r] = min(best[r], ob);
-        }
-    }
-
-    // the atomic fold and the arrival-counter finalize of k2nn_sweep_kernel, statement for statement (see there for why the returning
-    // atomics and the vmcnt(0) make the last arrival's exchange see every split, without a fence)
-    unsigned int* top = reinterpret_cast<unsigned int*>(partial + job.partial_off);
-    uint32_t seen = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t qi = qbase + 64u * r;
-        if (qi < job_nq && best[r] != kEmpty) {
-            const uint32_t bkey = best[r] + s0;
-            const uint32_t skey = second[r] == kEmpty ? kEmpty : second[r] + s0;
-            const uint32_t old = atomicMin(top + 2u * qi, bkey);
-            const uint32_t cand = bkey < old ? min(old, skey) : bkey;
-            seen |= old;
-            if (cand != kEmpty) seen |= atomicMin(top + 2u * qi + 1u, cand);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(seen) : : "memory");
-    unsigned int* cnt = reinterpret_cast<unsigned int*>(partial) + job.cnt_off + qblock;
-    uint32_t arrival = 0;
-    if (lane == 0) arrival = atomicAdd(cnt, 1u) + 1u;
-    arrival = __builtin_amdgcn_readfirstlane(arrival);
-    if (arrival != job.splits - 1u) return;
-    if (lane == 0) atomicExch(cnt, kEmpty);
-    K2nnJobDev fin{};                                     // what emit_result reads of a job
-    fin.out = job.out; fin.best_out = job.best_out; fin.second_out = job.second_out; fin.thr = job.thr;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t qi = qbase + 64u * r;
-        if (qi < job.nq) {          // every PLANNED row gets an answer; rows past a device-side count hold no key -> -1
-            const uint32_t bkey = atomicExch(top + 2u * qi, kEmpty);
-            const uint32_t skey = atomicExch(top + 2u * qi + 1u, kEmpty);
-            emit_result<false>(fin, qi, bkey, skey);
-        }
-    }
+    SweepSplit<R> sp;
+    if (sweep_split<R, Gate>(job, job_nq, job_nt, sp)) sweep_fold_finalize<R, false>(job, job_nq, partial, sp);
 }
 
-// jobs with an EMPTY planned train set: no sweep workgroup exists that could finalize them (k2nn_nomatch_kernel's part)
-__global__ __launch_bounds__(256) void guided_nomatch_kernel(const GuidedJobList jobs)
-{
-    const GuidedJobDev& job = jobs.j[blockIdx.y];
-    const uint32_t qi = blockIdx.x * 256u + threadIdx.x;
-    if (job.nt != 0u || qi >= job.nq) return;
-    K2nnJobDev fin{};
-    fin.out = job.out; fin.best_out = job.best_out; fin.second_out = job.second_out; fin.thr = job.thr;
-    emit_result<false>(fin, qi, kEmpty, kEmpty);
-}
+// jobs with an EMPTY planned train set (nomatch_rows, k2nn_sweep.h)
+__global__ __launch_bounds__(256) void guided_nomatch_kernel(const GuidedJobList jobs) { nomatch_rows(jobs); }
 
 // What the two gates share behind their argument checks.  kj: the live jobs' nq / nt.  The popcount formulation's plan, whatever the
 // context's sweeps run; the scratch -- every job's query floats (qf per row), then its train points, each block starting on 16 bytes --
