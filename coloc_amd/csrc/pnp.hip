@@ -16,7 +16,7 @@
 // relative tolerance on `cost` in the tests.
 #include "clc_internal.h"
 #include "p3p.h"
-#include "so3.h"
+#include "pose_lm.h"
 #include "fivept_wave.h"
 
 namespace clc {
@@ -167,217 +167,71 @@ __global__ __launch_bounds__(256) void pnp_select_mask_kernel(const double* __re
 }
 
 // ---- single-pose refinement + 6x6 covariance ------------------------
-// Role: Localizer::refine -> PoseRefiner::refinePose (reference include/coloc/Localizer.hpp:110-177,
-// include/coloc/Refiner.hpp:47-239): minimise 1/2 sum_i rho(||r_i||^2) over the 6 pose parameters
-// [angle-axis w | t] (x_cam = R(w) X + t), structure and intrinsics fixed, r_i = observed - projected
-// pixel, rho = ceres::HuberLoss(Square(4.0)) (Refiner.hpp:122): rho(s) = s for s <= 256, 2*16*sqrt(s) - 256
-// beyond; then the 6x6 covariance block of the pose = (J^T W J)^-1 at the solution (:177-197).
-// Ceres itself is absent (OpenMVG third_party, empty submodule) -> unpinned; this is a
-// Levenberg-Marquardt on the same cost with the same parametrisation, one workgroup per pose,
-// every iteration = one pass over the points (residual + 2x6 Jacobian + 27 sums reduced through
-// wave shuffles and LDS) + a 6x6 Cholesky solve by lane 0.
-// rodrigues / log_so3 / d_rodrigues_entry / solve6 / invert6_column: so3.h (host + device, so that the tests run them on the CPU too)
-
-static constexpr int kRefineSums = 29;   // 21 (upper JtWJ) + 6 (JtWr) + 1 (cost) + 1 (points used)
-static constexpr int kRefineThreads = 512;
-
-__global__ __launch_bounds__(kRefineThreads) void pnp_refine_kernel(const double* __restrict__ Rt_in, const double* __restrict__ X,
-                                                                    const double* __restrict__ x, const uint8_t* __restrict__ mask,
-                                                                    const int N, const double* __restrict__ K, const double huber_a,
-                                                                    const int max_iter, const int32_t* __restrict__ valid,
-                                                                    RefineOut* __restrict__ out_dev, RefineOut* __restrict__ out_host)
+// The Levenberg-Marquardt pass, its bookkeeping and the record are pose_lm.h's (shared with pose_prior.hip).  This kernel's own: the
+// optional byte mask, the record of a chained solve that found no pose (valid < 0), the number of points used as the 29th sum, and
+// where the record goes (out_host: the caller's pinned buffer, no device-to-host copy command; else out_dev).
+__global__ __launch_bounds__(kPoseThreads) void pnp_refine_kernel(const double* __restrict__ Rt_in, const double* __restrict__ X,
+                                                                  const double* __restrict__ x, const uint8_t* __restrict__ mask,
+                                                                  const int N, const double* __restrict__ K, const double huber_a,
+                                                                  const int max_iter, const int32_t* __restrict__ valid,
+                                                                  RefineOut* __restrict__ out_dev, RefineOut* __restrict__ out_host)
 {
-    // fused multiply-adds in this kernel (the file default is off for the residual kernels compared bit for bit with the oracle;
-    // the refinement is checked against scipy / numeric Jacobians to a tolerance)
 #pragma clang fp contract(fast)
-    RefineOut* const out = out_host ? out_host : out_dev;      // pinned host record (no D2H copy command) or device record
+    RefineOut* const out = out_host ? out_host : out_dev;
+    const int tid = threadIdx.x;
     if (valid && *valid < 0) {          // chained after clc_pnp_ransac that found no pose: nothing to refine
-        if (threadIdx.x < 12) out->Rt[threadIdx.x] = 0.0;
-        if (threadIdx.x < 36) out->cov[threadIdx.x] = 0.0;
-        if (threadIdx.x == 0) { out->cost = 0.0; out->rmse = 0.0; out->iterations = 0; out->n_used = 0; }
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(&out->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (tid < 12) out->Rt[tid] = 0.0;
+        if (tid < 36) out->cov[tid] = 0.0;
+        if (tid == 0) { out->cost = 0.0; out->rmse = 0.0; out->iterations = 0; out->n_used = 0; }
+        pose_publish(tid, &out->ready);
         return;
     }
-    extern __shared__ double red[];     // [kRefineSums][kRefineThreads] reduction scratch (dynamic: 116 KB)
-    __shared__ double s_par[6], s_try[6], s_R[9], s_dR[3][9], s_part[kRefineSums][16], s_tot[kRefineSums];
-    __shared__ double s_A[kRefineSums];   // sums (JtWJ, JtWr, cost, count) at the CURRENT parameters s_par
-    __shared__ int s_flag;
-    const int tid = threadIdx.x;
-    const double fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
-    const double b2 = huber_a * huber_a;
-    if (tid == 0) {
-        double R0[9] = { Rt_in[0], Rt_in[1], Rt_in[2], Rt_in[4], Rt_in[5], Rt_in[6], Rt_in[8], Rt_in[9], Rt_in[10] };
-        double w[3];
-        log_so3(R0, w);
-        s_par[0] = w[0]; s_par[1] = w[1]; s_par[2] = w[2]; s_par[3] = Rt_in[3]; s_par[4] = Rt_in[7]; s_par[5] = Rt_in[11];
-    }
-    __syncthreads();
+    extern __shared__ double red[];     // pose_reduce's scratch (kPoseRedBytes)
+    __shared__ PoseLds s;
+    const PoseCam cam = { K[0], K[1], K[2], K[4], K[5], huber_a, huber_a * huber_a };
+    pose_start(s, tid, Rt_in);
 
-    // One pass over the points at parameters `par`: cost AND the normal-equation sums, so that an
-    // accepted trial step needs no second pass (rejections are rare and only waste the Jacobian part).
     auto pass = [&](const double* par) {
-        if (tid < 64) {
-            // every lane of the first wave evaluates R (same operands, same result); lane 0 publishes it and lanes
-            // 0..26 each one entry of the three derivative matrices -- the serial prologue of a pass is one
-            // rotation + one entry instead of one rotation + 27 entries
-            double Rl[9];
-            rodrigues(par, Rl);
-            if (tid < 9) s_R[tid] = Rl[tid];
-            if (tid < 27) s_dR[tid / 9][tid % 9] = d_rodrigues_entry(par, Rl, tid / 9, tid % 9);
-        }
-        __syncthreads();
-        double acc[kRefineSums];
+        pose_rotation(s, tid, par);
+        double acc[kPoseSums];
 #pragma unroll
-        for (int i = 0; i < kRefineSums; ++i) acc[i] = 0.0;
-        for (int i = tid; i < N; i += kRefineThreads) {
+        for (int i = 0; i < kPoseSums; ++i) acc[i] = 0.0;
+        for (int i = tid; i < N; i += kPoseThreads) {
             if (mask && !mask[i]) continue;
-            const double X0 = X[3 * i], X1 = X[3 * i + 1], X2 = X[3 * i + 2];
-            const double xc = s_R[0] * X0 + s_R[1] * X1 + s_R[2] * X2 + par[3];
-            const double yc = s_R[3] * X0 + s_R[4] * X1 + s_R[5] * X2 + par[4];
-            const double zc = s_R[6] * X0 + s_R[7] * X1 + s_R[8] * X2 + par[5];
-            const double iz = 1.0 / zc, xn = xc * iz, yn = yc * iz;
-            const double r0 = x[2 * i] - (fx * xn + sk * yn + cx), r1 = x[2 * i + 1] - (fy * yn + cy);
-            const double sq = r0 * r0 + r1 * r1;
-            double rho = sq, wgt = 1.0;                                      // rho(s), rho'(s)
-            if (sq > b2) {                                                   // Huber tail: rare after RANSAC, and a real branch
-                const double r = sqrt(sq);                                   // (skipped when no lane of the wave needs it)
-                rho = 2.0 * huber_a * r - b2;
-                wgt = huber_a / r;
-            }
-            acc[27] += 0.5 * rho;
+            const PosePoint p = pose_residual(s, par, cam, X, x, i);
             acc[28] += 1.0;
-            // d(proj)/d(xc,yc,zc)
-            const double pu0 = fx * iz, pu1 = sk * iz, pu2 = -(fx * xn + sk * yn) * iz;
-            const double pv1 = fy * iz, pv2 = -fy * yn * iz;
-            double Ju[6], Jv[6];      // Jacobian of the PROJECTION (residual = obs - proj -> J_r = -J)
-            // the 27 derivative entries are read from LDS per point (uniform address: a broadcast read); hoisted out of the loop
-            // they take 54 VGPRs and push the kernel over its 256-register budget into scratch -- the opaque offset stops that
-            int dro = 0;
-            asm volatile("" : "+v"(dro));
-            const double (*dRp)[9] = reinterpret_cast<const double (*)[9]>(&s_dR[0][0] + dro);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double d0 = dRp[k][0] * X0 + dRp[k][1] * X1 + dRp[k][2] * X2;
-                const double d1 = dRp[k][3] * X0 + dRp[k][4] * X1 + dRp[k][5] * X2;
-                const double d2 = dRp[k][6] * X0 + dRp[k][7] * X1 + dRp[k][8] * X2;
-                Ju[k] = pu0 * d0 + pu1 * d1 + pu2 * d2;
-                Jv[k] = pv1 * d1 + pv2 * d2;
-            }
-            Ju[3] = pu0; Ju[4] = pu1; Ju[5] = pu2;
-            Jv[3] = 0.0; Jv[4] = pv1; Jv[5] = pv2;
-            int idx = 0;
-#pragma unroll
-            for (int a_ = 0; a_ < 6; ++a_) {
-#pragma unroll
-                for (int b_ = a_; b_ < 6; ++b_) acc[idx++] += wgt * (Ju[a_] * Ju[b_] + Jv[a_] * Jv[b_]);
-            }
-#pragma unroll
-            for (int a_ = 0; a_ < 6; ++a_) acc[21 + a_] += wgt * (Ju[a_] * r0 + Jv[a_] * r1);   // = -J_r^T W r : descent rhs
+            pose_accumulate(s, cam, p, acc);
         }
-        // Reduction of the 29 sums over the 512 threads THROUGH LDS, transposed: every thread parks its partials in
-        // red[sum][thread] (conflict-free 8-byte writes), then 29 x 16 threads each add 32 of them and 29 threads add
-        // the 16 partial results.  The shuffle tree it replaces (29 values x 6 levels x 2 ds_bpermute per wave, eight
-        // waves on one LDS pipe) took 16-18 k cycles per pass, measured; this takes ~3 k.
-#pragma unroll
-        for (int i = 0; i < kRefineSums; ++i) red[i * kRefineThreads + tid] = acc[i];
-        __syncthreads();
-        if (tid < kRefineSums * 16) {
-            const int i = tid >> 4, part = tid & 15;
-            const double* src = red + i * kRefineThreads + part;
-            double v = 0.0;
-#pragma unroll 8
-            for (int k = 0; k < kRefineThreads / 16; ++k) v += src[16 * k];
-            s_part[i][part] = v;
-        }
-        __syncthreads();
-        if (tid < kRefineSums) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v += s_part[tid][k];
-            s_tot[tid] = v;
-        }
-        __syncthreads();
+        pose_reduce(s, red, tid, acc);
     };
 
-    // ONE call site of pass() (it is inlined: two copies cost a dozen spilled VGPRs at the 256-register budget of a 512-thread
-    // workgroup): the first trip evaluates the start s_par, every later one the trial s_try; the Levenberg-Marquardt bookkeeping
-    // around it is the loop  "step -> [flag] -> evaluate -> accept / reject"  unrolled by half a turn.
-    double lambda = 1e-4, cost = 0.0;
-    int it = 0;
+    // ONE call site of pass(): the first trip evaluates the start s.par, every later one the trial s.try_; the bookkeeping around it
+    // is the loop  "step -> [flag] -> evaluate -> accept / reject"  unrolled by half a turn.
+    LmState lm;
     bool initial = true;
     for (;;) {
-        pass(initial ? s_par : s_try);
+        pass(initial ? s.par : s.try_);
         if (initial) {
-            if (tid < kRefineSums) s_A[tid] = s_tot[tid];
-            __syncthreads();
-            cost = s_A[27];
+            pose_keep_sums(s, tid);
+            lm.cost = s.A[27];
             initial = false;
         } else {
-            const double new_cost = s_tot[27];
-            bool stop = false;
-            if (new_cost < cost) {
-                const double rel = (cost - new_cost) / fmax(cost, 1e-300);
-                if (tid < 6) s_par[tid] = s_try[tid];
-                if (tid < kRefineSums) s_A[tid] = s_tot[tid];
-                cost = new_cost;
-                lambda = fmax(lambda * 0.1, 1e-12);
-                __syncthreads();
-                if (rel < 1e-8) { ++it; stop = true; }                // function tolerance 1e-8 (Refiner.hpp:169)
-            } else {
-                lambda *= 10.0;
-                __syncthreads();
-                if (lambda > 1e10) stop = true;
-            }
-            if (stop) break;
-            ++it;
+            bool accepted;
+            if (lm_judge(s, tid, lm, accepted)) break;
         }
-        // the next step (rejected factorizations only raise lambda and try again)
-        bool leave = false;
-        for (;;) {
-            if (!(it < max_iter)) { leave = true; break; }
-            if (tid == 0) {
-                double g[6], d[6];
-                for (int a_ = 0; a_ < 6; ++a_) g[a_] = s_A[21 + a_];
-                bool ok = solve6(s_A, g, lambda, d);
-                double gn = 0, dn = 0, pn = 0;
-                for (int a_ = 0; a_ < 6; ++a_) { gn = fmax(gn, fabs(g[a_])); dn += d[a_] * d[a_]; pn += s_par[a_] * s_par[a_]; }
-                // convergence like the reference's settings (gradient / parameter tolerance 1e-8, Refiner.hpp:169-171)
-                s_flag = !ok ? 2 : ((gn < 1e-8 * fmax(1.0, cost) || sqrt(dn) < 1e-8 * (sqrt(pn) + 1e-8)) ? 1 : 0);
-                for (int a_ = 0; a_ < 6; ++a_) s_try[a_] = s_par[a_] + (ok ? d[a_] : 0.0);
-            }
-            __syncthreads();
-            const int flag = s_flag;
-            if (flag == 1) { leave = true; break; }
-            if (flag == 2) {
-                lambda *= 10.0;
-                if (lambda > 1e10) { leave = true; break; }
-                __syncthreads();
-                ++it;
-                continue;
-            }
-            break;
-        }
-        if (leave) break;
+        if (lm_next_step(s, tid, lm, max_iter)) break;
     }
-    // s_A holds the sums at s_par
-    if (tid < 6) {
-        if (!invert6_column(s_A, tid, out->cov)) for (int r = 0; r < 6; ++r) out->cov[6 * r + tid] = 0.0;
-    }
+    // s.A holds the sums at s.par
+    pose_cov_column(s, tid, true, out->cov);
     if (tid == 0) {
-        double R[9];
-        rodrigues(s_par, R);
-        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) out->Rt[4 * i + j] = R[3 * i + j]; out->Rt[4 * i + 3] = s_par[3 + i]; }
-        const double n_used = s_A[28];
-        out->cost = s_A[27];
-        out->rmse = n_used > 0.0 ? sqrt(s_A[27] / (2.0 * n_used)) : 0.0;
-        out->iterations = it;
+        pose_Rt(s, out->Rt);
+        const double n_used = s.A[28];
+        out->cost = s.A[27];
+        out->rmse = pose_rmse(s.A[27], n_used);
+        out->iterations = lm.it;
         out->n_used = (int32_t)n_used;
     }
-    __threadfence_system();                 // every writer: its stores to the (possibly pinned host) record have left
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&out->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    pose_publish(tid, &out->ready);
 }
 
 hipError_t launch_pnp_refine(const double* d_Rt_in, const double* d_X, const double* d_x, const uint8_t* d_mask, int N,
@@ -385,17 +239,10 @@ hipError_t launch_pnp_refine(const double* d_Rt_in, const double* d_X, const dou
                              const int32_t* d_valid, void* h_out)
 {
     if (N <= 0) return hipSuccess;
-    constexpr size_t kRedBytes = sizeof(double) * kRefineSums * kRefineThreads;
-    static bool attr_set[64] = {};      // per device: more than the 64 KB a kernel gets by default
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)pnp_refine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRedBytes);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
+    const hipError_t e = pose_allow_lds<pnp_refine_kernel>();
+    if (e != hipSuccess) return e;
     prof_mark(prof, CLC_KERNEL_PNP_SCORE, true, stream);
-    hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(kRefineThreads), kRedBytes, stream, d_Rt_in, d_X, d_x, d_mask, N, d_K, huber_a, max_iter,
+    hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(kPoseThreads), kPoseRedBytes, stream, d_Rt_in, d_X, d_x, d_mask, N, d_K, huber_a, max_iter,
                        d_valid, (RefineOut*)d_out, (RefineOut*)h_out);
     prof_mark(prof, CLC_KERNEL_PNP_SCORE, false, stream);
     return hipGetLastError();

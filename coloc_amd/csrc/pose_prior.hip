@@ -2,19 +2,19 @@
 // clc_track_prior_dev / clc_track_prior_batch_dev / clc_pnp_refine_prior, THE RULE there).  The project's own statement: the reference's
 // intraPoseEstimator always calls Localize (coloc.hpp:223, Localizer.hpp:77-108).
 //
-// One workgroup of 512 threads per job (blockIdx.x = job), the shape of pnp_refine_kernel (pnp.hip), and that kernel's pass: residual,
-// 2 x 6 Jacobian and 29 sums per pass, reduced in a fixed order through LDS, a 6 x 6 Cholesky solve by lane 0.  What is new around it:
-//   the mask     is the kernel's own.  Thread t owns tracks t, t + 512, ... (at most 32 of the 16 384 a block holds), so a round's mask, the
-//                classification at the parameters just evaluated and the one at the current parameters are three 32-bit words per thread
-//                in registers -- no mask in LDS or global memory inside the loop; the bytes go out once, at the end.
+// One workgroup of 512 threads per job (blockIdx.x = job).  The Levenberg-Marquardt pass, its bookkeeping and the record are pose_lm.h's
+// (shared with pnp_refine_kernel, pnp.hip).  What is this kernel's own around them:
+//   the mask     Thread t owns tracks t, t + 512, ... (at most 32 of the 16 384 a block holds), so a round's mask, the classification at
+//                the parameters just evaluated and the one at the current parameters are three 32-bit words per thread in registers --
+//                no mask in LDS or global memory inside the loop; the bytes go out once, at the end.
 //   classify     rides the pass: zc and sq of EVERY track are computed anyway before a masked-out track is skipped, so "in" is taken from
 //                the very numbers the pass uses.  The three counts the rounds need (|mask|, |in|, |in xor mask|) travel in the 29th sum
 //                as one exact double, n_mask + 2^16 n_in + 2^32 n_differ (each <= 16 384): no reduction of their own.
 //   the count    N is read from the gather's DEVICE word (nothing on the host depends on it), clamped to the block's capacity.
-// Sums in a fixed order, no floating-point atomics: two runs on the same inputs give the same bits, and a job's result does not depend
-// on the jobs beside it.
+//   the rounds   START / TRIAL / FINAL below; few, moved, converged, capacity in the record.
+// A job's result does not depend on the jobs beside it.
 #include "clc_ctx.h"
-#include "so3.h"
+#include "pose_lm.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,25 +25,20 @@ namespace clc {
 
 namespace {
 
-constexpr int kPriorSums = 29;        // 21 (upper JtWJ) + 6 (JtWr) + 1 (cost) + 1 (the three counts, packed)
-constexpr int kPriorThreads = 512;
-static_assert(kAcrMaxN <= 32 * kPriorThreads, "a thread's tracks must fit its 32-bit mask words");
+static_assert(kAcrMaxN <= 32 * kPoseThreads, "a thread's tracks must fit its 32-bit mask words");
 constexpr double kInOne = 65536.0, kDifferOne = 4294967296.0;
 
 __device__ __forceinline__ int prior_n_mask(const double packed) { return (int)((unsigned long long)packed & 0xFFFFull); }
 __device__ __forceinline__ int prior_n_in(const double packed) { return (int)(((unsigned long long)packed >> 16) & 0xFFFFull); }
 __device__ __forceinline__ int prior_n_differ(const double packed) { return (int)((unsigned long long)packed >> 32); }
 
-__global__ __launch_bounds__(kPriorThreads) void pose_prior_kernel(const PriorJobs jobs)
+__global__ __launch_bounds__(kPoseThreads) void pose_prior_kernel(const PriorJobs jobs)
 {
-    // fused multiply-adds as in pnp_refine_kernel (the result is held to a 50-digit reference by tolerance, tests/pose_prior_mp.py)
 #pragma clang fp contract(fast)
     const PriorJobDev& jb = jobs.j[blockIdx.x];
     PriorOut* const out = jb.out;
-    extern __shared__ double red[];     // [kPriorSums][kPriorThreads] reduction scratch (dynamic: 116 KB)
-    __shared__ double s_par[6], s_try[6], s_R[9], s_dR[3][9], s_part[kPriorSums][16], s_tot[kPriorSums];
-    __shared__ double s_A[kPriorSums];  // the sums at the CURRENT parameters s_par over the round's mask
-    __shared__ int s_flag;
+    extern __shared__ double red[];     // pose_reduce's scratch (kPoseRedBytes)
+    __shared__ PoseLds s;               // s.A: the sums at the CURRENT parameters s.par over the round's mask
     const int tid = threadIdx.x;
     int n_raw = jb.n_dev ? *jb.n_dev : jb.n;
     if (n_raw < 0) n_raw = 0;
@@ -51,180 +46,69 @@ __global__ __launch_bounds__(kPriorThreads) void pose_prior_kernel(const PriorJo
     const int N = n_raw > cap ? (cap > 0 ? cap : 0) : n_raw;
     const double* __restrict__ X = jb.X;
     const double* __restrict__ x = jb.x;
-    const double fx = jb.fx, sk = jb.sk, cx = jb.cx, fy = jb.fy, cy = jb.cy;
-    const double huber_a = jb.huber_a, b2 = huber_a * huber_a, g2 = jb.g2;
+    const PoseCam cam = { jb.fx, jb.sk, jb.cx, jb.fy, jb.cy, jb.huber_a, jb.huber_a * jb.huber_a };
+    const double g2 = jb.g2;
     const int max_iter = jb.max_iter;
-    if (tid == 0) {
-        double R0[9] = { jb.Rt[0], jb.Rt[1], jb.Rt[2], jb.Rt[4], jb.Rt[5], jb.Rt[6], jb.Rt[8], jb.Rt[9], jb.Rt[10] };
-        double w[3];
-        log_so3(R0, w);
-        s_par[0] = w[0]; s_par[1] = w[1]; s_par[2] = w[2]; s_par[3] = jb.Rt[3]; s_par[4] = jb.Rt[7]; s_par[5] = jb.Rt[11];
-    }
-    __syncthreads();
+    pose_start(s, tid, jb.Rt);
 
     // bit k of a word <-> track tid + 512 k.  m_bits: the round's mask; c_new: classify at the parameters of the pass just made;
-    // c_cur: classify at s_par
+    // c_cur: classify at s.par
     uint32_t m_bits = 0, c_new = 0, c_cur = 0;
 
-    // pnp_refine_kernel's pass at parameters `par` over the tracks of m_bits -- front: over the tracks in front of the camera, which
-    // become m_bits (the first pass: m_0) -- with every track classified on the way
+    // the pass at parameters `par` over the tracks of m_bits -- front: over the tracks in front of the camera, which become m_bits
+    // (the first pass: m_0) -- with every track classified on the way
     auto pass = [&](const double* par, const bool front) {
-        if (tid < 64) {
-            double Rl[9];
-            rodrigues(par, Rl);
-            if (tid < 9) s_R[tid] = Rl[tid];
-            if (tid < 27) s_dR[tid / 9][tid % 9] = d_rodrigues_entry(par, Rl, tid / 9, tid % 9);
-        }
-        __syncthreads();
-        double acc[kPriorSums];
+        pose_rotation(s, tid, par);
+        double acc[kPoseSums];
 #pragma unroll
-        for (int i = 0; i < kPriorSums; ++i) acc[i] = 0.0;
+        for (int i = 0; i < kPoseSums; ++i) acc[i] = 0.0;
         uint32_t cls = 0, msk = front ? 0u : m_bits;
         uint32_t bit = 1u;
-        for (int i = tid; i < N; i += kPriorThreads, bit <<= 1) {
-            const double X0 = X[3 * i], X1 = X[3 * i + 1], X2 = X[3 * i + 2];
-            const double xc = s_R[0] * X0 + s_R[1] * X1 + s_R[2] * X2 + par[3];
-            const double yc = s_R[3] * X0 + s_R[4] * X1 + s_R[5] * X2 + par[4];
-            const double zc = s_R[6] * X0 + s_R[7] * X1 + s_R[8] * X2 + par[5];
-            const double iz = 1.0 / zc, xn = xc * iz, yn = yc * iz;
-            const double r0 = x[2 * i] - (fx * xn + sk * yn + cx), r1 = x[2 * i + 1] - (fy * yn + cy);
-            const double sq = r0 * r0 + r1 * r1;
-            const bool in = zc > 0.0 && sq <= g2;                            // classify: any NaN is "out", exactly g2 is "in"
-            const bool used = front ? zc > 0.0 : (msk & bit) != 0u;
+        for (int i = tid; i < N; i += kPoseThreads, bit <<= 1) {
+            const PosePoint p = pose_residual(s, par, cam, X, x, i);
+            const bool in = p.zc > 0.0 && p.sq <= g2;                        // classify: any NaN is "out", exactly g2 is "in"
+            const bool used = front ? p.zc > 0.0 : (msk & bit) != 0u;
             if (in) cls |= bit;
             if (front && used) msk |= bit;
             acc[28] += (used ? 1.0 : 0.0) + (in ? kInOne : 0.0) + (in != used ? kDifferOne : 0.0);
             if (!used) continue;
-            double rho = sq, wgt = 1.0;                                      // rho(s), rho'(s)
-            if (sq > b2) {                                                   // Huber tail
-                const double r = sqrt(sq);
-                rho = 2.0 * huber_a * r - b2;
-                wgt = huber_a / r;
-            }
-            acc[27] += 0.5 * rho;
-            // d(proj)/d(xc,yc,zc)
-            const double pu0 = fx * iz, pu1 = sk * iz, pu2 = -(fx * xn + sk * yn) * iz;
-            const double pv1 = fy * iz, pv2 = -fy * yn * iz;
-            double Ju[6], Jv[6];      // Jacobian of the PROJECTION (residual = obs - proj -> J_r = -J)
-            // the 27 derivative entries are read from LDS per point (a broadcast read); hoisted out of the loop they take 54 VGPRs and
-            // push the kernel over its 256-register budget into scratch -- the opaque offset stops that (pnp_refine_kernel's finding)
-            int dro = 0;
-            asm volatile("" : "+v"(dro));
-            const double (*dRp)[9] = reinterpret_cast<const double (*)[9]>(&s_dR[0][0] + dro);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double d0 = dRp[k][0] * X0 + dRp[k][1] * X1 + dRp[k][2] * X2;
-                const double d1 = dRp[k][3] * X0 + dRp[k][4] * X1 + dRp[k][5] * X2;
-                const double d2 = dRp[k][6] * X0 + dRp[k][7] * X1 + dRp[k][8] * X2;
-                Ju[k] = pu0 * d0 + pu1 * d1 + pu2 * d2;
-                Jv[k] = pv1 * d1 + pv2 * d2;
-            }
-            Ju[3] = pu0; Ju[4] = pu1; Ju[5] = pu2;
-            Jv[3] = 0.0; Jv[4] = pv1; Jv[5] = pv2;
-            int idx = 0;
-#pragma unroll
-            for (int a_ = 0; a_ < 6; ++a_) {
-#pragma unroll
-                for (int b_ = a_; b_ < 6; ++b_) acc[idx++] += wgt * (Ju[a_] * Ju[b_] + Jv[a_] * Jv[b_]);
-            }
-#pragma unroll
-            for (int a_ = 0; a_ < 6; ++a_) acc[21 + a_] += wgt * (Ju[a_] * r0 + Jv[a_] * r1);   // = -J_r^T W r : descent rhs
+            pose_accumulate(s, cam, p, acc);
         }
         c_new = cls;
         if (front) m_bits = msk;
-        // the 29 sums over the 512 threads THROUGH LDS, transposed (pnp_refine_kernel's measured reduction: ~3 k cycles against 16-18 k
-        // for the shuffle tree): red[sum][thread], then 29 x 16 threads add 32 each, then 29 threads add the 16 partial results
-#pragma unroll
-        for (int i = 0; i < kPriorSums; ++i) red[i * kPriorThreads + tid] = acc[i];
-        __syncthreads();
-        if (tid < kPriorSums * 16) {
-            const int i = tid >> 4, part = tid & 15;
-            const double* src = red + i * kPriorThreads + part;
-            double v = 0.0;
-#pragma unroll 8
-            for (int k = 0; k < kPriorThreads / 16; ++k) v += src[16 * k];
-            s_part[i][part] = v;
-        }
-        __syncthreads();
-        if (tid < kPriorSums) {
-            double v = 0.0;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v += s_part[tid][k];
-            s_tot[tid] = v;
-        }
-        __syncthreads();
+        pose_reduce(s, red, tid, acc);
     };
 
-    // ONE call site of pass() (inlined: a second copy costs spilled VGPRs at the 256-register budget of a 512-thread workgroup).  What a
-    // trip evaluates: START -- s_par over a round's mask, the sums its Levenberg-Marquardt starts from; TRIAL -- s_try, pnp_refine_kernel's
-    // loop "step -> [flag] -> evaluate -> accept / reject"; FINAL -- s_par over classify(s_par) where the last sums are over another mask.
+    // ONE call site of pass().  What a trip evaluates: START -- s.par over a round's mask, the sums its Levenberg-Marquardt starts
+    // from; TRIAL -- s.try_, the loop "step -> [flag] -> evaluate -> accept / reject"; FINAL -- s.par over classify(s.par) where the
+    // last sums are over another mask.
     enum { START, TRIAL, FINAL };
-    int phase = START, it = 0, it_total = 0, round = 0, rounds_run = 0;
+    int phase = START, it_total = 0, round = 0, rounds_run = 0;
     bool front = true, moved = false, converged = false;
-    double lambda = 1e-4, cost = 0.0;
+    LmState lm;
     for (;;) {
-        pass(phase == TRIAL ? s_try : s_par, front);
+        pass(phase == TRIAL ? s.try_ : s.par, front);
         front = false;
         bool ended = false;                                   // the round's minimisation is over (or there is none: fewer than 4 tracks)
         if (phase != TRIAL) {
-            if (tid < kPriorSums) s_A[tid] = s_tot[tid];
-            __syncthreads();
+            pose_keep_sums(s, tid);
             c_cur = c_new;
             if (phase == FINAL) break;
-            cost = s_A[27];
-            lambda = 1e-4;                                    // reset at the start of every round
-            it = 0;
+            lm = LmState();                                   // lambda and the count start again with every round
+            lm.cost = s.A[27];
             phase = TRIAL;
-            if (prior_n_mask(s_A[28]) < 4) ended = true;
+            if (prior_n_mask(s.A[28]) < 4) ended = true;
             else ++rounds_run;
         } else {
-            const double new_cost = s_tot[27];
-            if (new_cost < cost) {
-                const double rel = (cost - new_cost) / fmax(cost, 1e-300);
-                if (tid < 6) s_par[tid] = s_try[tid];
-                if (tid < kPriorSums) s_A[tid] = s_tot[tid];
-                cost = new_cost;
-                lambda = fmax(lambda * 0.1, 1e-12);
-                c_cur = c_new;
-                moved = true;
-                __syncthreads();
-                if (rel < 1e-8) ended = true;                 // function tolerance 1e-8
-            } else {
-                lambda *= 10.0;
-                __syncthreads();
-                if (lambda > 1e10) { ended = true; --it; }   // (the stop above 1e10 is not counted, as in pnp_refine_kernel)
-            }
-            ++it;
+            bool accepted;
+            ended = lm_judge(s, tid, lm, accepted);
+            if (accepted) { c_cur = c_new; moved = true; }
         }
-        // the next step (a failed factorization counts as a rejected step: lambda up, try again)
-        while (!ended) {
-            if (!(it < max_iter)) { ended = true; break; }
-            if (tid == 0) {
-                double g[6], d[6];
-                for (int a_ = 0; a_ < 6; ++a_) g[a_] = s_A[21 + a_];
-                const bool ok = solve6(s_A, g, lambda, d);
-                double gn = 0, dn = 0, pn = 0;
-                for (int a_ = 0; a_ < 6; ++a_) { gn = fmax(gn, fabs(g[a_])); dn += d[a_] * d[a_]; pn += s_par[a_] * s_par[a_]; }
-                // gradient / parameter tolerance 1e-8
-                s_flag = !ok ? 2 : ((gn < 1e-8 * fmax(1.0, cost) || sqrt(dn) < 1e-8 * (sqrt(pn) + 1e-8)) ? 1 : 0);
-                for (int a_ = 0; a_ < 6; ++a_) s_try[a_] = s_par[a_] + (ok ? d[a_] : 0.0);
-            }
-            __syncthreads();
-            const int flag = s_flag;
-            if (flag == 1) { ended = true; break; }
-            if (flag == 2) {
-                lambda *= 10.0;
-                if (lambda > 1e10) { ended = true; break; }
-                __syncthreads();
-                ++it;
-                continue;
-            }
-            break;
-        }
+        if (!ended) ended = lm_next_step(s, tid, lm, max_iter);
         if (!ended) continue;
-        // the round is over: s_A holds the sums at s_par over m_bits, c_cur = classify(s_par)
-        it_total += it;
-        const double counts = s_A[28];
+        // the round is over: s.A holds the sums at s.par over m_bits, c_cur = classify(s.par)
+        it_total += lm.it;
+        const double counts = s.A[28];
         const bool ran = prior_n_mask(counts) >= 4;
         if (prior_n_differ(counts) == 0) { converged = ran; break; }      // the mask is stable: these sums are the final ones
         m_bits = c_cur;
@@ -232,23 +116,16 @@ __global__ __launch_bounds__(kPriorThreads) void pose_prior_kernel(const PriorJo
         phase = (ran && round < jb.rounds && prior_n_in(counts) >= 4) ? START : FINAL;
     }
 
-    // s_A: the sums at s_par over classify(s_par) = c_cur
-    const int n_in = prior_n_in(s_A[28]);
+    // s.A: the sums at s.par over classify(s.par) = c_cur
+    const int n_in = prior_n_in(s.A[28]);
     const int need = jb.min_inliers > 4 ? jb.min_inliers : 4;
     const bool few = n_in < need;
-    if (tid < 6) {
-        if (few || !invert6_column(s_A, tid, out->cov)) for (int r = 0; r < 6; ++r) out->cov[6 * r + tid] = 0.0;
-    }
+    pose_cov_column(s, tid, !few, out->cov);
     if (tid == 0) {
-        if (moved) {
-            double R[9];
-            rodrigues(s_par, R);
-            for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) out->Rt[4 * i + j] = R[3 * i + j]; out->Rt[4 * i + 3] = s_par[3 + i]; }
-        } else {
-            for (int i = 0; i < 12; ++i) out->Rt[i] = jb.Rt[i];          // no step was accepted: the prior, bit for bit
-        }
-        out->cost = s_A[27];
-        out->rmse = n_in > 0 ? sqrt(s_A[27] / (2.0 * (double)n_in)) : 0.0;
+        if (moved) pose_Rt(s, out->Rt);
+        else for (int i = 0; i < 12; ++i) out->Rt[i] = jb.Rt[i];          // no step was accepted: the prior, bit for bit
+        out->cost = s.A[27];
+        out->rmse = pose_rmse(s.A[27], (double)n_in);
         out->n_tracks = n_raw;
         out->n_inliers = n_in;
         out->iterations = it_total;
@@ -259,11 +136,9 @@ __global__ __launch_bounds__(kPriorThreads) void pose_prior_kernel(const PriorJo
     }
     if (jb.h_mask) {
         uint32_t bit = 1u;
-        for (int i = tid; i < N; i += kPriorThreads, bit <<= 1) jb.h_mask[i] = (c_cur & bit) ? 1 : 0;
+        for (int i = tid; i < N; i += kPoseThreads, bit <<= 1) jb.h_mask[i] = (c_cur & bit) ? 1 : 0;
     }
-    __threadfence_system();                 // every writer: its stores to the pinned record and mask have left
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&out->ready, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    pose_publish(tid, &out->ready);
 }
 
 } // namespace
@@ -271,16 +146,9 @@ __global__ __launch_bounds__(kPriorThreads) void pose_prior_kernel(const PriorJo
 hipError_t launch_pose_prior(const PriorJobs& jobs, const int n_jobs, hipStream_t stream)
 {
     if (n_jobs < 1 || n_jobs > kMaxBatch) return hipErrorInvalidValue;
-    constexpr size_t kRedBytes = sizeof(double) * kPriorSums * kPriorThreads;
-    static bool attr_set[64] = {};      // per device: more than the 64 KB a kernel gets by default
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_set[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)pose_prior_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRedBytes);
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(pose_prior_kernel, dim3(n_jobs), dim3(kPriorThreads), kRedBytes, stream, jobs);
+    const hipError_t e = pose_allow_lds<pose_prior_kernel>();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pose_prior_kernel, dim3(n_jobs), dim3(kPoseThreads), kPoseRedBytes, stream, jobs);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-// so3.h -- rotation helpers and the 6x6 solve of the single-pose refinement (pnp.hip pnp_refine_kernel), host + device inline
+// so3.h -- rotation helpers and the 6x6 solve of the single-pose refinement (pose_lm.h: pnp_refine_kernel, pose_prior_kernel), host + device inline
 // so that the tests can run the very statements of the kernel on the CPU (tests/host/so3_host_lib.cpp) against a 50-digit
 // reference (tests/pose_mp.py).  fp64 throughout, contraction off: an expression is the IEEE operations written here, in this order.
 //

@@ -1,7 +1,8 @@
 """The pose-from-the-prediction rule (include/coloc_hip.h, THE RULE of clc_track_prior_dev) in plain float64 numpy: the statement the
 50-digit reference tests/pose_prior_mp.py is compared with on the CPU (tests/test_pose_prior_reference.py).  It shares no code with
 coloc_amd/csrc/pose_prior.hip: rotations and their derivatives are the yardsticks of tests/test_so3_host.py, the 6 x 6 solve is a Cholesky
-written out here.
+written out here.  The device states the Levenberg-Marquardt rules restated below once, in coloc_amd/csrc/pose_lm.h (lm_judge,
+lm_next_step and what counts as an iteration), for clc_pnp_refine and clc_pnp_refine_prior alike; this file stays an independent model.
 
   sums(p, ..., used)      zc, sq of EVERY track at p; A = sum w J^T J, g = sum w J^T r, cost = 1/2 sum rho over the tracks of `used`
   classify(zc, sq, g2)    in iff zc > 0 and sq <= g2 (NaN: out)

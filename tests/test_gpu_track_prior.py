@@ -8,6 +8,8 @@ clc_pnp_refine_prior; THE RULE there).
   batch, after_stream, the rendered chain, a wrong prior, errors and edges
 With -s the tests print what they measured.
 """
+import functools
+
 import numpy as np
 import pytest
 from mpmath import mp
@@ -108,6 +110,58 @@ def test_case_table_against_the_reference(gpu_ctx, cid):
         rec.append("d: rmse %.12g vs %.12g" % (got["rmse"], rmse_ref))
         assert abs(got["rmse"] - rmse_ref) <= 1e-9 * rmse_ref + 64 * EPS * np.abs(x).max(), rec
     print("\n" + " | ".join(rec))
+
+
+# ---- the two entries of the one Levenberg-Marquardt pass (csrc/pose_lm.h) --------------------------------------------------------------
+
+AGREE_NS = (4, 513, 600)        # the least the prior runs on; the first size at which a thread owns two tracks; an active Huber tail
+AGREE_GATE, AGREE_HUBER = 1e4, 16.0
+
+
+@functools.lru_cache(maxsize=None)
+def _agree_scene(n):
+    """synth.pnp_scene without outliers (points 4 - 20 units in front, 0.5 px noise), the start its pose turned by a degree and shifted
+    by two centimetres; at N = 600 seven observations are moved 40 .. 70 px away, past huber_a -> X, x, K, start"""
+    s = synth.pnp_scene(n, seed=4300 + n, outlier_frac=0.0)
+    x = s["x"].copy()
+    if n == 600:
+        rng = np.random.default_rng(n)
+        ang = rng.uniform(0, 2 * np.pi, 7)
+        x[rng.choice(n, 7, replace=False)] += rng.uniform(40, 70, (7, 1)) * np.stack([np.cos(ang), np.sin(ang)], 1)
+    start = np.concatenate([pc._rot(np.radians(1.0), pc._axis(n + 1)) @ s["R"], (s["t"] + 0.02 * pc._axis(n + 2))[:, None]], 1)
+    return s["X"], x, s["K"], start
+
+
+@pytest.mark.parametrize("n", AGREE_NS)
+def test_prior_with_every_track_in_equals_the_refine(gpu_ctx, n):
+    """Where their rules coincide, clc_pnp_refine_prior performs the Levenberg-Marquardt clc_pnp_refine performs without a mask, on the
+    same X, x, K, start, huber_a and max_iter.  The conditions: every point in front of the camera at the start (the first mask is all
+    of them), a gate no residual reaches at any pose the minimisation visits (every track is "in", so the mask is stable after round 1:
+    converged, no FINAL pass), rounds = 1, N >= 4 and min_inliers <= N.  Then iterations and n_inliers == N are equal, and Rt, cov and
+    rmse agree within the bounds each entry is held to against the 50-digit reference (rules b, c, d of tests/test_gpu_pose_edges.py and
+    tests/test_pose_prior_reference.py, the same for both entries; A for rule c in float64 numpy, which its bound allows a quarter).
+    The seeds give equal iterations on the library before the pass was stated once as well (profiles/pose_lm_once.txt)."""
+    X, x, K, start = _agree_scene(n)
+    assert ((X @ start[:, :3].T + start[:, 3])[:, 2] > 0).all()
+    Rt, cov, rmse, it = gpu_ctx.pnp_refine(X, x, K, start, huber_a=AGREE_HUBER, max_iter=50)
+    got = gpu_ctx.pnp_refine_prior(X, x, K, start, AGREE_GATE, huber_a=AGREE_HUBER, rounds=1, max_iter=50, min_inliers=4)
+    uvw = (X @ Rt[:, :3].T + Rt[:, 3]) @ K.T
+    sq = ((x - uvw[:, :2] / uvw[:, 2:3]) ** 2).sum(1)
+    assert sq.max() < AGREE_GATE ** 2 and int((sq > AGREE_HUBER ** 2).sum()) == (7 if n == 600 else 0)
+    p, q = pm.to_float(_params(Rt)), pm.to_float(_params(got["Rt"]))
+    A = _np_normal_matrix(p, X, x, K, AGREE_HUBER)
+    Ainv = np.linalg.inv(A)
+    Dh = 1.0 / np.sqrt(np.diag(A))
+    bound = 256.0 * float(np.linalg.cond(A * Dh[:, None] * Dh[None, :])) * EPS * np.abs(Ainv).max()
+    rec = "N %d: iterations %d / %d, inliers %d, rounds %d, converged %d, result %d; |p - q| %.2e <= 1e-5; |cov - cov'| %.2e <= %.2e; rmse %.12g / %.12g" % (
+        n, it, got["iterations"], got["n_inliers"], got["rounds_run"], got["converged"], got["result"], np.abs(p - q).max(),
+        np.abs(cov - got["cov"]).max(), bound, rmse, got["rmse"])
+    print("\n" + rec)
+    assert it > 0 and got["iterations"] == it, rec
+    assert got["n_inliers"] == n and got["mask"].all() and (got["rounds_run"], got["converged"], got["result"]) == (1, 1, OK), rec
+    assert np.abs(p - q).max() <= 1e-5, rec
+    assert np.abs(cov - got["cov"]).max() <= bound, rec
+    assert abs(rmse - got["rmse"]) <= 1e-9 * rmse + 64 * EPS * np.abs(x).max(), rec
 
 
 # ---- the device path ---------------------------------------------------------------------------------------------------------------------
