@@ -951,6 +951,43 @@ def map_init_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3
     pair_cams[p] = (cam_a, cam_b); rows / cams as Context.map_build_dev.  The filters run under 'E'; the pairs with at least 13 inliers
     and a successful chirality vote enter the tracks, the one with the most inliers is the seed; the map is installed on ctxs[0].
     Returns (map result dict with seed_pair / Rt_seed_* / entered, [pair filter result dicts])."""
+    return _map_compose("clc_map_init_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale)
+
+
+def _steps_fill(keep, rows, ctx, align=None, sim=None, grow=None, ba=None):
+    """The optional steps of a map composition, each None (absent) or the tuple of that step's fill arguments -- align: (threshold,); sim,
+    grow, ba: those of _sim_fill, _grow_fill, _ba_fill -> [(key, filled struct, its host arrays), ...] in the order the header passes
+    them: align or sim, grow, ba.  ctx: the context whose map is replaced (the room for match / inlier is its maxkp)"""
+    steps = []
+    if align is not None:
+        al = MapAlign()
+        match = np.full(max(int(ctx.mopts.maxkp), 1), -2, dtype=np.int32)
+        al.threshold, al.match = int(align[0]), match.ctypes.data
+        steps.append(("align", al, (match, None)))
+    if sim is not None:
+        a = MapAlignSim()
+        steps.append(("sim", a, _sim_fill(a, ctx.mopts.maxkp, *sim) + (None,)))
+    if grow is not None:
+        g = MapGrow()
+        steps.append(("grow", g, _grow_fill(g, keep, rows, *grow)))
+    if ba is not None:
+        b = MapBa()
+        _ba_fill(b, *ba)
+        steps.append(("ba", b, ()))
+    return steps
+
+
+def _steps_result(res, j, n_cams, steps):
+    """one dict per step of _steps_fill into the map result dict, under the step's key"""
+    for key, s, host in steps:
+        res[key] = (_align_result(s, *host) if key == "align" else _sim_result(s, *host) if key == "sim" else
+                    _grow_result(s, n_cams, j.map_n, *host) if key == "grow" else _ba_result(s))
+    return res
+
+
+def _map_compose(entry, ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale, **steps):
+    """What the seven clc_map_*_batch_dev wrappers share: the pair jobs, the map job, the steps' structs (_steps_fill's keywords), the call
+    of `entry` and the results.  The sim entry takes all of sim, grow and ba, NULL for an absent one; the others exactly theirs."""
     lib = load_library()
     n = len(pair_jobs)
     assert len(ctxs) == n == len(pair_cams)
@@ -959,11 +996,14 @@ def map_init_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3
     outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
     j = MapJob()
     out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
+    filled = _steps_fill(keep, rows, ctxs[0], **steps)
+    refs = {key: C.byref(s) for key, s, _ in filled}
+    args = [refs.get(key) for key in ("sim", "grow", "ba")] if "sim" in refs else list(refs.values())
     hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_init_batch_dev(hs, arr, n, C.byref(j))
+    rc = getattr(lib, entry)(hs, arr, n, C.byref(j), *args)
     if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_init_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    return _map_result(j, *out), [_pair_result(arr[i], *outs[i]) for i in range(n)]
+        raise CLCError(rc, "%s: %s: %s" % (entry, lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
+    return _steps_result(_map_result(j, *out), j, len(rows), filled), [_pair_result(arr[i], *outs[i]) for i in range(n)]
 
 
 def _align_result(a, match, X):
@@ -976,24 +1016,7 @@ def map_update_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye
     """clc_map_update_batch_dev: map_init_batch_dev's arguments; the new map is brought to the scale of the map ctxs[0] holds and replaces
     it.  Returns (map result dict -- X and Rt_seed_* RESCALED -- with an "align" dict: scale, n_old, n_common, n_terms, status, match;
     [pair filter result dicts])."""
-    lib = load_library()
-    n = len(pair_jobs)
-    assert len(ctxs) == n == len(pair_cams)
-    arr = (PairJob * n)()
-    keep = []
-    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
-    j = MapJob()
-    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
-    al = MapAlign()
-    match = np.full(max(int(ctxs[0].mopts.maxkp), 1), -2, dtype=np.int32)
-    al.threshold, al.match = int(threshold), match.ctypes.data
-    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_update_batch_dev(hs, arr, n, C.byref(j), C.byref(al))
-    if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_update_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    res = _map_result(j, *out)
-    res["align"] = _align_result(al, match, None)
-    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+    return _map_compose("clc_map_update_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale, align=(threshold,))
 
 
 def _sim_fill(a, maxkp, threshold=0, apply=SIM_APPLY_SCALE, sim_max_iteration=0, sim_seed=1, sim_precision=float("inf"), want_match=True):
@@ -1019,28 +1042,9 @@ def map_update_sim_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np
     """clc_map_update_sim_batch_dev: map_update_batch_dev (grow=False), map_update_grow_batch_dev (grow=True) or
     map_update_grow_ba_batch_dev (grow=True, ba=True) with the a-contrario similarity in place of the align step.  Returns (map result
     dict -- X, Rt_seed_* and grow["Rt"] under the apply rule -- with a "sim" dict and, as asked, "grow" and "ba"; [pair filter results])."""
-    lib = load_library()
-    n = len(pair_jobs)
-    assert len(ctxs) == n == len(pair_cams)
-    arr = (PairJob * n)()
-    keep = []
-    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
-    j, g, b, a = MapJob(), MapGrow(), MapBa(), MapAlignSim()
-    out = _map_fill(j, keep, rows, [dict(cam_a=ca, cam_b=cb) for ca, cb in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
-    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision) if grow else None
-    _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
-    match, inlier = _sim_fill(a, ctxs[0].mopts.maxkp, threshold, apply, sim_max_iteration, sim_seed, sim_precision)
-    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_update_sim_batch_dev(hs, arr, n, C.byref(j), C.byref(a), C.byref(g) if grow else None, C.byref(b) if ba else None)
-    if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_update_sim_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    res = _map_result(j, *out)
-    res["sim"] = _sim_result(a, match, inlier, None)
-    if grow:
-        res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-    if ba:
-        res["ba"] = _ba_result(b)
-    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+    return _map_compose("clc_map_update_sim_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale,
+                        sim=(threshold, apply, sim_max_iteration, sim_seed, sim_precision), grow=(max_iteration, seed, precision) if grow else None,
+                        ba=(ba_max_iterations, huber_a, function_tolerance) if ba else None)
 
 
 def _grow_fill(g, keep, rows, max_iteration=256, seed=0, precision=float("inf")):
@@ -1066,47 +1070,16 @@ def map_init_grow_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.
     """clc_map_init_grow_batch_dev: map_init_batch_dev's arguments + the resections' max_iteration / seed / precision; the map grown past
     the seed pair is installed on ctxs[0].  Returns (map result dict with a "grow" dict: resected, status, n_corr, n_inliers, error_max,
     Rt per camera, n_seed_rows, n_added, map_cam, map_obs; [pair filter result dicts])."""
-    lib = load_library()
-    n = len(pair_jobs)
-    assert len(ctxs) == n == len(pair_cams)
-    arr = (PairJob * n)()
-    keep = []
-    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
-    j, g = MapJob(), MapGrow()
-    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
-    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
-    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_init_grow_batch_dev(hs, arr, n, C.byref(j), C.byref(g))
-    if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_init_grow_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    res = _map_result(j, *out)
-    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+    return _map_compose("clc_map_init_grow_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale,
+                        grow=(max_iteration, seed, precision))
 
 
 def map_update_grow_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, threshold=0,
                               max_iteration=256, seed=0, precision=float("inf")):
     """clc_map_update_grow_batch_dev: map_update_batch_dev on the grown map.  Returns (map result dict -- X, Rt_seed_* and grow["Rt"]
     RESCALED -- with "align" and "grow" dicts; [pair filter result dicts])."""
-    lib = load_library()
-    n = len(pair_jobs)
-    assert len(ctxs) == n == len(pair_cams)
-    arr = (PairJob * n)()
-    keep = []
-    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
-    j, g, al = MapJob(), MapGrow(), MapAlign()
-    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b) for a, b in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
-    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
-    match = np.full(max(int(ctxs[0].mopts.maxkp), 1), -2, dtype=np.int32)
-    al.threshold, al.match = int(threshold), match.ctypes.data
-    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_update_grow_batch_dev(hs, arr, n, C.byref(j), C.byref(al), C.byref(g))
-    if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_update_grow_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    res = _map_result(j, *out)
-    res["align"] = _align_result(al, match, None)
-    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+    return _map_compose("clc_map_update_grow_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale,
+                        align=(threshold,), grow=(max_iteration, seed, precision))
 
 
 def _ba_fill(b, max_iterations=0, huber_a=0.0, function_tolerance=0.0):
@@ -1122,51 +1095,16 @@ def map_init_grow_ba_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=
                                precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
     """clc_map_init_grow_ba_batch_dev: map_init_grow_batch_dev with the grown map bundle-adjusted before it is installed.  Returns (map
     result dict -- X, Rt_seed_* and grow["Rt"] REFINED -- with "grow" and "ba" dicts; [pair filter result dicts])."""
-    lib = load_library()
-    n = len(pair_jobs)
-    assert len(ctxs) == n == len(pair_cams)
-    arr = (PairJob * n)()
-    keep = []
-    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
-    j, g, b = MapJob(), MapGrow(), MapBa()
-    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b_) for a, b_ in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
-    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
-    _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
-    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_init_grow_ba_batch_dev(hs, arr, n, C.byref(j), C.byref(g), C.byref(b))
-    if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_init_grow_ba_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    res = _map_result(j, *out)
-    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-    res["ba"] = _ba_result(b)
-    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+    return _map_compose("clc_map_init_grow_ba_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale,
+                        grow=(max_iteration, seed, precision), ba=(ba_max_iterations, huber_a, function_tolerance))
 
 
 def map_update_grow_ba_batch_dev(ctxs, pair_jobs, rows, pair_cams, cams, origin_R=np.eye(3), origin_C=np.zeros(3), scale=1.0, threshold=0,
                                  max_iteration=256, seed=0, precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
     """clc_map_update_grow_ba_batch_dev: map_update_grow_batch_dev with the grown map bundle-adjusted before the align step.  Returns (map
     result dict -- X, Rt_seed_* and grow["Rt"] REFINED, then RESCALED -- with "align", "grow" and "ba" dicts; [pair filter result dicts])."""
-    lib = load_library()
-    n = len(pair_jobs)
-    assert len(ctxs) == n == len(pair_cams)
-    arr = (PairJob * n)()
-    keep = []
-    outs = [_pair_fill(arr[i], keep, **pair_jobs[i]) for i in range(n)]
-    j, g, al, b = MapJob(), MapGrow(), MapAlign(), MapBa()
-    out = _map_fill(j, keep, rows, [dict(cam_a=a, cam_b=b_) for a, b_ in pair_cams], cams, origin_R=origin_R, origin_C=origin_C, scale=scale)
-    gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
-    _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
-    match = np.full(max(int(ctxs[0].mopts.maxkp), 1), -2, dtype=np.int32)
-    al.threshold, al.match = int(threshold), match.ctypes.data
-    hs = (C.c_void_p * n)(*[c.h for c in ctxs])
-    rc = lib.clc_map_update_grow_ba_batch_dev(hs, arr, n, C.byref(j), C.byref(al), C.byref(g), C.byref(b))
-    if rc != CLC_OK:
-        raise CLCError(rc, "clc_map_update_grow_ba_batch_dev: %s: %s" % (lib.clc_status_string(rc).decode(), lib.clc_last_error_string(ctxs[0].h).decode()))
-    res = _map_result(j, *out)
-    res["align"] = _align_result(al, match, None)
-    res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-    res["ba"] = _ba_result(b)
-    return res, [_pair_result(arr[i], *outs[i]) for i in range(n)]
+    return _map_compose("clc_map_update_grow_ba_batch_dev", ctxs, pair_jobs, rows, pair_cams, cams, origin_R, origin_C, scale,
+                        align=(threshold,), grow=(max_iteration, seed, precision), ba=(ba_max_iterations, huber_a, function_tolerance))
 
 
 def desc_handle_live(handle):
@@ -1515,11 +1453,16 @@ class Context:
         set_map_points).  cams = [dict(cam=(focal, ppx, ppy, k1, k2, k3), d_kps= | d_feat= [, feat_stride], d_desc=), ...] per camera;
         Rt_seed_a / Rt_seed_b: [R|t] of the seed pair's two cameras (seed_poses).  Returns a dict: n_tracks, track_feat, map_n, map_track,
         map_row, X."""
+        return self._map_build("clc_map_build_dev", rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream)
+
+    def _map_build(self, entry, rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream, **steps):
+        """what the three clc_map_build*_dev wrappers share: the map job, the steps' structs (_steps_fill's grow and ba), the call, the results"""
         j = MapJob()
         keep = []
         out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
-        self._chk(self.lib.clc_map_build_dev(self.h, C.byref(j)))
-        return _map_result(j, *out)
+        filled = _steps_fill(keep, rows, self, **steps)
+        self._chk(getattr(self.lib, entry)(self.h, C.byref(j), *[C.byref(s) for _, s, _ in filled]))
+        return _steps_result(_map_result(j, *out), j, len(rows), filled)
 
     def map_build_grow_dev(self, rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream=None, max_iteration=256, seed=0,
                            precision=float("inf")):
@@ -1527,30 +1470,16 @@ class Context:
         pnp_acransac with seed + k for the k-th of them) and its tracks added; the grown map is installed.  Every camera needs d_desc.
         Returns map_build_dev's dict for the GROWN map with a "grow" dict: resected, status, n_corr, n_inliers, error_max, Rt per
         camera, n_seed_rows, n_added, map_cam, map_obs."""
-        j, g = MapJob(), MapGrow()
-        keep = []
-        out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
-        gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
-        self._chk(self.lib.clc_map_build_grow_dev(self.h, C.byref(j), C.byref(g)))
-        res = _map_result(j, *out)
-        res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-        return res
+        return self._map_build("clc_map_build_grow_dev", rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream,
+                               grow=(max_iteration, seed, precision))
 
     def map_build_grow_ba_dev(self, rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream=None, max_iteration=256, seed=0,
                               precision=float("inf"), ba_max_iterations=0, huber_a=0.0, function_tolerance=0.0):
         """clc_map_build_grow_ba_dev: map_build_grow_dev with the grown map -- the valid cameras' poses and every landmark -- bundle-adjusted
         before it is installed.  Returns map_build_grow_dev's dict (X, Rt_seed_* and grow["Rt"] refined) with a "ba" dict: status,
         iterations, n_cams, n_points, n_obs, cost_initial, cost_final, rmse."""
-        j, g, b = MapJob(), MapGrow(), MapBa()
-        keep = []
-        out = _map_fill(j, keep, rows, pairs, cams, seed_pair=seed_pair, Rt_seed_a=Rt_seed_a, Rt_seed_b=Rt_seed_b, after_stream=after_stream)
-        gout = _grow_fill(g, keep, rows, max_iteration, seed, precision)
-        _ba_fill(b, ba_max_iterations, huber_a, function_tolerance)
-        self._chk(self.lib.clc_map_build_grow_ba_dev(self.h, C.byref(j), C.byref(g), C.byref(b)))
-        res = _map_result(j, *out)
-        res["grow"] = _grow_result(g, len(rows), j.map_n, *gout)
-        res["ba"] = _ba_result(b)
-        return res
+        return self._map_build("clc_map_build_grow_ba_dev", rows, pairs, cams, seed_pair, Rt_seed_a, Rt_seed_b, after_stream,
+                               grow=(max_iteration, seed, precision), ba=(ba_max_iterations, huber_a, function_tolerance))
 
     def ba_dev(self, cams, cam_mask, Rt, n_points, d_X, d_obs, d_x, after_stream=None, max_iterations=0, huber_a=0.0, function_tolerance=0.0):
         """clc_ba_dev: the bundle adjustment alone on arrays in device memory (pointers as integers): cams = [(focal, ppx, ppy, k1, k2,

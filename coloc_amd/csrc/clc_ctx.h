@@ -295,11 +295,12 @@ hipError_t launch_gather_rows_multi(const RowSources& srcs, const int32_t* d_cam
 // (pose_batch.hip): clc_pnp_acransac's result on the same correspondences, bit for bit.  Rt: 12 doubles, zeros without a model.
 int resect_solve(clc_ctx* ctx, int N, const clc_camera_k3& cam, int max_iteration, uint64_t seed, double precision, double* Rt, int* n_inliers,
                  double* error_max);
-// clc_map_init_batch_dev (align == null: map_install) / clc_map_update_batch_dev (map_align_staged) behind their extern "C" names
-// (gr != null: the grown stage, clc_map_init_grow_batch_dev; ba != null: the grown stage bundle-adjusted, the _grow_ba_ entries)
-// (sim != null, align == null: the similarity step in place of the align step, clc_map_update_sim_batch_dev)
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr = nullptr,
-                   clc_map_ba* ba = nullptr, clc_map_align_sim* sim = nullptr);
+// The optional steps of a batch composition, null where absent: grow -- the grown stage; ba -- that stage bundle-adjusted (needs grow);
+// align or sim, not both -- a replacement rule of map_update.hip in place of map_install.  map_init_batch (map_build.hip) is the seven
+// clc_map_{init,update}_*_batch_dev entries behind their extern "C" names: it refuses an illegal combination or a ba that fails ba_check
+// with CLC_ERR_BAD_ARG before any out field of grow, align or sim is written, then clears the given steps' out fields.
+struct MapSteps { clc_map_grow* grow = nullptr; clc_map_ba* ba = nullptr; clc_map_align* align = nullptr; clc_map_align_sim* sim = nullptr; };
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, const MapSteps& steps);
 int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, clc_map_ba* ba);
 // ---- the bundle adjustment (map_ba.hip) ---------------------------------------------------------------------------------------------
 // ba's in fields checked (CLC_ERR_BAD_ARG on `who`) and its out fields cleared
@@ -314,13 +315,17 @@ struct BaProblem {
 };
 // the whole step on the context's stream: the rounds, the waits, ba's out fields.  Returns CLC_OK for every CLC_BA_* status.
 int ba_drive(clc_ctx* ctx, BaProblem& pb, clc_map_ba& ba);
-// map_update.hip: CLC_ERR_STATE unless the context holds a map with points; the align step on a staged map, installing it, with the
-// job's host points and seed poses rescaled
+// ---- the map replaced (map_update.hip) ---------------------------------------------------------------------------------------------------
+// CLC_ERR_STATE unless the context holds a map with points
 int map_align_state(clc_ctx* ctx, const char* who);
-// (gr != null: a grown stage -- the rows gathered by the stage's camera list, the resected cameras' poses rescaled as well)
-int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align, clc_map_grow* gr = nullptr);
-// the same under the a-contrario similarity (clc_map_align_sim_dev's step): points and poses under sim.apply
-int map_align_sim_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align_sim& sim, clc_map_grow* gr = nullptr);
+// the out fields of the two rules as a call leaves them when it ends before its step: no scale (1), no model (the identity)
+void align_outputs_none(clc_map_align& job);
+void sim_outputs_none(clc_map_align_sim& job);
+// A rule on a staged map, installing it: the scale rule (job.X, the seed poses and -- gr != null, a grown stage whose rows are gathered by
+// the stage's camera list -- the resected cameras' poses rescaled) or the a-contrario similarity (points and poses under sim.apply; no
+// model: as they are).  Both are thin over the one step of map_update.hip.
+int map_align_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align& align, clc_map_grow* gr);
+int map_align_sim_staged(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged, clc_map_align_sim& sim, clc_map_grow* gr);
 
 // Every consumer stream behind what `producer` holds now (pose_batch.hip): ONE event (ev: its owner's, created on first use), no host
 // synchronisation; where an event call fails the host waits for the producer instead, and what that synchronisation reports is returned.

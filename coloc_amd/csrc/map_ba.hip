@@ -1,5 +1,5 @@
-// map_ba.hip -- the grown map bundle-adjusted on the device (include/coloc_hip.h: clc_ba_dev, clc_map_build_grow_ba_dev,
-// clc_map_init_grow_ba_batch_dev, clc_map_update_grow_ba_batch_dev): `refiner.refinePose(*scene, ba_refine_options, rmse, cov)` at the end of
+// map_ba.hip -- the grown map bundle-adjusted on the device (include/coloc_hip.h: clc_ba_dev, clc_map_build_grow_ba_dev, and
+// through map_build.hip's map_init_batch the _grow_ba_ and _sim_ batch entries): `refiner.refinePose(*scene, ba_refine_options, rmse, cov)` at the end of
 // Reconstructor::reconstructScene (reference include/coloc/Reconstructor.hpp:160-161, Refiner.hpp:47-239) -- every valid camera's pose
 // and every landmark under a Huber loss, by Levenberg-Marquardt through the Schur complement on the landmarks.  The arithmetic of a point
 // and of an entry of the reduced system is ba_math.h's, host + device; here are the launches.  All enqueue-only on one stream; no kernel
@@ -439,21 +439,6 @@ int clc_map_build_grow_ba_dev(clc_ctx* ctx, clc_map_job* job, clc_map_grow* grow
     if (!ctx || !job || !grow || !ba) return fail(ctx, CLC_ERR_BAD_ARG, "map_build_grow_ba: null context / job / grow / ba");
     const int rc = ba_check(ctx, ba, "map_build_grow_ba");
     return rc == CLC_OK ? map_build_grow(ctx, *job, *grow, ba) : rc;
-}
-
-int clc_map_init_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow, clc_map_ba* ba)
-{
-    if (!grow || !ba) return CLC_ERR_BAD_ARG;
-    if (ba_check(nullptr, ba, "map_init_grow_ba_batch") != CLC_OK) return CLC_ERR_BAD_ARG;
-    return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr, grow, ba);
-}
-
-int clc_map_update_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* grow,
-                                     clc_map_ba* ba)
-{
-    if (!align || !grow || !ba) return CLC_ERR_BAD_ARG;
-    if (ba_check(nullptr, ba, "map_update_grow_ba_batch") != CLC_OK) return CLC_ERR_BAD_ARG;
-    return map_init_batch(ctxs, pair_jobs, n_pairs, job, align, grow, ba);
 }
 
 } // extern "C"

@@ -499,19 +499,19 @@ int map_build_grow(clc_ctx* ctx, clc_map_job& job, clc_map_grow& gr, clc_map_ba*
     return rc == CLC_OK ? map_install(ctx, job, staged) : rc;
 }
 
-// clc_map_init_batch_dev (align == null) and clc_map_update_batch_dev (map_update.hip): the filters, the selection, the seed poses and the
-// stage half are ONE path; what follows the stage half differs -- the install above, or the align step at the old map's scale.
-int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* gr, clc_map_ba* ba,
-                   clc_map_align_sim* sim)
+// The seven batch compositions (their extern "C" entries side by side below): the filters, the selection, the seed poses and the stage
+// half are ONE path; what the optional steps change is the stage half (grown, bundle-adjusted) and what follows it -- the install above,
+// or a replacement rule of map_update.hip.  Which steps go together is checked HERE, ahead of the first write to an out field of grow,
+// align or sim (ba_check clears ba's own as it checks, as it did in the entries).
+int map_init_batch(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, const MapSteps& steps)
 {
+    clc_map_grow* const gr = steps.grow; clc_map_ba* const ba = steps.ba;
+    clc_map_align* const align = steps.align; clc_map_align_sim* const sim = steps.sim;
+    if ((ba && !gr) || (align && sim)) return CLC_ERR_BAD_ARG;
+    if (ba && ba_check(nullptr, ba, "map_init_batch") != CLC_OK) return CLC_ERR_BAD_ARG;
     if (gr) grow_outputs_none(*gr);
-    if (sim) {
-        sim->n_old = 0; sim->n_common = 0; sim->n_inliers = 0; sim->iterations = 0; sim->refit = 0; sim->status = CLC_MAP_SIM_NO_MODEL;
-        sim->s = 1.0; sim->error_max = 0.0; sim->min_nfa = INFINITY;
-        for (int q = 0; q < 9; ++q) sim->R[q] = q % 4 == 0 ? 1.0 : 0.0;
-        for (int q = 0; q < 3; ++q) sim->t[q] = 0.0;
-    }
-    if (align) { align->n_old = 0; align->n_common = 0; align->n_terms = 0; align->status = CLC_MAP_ALIGN_NO_SCALE; align->scale = 1.0; }
+    if (sim) sim_outputs_none(*sim);
+    if (align) align_outputs_none(*align);
     if (n_pairs < 1 || n_pairs > kMaxPairs || !ctxs || !pair_jobs || !job) return CLC_ERR_BAD_ARG;
     const int rc0 = check_batch_contexts(ctxs, n_pairs, "map_init_batch: every pair needs a context of its own");
     if (rc0 != CLC_OK) return rc0;
@@ -606,21 +606,54 @@ int clc_map_build_dev(clc_ctx* ctx, clc_map_job* job)
     return map_build(ctx, *job);
 }
 
-int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job)
-{
-    return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr);
-}
-
 int clc_map_build_grow_dev(clc_ctx* ctx, clc_map_job* job, clc_map_grow* grow)
 {
     if (!ctx || !job || !grow) return fail(ctx, CLC_ERR_BAD_ARG, "map_build_grow: null context / job / grow");
     return map_build_grow(ctx, *job, *grow, nullptr);
 }
 
+// ---- the seven batch compositions: each names the steps it REQUIRES; every other rule is map_init_batch's (MapSteps: grow, ba, align, sim)
+int clc_map_init_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job)
+{
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{});
+}
+
 int clc_map_init_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow)
 {
     if (!grow) return CLC_ERR_BAD_ARG;
-    return map_init_batch(ctxs, pair_jobs, n_pairs, job, nullptr, grow);
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{ grow });
+}
+
+int clc_map_init_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_grow* grow, clc_map_ba* ba)
+{
+    if (!grow || !ba) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{ grow, ba });
+}
+
+int clc_map_update_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align)
+{
+    if (!align) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{ nullptr, nullptr, align });
+}
+
+int clc_map_update_grow_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* grow)
+{
+    if (!align || !grow) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{ grow, nullptr, align });
+}
+
+int clc_map_update_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align* align, clc_map_grow* grow,
+                                     clc_map_ba* ba)
+{
+    if (!align || !grow || !ba) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{ grow, ba, align });
+}
+
+int clc_map_update_sim_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align_sim* sim,
+                                 clc_map_grow* grow, clc_map_ba* ba)
+{
+    if (!sim) return CLC_ERR_BAD_ARG;
+    return map_init_batch(ctxs, pair_jobs, n_pairs, job, MapSteps{ grow, ba, nullptr, sim });
 }
 
 int clc_map_resect_build_dev(clc_ctx* ctx, const clc_map_job* job, int camera, double* d_X, double* d_x, int32_t* d_track, int32_t* d_row, int32_t* d_n,
