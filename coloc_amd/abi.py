@@ -104,6 +104,11 @@ class MapGuidedJob(C.Structure):
                 ("d_match", C.c_void_p), ("d_best", C.c_void_p), ("d_second", C.c_void_p), ("d_qpos", C.c_void_p), ("d_proj", C.c_void_p)]
 
 
+class UniqueJob(C.Structure):
+    """clc_unique_job (include/coloc_hip.h)"""
+    _fields_ = [("d_match", C.c_void_p), ("d_best", C.c_void_p), ("nq", C.c_int), ("nt", C.c_int), ("d_owner", C.c_void_p)]
+
+
 MAX_BATCH, MAX_TRACK_PAIRS = 8, 28          # CLC_MAX_BATCH, CLC_MAX_TRACK_PAIRS
 
 
@@ -241,6 +246,8 @@ EXPORTS = [
     "clc_match_map_binned_dev", "clc_match_map_binned_batch_dev", "clc_map_bin_build_dev", "clc_map_binned_plan",
     "clc_sim3_acransac", "clc_sim3_minimal", "clc_map_align_sim_dev", "clc_map_update_sim_batch_dev",
     "clc_track_prior_dev", "clc_track_prior_batch_dev", "clc_pnp_refine_prior",
+    "clc_match_unique_dev", "clc_match_unique_batch_dev", "clc_match_2nn_unique_dev", "clc_match_map_unique_dev",
+    "clc_match_map_binned_unique_dev", "clc_match_2nn_unique",
 ]
 # clc_track_prior_job.result
 TRACK_PRIOR_OK, TRACK_PRIOR_FEW = 0, 1
@@ -428,6 +435,12 @@ def load_library():
     lib.clc_match_map_binned_batch_dev.argtypes = [vp, vp, ci, vp]
     lib.clc_map_bin_build_dev.argtypes = [vp, vp, vp, vp, vp]
     lib.clc_map_binned_plan.argtypes = [vp, vp, C.c_float, vp, vp]
+    lib.clc_match_unique_dev.argtypes = [vp, vp, vp]
+    lib.clc_match_unique_batch_dev.argtypes = [vp, vp, ci, vp]
+    lib.clc_match_2nn_unique_dev.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp, vp]
+    lib.clc_match_map_unique_dev.argtypes = [vp, vp, ci, ci, vp, vp, vp]
+    lib.clc_match_map_binned_unique_dev.argtypes = [vp, vp, vp, vp]
+    lib.clc_match_2nn_unique.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp]
     _lib = lib
     return lib
 
@@ -1650,6 +1663,48 @@ class Context:
         c = CameraK3(*[float(v) for v in cam])
         self._chk(self.lib.clc_map_binned_plan(self.h, C.byref(c), C.c_float(radius), info, C.byref(side)))
         return dict(plan=info[0], cells_per_axis=info[1], lanes_per_query=info[2], cell_side=side.value)
+
+    def match_unique_dev(self, d_match, d_best, nq, nt, d_owner=None, stream=None):
+        """clc_match_unique_dev: d_match (nq int32, device) made one-to-one IN PLACE from the distances d_best (nq uint16, device) the
+        producer wrote beside it -- every train row below nt keeps the claimant with the smallest (distance, query row); d_owner (nullable,
+        nt int32, device) receives the inverse list.  Enqueue only."""
+        j = UniqueJob(d_match, d_best, int(nq), int(nt), d_owner)
+        self._chk(self.lib.clc_match_unique_dev(self.h, C.byref(j), stream))
+
+    def match_unique_batch_dev(self, jobs, stream=None):
+        """clc_match_unique_batch_dev: jobs = [dict(d_match, d_best, nq, nt, d_owner=None), ...], at most MAX_TRACK_PAIRS, the same three
+        enqueued operations as one call."""
+        n = len(jobs)
+        arr = (UniqueJob * max(n, 1))()
+        for i in range(n):
+            jb = jobs[i]
+            arr[i] = UniqueJob(jb["d_match"], jb["d_best"], int(jb["nq"]), int(jb["nt"]), jb.get("d_owner"))
+        self._chk(self.lib.clc_match_unique_batch_dev(self.h, arr, n, stream))
+
+    def match_2nn_unique_dev(self, d_q, nq, d_t, nt, threshold, d_match, d_owner=None, stream=None):
+        """clc_match_2nn_unique_dev: match_2nn_dev and then the one-to-one filter on the same stream."""
+        self._chk(self.lib.clc_match_2nn_unique_dev(self.h, d_q, nq, d_t, nt, int(threshold), d_match, d_owner, stream))
+
+    def match_map_unique_dev(self, d_q, nq, threshold, d_match, d_owner=None, stream=None):
+        """clc_match_map_unique_dev: match_map_dev and then the one-to-one filter; d_owner: one entry per map row."""
+        self._chk(self.lib.clc_match_map_unique_dev(self.h, d_q, nq, int(threshold), d_match, d_owner, stream))
+
+    def match_map_binned_unique_dev(self, d_owner=None, stream=None, **job):
+        """clc_match_map_binned_unique_dev: match_map_binned_dev (the keywords of match_map_guided_dev; d_best may be left out) and then
+        the one-to-one filter; d_owner: one entry per map row."""
+        j = MapGuidedJob()
+        _map_guided_fill(j, **job)
+        self._chk(self.lib.clc_match_map_binned_unique_dev(self.h, C.byref(j), d_owner, stream))
+
+    def match_unique(self, Q, T, threshold=40):
+        """clc_match_2nn_unique on host arrays: (match, owner) -- match_2nn's list made one-to-one, and for every row of T the query that
+        keeps it or -1."""
+        Q = np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, 64)
+        T = np.ascontiguousarray(T, dtype=np.uint8).reshape(-1, 64)
+        m = np.full(Q.shape[0], -2, dtype=np.int32)
+        o = np.full(T.shape[0], -2, dtype=np.int32)
+        self._chk(self.lib.clc_match_2nn_unique(self.h, _p(Q), Q.shape[0], _p(T), T.shape[0], int(threshold), _p(m), _p(o)))
+        return m, o
 
     def pair_filter_dev(self, model, **job):
         """clc_pair_filter_dev: computeRelativePose's gather + the a-contrario filter of model 'E' | 'F' | 'H' from device memory.  Keywords:

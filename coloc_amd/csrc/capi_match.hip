@@ -218,7 +218,8 @@ Rule ratio_rule(float ratio) { Rule r; r.rule = K2NN_RULE_RATIO; r.r2 = ratio * 
 bool bad_ratio(float ratio) { return !(ratio > 0.f) || !std::isfinite(ratio); }
 
 // one device query set against one device train set, arguments checked: enqueue on `stream`
-int match_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, const Rule& rule, int32_t* d_match, void* stream)
+// (best_out: nullable, where the sweep leaves the best distances beside d_match)
+int match_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, const Rule& rule, int32_t* d_match, void* stream, uint16_t* best_out = nullptr)
 {
     if (nq == 0) return CLC_OK;
     CLC_HIP(ctx, hipSetDevice(ctx->device));
@@ -227,6 +228,7 @@ int match_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, co
     jobs[0].q = (const uint4*)d_q;
     jobs[0].t = (const uint4*)d_t;
     jobs[0].out = d_match;
+    jobs[0].best_out = best_out;
     jobs[0].nq = (uint32_t)nq;
     jobs[0].nt = (uint32_t)nt;
     rule.apply(jobs[0]);
@@ -245,6 +247,28 @@ int clc_match_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, in
     if (((uintptr_t)d_q & 15u) || ((uintptr_t)d_t & 15u) || ((uintptr_t)d_match & 3u))
         return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn: device pointers must be 16-byte aligned");
     return match_dev(ctx, d_q, nq, d_t, nt, k2nn_rule(threshold), d_match, stream);
+}
+
+/* clc_match_2nn_dev and then the one-to-one filter (k2nn_unique.hip) on the same stream: the sweep is the context's, through run_jobs as
+ * ever, with its best distances in the context's scratch beside the filter's claim words */
+int clc_match_2nn_unique_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, int threshold, int32_t* d_match, int32_t* d_owner,
+                             void* stream)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!d_q || !d_match)) || (nt > 0 && !d_t))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn_unique: bad argument");
+    if (((uintptr_t)d_q & 15u) || ((uintptr_t)d_t & 15u))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn_unique: device pointers must be 16-byte aligned");
+    clc_unique_job uj{};
+    uj.d_match = d_match; uj.nq = nq; uj.nt = nt; uj.d_owner = d_owner;
+    int rc = unique_check(ctx, "match_2nn_unique", &uj, 1, false);       // everything is checked before anything is allocated or enqueued
+    if (rc != CLC_OK) return rc;
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    UniqueDev dv;
+    rc = unique_scratch(ctx, nq, nt, true, false, dv);
+    if (rc != CLC_OK) return rc;
+    uj.d_best = dv.best;
+    rc = match_dev(ctx, d_q, nq, d_t, nt, k2nn_rule(threshold), d_match, stream, dv.best);
+    return rc == CLC_OK ? unique_enqueue(ctx, &uj, &dv, 1, pick(ctx, stream)) : rc;
 }
 
 int clc_match_ratio_2nn_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, float ratio, int32_t* d_match, void* stream)
@@ -414,11 +438,15 @@ void release_sets(HostSet* sets, int n_sets)
 }
 
 // one query set against one train set, both resolved; results into the caller's arrays
-int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* h_match, uint16_t* h_best, uint16_t* h_second)
+// uq (nullable): the one-to-one filter stands between every sweep of the call and its download
+struct UniqueHost { int32_t* h_owner = nullptr; UniqueDev dv{}; int32_t* pin_owner = nullptr; };
+int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* h_match, uint16_t* h_best, uint16_t* h_second, UniqueHost* uq = nullptr)
 {
     const size_t nq = (size_t)q.n;
+    const size_t n_owner = uq && uq->h_owner ? (size_t)t.n : 0;
     MatchPin pin;
-    int rc = ensure_results(ctx, [&](Carve& c) { pin.carve(c, nq); });
+    int rc = ensure_results(ctx, [&](Carve& c) { pin.carve(c, nq); if (uq) uq->pin_owner = c.take<int32_t>(n_owner); });
+    if (rc == CLC_OK && uq) rc = unique_scratch(ctx, q.n, t.n, false, n_owner > 0, uq->dv);
     if (rc != CLC_OK) return rc;
     HostSet* sets[2] = { &q, &t };
     for (HostSet* s : sets) { rc = resolve(ctx, *s); if (rc != CLC_OK) { release_sets(&q, 1); release_sets(&t, 1); return rc; } }
@@ -428,16 +456,23 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
         jobs[0].q = (const uint4*)q.d;
         jobs[0].t = (const uint4*)t.d;
         jobs[0].out = ctx->d_match.as<int32_t>();
-        jobs[0].best_out = h_best ? ctx->d_best.as<uint16_t>() : nullptr;
+        jobs[0].best_out = h_best || uq ? ctx->d_best.as<uint16_t>() : nullptr;
         jobs[0].second_out = h_second ? ctx->d_second.as<uint16_t>() : nullptr;
         jobs[0].nq = (uint32_t)q.n;
         jobs[0].nt = (uint32_t)t.n;
         rule.apply(jobs[0]);
         rc = run_jobs(ctx, jobs, ctx->stream);
+        if (rc == CLC_OK && uq) {                                      // behind THIS sweep: a re-sweep is filtered anew
+            clc_unique_job uj{};
+            uj.d_match = ctx->d_match.as<int32_t>(); uj.d_best = ctx->d_best.as<uint16_t>(); uj.nq = q.n; uj.nt = t.n;
+            uj.d_owner = n_owner ? uq->dv.owner : nullptr;
+            rc = unique_enqueue(ctx, &uj, &uq->dv, 1, ctx->stream);
+        }
         hipError_t e = hipSuccess;
         if (rc == CLC_OK) e = hipMemcpyAsync(pin.match, ctx->d_match.ptr, nq * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
         if (rc == CLC_OK && e == hipSuccess && h_best) e = hipMemcpyAsync(pin.best, ctx->d_best.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
         if (rc == CLC_OK && e == hipSuccess && h_second) e = hipMemcpyAsync(pin.second, ctx->d_second.ptr, nq * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream);
+        if (rc == CLC_OK && e == hipSuccess && n_owner) e = hipMemcpyAsync(uq->pin_owner, uq->dv.owner, n_owner * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
         if (rc == CLC_OK && e != hipSuccess) rc = fail(ctx, CLC_ERR_HIP, "match: result download", e);
         // the GPU is sweeping: now the pass over the host blocks that stand on published rows
         bool good = true;
@@ -450,6 +485,7 @@ int match_host(clc_ctx* ctx, HostSet& q, HostSet& t, const Rule& rule, int32_t* 
     memcpy(h_match, pin.match, nq * sizeof(int32_t));
     if (h_best) memcpy(h_best, pin.best, nq * sizeof(uint16_t));
     if (h_second) memcpy(h_second, pin.second, nq * sizeof(uint16_t));
+    if (n_owner) memcpy(uq->h_owner, uq->pin_owner, n_owner * sizeof(int32_t));
     return CLC_OK;
 }
 
@@ -546,6 +582,27 @@ int clc_match_2nn(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt
     return match_host(ctx, q, t, k2nn_rule(threshold), h_match, h_best, h_second);
 }
 
+int clc_match_2nn_unique(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt, int threshold, int32_t* h_match, int32_t* h_owner)
+{
+    if (!ctx || nq < 0 || nt < 0 || (nq > 0 && (!h_q || !h_match)) || (nt > 0 && !h_t))
+        return fail(ctx, CLC_ERR_BAD_ARG, "match_2nn_unique: bad argument");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_2nn_unique: context created without matcher options");
+    if ((uint32_t)nq > ctx->mopts.maxkp || (uint32_t)nt > ctx->mopts.maxkp)
+        return fail(ctx, CLC_ERR_CAPACITY, "match_2nn_unique: more descriptors than MatcherOptions.maxkp");
+    if ((uint32_t)nq > (1u << 22)) return fail(ctx, CLC_ERR_CAPACITY, "match_2nn_unique: more than 2^22 query rows");
+    if (nq == 0) {                                                     // no claim: nobody holds a row
+        for (int i = 0; h_owner && i < nt; ++i) h_owner[i] = -1;
+        return CLC_OK;
+    }
+    CLC_HIP(ctx, hipSetDevice(ctx->device));
+    HostSet q, t;
+    q.h = h_q; q.n = nq; q.d_upload = ctx->d_q.as<uint8_t>();
+    t.h = h_t; t.n = nt; t.d_upload = ctx->d_t.as<uint8_t>();
+    UniqueHost uq;
+    uq.h_owner = h_owner;
+    return match_host(ctx, q, t, k2nn_rule(threshold), h_match, nullptr, nullptr, &uq);
+}
+
 int clc_match_pairs(clc_ctx* ctx, const void* const* h_desc, const int* counts, int ncams, const int* pairs,
                     int npairs, int threshold, int32_t* const* h_match)
 {
@@ -584,6 +641,14 @@ int clc_match_map_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int3
     if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_dev: context created without matcher options");
     if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_dev before set_map");
     return clc_match_2nn_dev(ctx, d_q, nq, ctx->d_m.ptr, ctx->map_n, threshold, d_match, stream);
+}
+
+int clc_match_map_unique_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int32_t* d_match, int32_t* d_owner, void* stream)
+{
+    if (!ctx || nq < 0 || (nq > 0 && (!d_q || !d_match))) return fail(ctx, CLC_ERR_BAD_ARG, "match_map_unique_dev: bad argument");
+    if (!ctx->has_mat) return fail(ctx, CLC_ERR_STATE, "match_map_unique_dev: context created without matcher options");
+    if (ctx->map_n < 0) return fail(ctx, CLC_ERR_STATE, "match_map_unique_dev before set_map");
+    return clc_match_2nn_unique_dev(ctx, d_q, nq, ctx->d_m.ptr, ctx->map_n, threshold, d_match, d_owner, stream);
 }
 
 /* ---- the distance-ratio rule: CPUMatcher's matches (include/coloc/CPUMatcher.hpp:56-98) ------------------------------------------

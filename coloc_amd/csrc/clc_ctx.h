@@ -95,6 +95,7 @@ struct clc_ctx {
     clc::DevBuf d_guided;            // float: the lines (3 per query row) and train points (2 per train row) of a guided match, or the query
                                      // points (2) and the landmarks' projections (2 per map row) of a map match around a pose (GuidedDev)
     clc::DevBuf d_binned;            // the binned map match's query points, projections, cell table and records (BinnedDev)
+    clc::DevBuf d_unique;            // the one-to-one filter's claim words, and a composed entry's distances / inverse list (UniqueDev)
     int formulation = clc::K2NN_MATRIX;   // K2NN sweep formulation (k2nn.hip): FP4 matrix pipe, or round 1's popcount kernel for A/B runs
     int target_blocks = 0;           // K2NN sweep workgroups aimed at per launch; 0 = the formulation's default
     int bias_a = 326, bias_b = 249;  // matrix sweep, one-round single-job plans: train share of a workgroup on wave slot 0 / 1 in 1/256 of the
@@ -227,6 +228,15 @@ void rows_leave(clc_ctx* ctx);
 int default_target_blocks(int formulation, const K2nnDevice& dev = K2nnDevice{});
 int run_jobs(clc_ctx* ctx, std::vector<K2nnJobDev>& jobs, hipStream_t st, bool probe = false);
 void k2nn_probe_bias(clc_ctx* ctx);                       // once per process and device: which unequal shares suit this device
+
+// ---- the one-to-one filter (k2nn_unique.hip) ---------------------------------------------------------------------------------------------
+// What the entries that compose a producer with the filter share.  unique_check: the filter's own rules for the n_jobs jobs -- CLC_ERR_BAD_ARG,
+// CLC_ERR_STATE, CLC_ERR_CAPACITY on `who` --, with nothing allocated or enqueued (need_best: false where the distances will come from
+// the context's scratch).  unique_scratch: ONE pair's claim words in d_unique, and where asked the distances a producer writes and an
+// inverse list for a download.  unique_enqueue: arm, claim, resolve on `st` for jobs whose claim words are dv[j].claim.
+int unique_check(clc_ctx* ctx, const char* who, const clc_unique_job* jobs, int n_jobs, bool need_best);
+int unique_scratch(clc_ctx* ctx, int nq, int nt, bool with_best, bool with_owner, UniqueDev& dv);
+int unique_enqueue(clc_ctx* ctx, const clc_unique_job* jobs, const UniqueDev* dv, int n_jobs, hipStream_t st);
 
 // all two-view a-contrario filters of a batch (pose_batch.hip); jobs[i] on ctxs[i]
 int acr_two_view_batch(clc_ctx* const* ctxs, clc_two_view_job* const* jobs, int n_jobs, int kind /* kAcrEssential, kAcrFundamental or kAcrHomography */);

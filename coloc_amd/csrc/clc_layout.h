@@ -426,6 +426,18 @@ struct BinnedDev {
     }
 };
 
+// ---- the one-to-one filter's scratch d_unique (k2nn_unique.hip) --------------------------------------------------------------------------
+// per job [ claim words up64(nt) | the producer's distances up64(nq) x 2 B (a composed entry whose caller gave none) | the inverse list
+//           up64(nt) (the host entry's, for the download) ], each starting on 256 bytes: the claim words of a batch are ONE range
+struct UniqueDev {
+    uint32_t* claim; uint16_t* best; int32_t* owner;
+    void carve(Carve& c, size_t nq, size_t nt, bool with_best, bool with_owner)
+    {
+        claim = c.take<uint32_t>(up64(nt), 256); best = c.take<uint16_t>(with_best ? up64(nq) : 0, 256);
+        owner = c.take<int32_t>(with_owner ? up64(nt) : 0, 256);
+    }
+};
+
 // ---- the host-pointer K2NN entries' pinned mirror h_res (capi_match.hip): [ match nq | best nq | second nq | 64 B ] --------------------
 struct MatchPin {
     int32_t* match; uint16_t *best, *second;

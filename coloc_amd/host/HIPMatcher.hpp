@@ -204,6 +204,39 @@ public:
         return !check(clc_match_map_binned_dev(ctx_, &jb, after_stream), "matchSceneWithMapBinnedDev");
     }
 
+    // matchSceneWithMapBinnedDev and then the one-to-one filter (clc_match_map_binned_unique_dev, which states the rule; no counterpart in
+    // the reference): of the keypoints that took one landmark only the nearest keeps it, so the solve behind sees every landmark once.
+    // d_owner_out: nullable, one int32 per map row -- the keypoint that holds the landmark, or -1.  false = enqueued.
+    bool matchSceneWithMapBinnedUniqueDev(const openMVG::geometry::Pose3& predictedPose, const clc_camera_k3& intrinsics, const void* d_desc, int nq,
+                                          const clc_keypoint* d_kps, const uint32_t* d_count, float radius, int32_t* d_match_out, void* after_stream,
+                                          int32_t* d_owner_out)
+    {
+        clc_map_guided_job jb{};
+        jb.d_q = d_desc; jb.nq = nq; jb.d_count = d_count; jb.d_kps = d_kps;
+        jb.cam = intrinsics;
+        const openMVG::Vec3 t = predictedPose.translation();                     // t = -R C
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) jb.Rt[4 * i + j] = predictedPose.rotation()(i, j); jb.Rt[4 * i + 3] = t[i]; }
+        jb.radius = radius; jb.threshold = matchThreshold_;
+        jb.d_match = d_match_out;
+        return !check(clc_match_map_binned_unique_dev(ctx_, &jb, d_owner_out, after_stream), "matchSceneWithMapBinnedUniqueDev");
+    }
+
+    // computeMatchesPair with the one-to-one filter behind the sweep (clc_match_2nn_unique): the same IndMatch(i_ = query idx in
+    // regions[first], j_ = train idx in regions[second]) list, thr 40, in which no train index appears twice -- of the queries that named
+    // one train row the nearest keeps it, the lowest query index among equals.
+    void computeMatchesPairUnique(const openMVG::Pair& pairIdx, FeatureMap& regions, openMVG::matching::IndMatches& putativeMatches)
+    {
+        const int numKPQuery = static_cast<int>(regions[pairIdx.first]->RegionCount());
+        const int numKPTraining = static_cast<int>(regions[pairIdx.second]->RegionCount());
+        std::vector<int32_t> m(numKPQuery > 0 ? numKPQuery : 0);
+        putativeMatches.clear();
+        if (!check(clc_match_2nn_unique(ctx_, regions[pairIdx.first]->DescriptorRawData(), numKPQuery, regions[pairIdx.second]->DescriptorRawData(),
+                                        numKPTraining, 40, m.data(), nullptr), "computeMatchesPairUnique"))
+            return;
+        for (size_t i = 0; i < m.size(); ++i)
+            if (m[i] != -1) putativeMatches.emplace_back(static_cast<openMVG::IndexT>(i), static_cast<openMVG::IndexT>(m[i]));
+    }
+
     // GPUMatcher.hpp:180-226: IndMatch(i_ = query index, j_ = train index); dmatches(train, query, 0)
     openMVG::matching::IndMatches computeMatches(void* h_descriptorsQuery, void* h_descriptorsTraining, int numKPQuery,
                                                  int numKPTraining, uint8_t threshold = 40)

@@ -1053,6 +1053,68 @@ int clc_match_map_binned_batch_dev(clc_ctx* ctx, const clc_map_guided_job* jobs,
 int clc_map_bin_build_dev(clc_ctx* ctx, const clc_map_guided_job* job, int32_t* d_cell_start, int32_t* d_cell_row, void* stream);
 int clc_map_binned_plan(const clc_ctx* ctx, const clc_camera_k3* cam, float radius, int32_t* info, double* cell_side);
 
+/* ---- one-to-one matches: each train row keeps its best claimant -----------------------------------------------------------------------
+ * K2NN answers each query on its own, so several queries can name ONE train row -- from the plain sweep, the map sweep, the ratio rule,
+ * the guided and the binned match alike.  Downstream that costs a whole track (the TRACKS rule below drops a component with two nodes of
+ * one camera), hands clc_track_prior_dev one landmark with two observations that no gate can tell apart, and is the division by zero
+ * clc_map_align_dev guards.  This filter turns any (d_match, d_best) pair into a one-to-one d_match in place, on the device.  The
+ * reference has no such step: like the guided match this is THIS library's statement, parity with nothing is pinned, and no existing
+ * entry changes.  (Later under ABI 4: new entry points only.)
+ *
+ * THE RULE (coloc_amd/csrc/unique_math.h, host and device), for nq entries against a train set of nt rows:
+ *   claim        entry q is a CLAIM on train row t = d_match[q] iff 0 <= t < nt and d_best[q] <= 512.
+ *   sanitising   any other entry that is not -1 -- a row outside the train set, a distance no producer writes beside a match -- is NOT a
+ *                claim and is set to -1.  The library never uses an unchecked index as an address.
+ *   key          key(q) = (d_best[q] << 22) | q, 32 bits: the (distance << 22) + row key the binned match folds, with the query row as
+ *                the index.  512 << 22 is 2^31, so it fits; nq > 2^22 is CLC_ERR_CAPACITY, refused before anything is allocated or
+ *                enqueued.
+ *   holder       holder(t) = the claimant of t with the smallest key: the smallest distance wins, a tie goes to the lowest query row, the
+ *                way K2NN keeps the lowest index.
+ *   outputs      d_match[q] stays iff holder(d_match[q]) == q, else -1.  d_owner[t] (nullable, nt int32) = holder(t), or -1 where nobody
+ *                claims t.
+ * So: no train row appears twice and d_owner[d_match[q]] == q for every kept q; the kept set is a subset of the input with exactly one
+ * survivor per claimed row; applying the filter twice changes nothing; and nothing depends on scheduling -- it is an integer minimum.
+ * This is deliberately NOT the mutual-nearest rule, which needs a second sweep with the roles swapped: this rule needs only the distances
+ * the first sweep already has, so it also serves the gated producers (guided, map-guided, binned), which have no reverse sweep.
+ * nq == 0: d_match is untouched and d_owner (if given) is all -1.  nt == 0: every entry becomes -1.
+ *
+ * clc_match_unique_dev / _batch_dev: the filter alone.  Enqueue only on `stream` (0: the context's), no host wait, capturable once the
+ * context's scratch has its size (one call at the planned sizes before a capture).  AT MOST THREE enqueued operations per call whatever
+ * the batch size: the claim words armed (one uint32 per train row per job, in a workspace of the context), the claim launch (one thread
+ * per query, a 32-bit unsigned atomic minimum into the word of its row), the resolve launch (thread i: query i and train row i, both only
+ * reading claim words).  The words are armed on EVERY call.  Batch: n_jobs in [0, CLC_MAX_TRACK_PAIRS] on one context, jobs on a grid
+ * dimension, every job's result the single call's.
+ * The producers whose job carries d_best -- clc_match_guided_dev, clc_match_map_guided_dev and their batches -- need no entry of their
+ * own: set d_best in the job and call clc_match_unique_dev behind them on the same stream.
+ *
+ * The composed entries are their producer and then the filter on the same stream; d_match before the filter is exactly the producer's:
+ *   clc_match_2nn_unique_dev         clc_match_2nn_dev (the context's formulation, unchanged), its distances in the context's scratch
+ *   clc_match_map_unique_dev         clc_match_map_dev likewise; nt = the context's map rows
+ *   clc_match_map_binned_unique_dev  clc_match_map_binned_dev with job->d_best, or the context's scratch where that is null; BINNED and
+ *                                    SWEEP plans alike; nt = the context's map rows
+ *   clc_match_2nn_unique             clc_match_2nn (host arrays, published blocks, the VERIFY re-sweep) with the filter in front of the
+ *                                    download: the filter always stands behind the sweep whose result is returned.  h_owner: nullable, nt.
+ * Errors follow each producer's rules.  Further, all before anything is allocated or enqueued: a null context or job, a null d_match or
+ * d_best with nq > 0, a negative count, a pointer that is not 4-byte aligned (d_best: 2-byte), n_jobs out of range: CLC_ERR_BAD_ARG; a
+ * context without matcher options: CLC_ERR_STATE; nq > 2^22: CLC_ERR_CAPACITY.
+ * OUT OF SCOPE: a query set dealt out in slices -- clc_match_jobs_dev / _counted_dev and clc_mc_* -- because a claim must see every
+ * query of the pair: call the pair entry per pair there.  clc_map_align_dev's internal sweep is as it was. */
+typedef struct clc_unique_job {
+    int32_t*        d_match;   /* nq, device, filtered IN PLACE */
+    const uint16_t* d_best;    /* nq, device: the distances the producer wrote beside d_match */
+    int             nq;
+    int             nt;        /* rows of the train set (the planned capacity where its count lives on the device) */
+    int32_t*        d_owner;   /* nullable, nt, device */
+} clc_unique_job;
+int clc_match_unique_dev(clc_ctx* ctx, const clc_unique_job* job, void* stream);
+int clc_match_unique_batch_dev(clc_ctx* ctx, const clc_unique_job* jobs, int n_jobs, void* stream);   /* n_jobs in [0, CLC_MAX_TRACK_PAIRS] */
+int clc_match_2nn_unique_dev(clc_ctx* ctx, const void* d_q, int nq, const void* d_t, int nt, int threshold, int32_t* d_match,
+                             int32_t* d_owner, void* stream);
+int clc_match_map_unique_dev(clc_ctx* ctx, const void* d_q, int nq, int threshold, int32_t* d_match, int32_t* d_owner, void* stream);
+int clc_match_map_binned_unique_dev(clc_ctx* ctx, const clc_map_guided_job* job, int32_t* d_owner, void* stream);
+int clc_match_2nn_unique(clc_ctx* ctx, const void* h_q, int nq, const void* h_t, int nt, int threshold, int32_t* h_match,
+                         int32_t* h_owner /* nullable */);
+
 /* ---- a tracked frame's pose from the prediction: the solve behind the match by projection -----------------------------------------------
  * clc_track_localize_dev runs Localize for every frame: the host waits for the track count, drives the a-contrario P3P solve round by
  * round, then refines.  With a predicted pose and tracks that all lie within `radius` of where that pose puts them (the guided / binned
@@ -1205,7 +1267,7 @@ int clc_inter_front_dev(clc_ctx* ctx, const double* d_x1, const double* d_x2, in
  * track is a connected component.  The rules are this project's statement of OpenMVG's TracksBuilder (an empty submodule in the
  * reference tree, so unpinned, as for the ratio matcher):
  *   - a component that holds two nodes of ONE camera is dropped whole (Filter), also where the conflict only arises through a third
- *     camera (A5-B7, B7-C2, C2-A9).  K2NN is not one-to-one, so this is common;
+ *     camera (A5-B7, B7-C2, C2-A9).  K2NN is not one-to-one, so this is common (clc_match_2nn_unique_dev gives lists that are);
  *   - a surviving track has at least two nodes (Filter(2): every edge joins two cameras, so every component has);
  *   - the survivors get ids 0, 1, ... in ascending order of their smallest node in (camera, row) order.  The SET of tracks does not
  *     depend on that rule, only their order does; nothing depends on scheduling.
