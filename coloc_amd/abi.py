@@ -109,6 +109,20 @@ class UniqueJob(C.Structure):
     _fields_ = [("d_match", C.c_void_p), ("d_best", C.c_void_p), ("nq", C.c_int), ("nt", C.c_int), ("d_owner", C.c_void_p)]
 
 
+class ExtendView(C.Structure):
+    """clc_extend_view (include/coloc_hip.h)"""
+    _fields_ = [("d_desc", C.c_void_p), ("n", C.c_int), ("d_count", C.c_void_p), ("d_kps", C.c_void_p), ("d_feat", C.c_void_p),
+                ("feat_stride", C.c_int), ("cam", CameraK3), ("Rt", C.c_double * 12), ("d_track", C.c_void_p)]
+
+
+class MapExtend(C.Structure):
+    """clc_map_extend (include/coloc_hip.h)"""
+    _fields_ = [("a", ExtendView), ("b", ExtendView), ("band", C.c_float), ("threshold", C.c_int), ("max_distance", C.c_int),
+                ("update_tracks", C.c_int), ("after_stream", C.c_void_p), ("d_new_q", C.c_void_p), ("d_new_t", C.c_void_p),
+                ("new_q", C.c_void_p), ("new_t", C.c_void_p), ("X", C.c_void_p), ("F", C.c_double * 9),
+                ("map_n_before", C.c_int), ("n_guided", C.c_int), ("n_added", C.c_int), ("n_dropped", C.c_int), ("status", C.c_int)]
+
+
 MAX_BATCH, MAX_TRACK_PAIRS = 8, 28          # CLC_MAX_BATCH, CLC_MAX_TRACK_PAIRS
 
 
@@ -248,6 +262,7 @@ EXPORTS = [
     "clc_track_prior_dev", "clc_track_prior_batch_dev", "clc_pnp_refine_prior",
     "clc_match_unique_dev", "clc_match_unique_batch_dev", "clc_match_2nn_unique_dev", "clc_match_map_unique_dev",
     "clc_match_map_binned_unique_dev", "clc_match_2nn_unique",
+    "clc_map_extend_dev", "clc_map_extend_batch_dev", "clc_fundamental_from_poses", "clc_append_map_points",
 ]
 # clc_track_prior_job.result
 TRACK_PRIOR_OK, TRACK_PRIOR_FEW = 0, 1
@@ -441,6 +456,10 @@ def load_library():
     lib.clc_match_map_unique_dev.argtypes = [vp, vp, ci, ci, vp, vp, vp]
     lib.clc_match_map_binned_unique_dev.argtypes = [vp, vp, vp, vp]
     lib.clc_match_2nn_unique.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp]
+    lib.clc_map_extend_dev.argtypes = [vp, vp]
+    lib.clc_map_extend_batch_dev.argtypes = [vp, vp, ci]
+    lib.clc_fundamental_from_poses.argtypes = [vp, vp, vp, vp, vp]
+    lib.clc_append_map_points.argtypes = [vp, vp, ci]
     _lib = lib
     return lib
 
@@ -837,6 +856,45 @@ def _map_guided_fill(j, d_q, nq, cam, Rt, radius, threshold, d_match, d_kps=None
     j.Rt = (C.c_double * 12)(*[float(v) for v in np.asarray(Rt, dtype=np.float64).reshape(12)])
     j.radius, j.threshold = float(radius), int(threshold)
     j.d_match, j.d_best, j.d_second, j.d_qpos, j.d_proj = d_match, d_best, d_second, d_qpos, d_proj
+
+
+def _extend_view_fill(v, d_desc, n, cam, Rt, d_kps=None, d_feat=None, feat_stride=4, d_count=None, d_track=None):
+    """fills an ExtendView; cam = (focal, ppx, ppy, k1, k2, k3), Rt = 12 numbers, the view's [R|t] row-major 3 x 4; device pointers as integers"""
+    v.d_desc, v.n, v.d_count, v.d_kps, v.d_feat, v.feat_stride = d_desc, int(n), d_count, d_kps, d_feat, int(feat_stride)
+    v.cam = CameraK3(*[float(c) for c in cam])
+    v.Rt = (C.c_double * 12)(*[float(c) for c in np.asarray(Rt, dtype=np.float64).reshape(12)])
+    v.d_track = d_track
+
+
+def _extend_fill(j, keep, view_a, view_b, band, threshold, max_distance, update_tracks=True, after_stream=None, d_new_q=None, d_new_t=None):
+    _extend_view_fill(j.a, **view_a)
+    _extend_view_fill(j.b, **view_b)
+    j.band, j.threshold, j.max_distance, j.update_tracks, j.after_stream = float(band), int(threshold), int(max_distance), int(bool(update_tracks)), after_stream
+    j.d_new_q, j.d_new_t = d_new_q, d_new_t
+    n = max(int(view_a["n"]), 1)
+    q, t, X = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32), np.zeros((n, 3))
+    j.new_q, j.new_t, j.X = _p(q), _p(t), _p(X)
+    keep.append((q, t, X))
+    return q, t, X
+
+
+def _extend_result(j, q, t, X):
+    n = j.n_added
+    return dict(new_q=q[:n].copy(), new_t=t[:n].copy(), X=X[:n].copy(), F=np.array(list(j.F)).reshape(3, 3), map_n_before=j.map_n_before,
+                n_guided=j.n_guided, n_added=n, n_dropped=j.n_dropped, status=j.status)
+
+
+def fundamental_from_poses(cam_a, Rt_a, cam_b, Rt_b):
+    """clc_fundamental_from_poses: F (3, 3) of two posed views, x_b^T F x_a = 0 in undistorted pixels; cam = (focal, ppx, ppy, ...),
+    Rt = 12 numbers, [R|t] row-major.  Host arithmetic: no context, no GPU."""
+    lib = load_library()
+    ca, cb = CameraK3(*([float(v) for v in cam_a] + [0.0] * 6)[:6]), CameraK3(*([float(v) for v in cam_b] + [0.0] * 6)[:6])
+    Ra, Rb = np.ascontiguousarray(Rt_a, dtype=np.float64).reshape(12), np.ascontiguousarray(Rt_b, dtype=np.float64).reshape(12)
+    F = np.zeros(9)
+    rc = lib.clc_fundamental_from_poses(C.byref(ca), _p(Ra), C.byref(cb), _p(Rb), _p(F))
+    if rc != 0:
+        raise CLCError(rc, "clc_fundamental_from_poses: " + lib.clc_status_string(rc).decode())
+    return F.reshape(3, 3)
 
 
 def pair_filter_batch_dev(ctxs, model, jobs):
@@ -1451,6 +1509,31 @@ class Context:
         """clc_set_map_points: (n, 3) float64, row i = the landmark of map descriptor row i; an empty array clears"""
         X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
         self._chk(self.lib.clc_set_map_points(self.h, _p(X) if X.shape[0] else None, X.shape[0]))
+
+    def append_map_points(self, X):
+        """clc_append_map_points: (n, 3) float64 behind the points of a context that holds only points (no set_map)"""
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+        self._chk(self.lib.clc_append_map_points(self.h, _p(X) if X.shape[0] else None, X.shape[0]))
+
+    fundamental_from_poses = staticmethod(fundamental_from_poses)
+
+    def extend_map(self, view_a, view_b, band, threshold, max_distance, update_tracks=True, after_stream=None, d_new_q=None, d_new_t=None):
+        """clc_map_extend_dev: the untracked guided matches of two posed views triangulated and appended to the context's map.  A view =
+        dict(d_desc, n, cam = (focal, ppx, ppy, k1, k2, k3), Rt (12, host), d_kps or d_feat (+ feat_stride), d_count, d_track); device
+        pointers as integers.  Returns dict(new_q, new_t, X (n_added, 3), F, map_n_before, n_guided, n_added, n_dropped, status)."""
+        j, keep = MapExtend(), []
+        out = _extend_fill(j, keep, view_a, view_b, band, threshold, max_distance, update_tracks, after_stream, d_new_q, d_new_t)
+        self._chk(self.lib.clc_map_extend_dev(self.h, C.byref(j)))
+        return _extend_result(j, *out)
+
+    def extend_map_batch(self, jobs):
+        """clc_map_extend_batch_dev: jobs = [dict(view_a, view_b, band, threshold, max_distance [, update_tracks, after_stream, d_new_q,
+        d_new_t]), ...], at most MAX_TRACK_PAIRS, in order on the context's stream with one host wait.  Returns a list of result dicts."""
+        n, keep = len(jobs), []
+        arr = (MapExtend * max(n, 1))()
+        outs = [_extend_fill(arr[i], keep, **jobs[i]) for i in range(n)]
+        self._chk(self.lib.clc_map_extend_batch_dev(self.h, arr, n))
+        return [_extend_result(arr[i], *outs[i]) for i in range(n)]
 
     def tracks_build_dev(self, rows, pairs, d_track_feat, d_n_tracks, stream=None):
         """clc_tracks_build_dev: the multi-view tracks alone, enqueue only.  rows = row capacity per camera; pairs = [dict(cam_a=, cam_b=,

@@ -96,6 +96,8 @@ struct clc_ctx {
                                      // points (2) and the landmarks' projections (2 per map row) of a map match around a pose (GuidedDev)
     clc::DevBuf d_binned;            // the binned map match's query points, projections, cell table and records (BinnedDev)
     clc::DevBuf d_unique;            // the one-to-one filter's claim words, and a composed entry's distances / inverse list (UniqueDev)
+    clc::DevBuf d_extend;            // the map extension's running row count and per-job lists, flags and points (ExtendDev / ExtendJobDev)
+    clc::PinBuf h_extend;            // its records and mirrors (ExtendJobPin)
     int formulation = clc::K2NN_MATRIX;   // K2NN sweep formulation (k2nn.hip): FP4 matrix pipe, or round 1's popcount kernel for A/B runs
     int target_blocks = 0;           // K2NN sweep workgroups aimed at per launch; 0 = the formulation's default
     int bias_a = 326, bias_b = 249;  // matrix sweep, one-round single-job plans: train share of a workgroup on wave slot 0 / 1 in 1/256 of the

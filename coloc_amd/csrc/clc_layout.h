@@ -438,6 +438,32 @@ struct UniqueDev {
     }
 };
 
+// ---- the map extension's scratch d_extend and its pinned mirror h_extend (map_extend.hip) -----------------------------------------------
+// device: [ the running row count 64 B | per job: the guided list | the masked, then one-to-one list | distances 2 B | flags 1 B | X 3 doubles,
+//           up64(nq) entries each ], every array on 64 bytes
+struct ExtendJobDev {
+    int32_t *guided, *match; uint16_t* best; uint8_t* flag; double* X;
+    void carve(Carve& c, size_t nq)
+    {
+        const size_t n = up64(nq);
+        guided = c.take<int32_t>(n, 64); match = c.take<int32_t>(n, 64); best = c.take<uint16_t>(n, 64); flag = c.take<uint8_t>(n, 64);
+        X = c.take<double>(3 * n, 64);
+    }
+};
+struct ExtendDev {
+    int32_t* rows;
+    void carve(Carve& c) { rows = c.take<int32_t>(16, 64); }
+};
+// pinned, per job: [ the record 64 B (its first 8 bytes the polled word, 0xFF.. = not out yet) | X 3 doubles | q | t, up64(nq) entries each ]
+struct ExtendJobPin {
+    void* rec; double* X; int32_t *q, *t;
+    void carve(Carve& c, size_t nq)
+    {
+        const size_t n = up64(nq);
+        rec = c.take_bytes(64, 64); X = c.take<double>(3 * n, 64); q = c.take<int32_t>(n, 64); t = c.take<int32_t>(n, 64);
+    }
+};
+
 // ---- the host-pointer K2NN entries' pinned mirror h_res (capi_match.hip): [ match nq | best nq | second nq | 64 B ] --------------------
 struct MatchPin {
     int32_t* match; uint16_t *best, *second;

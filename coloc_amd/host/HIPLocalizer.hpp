@@ -115,6 +115,23 @@ public:
         return rc == CLC_OK ? EXIT_SUCCESS : EXIT_FAILURE;
     }
 
+    // The landmarks of rows first .. mapRegionIdx.size() - 1 behind the points already on the device (clc_append_map_points): call it
+    // after HIPMatcher::extendMapPairDev grew the map, with `first` = the rows the map had before, so the tracks of the extended map
+    // find their landmarks without the whole map going up again.  false = success.
+    bool appendMapPoints(colocData& data, size_t first)
+    {
+        if (first > data.mapRegionIdx.size()) return EXIT_FAILURE;
+        const size_t n = data.mapRegionIdx.size() - first;
+        std::vector<double> X(3 * n);
+        for (size_t i = 0; i < n; ++i) {
+            const auto& P = data.scene.GetLandmarks().at(data.mapRegionIdx[first + i]).X;
+            for (int r = 0; r < 3; ++r) X[3 * i + r] = P[r];
+        }
+        const int rc = ctx_ ? clc_append_map_points(ctx_, X.data(), static_cast<int>(n)) : CLC_ERR_STATE;
+        if (rc != CLC_OK) std::cerr << "HIPLocalizer: clc_append_map_points: " << clc_status_string(rc) << std::endl;
+        return rc == CLC_OK ? EXIT_SUCCESS : EXIT_FAILURE;
+    }
+
     // localizeImage from tracks built ON THE DEVICE (clc_track_localize_dev): d_match is what clc_match_map_dev left on the GPU for this
     // frame (nq planned rows, d_count the detector's count pair or NULL), the 2-D side the detector's d_kps or a device block of feature
     // positions (d_feat, feat_stride floats per row); after_stream = the stream that produced them (NULL: the localizer's own, or done).

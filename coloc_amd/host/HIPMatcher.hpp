@@ -221,6 +221,56 @@ public:
         return !check(clc_match_map_binned_unique_dev(ctx_, &jb, d_owner_out, after_stream), "matchSceneWithMapBinnedUniqueDev");
     }
 
+    // The map extended in place from two posed views (clc_map_extend_dev, which states the rule; no counterpart in the reference): the
+    // untracked guided matches of views pair.first (A, the query side) and pair.second (B) are triangulated and appended behind the map
+    // of this matcher's context (setMapData + setMapPoints, or an earlier extension).  The views arrive as their device blocks -- the
+    // descriptor rows, a side each (positions, the count word, the view's map match d_track, nullable) -- and their two poses; the
+    // threshold is MatcherOptions'.  On success colocData receives what setupMapDatabase (colocData.hpp:89-121) would hold for the new
+    // landmarks, in the entry's row order: mapRegions gains A's feature and descriptor of every appended row (from data.regions[A], the
+    // host copy of the block), mapRegionIdx a fresh landmark id each -- one past the largest key of the scene, ascending --, the scene
+    // the landmarks.  n_added / n_dropped (nullable): the entry's counts.  false = success, as the reference's members return it.
+    struct ExtendSideDev { const clc_keypoint* d_kps; const float* d_feat; int feat_stride; const uint32_t* d_count; int32_t* d_track; };
+    bool extendMapPairDev(colocData& data, openMVG::Pair pair, const void* d_desc_a, int na, const void* d_desc_b, int nb, const ExtendSideDev& a,
+                          const ExtendSideDev& b, const clc_camera_k3& cam_a, const clc_camera_k3& cam_b, const openMVG::geometry::Pose3& pose_a,
+                          const openMVG::geometry::Pose3& pose_b, float band, int max_distance, void* after_stream, int* n_added = nullptr,
+                          int* n_dropped = nullptr)
+    {
+        if (n_added) *n_added = 0;
+        if (n_dropped) *n_dropped = 0;
+        const auto ra = data.regions.find(pair.first);
+        if (ra == data.regions.end() || !ra->second || static_cast<int>(ra->second->RegionCount()) < na) {
+            std::cerr << "HIPMatcher::extendMapPairDev: data.regions holds no host copy of view A's rows" << std::endl;
+            return true;
+        }
+        clc_map_extend jb{};
+        const auto side = [](clc_extend_view& v, const void* d_desc, int n, const ExtendSideDev& s, const clc_camera_k3& cam,
+                             const openMVG::geometry::Pose3& pose) {
+            v.d_desc = d_desc; v.n = n; v.d_count = s.d_count; v.d_kps = s.d_kps; v.d_feat = s.d_feat; v.feat_stride = s.feat_stride;
+            v.cam = cam; v.d_track = s.d_track;
+            const openMVG::Vec3 t = pose.translation();                            // t = -R C
+            for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) v.Rt[4 * i + j] = pose.rotation()(i, j); v.Rt[4 * i + 3] = t[i]; }
+        };
+        side(jb.a, d_desc_a, na, a, cam_a, pose_a);
+        side(jb.b, d_desc_b, nb, b, cam_b, pose_b);
+        jb.band = band; jb.threshold = matchThreshold_; jb.max_distance = max_distance; jb.update_tracks = 1; jb.after_stream = after_stream;
+        std::vector<int32_t> q(na > 0 ? na : 0), t(na > 0 ? na : 0);
+        std::vector<double> X(3 * static_cast<size_t>(na > 0 ? na : 0));
+        jb.new_q = q.data(); jb.new_t = t.data(); jb.X = X.data();
+        if (!check(clc_map_extend_dev(ctx_, &jb), "extendMapPairDev")) return true;
+        if (!data.mapRegions) data.mapRegions.reset(new openMVG::features::AKAZE_Binary_Regions());
+        openMVG::IndexT id = data.scene.structure.empty() ? 0 : data.scene.structure.rbegin()->first + 1;
+        for (int k = 0; k < jb.n_added; ++k, ++id) {
+            data.mapRegions->Features().push_back(ra->second->Features()[q[k]]);
+            data.mapRegions->Descriptors().push_back(ra->second->Descriptors()[q[k]]);
+            data.mapRegionIdx.push_back(id);
+            data.scene.structure[id].X = openMVG::Vec3(X[3 * k], X[3 * k + 1], X[3 * k + 2]);
+        }
+        kpMap_ += static_cast<unsigned int>(jb.n_added);
+        if (n_added) *n_added = jb.n_added;
+        if (n_dropped) *n_dropped = jb.n_dropped;
+        return false;
+    }
+
     // computeMatchesPair with the one-to-one filter behind the sweep (clc_match_2nn_unique): the same IndMatch(i_ = query idx in
     // regions[first], j_ = train idx in regions[second]) list, thr 40, in which no train index appears twice -- of the queries that named
     // one train row the nearest keeps it, the lowest query index among equals.

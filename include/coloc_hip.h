@@ -1636,6 +1636,99 @@ int clc_map_update_grow_ba_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jo
 int clc_map_update_sim_batch_dev(clc_ctx* const* ctxs, clc_pair_job* pair_jobs, int n_pairs, clc_map_job* job, clc_map_align_sim* sim,
                                  clc_map_grow* grow /* nullable */, clc_map_ba* ba /* nullable, needs grow */);
 
+/* ---- the map extended in place: untracked matches of two posed views become new landmarks -----------------------------------------------
+ * Every entry above that produces landmarks REPLACES the map: new landmark identities, a new scale, and clc_map_align_dev / clc_sim3_* to
+ * tie the new map to the old one.  Between rebuilds the frame loop already holds what it takes to ADD landmarks where the cameras now
+ * look: two views with poses (clc_track_prior_dev / clc_track_localize_dev) and each view's map match (clc_match_map_binned_unique_dev),
+ * which says which keypoints are landmarks already.  clc_map_extend_dev joins them and appends to the context's map: old rows keep their
+ * index, their descriptor and their coordinates, so nothing has to be aligned and every list that names map rows stays valid.  The
+ * reference has no such step: like the guided, binned, unique and prior entries this is THIS library's statement, parity with nothing
+ * is pinned, and no existing entry changes.  (Later under ABI 4: new entry points only.)
+ *
+ * THE RULE (coloc_amd/csrc/extend_math.h, host and device, over guided_math.h, unique_math.h and map_math.h as they stand).  View A is
+ * the query side, view B the train side.  A view: n descriptor rows of 64 bytes (d_desc), clipped by d_count[0] where given; positions
+ * as d_kps or d_feat + feat_stride, exactly one; its clc_camera_k3; its pose Rt (HOST, 12 doubles, [R|t] row-major, world to camera);
+ * d_track (nullable, n int32 on the device): the map row of every keypoint or -1, as clc_match_map_* leaves it; null = no row tracked.
+ *   1 F          clc_fundamental_from_poses: R = R_b R_a^T, t = t_b - R t_a, E = [t]x R, F = K_b^-T E K_a^-1 with K = { focal, 0, ppx; 0,
+ *                focal, ppy; 0, 0, 1 }, in fp64, one fixed operation order, no contraction, on the host.  x_b^T F x_a = 0 in undistorted
+ *                pixels: clc_guided_job.F's orientation and units.  It comes back in job.F.
+ *   2 guided     clc_match_guided_dev's rule and launches under that F with `band` and `threshold`, the distances kept.
+ *   3 mask       entry q with t = match[q] >= 0 becomes -1 if d_track_a[q] >= 0 (q is a landmark already), if d_track_b[t] >= 0 (q's
+ *                best row inside the band is a landmark already: q is most likely an unmatched observation of that landmark, and its
+ *                second choice would plant a duplicate -- which is why the mask stands BEHIND the sweep and not in its gate), or if
+ *                best[q] > max_distance (the guided rule accepts a lone candidate at any distance).  max_distance in [0, 512].
+ *   4 one-to-one clc_match_unique_dev's rule and launches on the masked list, nt = B's rows.
+ *   5 point      for every surviving (q, t): both positions through get_ud_pixel in fp64 (the track kernel's bits), then the grow rule
+ *                of one landmark (Reconstructor.hpp:383; grow_point, map_math.h) with camera A in the place of the resected camera:
+ *                accepted iff the ray angle is over 2 degrees, X is finite, both depths are positive and |X[2]| < 1000.
+ *   6 append     the accepted entries in ASCENDING q become map rows map_n + k, k = 0, 1, ..., while map_n + k < MatcherOptions.maxkp.
+ *                Row map_n + k holds X in the map's points and A's descriptor row q in the map's rows (A is the lower camera: the rule
+ *                of the grown map); (q, t) goes into the output lists.  Entries past the capacity are dropped and counted (n_dropped),
+ *                not an error: the order is fixed, so the truncation is reproducible.  Old rows are never rewritten.  update_tracks != 0:
+ *                d_track_a[q] and d_track_b[t] of every APPENDED entry are set to its new row, so a later job that shares a view skips
+ *                them; no other entry of d_track_* is written.
+ *   7 Degenerate cases add nothing and return CLC_OK, each by rules 1 - 6: two views with one centre where t comes out 0 (F = 0, no
+ *     query has a line), a.n == 0 or b.n == 0, a map at capacity (everything accepted is dropped and counted).
+ *
+ * clc_map_extend_dev runs on the CONTEXT's stream (after_stream: as clc_map_job, one event, no host synchronisation): the guided prep
+ * and sweep, the mask (one thread per query), the filter's three launches, the point launch (one thread per query) and ONE workgroup
+ * that appends by the ordered compaction and publishes { n_added, n_dropped } in pinned memory last, behind a system-scope fence.  The
+ * host waits for that one word, once per call.  OUTPUTS: d_new_q / d_new_t (nullable, device, room for a.n) and new_q / new_t / X
+ * (nullable, host, room for a.n entries / 3 a.n doubles): the appended (q, t) and their points, n_added of each; F; map_n_before (the
+ * map's rows when the job ran), n_guided (entries the guided match accepted, before the mask), n_added, n_dropped, status.
+ * The context's map points are brought to MatcherOptions.maxkp rows first, contents kept; a call at a size no call before it had may
+ * grow scratch, which synchronises the context's stream.
+ * ORDERING, as clc_map_build_dev: on return the map serves clc_match_map_*, clc_match_map_guided_* / _binned_*, clc_track_* with
+ * map_n_before + n_added rows.  Work on other streams that reads the map while the call runs is the caller's to order; the old rows are
+ * not written, so such work is correct under either count.
+ * clc_map_extend_batch_dev: n_jobs in [0, CLC_MAX_TRACK_PAIRS] on one context, enqueued in order on the one stream; job k sees job
+ * k - 1's rows and d_track updates, the running row count lives in a device word, and the host still waits once.  The results equal
+ * the single calls made in that order.
+ * ERRORS, all before anything is enqueued: a null context, job, descriptor block (n > 0) or a negative n, both or neither position
+ * form, a misaligned pointer (descriptor rows: 16 bytes), a non-positive focal, a band that is not finite and positive, max_distance
+ * outside [0, 512], n_jobs out of range: CLC_ERR_BAD_ARG; a context without matcher options, without a map (no clc_set_map / build),
+ * or whose map points are not exactly its map rows (the partially-owned state clc_track_localize_dev refuses): CLC_ERR_STATE -- a map
+ * of 0 rows with its points cleared is an empty map and is extendable; n > 2^22: CLC_ERR_CAPACITY.  The map is as it was.
+ *
+ * clc_fundamental_from_poses: rule 1 alone, host arithmetic, no context.  Null pointer or a focal that is not positive: CLC_ERR_BAD_ARG.
+ * clc_append_map_points: n more points behind the points of a context that holds ONLY points (the localizer's, whose tracks name the
+ * matcher's rows): the points it has are kept, the new ones follow.  A context that holds map rows is extended by clc_map_extend_dev
+ * alone (CLC_ERR_STATE), so rows and points cannot part ways.  Synchronises the context's stream, as clc_set_map_points. */
+typedef struct clc_extend_view {
+    const void*         d_desc;         /* n rows of 64 bytes, 16-byte aligned */
+    int                 n;
+    const uint32_t*     d_count;        /* nullable, as clc_pair_job */
+    const clc_keypoint* d_kps;          /* or */
+    const float*        d_feat;
+    int                 feat_stride;
+    clc_camera_k3       cam;
+    double              Rt[12];         /* host: the view's pose */
+    int32_t*            d_track;        /* nullable, n, device: map row or -1; written where update_tracks != 0 */
+} clc_extend_view;
+typedef struct clc_map_extend {
+    /* in */
+    clc_extend_view a, b;
+    float           band;               /* pixels */
+    int             threshold;
+    int             max_distance;       /* [0, 512] */
+    int             update_tracks;
+    void*           after_stream;       /* nullable */
+    /* out, nullable: device, room for a.n */
+    int32_t*        d_new_q;
+    int32_t*        d_new_t;
+    /* out, nullable: host, room for a.n (X: 3 a.n) */
+    int32_t*        new_q;
+    int32_t*        new_t;
+    double*         X;
+    /* out */
+    double          F[9];
+    int             map_n_before, n_guided, n_added, n_dropped, status;
+} clc_map_extend;
+int clc_map_extend_dev(clc_ctx* ctx, clc_map_extend* job);
+int clc_map_extend_batch_dev(clc_ctx* ctx, clc_map_extend* jobs, int n_jobs);   /* n_jobs in [0, CLC_MAX_TRACK_PAIRS], in order, one stream */
+int clc_fundamental_from_poses(const clc_camera_k3* cam_a, const double* Rt_a, const clc_camera_k3* cam_b, const double* Rt_b, double* F);
+int clc_append_map_points(clc_ctx* ctx, const double* h_X, int n);
+
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
  * (include/coloc/CovIntersection.hpp:24-49, called at include/coloc/coloc.hpp:362-389): omega in [0,1]
