@@ -126,6 +126,31 @@ class MapExtend(C.Structure):
 MAX_BATCH, MAX_TRACK_PAIRS = 8, 28          # CLC_MAX_BATCH, CLC_MAX_TRACK_PAIRS
 
 
+class ObserveView(C.Structure):
+    """clc_observe_view (include/coloc_hip.h)"""
+    _fields_ = [("n", C.c_int), ("d_count", C.c_void_p), ("d_kps", C.c_void_p), ("d_feat", C.c_void_p), ("feat_stride", C.c_int),
+                ("cam", CameraK3), ("Rt", C.c_double * 12), ("d_track", C.c_void_p), ("d_counts", C.c_void_p)]
+
+
+class MapObserve(C.Structure):
+    """clc_map_observe (include/coloc_hip.h)"""
+    _fields_ = [("view", ObserveView), ("width", C.c_int), ("height", C.c_int), ("gate", C.c_float), ("margin", C.c_float),
+                ("after_stream", C.c_void_p), ("epoch", C.c_uint32), ("map_n", C.c_int), ("status", C.c_int)]
+
+
+class MapCull(C.Structure):
+    """clc_map_cull (include/coloc_hip.h)"""
+    _fields_ = [("min_visible", C.c_int), ("num", C.c_int), ("den", C.c_int), ("max_idle", C.c_uint32), ("d_flagged", C.c_void_p),
+                ("d_track", C.c_void_p * MAX_BATCH), ("track_n", C.c_int * MAX_BATCH), ("n_lists", C.c_int), ("after_stream", C.c_void_p),
+                ("d_remap", C.c_void_p), ("h_remap", C.c_void_p),
+                ("map_n_before", C.c_int), ("n_kept", C.c_int), ("n_dropped", C.c_int), ("n_flagged", C.c_int), ("n_ratio", C.c_int),
+                ("n_idle", C.c_int), ("status", C.c_int)]
+
+
+# the customary cull rule (clc_map_cull_rule_default): UNTUNED
+CULL_RULE_DEFAULT = dict(min_visible=8, num=1, den=4, max_idle=0)
+
+
 class TracksPair(C.Structure):
     """clc_tracks_pair (include/coloc_hip.h)"""
     _fields_ = [("cam_a", C.c_int32), ("cam_b", C.c_int32), ("d_q", C.c_void_p), ("d_t", C.c_void_p), ("n", C.c_int), ("d_n", C.c_void_p),
@@ -263,6 +288,8 @@ EXPORTS = [
     "clc_match_unique_dev", "clc_match_unique_batch_dev", "clc_match_2nn_unique_dev", "clc_match_map_unique_dev",
     "clc_match_map_binned_unique_dev", "clc_match_2nn_unique",
     "clc_map_extend_dev", "clc_map_extend_batch_dev", "clc_fundamental_from_poses", "clc_append_map_points",
+    "clc_map_observe_dev", "clc_map_observe_batch_dev", "clc_map_cull_dev", "clc_map_cull_rule_default", "clc_map_stats_get",
+    "clc_cull_map_points",
 ]
 # clc_track_prior_job.result
 TRACK_PRIOR_OK, TRACK_PRIOR_FEW = 0, 1
@@ -460,6 +487,12 @@ def load_library():
     lib.clc_map_extend_batch_dev.argtypes = [vp, vp, ci]
     lib.clc_fundamental_from_poses.argtypes = [vp, vp, vp, vp, vp]
     lib.clc_append_map_points.argtypes = [vp, vp, ci]
+    lib.clc_map_observe_dev.argtypes = [vp, vp]
+    lib.clc_map_observe_batch_dev.argtypes = [vp, vp, ci]
+    lib.clc_map_cull_dev.argtypes = [vp, vp]
+    lib.clc_map_cull_rule_default.argtypes = [vp]
+    lib.clc_map_stats_get.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.clc_cull_map_points.argtypes = [vp, vp, ci]
     _lib = lib
     return lib
 
@@ -882,6 +915,17 @@ def _extend_result(j, q, t, X):
     n = j.n_added
     return dict(new_q=q[:n].copy(), new_t=t[:n].copy(), X=X[:n].copy(), F=np.array(list(j.F)).reshape(3, 3), map_n_before=j.map_n_before,
                 n_guided=j.n_guided, n_added=n, n_dropped=j.n_dropped, status=j.status)
+
+
+def _observe_fill(j, n, cam, Rt, width, height, gate, margin=0.0, d_kps=None, d_feat=None, feat_stride=4, d_count=None, d_track=None, d_counts=None,
+                  after_stream=None):
+    """fills a MapObserve; cam = (focal, ppx, ppy, k1, k2, k3), Rt = 12 numbers, the frame's [R|t] row-major 3 x 4; device pointers as integers"""
+    v = j.view
+    v.n, v.d_count, v.d_kps, v.d_feat, v.feat_stride = int(n), d_count, d_kps, d_feat, int(feat_stride)
+    v.cam = CameraK3(*[float(c) for c in cam])
+    v.Rt = (C.c_double * 12)(*[float(c) for c in np.asarray(Rt, dtype=np.float64).reshape(12)])
+    v.d_track, v.d_counts = d_track, d_counts
+    j.width, j.height, j.gate, j.margin, j.after_stream = int(width), int(height), float(gate), float(margin), after_stream
 
 
 def fundamental_from_poses(cam_a, Rt_a, cam_b, Rt_b):
@@ -1534,6 +1578,58 @@ class Context:
         outs = [_extend_fill(arr[i], keep, **jobs[i]) for i in range(n)]
         self._chk(self.lib.clc_map_extend_batch_dev(self.h, arr, n))
         return [_extend_result(arr[i], *outs[i]) for i in range(n)]
+
+    def map_observe_dev(self, **view):
+        """clc_map_observe_dev: one frame's map match folded into the map rows' observation statistics; enqueue only, no host wait.
+        view = n, cam, Rt, width, height, gate [, margin, d_kps | d_feat (+ feat_stride), d_count, d_track, d_counts, after_stream];
+        device pointers as integers.  Returns dict(epoch, map_n, status)."""
+        j = MapObserve()
+        _observe_fill(j, **view)
+        self._chk(self.lib.clc_map_observe_dev(self.h, C.byref(j)))
+        return dict(epoch=int(j.epoch), map_n=j.map_n, status=j.status)
+
+    def map_observe_batch_dev(self, views):
+        """clc_map_observe_batch_dev: views = [dict as map_observe_dev takes, ...], at most MAX_BATCH, ONE epoch, one pair of launches.
+        Returns a list of dict(epoch, map_n, status)."""
+        n = len(views)
+        arr = (MapObserve * max(n, 1))()
+        for i in range(n):
+            _observe_fill(arr[i], **views[i])
+        self._chk(self.lib.clc_map_observe_batch_dev(self.h, arr, n))
+        return [dict(epoch=int(arr[i].epoch), map_n=arr[i].map_n, status=arr[i].status) for i in range(n)]
+
+    def map_cull_dev(self, min_visible=8, num=1, den=4, max_idle=0, d_flagged=None, lists=(), after_stream=None, d_remap=None, want_remap=True):
+        """clc_map_cull_dev: rows dropped by the rule, the map compacted in order, lists = [(d_track, n), ...] (device pointers as integers)
+        remapped in place.  The defaults are the customary rule (CULL_RULE_DEFAULT), UNTUNED.  Returns dict(remap (map_n_before,) int32 or
+        None, map_n_before, n_kept, n_dropped, n_flagged, n_ratio, n_idle, status)."""
+        j = MapCull()
+        j.min_visible, j.num, j.den, j.max_idle, j.d_flagged = int(min_visible), int(num), int(den), int(max_idle), d_flagged
+        j.n_lists = len(lists)
+        for i, (d, n) in enumerate(lists[:MAX_BATCH]):
+            j.d_track[i], j.track_n[i] = d, int(n)
+        j.after_stream, j.d_remap = after_stream, d_remap
+        remap = np.full(max(int(self.mopts.maxkp), 1), -7, dtype=np.int32) if want_remap else None      # (a map never has more rows)
+        j.h_remap = _p(remap)
+        self._chk(self.lib.clc_map_cull_dev(self.h, C.byref(j)))
+        return dict(remap=None if remap is None else remap[:j.map_n_before].copy(), map_n_before=j.map_n_before, n_kept=j.n_kept,
+                    n_dropped=j.n_dropped, n_flagged=j.n_flagged, n_ratio=j.n_ratio, n_idle=j.n_idle, status=j.status)
+
+    def map_stats(self, counters=True):
+        """clc_map_stats_get: dict(visible, found, last_view ((rows,) uint32 each; counters=False: left out), epoch, rows); covers new
+        rows first and synchronises the context's stream"""
+        epoch, rows = C.c_uint32(0), C.c_int(0)
+        self._chk(self.lib.clc_map_stats_get(self.h, None, None, None, C.byref(epoch), C.byref(rows)))
+        out = dict(epoch=int(epoch.value), rows=int(rows.value))
+        if counters:
+            arrs = [np.zeros(max(out["rows"], 1), dtype=np.uint32) for _ in range(3)]
+            self._chk(self.lib.clc_map_stats_get(self.h, _p(arrs[0]), _p(arrs[1]), _p(arrs[2]), None, None))
+            out.update(visible=arrs[0][:out["rows"]], found=arrs[1][:out["rows"]], last_view=arrs[2][:out["rows"]])
+        return out
+
+    def cull_map_points(self, remap):
+        """clc_cull_map_points: the points of a context that holds only points compacted by a host remap (one entry per point)"""
+        remap = np.ascontiguousarray(remap, dtype=np.int32).reshape(-1)
+        self._chk(self.lib.clc_cull_map_points(self.h, _p(remap) if len(remap) else None, len(remap)))
 
     def tracks_build_dev(self, rows, pairs, d_track_feat, d_n_tracks, stream=None):
         """clc_tracks_build_dev: the multi-view tracks alone, enqueue only.  rows = row capacity per camera; pairs = [dict(cam_a=, cam_b=,

@@ -12,8 +12,8 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libcoloc_hip.so")
 SOURCES = ["capi_core.hip", "capi_match.hip", "desc_cache.hip", "capi_pose.hip", "pose_batch.hip", "inter_pose.hip", "inter_geometry.cpp",
-           "k2nn.hip", "clatch.hip", "lerp.hip", "pnp.hip", "detect.hip", "acransac.hip", "multicam.hip", "gather.hip", "inter_dev.hip", "map_build.hip", "map_update.hip", "map_grow.hip", "map_ba.hip", "k2nn_guided.hip", "k2nn_binned.hip", "pose_prior.hip", "k2nn_unique.hip", "map_extend.hip"]
-HEADERS = ["clc_internal.h", "clc_ctx.h", "clc_buf.h", "clc_carve.h", "clc_layout.h", "acr_kind.h", "desc_cache.h", "inter_geometry.h", "clc_sincos.h", "clc_acr.h", "p3p.h", "so3.h", "inter_math.h", "map_math.h", "ba_math.h", "k2nn_top2.h", "k2nn_sweep.h", "pose_lm.h", "guided_math.h", "sim3_math.h", "proj_math.h", "bin_math.h", "unique_math.h", "extend_math.h", "k2nn_proj.h", "wg_compact.h", "fivept.h", "fivept_wave.h", "twoview_min.h", "ud_pixel.h", "latch_pattern.inc", "latch_layout.inc", "latch_layout_swap.inc", os.path.join("..", "host", "HIPCovIntersection.hpp"), os.path.join("..", "host", "HIPRobustMatcher.hpp"), os.path.join("..", "host", "coloc_hip_geometry.hpp"), os.path.join("..", "..", "include", "coloc_hip.h")]
+           "k2nn.hip", "clatch.hip", "lerp.hip", "pnp.hip", "detect.hip", "acransac.hip", "multicam.hip", "gather.hip", "inter_dev.hip", "map_build.hip", "map_update.hip", "map_grow.hip", "map_ba.hip", "k2nn_guided.hip", "k2nn_binned.hip", "pose_prior.hip", "k2nn_unique.hip", "map_extend.hip", "map_cull.hip"]
+HEADERS = ["clc_internal.h", "clc_ctx.h", "clc_buf.h", "clc_carve.h", "clc_layout.h", "acr_kind.h", "desc_cache.h", "inter_geometry.h", "clc_sincos.h", "clc_acr.h", "p3p.h", "so3.h", "inter_math.h", "map_math.h", "ba_math.h", "k2nn_top2.h", "k2nn_sweep.h", "pose_lm.h", "guided_math.h", "sim3_math.h", "proj_math.h", "bin_math.h", "unique_math.h", "extend_math.h", "cull_math.h", "k2nn_proj.h", "wg_compact.h", "fivept.h", "fivept_wave.h", "twoview_min.h", "ud_pixel.h", "latch_pattern.inc", "latch_layout.inc", "latch_layout_swap.inc", os.path.join("..", "host", "HIPCovIntersection.hpp"), os.path.join("..", "host", "HIPRobustMatcher.hpp"), os.path.join("..", "host", "coloc_hip_geometry.hpp"), os.path.join("..", "..", "include", "coloc_hip.h")]
 # -ffp-contract=off: the fp32 sample-coordinate / bilinear expressions and the fp64 residuals must
 # evaluate in source order without fused multiply-add.
 # -amdgpu-mfma-vgpr-form: MFMA accumulators in plain VGPRs (gfx950's register file is unified), so the K2NN top-2 reads

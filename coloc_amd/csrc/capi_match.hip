@@ -618,6 +618,7 @@ int clc_set_map(clc_ctx* ctx, const void* h_desc, int n)
     if (n > 0) CLC_HIP(ctx, hipMemcpyAsync(ctx->d_m.ptr, h_desc, (size_t)n * CLC_DESC_BYTES, hipMemcpyHostToDevice, ctx->stream));
     CLC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->map_n = n;
+    map_rows_replaced(ctx);
     return CLC_OK;
 }
 

@@ -98,6 +98,16 @@ struct clc_ctx {
     clc::DevBuf d_unique;            // the one-to-one filter's claim words, and a composed entry's distances / inverse list (UniqueDev)
     clc::DevBuf d_extend;            // the map extension's running row count and per-job lists, flags and points (ExtendDev / ExtendJobDev)
     clc::PinBuf h_extend;            // its records and mirrors (ExtendJobPin)
+    // the map rows' observation statistics and the cull (map_cull.hip): visible | found | last_view of every row (CullStat, room for
+    // MatcherOptions.maxkp rows, allocated on first use) in d_stat; d_stat_next changes places with it when a cull installs, as d_m_next and
+    // d_map_X_next do.  stat_rows: the rows the counters cover (whatever replaces the map's rows: 0, map_rows_replaced below); epoch: the
+    // observe calls since then; obs_serial: the observe calls of the context's life, the stamp of a hit (never 0, never reset)
+    clc::DevBuf d_stat, d_stat_next;
+    clc::DevBuf d_obs;               // a call's hit stamps, one word per (view, row) (ObserveDev)
+    clc::DevBuf d_cull;              // the cull's remap and record (CullDev)
+    clc::PinBuf h_cull;              // its polled word, counts and remap mirror (CullPin)
+    int stat_rows = 0;
+    uint32_t epoch = 0, obs_serial = 0;
     int formulation = clc::K2NN_MATRIX;   // K2NN sweep formulation (k2nn.hip): FP4 matrix pipe, or round 1's popcount kernel for A/B runs
     int target_blocks = 0;           // K2NN sweep workgroups aimed at per launch; 0 = the formulation's default
     int bias_a = 326, bias_b = 249;  // matrix sweep, one-round single-job plans: train share of a workgroup on wave slot 0 / 1 in 1/256 of the
@@ -169,6 +179,10 @@ inline bool pose_K_ok(const double* K) { return K[3] == 0.0 && K[6] == 0.0 && K[
     } while (0)
 
 inline hipStream_t pick(clc_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+
+// the map's rows were replaced (clc_set_map, an install of map_build.hip / map_update.hip, an empty map): row identities are new, so the
+// observation statistics cover nothing and the epochs start again (map_cull.hip)
+inline void map_rows_replaced(clc_ctx* ctx) { ctx->stat_rows = 0; ctx->epoch = 0; }
 
 // THE way a context's workspace grows: a buffer that holds `need` bytes stays; any other is freed and allocated anew with
 // need + need * num / den bytes -- behind a synchronisation of the context's stream where work in flight may still use the old block

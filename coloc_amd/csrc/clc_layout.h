@@ -464,6 +464,32 @@ struct ExtendJobPin {
     }
 };
 
+// ---- the map rows' observation statistics and the cull (map_cull.hip) -------------------------------------------------------------------
+// d_stat / d_stat_next: [ visible | found | last_view ], up64(cap) words each (cap = MatcherOptions.maxkp), every array on 256 bytes
+struct CullStat {
+    uint32_t *visible, *found, *last_view;
+    void carve(Carve& c, size_t cap)
+    {
+        const size_t n = up64(cap);
+        visible = c.take<uint32_t>(n, 256); found = c.take<uint32_t>(n, 256); last_view = c.take<uint32_t>(n, 256);
+    }
+};
+// d_obs: the hit stamps of an observe call, [view][up64(cap)] words: a hit of the call with serial s stores s
+struct ObserveDev {
+    uint32_t* hit; size_t stride;
+    void carve(Carve& c, size_t cap, size_t views) { stride = up64(cap); hit = c.take<uint32_t>(stride * views, 256); }
+};
+// d_cull: [ the record 64 B { n_kept, flagged, ratio, idle } | remap up64(rows) ]; h_cull: [ the record 64 B (its first 8 bytes the polled
+// word, 0xFF.. = not out yet; then the three clause counts) | remap up64(rows) ]
+struct CullDev {
+    uint32_t* rec; int32_t* remap;
+    void carve(Carve& c, size_t rows) { rec = c.take<uint32_t>(16, 64); remap = c.take<int32_t>(up64(rows), 64); }
+};
+struct CullPin {
+    void* rec; int32_t* remap;
+    void carve(Carve& c, size_t rows) { rec = c.take_bytes(64, 64); remap = c.take<int32_t>(up64(rows), 64); }
+};
+
 // ---- the host-pointer K2NN entries' pinned mirror h_res (capi_match.hip): [ match nq | best nq | second nq | 64 B ] --------------------
 struct MatchPin {
     int32_t* match; uint16_t *best, *second;

@@ -342,6 +342,7 @@ int map_install(clc_ctx* ctx, clc_map_job& job, const MapStaged& staged)
     const int cam_i = staged.cam_i;
     const int32_t* d_row = staged.d_row;
     hipStream_t st = ctx->stream;
+    map_rows_replaced(ctx);
     if (n == 0) { ctx->map_n = 0; ctx->map_X_n = -1; return CLC_OK; }
     // install: the points change places with the previous map's (whatever read those was enqueued on this stream before), the
     // descriptor rows are gathered from the lower seed camera's block straight into the matcher's map.  The map is published only

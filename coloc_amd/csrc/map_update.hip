@@ -194,7 +194,7 @@ int step_state(clc_ctx* ctx, const StepView& v, bool* empty)
     if (*empty) {
         // nothing to match, nothing to scale: the empty map, as clc_map_build_dev installs it
         if (v.match) for (int q = 0; q < n_old; ++q) v.match[q] = -1;
-        if (v.install) { ctx->map_n = 0; ctx->map_X_n = -1; }
+        if (v.install) { ctx->map_n = 0; ctx->map_X_n = -1; map_rows_replaced(ctx); }
     }
     return CLC_OK;
 }
@@ -246,6 +246,7 @@ void step_finish(clc_ctx* ctx, const StepView& v, const int32_t* h_match, const 
         std::swap(ctx->d_m, ctx->d_m_next);
         std::swap(ctx->d_map_X, ctx->d_map_X_next);
         ctx->map_n = v.n_new; ctx->map_X_n = v.n_new;
+        map_rows_replaced(ctx);
     }
 }
 

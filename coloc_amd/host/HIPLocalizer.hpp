@@ -132,6 +132,19 @@ public:
         return rc == CLC_OK ? EXIT_SUCCESS : EXIT_FAILURE;
     }
 
+    // The points on the device compacted by the remap HIPMatcher::cullMapDev returned (clc_cull_map_points), so the tracks of the culled
+    // map find their landmarks without the whole map going up again: call it after cullMapDev, which has compacted colocData already --
+    // the remap must keep exactly mapRegionIdx.size() rows.  false = success.
+    bool cullMapPoints(colocData& data, const std::vector<int32_t>& remap)
+    {
+        size_t kept = 0;
+        for (const int32_t m : remap) kept += m >= 0 ? 1 : 0;
+        if (kept != data.mapRegionIdx.size()) return EXIT_FAILURE;
+        const int rc = ctx_ ? clc_cull_map_points(ctx_, remap.data(), static_cast<int>(remap.size())) : CLC_ERR_STATE;
+        if (rc != CLC_OK) std::cerr << "HIPLocalizer: clc_cull_map_points: " << clc_status_string(rc) << std::endl;
+        return rc == CLC_OK ? EXIT_SUCCESS : EXIT_FAILURE;
+    }
+
     // localizeImage from tracks built ON THE DEVICE (clc_track_localize_dev): d_match is what clc_match_map_dev left on the GPU for this
     // frame (nq planned rows, d_count the detector's count pair or NULL), the 2-D side the detector's d_kps or a device block of feature
     // positions (d_feat, feat_stride floats per row); after_stream = the stream that produced them (NULL: the localizer's own, or done).
@@ -336,6 +349,9 @@ public:
     {
         return localize_with(ctx_, seed++, cam, matching_data, pose, nullptr, nullptr, nullptr);
     }
+
+    // the context behind this localizer, for the entries of the C ABI that have no member here (clc_track_build_dev)
+    clc_ctx* context() const { return ctx_; }
 
     // the solve itself, on any context (shared with HIP_SfM_Localizer::Localize).  covariance != nullptr: the refinement (Huber(4^2) LM on
     // the inliers + 6 x 6 covariance, refine() below) rides in the same submission; *refined says whether it ran, *rmse is the mean

@@ -271,6 +271,68 @@ public:
         return false;
     }
 
+    // A tracked frame folded into the map rows' observation statistics (clc_map_observe_dev, which states the rule; no counterpart in the
+    // reference): which landmarks the frame's pose should see inside the width x height image less `margin`, and which of them the
+    // frame's map match d_track (matchSceneWithMapBinnedUniqueDev's d_match_out) found within `gate` pixels of their projection.  Enqueue
+    // only, on the context's stream behind `after_stream`: NO host wait -- call it behind every tracked frame.  false = enqueued.
+    bool observeMapDev(const openMVG::geometry::Pose3& pose, const clc_camera_k3& intrinsics, int nq, const clc_keypoint* d_kps, const float* d_feat,
+                       int feat_stride, const uint32_t* d_count, const int32_t* d_track, int width, int height, float gate, float margin,
+                       void* after_stream)
+    {
+        clc_map_observe jb{};
+        jb.view.n = nq; jb.view.d_count = d_count; jb.view.d_kps = d_kps; jb.view.d_feat = d_feat; jb.view.feat_stride = feat_stride;
+        jb.view.cam = intrinsics; jb.view.d_track = d_track;
+        const openMVG::Vec3 t = pose.translation();                              // t = -R C
+        for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) jb.view.Rt[4 * i + j] = pose.rotation()(i, j); jb.view.Rt[4 * i + 3] = t[i]; }
+        jb.width = width; jb.height = height; jb.gate = gate; jb.margin = margin; jb.after_stream = after_stream;
+        return !check(clc_map_observe_dev(ctx_, &jb), "observeMapDev");
+    }
+
+    // The map culled in place (clc_map_cull_dev, which states the rule; no counterpart in the reference): rows dropped by their
+    // observation statistics under `rule` -- and by the caller's own d_flagged bytes, nullable --, the map of this matcher's context
+    // compacted in order, the device lists that name map rows (the frames' d_track lists) remapped in place.  On success colocData holds
+    // what setupMapDatabase (colocData.hpp:89-121) would hold for the SURVIVING landmarks: the rows of mapRegions and mapRegionIdx compacted
+    // in order, the dropped landmarks erased from the scene -- the mirror of what extendMapPairDev does for new ones.  removed (nullable):
+    // the rows dropped; remap (nullable): old row -> new row or -1, for HIPLocalizer::cullMapPoints and whatever else names rows.
+    // The default rule is the customary one (a quarter of the frames that should see a point) and is UNTUNED.  false = success.
+    struct CullRule { int min_visible = 8, num = 1, den = 4; uint32_t max_idle = 0; const uint8_t* d_flagged = nullptr; };
+    struct CullListDev { int32_t* d_track; int n; };
+    bool cullMapDev(colocData& data, const CullRule& rule, const std::vector<CullListDev>& lists, void* after_stream, int* removed = nullptr,
+                    std::vector<int32_t>* remap = nullptr)
+    {
+        if (removed) *removed = 0;
+        if (remap) remap->clear();
+        const size_t rows = data.mapRegionIdx.size();
+        if (rows != kpMap_ || lists.size() > CLC_MAX_BATCH || (rows > 0 && (!data.mapRegions || data.mapRegions->RegionCount() != rows))) {
+            std::cerr << "HIPMatcher::cullMapDev: colocData's map database is not the context's map, or more than CLC_MAX_BATCH lists" << std::endl;
+            return true;
+        }
+        clc_map_cull jb{};
+        jb.min_visible = rule.min_visible; jb.num = rule.num; jb.den = rule.den; jb.max_idle = rule.max_idle; jb.d_flagged = rule.d_flagged;
+        jb.n_lists = static_cast<int>(lists.size());
+        for (size_t l = 0; l < lists.size(); ++l) { jb.d_track[l] = lists[l].d_track; jb.track_n[l] = lists[l].n; }
+        jb.after_stream = after_stream;
+        std::vector<int32_t> map(rows);
+        jb.h_remap = map.data();
+        if (!check(clc_map_cull_dev(ctx_, &jb), "cullMapDev")) return true;
+        size_t k = 0;
+        for (size_t r = 0; r < rows; ++r) {
+            if (map[r] < 0) { data.scene.structure.erase(data.mapRegionIdx[r]); continue; }
+            if (k != r) {
+                data.mapRegions->Features()[k] = data.mapRegions->Features()[r];
+                data.mapRegions->Descriptors()[k] = data.mapRegions->Descriptors()[r];
+                data.mapRegionIdx[k] = data.mapRegionIdx[r];
+            }
+            ++k;
+        }
+        if (data.mapRegions) { data.mapRegions->Features().resize(k); data.mapRegions->Descriptors().resize(k); }
+        data.mapRegionIdx.resize(k);
+        kpMap_ = static_cast<unsigned int>(jb.n_kept);
+        if (removed) *removed = jb.n_dropped;
+        if (remap) *remap = map;
+        return false;
+    }
+
     // computeMatchesPair with the one-to-one filter behind the sweep (clc_match_2nn_unique): the same IndMatch(i_ = query idx in
     // regions[first], j_ = train idx in regions[second]) list, thr 40, in which no train index appears twice -- of the queries that named
     // one train row the nearest keeps it, the lowest query index among equals.
@@ -328,6 +390,8 @@ public:
     openMVG::matching::IndMatches matchFeaturesWithMap() { return matchWithMap(queryData(), static_cast<int>(kpQuery_)); }
 
     const char* lastError() const { return ctx_ ? clc_last_error_string(ctx_) : "no context"; }
+    // the context behind this matcher, for the entries of the C ABI that have no member here (clc_map_stats_get, clc_track_build_dev)
+    clc_ctx* context() const { return ctx_; }
 
 private:
     const void* queryData() const { return queryRef_ ? queryRef_ : static_cast<const void*>(query_.data()); }

@@ -1729,6 +1729,117 @@ int clc_map_extend_batch_dev(clc_ctx* ctx, clc_map_extend* jobs, int n_jobs);   
 int clc_fundamental_from_poses(const clc_camera_k3* cam_a, const double* Rt_a, const clc_camera_k3* cam_b, const double* Rt_b, double* F);
 int clc_append_map_points(clc_ctx* ctx, const double* h_X, int n);
 
+/* ---- the map culled in place: observation statistics per row, drop, compact, remap ----------------------------------------------------
+ * clc_map_extend_dev only ever adds rows; once the map holds MatcherOptions.maxkp of them it counts what it could not add.  A rebuild
+ * (clc_map_update_*) forgets old rows, at the price of new identities and a new scale.  The other half of map maintenance is here: the
+ * context keeps, per map row, how often the row's landmark projected into a frame (visible), how often the frame's map match then found
+ * it (found) and when it was last in view (last_view), as a by-product of the frame's own match; clc_map_cull_dev drops rows by those
+ * counters, compacts rows, points and counters in order and returns the remap, under which every list that names map rows stays valid.
+ * The reference has no such step: like the guided, binned, unique, prior and extend entries this is THIS library's statement, parity
+ * with nothing is pinned, and no existing entry changes.  (Later under ABI 4: new entry points only.)
+ *
+ * THE RULE (coloc_amd/csrc/cull_math.h, host and device, over proj_math.h and get_ud_pixel as they stand).
+ *   STATE    three uint32 per map row -- visible, found, last_view -- on the device; epoch (uint32) and stat_rows (the rows the counters
+ *            cover) on the host side of the context.
+ *   RESET    whatever REPLACES the map's rows (clc_set_map, the installs of clc_map_build_* / clc_map_init_* / clc_map_update_* /
+ *            clc_map_align_*, an empty map installed) sets stat_rows = 0 and epoch = 0: row identities are new.
+ *   COVER    every observe, cull or clc_map_stats_get call begins by giving rows [stat_rows, map_n) -- the rows clc_map_extend_dev
+ *            appended -- visible = found = 0 and last_view = epoch (as it stands before the call increments it); then stat_rows = map_n.
+ *   IN VIEW  lo = margin, hi_x = (float)(width - 1) - margin, hi_y = (float)(height - 1) - margin, formed once on the host;
+ *            cull_in_view(u, v) = u >= lo && u <= hi_x && v >= lo && v <= hi_y in float.  NaN is false: a landmark without a projection
+ *            is never in view.  The rectangle is tested in UNDISTORTED pixels, a stated deviation (the one the projection gate of
+ *            clc_match_map_guided_dev makes).
+ *   OBSERVE  one view: p(r) = proj_point(Rt, { focal, ppx, ppy }, X[r]).  in_view(r) = cull_in_view(p(r)).  hit(r) iff some keypoint
+ *            q < n (clipped by d_count[0] where given) has d_track[q] == r and proj_in_radius(xq, yq, p(r), gate * gate), (xq, yq) the
+ *            keypoint through get_ud_pixel in fp64 rounded once to float: the bits the prep launch of clc_match_map_guided_dev
+ *            produces.  An entry of d_track outside [0, map_n) names no row.  visible[r] += in_view(r); found[r] += in_view(r) &&
+ *            hit(r), so found <= visible always; last_view[r] = epoch where in_view(r).  ONE call is ONE epoch, whether it carries one
+ *            view or a batch: epoch is incremented once BEFORE stamping, and a row counts once per view of the batch that sees it.
+ *   DROP     cull_drops = flagged || (visible >= min_visible && (uint64)found * den < (uint64)num * visible)
+ *                                 || (max_idle > 0 && (uint32)(epoch - last_view) > max_idle).
+ *            Rows younger than min_visible are safe from the ratio test; max_idle == 0 switches the idle test off; d_flagged (nullable,
+ *            one byte per row, device) is the caller's own list -- say, landmarks with a large residual after clc_ba_dev.  The customary
+ *            rule is min_visible 8, num / den 1 / 4, max_idle 0 (clc_map_cull_rule_default): a quarter of the frames that should see a
+ *            point.  These values are UNTUNED.
+ *   REMAP    remap[r] = the number of kept rows below r where row r is kept, -1 otherwise: kept rows stay in ASCENDING old order.  New
+ *            row remap[r] takes old row r's point (3 doubles), descriptor (64 bytes) and three counters, bit for bit.  A track-list
+ *            entry e becomes remap[e] if 0 <= e < map_n_before, -1 otherwise.
+ *
+ * clc_map_observe_dev / clc_map_observe_batch_dev (n_views in [0, CLC_MAX_BATCH], one job per view) enqueue on the CONTEXT's stream
+ * behind each job's after_stream (one event, as clc_map_job) and return: there is NO host wait, this runs every frame for every camera.
+ * Two launches whatever the batch: one thread per (keypoint, view) for the hits -- it reads d_track[q] and recomputes that row's
+ * proj_point, the same function, hence the same bits -- and one thread per (map row, view) for in_view and the counters, which are
+ * 32-bit integer adds and commute.  d_counts (nullable, device, 2 int32 per view): { n_in_view, n_hit } of the view.  On return
+ * job.epoch is the call's epoch and job.map_n the rows it covered.
+ * clc_map_cull_dev is a chain on the context's stream in which nothing waits for another workgroup: ONE workgroup of 1 024 runs
+ * cull_drops and the ordered compaction and writes the remap; a wide gather moves rows, points and counters into the context's OTHER
+ * buffers (never in place); a launch remaps up to CLC_MAX_BATCH track lists in place; { n_kept, n_dropped } comes out in ONE pinned word
+ * last.  The host waits for that word once, then installs by buffer swaps, exactly as clc_map_update_batch_dev installs.  OUTPUTS: d_remap
+ * (nullable, device, room for map_n_before), h_remap (nullable, host, the same), map_n_before, n_kept, n_dropped, and of the dropped rows
+ * how many fell to each clause (n_flagged, n_ratio, n_idle: the first clause that fires in the order written), status.
+ * A cull rewrites the row numbering: the per-track state of the last grown build ends (clc_map_resect_build_dev answers
+ * CLC_ERR_STATE), and whatever the CALLER holds by row index -- d_owner lists, the cell lists of clc_map_bin_build_dev, host-side
+ * databases -- must follow the remap or be rebuilt.  The context itself caches nothing else across calls: the binned table and the
+ * projections are rebuilt by every match call.
+ * DEGENERATE cases, each by the rules and CLC_OK: a map of 0 rows (n_kept = 0); nothing dropped (the identity remap); everything dropped
+ * (the map has 0 rows and its points are cleared: the extendable empty map of clc_map_extend_dev).
+ * ORDERING: on return of clc_map_cull_dev the map serves every entry with n_kept rows.  Work on other streams that reads the map while
+ * the call runs is the caller's to order.
+ * ERRORS, all before anything is enqueued, the map and the statistics as they were: a null context or job, den <= 0, num < 0,
+ * min_visible < 1, a gate or margin that is negative or not finite (or whose square is not), a non-positive width / height / focal,
+ * both or neither position form, a non-finite Rt, a misaligned pointer, more lists or views than CLC_MAX_BATCH, a negative n:
+ * CLC_ERR_BAD_ARG; a context without matcher options, without a map, or whose points are not exactly its rows (the state
+ * clc_track_localize_dev refuses): CLC_ERR_STATE.
+ *
+ * clc_map_stats_get: the counters out for tests and tools (pointers nullable; room for map_n words each); covers new rows first and
+ * synchronises the context's stream.  A context without a map: rows = 0.
+ * clc_cull_map_points: the companion of clc_append_map_points for a context that holds ONLY points (the localizer's): the points
+ * compacted by a host remap of n == its points.  The kept entries must read 0, 1, 2, ... in ascending order, else CLC_ERR_BAD_ARG; a
+ * context that holds rows is culled by clc_map_cull_dev alone (CLC_ERR_STATE), so rows and points cannot part ways.  Synchronises. */
+typedef struct clc_observe_view {
+    int                 n;              /* planned keypoints */
+    const uint32_t*     d_count;        /* nullable, as clc_track_job */
+    const clc_keypoint* d_kps;          /* or */
+    const float*        d_feat;
+    int                 feat_stride;
+    clc_camera_k3       cam;
+    double              Rt[12];         /* host: the frame's pose */
+    const int32_t*      d_track;        /* nullable, n, device: the frame's map match (map row or -1); null: nothing is found */
+    int32_t*            d_counts;       /* nullable, device, 2: { n_in_view, n_hit } */
+} clc_observe_view;
+typedef struct clc_map_observe {
+    /* in */
+    clc_observe_view view;
+    int              width, height;     /* the image */
+    float            gate;              /* pixels: a hit lies within it of the landmark's projection */
+    float            margin;            /* pixels */
+    void*            after_stream;      /* nullable */
+    /* out */
+    uint32_t         epoch;
+    int              map_n, status;
+} clc_map_observe;
+typedef struct clc_map_cull {
+    /* in */
+    int              min_visible, num, den;
+    uint32_t         max_idle;
+    const uint8_t*   d_flagged;         /* nullable, device, one byte per map row */
+    int32_t*         d_track[CLC_MAX_BATCH];   /* lists that name map rows, device, rewritten in place */
+    int              track_n[CLC_MAX_BATCH];
+    int              n_lists;
+    void*            after_stream;      /* nullable */
+    /* out, nullable: room for map_n_before */
+    int32_t*         d_remap;
+    int32_t*         h_remap;
+    /* out */
+    int              map_n_before, n_kept, n_dropped, n_flagged, n_ratio, n_idle, status;
+} clc_map_cull;
+int clc_map_observe_dev(clc_ctx* ctx, clc_map_observe* job);
+int clc_map_observe_batch_dev(clc_ctx* ctx, clc_map_observe* jobs, int n_views);   /* n_views in [0, CLC_MAX_BATCH]: ONE epoch */
+int clc_map_cull_dev(clc_ctx* ctx, clc_map_cull* job);
+int clc_map_cull_rule_default(clc_map_cull* job);                                   /* min_visible 8, num / den 1 / 4, max_idle 0 */
+int clc_map_stats_get(clc_ctx* ctx, uint32_t* h_visible, uint32_t* h_found, uint32_t* h_last_view, uint32_t* epoch, int* rows);
+int clc_cull_map_points(clc_ctx* ctx, const int32_t* h_remap, int n);
+
 /* ---- fusion (host arithmetic; no GPU work) ---------------------------------------------------------
  * Covariance intersection of two 3-D position estimates as CoLoC fuses intra- and inter-camera poses
  * (include/coloc/CovIntersection.hpp:24-49, called at include/coloc/coloc.hpp:362-389): omega in [0,1]
