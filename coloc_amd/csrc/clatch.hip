@@ -24,9 +24,11 @@
 //   * lane = triplet (8 rounds x 64 lanes): no cross-lane reduction.  With four pixels per dword,
 //     S = sum(A*A) - sum(C*C) - 2*(sum(A*B) - sum(C*B)) is four v_dot4_u32_u8 per dword triple,
 //     i.e. ONE VALU op per pixel-test.
-//   * WHICH triplet a (round, lane) slot evaluates is chosen offline (tools/opt_latch_layout.py) so
+//   * WHICH triplet a (round, lane) slot evaluates is chosen offline (tools/opt_latch_layout.py, then tools/latch_anneal.c) so
 //     that the 32 lanes of a half-wave hit distinct LDS banks as far as the learned pattern allows
-//     (average conflict degree 3.4 -> 1.7); one ds_bpermute per output round puts the sign bits
+//     (average conflict degree 3.4 -> 1.7) -- or the SAME ADDRESS: the LDS serves lanes that read one address with one access, and
+//     the 1 536 patches of the 512 triplets sit at only 1 113 positions, so triplets that share a patch are seated in one half-wave
+//     of one round (average degree 1.23, k_slot_triplet below); one ds_bpermute per output round puts the sign bits
 //     back into descriptor order before the wave ballot that forms two output words.
 //
 // Bound: LDS reads (48 dwords per test) and the window gather; compulsory HBM is 20 B in + 64 B
@@ -54,6 +56,13 @@ static constexpr PatchRow k_pattern[512] = {
 // (round, lane) -> learned triplet.  Round 4: the assignment searched WITH role exchange (tools/latch_anneal.c mode 0, swap 1) -- a slot may
 // read its triplet's a and c patches the other way round, which gives the bank assignment more freedom: conflict degree sum 81 -> 77.
 // Such a slot computes -S; its bit is taken as S' > 0.  -DCLC_CLATCH_NO_SWAP: round 3's assignment (A/B runs).
+// What the assignment optimises now is the MERGED-read model (tools/latch_anneal.c --merged): the degree of a half-wave read of one patch
+// kind is the largest number of DISTINCT LDS addresses on one bank, because lanes of a half-wave that read the same address are served by
+// one access (measured: profiles/clatch_shared_patches.txt, SQ_LDS_BANK_CONFLICT follows the merged sum, not the lane count).  423 of the
+// 1 536 patch uses repeat a position another triplet uses; the search seats such triplets in the same (round, half-wave) with the shared
+// patch in the same role -- a-or-c after the exchange flag, or anchor -- where they cost one read: LATCH_COLOCATIONS of them, merged sum
+// LATCH_DEGREE_MERGED = 59 (the table searched under the lane-count model: 71; lower bound 48).  Counted by lanes the same table is worse
+// (LATCH_DEGREE_PLAIN), so it pays only because the reads merge.  tests/test_latch_layout_merged.py recomputes all three figures.
 #ifdef CLC_CLATCH_NO_SWAP
 static constexpr uint16_t k_slot_triplet[512] = LATCH_SLOT_TRIPLET;
 #else
