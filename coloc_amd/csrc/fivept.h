@@ -5,7 +5,11 @@
 // which asks OpenMVG for essential::kernel::FivePointSolver inside AC-RANSAC.  OpenMVG is an empty, unpinned submodule in
 // the reference snapshot, so this follows the published method (Nister 2004 / Stewenius et al. 2006), derived from scratch
 // and built by polynomial arithmetic rather than by a transcribed coefficient table:
-//   1. the 5 epipolar constraints q2^T E q1 = 0 leave a 4-D null space {E1..E4}: E = x E1 + y E2 + z E3 + E4;
+//   1. the 5 epipolar constraints q2^T E q1 = 0 leave a 4-D null space {E1..E4}: E = x E1 + y E2 + z E3 + E4.  The basis is
+//      ORTHONORMAL and tied to no column: Gauss-Jordan with complete pivoting, modified Gram-Schmidt, then the 4 x 4 Hadamard
+//      rotation.  A solution with no E4 component lies at infinity in (x, y, z) and makes step 3's pivot block singular, which
+//      costs every solution of the sample, not that one; with the elimination's own basis (a unit entry per free column, E4
+//      the last) that is what motion along the optical axis does -- the third row of its E is zero;
 //   2. det(E) = 0 and 2 E E^T E - trace(E E^T) E = 0 are 10 cubic polynomials in (x, y, z) over 20 monomials,
 //      ordered [x3 x2y x2z xy2 xyz xz2 y3 y2z yz2 z3 | x2 xy xz y2 yz z2 x y z 1];
 //   3. Gauss-Jordan on the 10 cubic monomials gives [I | B]; with basis b = [x2 xy xz y2 yz z2 x y z 1]^T the
@@ -119,12 +123,34 @@ __device__ __forceinline__ double fpt_rcp_rough(const double x) { return __built
 FPT_HD double fpt_rcp(const double x) { return 1.0 / x; }
 FPT_HD double fpt_rcp_rough(const double x) { return 1.0 / x; }
 #endif
+// Switches of the HOST build, for the study in DESIGN.md section 11 (tools/fivept_attribution.py study); the defaults are the
+// solver, and csrc/fivept_wave.h states the defaults only.  FPT_NULL_COMPLETE 0: the null space pivots by row on the columns in
+// order; FPT_ORTHO_BASIS 0: the basis stays as the elimination leaves it (a unit entry per free column); FPT_BASIS_MIX 0: no
+// Hadamard rotation; FPT_E_STEPS n: n Gauss-Newton steps on the constraints evaluated from E itself after the polish.
+#ifndef FPT_NULL_COMPLETE
+#define FPT_NULL_COMPLETE 1
+#endif
+#ifndef FPT_ORTHO_BASIS
+#define FPT_ORTHO_BASIS 1
+#endif
+#ifndef FPT_BASIS_MIX
+#define FPT_BASIS_MIX 1
+#endif
+#ifndef FPT_E_STEPS
+#define FPT_E_STEPS 0
+#endif
+constexpr int kFptEssentialSteps = FPT_E_STEPS;
 // phase time stamps for tools/archive/fivept_bench.hip (no-op in the library)
 #ifndef FPT_STAMP
 #define FPT_STAMP(i) ((void)0)
 #endif
 #ifndef FPT_SWEEP_HOOK
 #define FPT_SWEEP_HOOK(it) ((void)0)
+#endif
+// a root's (x, y, z) as it leaves a stage (0: the start, 1: the polish on the monomial rows, 2: the polish on E), for
+// tests/host/fivept_host_lib.cpp (no-op in the library)
+#ifndef FPT_ROOT_HOOK
+#define FPT_ROOT_HOOK(k, stage, x, y, z) ((void)0)
 #endif
 
 
@@ -572,6 +598,63 @@ FPT_HD int fpt_polish_update(const double (&s)[9], double* x, double* y, double*
     return fabs(dx) + fabs(dy) + fabs(dz) < 1e-15 * (1.0 + fabs(*x) + fabs(*y) + fabs(*z)) ? 1 : 0;
 }
 
+// (Study only, FPT_E_STEPS: measured, the rules do not need it.)  One Gauss-Newton step on the constraints evaluated from
+// E = x E1 + y E2 + z E3 + E4 ITSELF: r = (2 G E - tr(G) E, det E) with
+// G = E E^T, ten values, and their derivatives along E1, E2, E3: 2 (dG E + G D) - tr(dG) E - tr(G) D with dG = D E^T + E D^T, and
+// cof(E) . D.  Nothing here went through the monomial coefficients, whose rounding is relative to a row's largest term: the
+// residual's rounding is that of |E|^3, so the step's fixed point is a zero of the constraints to working precision.  Same
+// return value as fpt_polish_update.
+FPT_HD int fpt_essential_step(const double (&EE)[4][9], double* x, double* y, double* z)
+{
+    double E[9], G[9];
+FPT_UNROLL
+    for (int c = 0; c < 9; ++c) E[c] = *x * EE[0][c] + *y * EE[1][c] + *z * EE[2][c] + EE[3][c];
+FPT_UNROLL
+    for (int a = 0; a < 3; ++a)
+FPT_UNROLL
+        for (int b = 0; b < 3; ++b) G[3 * a + b] = E[3 * a] * E[3 * b] + E[3 * a + 1] * E[3 * b + 1] + E[3 * a + 2] * E[3 * b + 2];
+    const double tr = G[0] + G[4] + G[8];
+    const double cof[9] = { E[4] * E[8] - E[5] * E[7], E[5] * E[6] - E[3] * E[8], E[3] * E[7] - E[4] * E[6],
+                            E[2] * E[7] - E[1] * E[8], E[0] * E[8] - E[2] * E[6], E[1] * E[6] - E[0] * E[7],
+                            E[1] * E[5] - E[2] * E[4], E[2] * E[3] - E[0] * E[5], E[0] * E[4] - E[1] * E[3] };
+    double r[10], J[3][10];
+FPT_UNROLL
+    for (int a = 0; a < 3; ++a)
+FPT_UNROLL
+        for (int b = 0; b < 3; ++b) r[3 * a + b] = 2.0 * (G[3 * a] * E[b] + G[3 * a + 1] * E[3 + b] + G[3 * a + 2] * E[6 + b]) - tr * E[3 * a + b];
+    r[9] = E[0] * cof[0] + E[1] * cof[1] + E[2] * cof[2];
+FPT_UNROLL
+    for (int p = 0; p < 3; ++p) {
+        const double* D = EE[p];
+        double dG[9];
+FPT_UNROLL
+        for (int a = 0; a < 3; ++a)
+FPT_UNROLL
+            for (int b = 0; b < 3; ++b)
+                dG[3 * a + b] = (D[3 * a] * E[3 * b] + D[3 * a + 1] * E[3 * b + 1] + D[3 * a + 2] * E[3 * b + 2])
+                              + (E[3 * a] * D[3 * b] + E[3 * a + 1] * D[3 * b + 1] + E[3 * a + 2] * D[3 * b + 2]);
+        const double dtr = dG[0] + dG[4] + dG[8];
+        double dd = 0.0;
+FPT_UNROLL
+        for (int a = 0; a < 3; ++a)
+FPT_UNROLL
+            for (int b = 0; b < 3; ++b) {
+                const int i = 3 * a + b;
+                J[p][i] = 2.0 * ((dG[3 * a] * E[b] + dG[3 * a + 1] * E[3 + b] + dG[3 * a + 2] * E[6 + b])
+                               + (G[3 * a] * D[b] + G[3 * a + 1] * D[3 + b] + G[3 * a + 2] * D[6 + b])) - dtr * E[i] - tr * D[i];
+                dd += cof[i] * D[i];
+            }
+        J[p][9] = dd;
+    }
+    double s[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+FPT_UNROLL
+    for (int i = 0; i < 10; ++i) {
+        s[0] += J[0][i] * J[0][i]; s[1] += J[0][i] * J[1][i]; s[2] += J[0][i] * J[2][i]; s[3] += J[1][i] * J[1][i]; s[4] += J[1][i] * J[2][i];
+        s[5] += J[2][i] * J[2][i]; s[6] += J[0][i] * r[i]; s[7] += J[1][i] * r[i]; s[8] += J[2][i] * r[i];
+    }
+    return fpt_polish_update(s, x, y, z);
+}
+
 // (x, y, z) -> candidate essential matrix w.root[k].cand; valid only if it satisfies the cubic constraints: an eigenvalue
 // that was not a true real root yields a matrix that is not essential
 FPT_HD void fpt_root_finish(FptWorkspace& w, const int k, const double x, const double y, const double z)
@@ -609,11 +692,22 @@ FPT_HD int fpt_compact(const FptWorkspace& w, double* E_out)
 }
 
 // ---- the sequential statement ---------------------------------------------------------------------------------------------
-// q1, q2: 5 x 2 normalised coordinates in view 1 / view 2 (q2^T E q1 = 0).  E_out: up to 10 x 9 (row-major 3x3).
 #if !defined(__HIP_DEVICE_COMPILE__)
+// The eigenvalue stage: the matrix in w.hr -> its ten eigenvalues in w.zr, w.zi.  false for a zero matrix.
+static inline bool fpt_eigenvalues10_seq(FptWorkspace& w)
+{
+    fpt_hessenberg10_seq(w);
+    fpt_balance10(w);
+    double anorm = 0.0;
+    for (int r = 0; r < 10; ++r) for (int c = (r > 0 ? r - 1 : 0); c < 10; ++c) anorm += fabs(w.hr[r][c]);
+    if (!(anorm > 0.0)) return false;
+    fpt_aberth10(w, w.zr, w.zi, anorm);
+    return true;
+}
+// q1, q2: 5 x 2 normalised coordinates in view 1 / view 2 (q2^T E q1 = 0).  E_out: up to 10 x 9 (row-major 3x3).
 static inline int fivept_solve(const double q1[5][2], const double q2[5][2], double* E_out, FptWorkspace& w)
 {
-    // ---- 1. null space of the 5 x 9 constraint matrix by reduced row echelon form
+    // ---- 1. null space of the 5 x 9 constraint matrix: Gauss-Jordan with complete pivoting, then an orthonormal basis
     double A[5][9];
     for (int i = 0; i < 5; ++i) {
         const double a[3] = { q2[i][0], q2[i][1], 1.0 }, b[3] = { q1[i][0], q1[i][1], 1.0 };
@@ -621,12 +715,19 @@ static inline int fivept_solve(const double q1[5][2], const double q2[5][2], dou
     }
     int piv[5], is_piv[9];
     for (int i = 0; i < 9; ++i) is_piv[i] = 0;
-    int row = 0;
-    for (int col = 0; col < 9 && row < 5; ++col) {
-        int p = row;
-        double best = fabs(A[row][col]);
-        for (int r = row + 1; r < 5; ++r) if (fabs(A[r][col]) > best) { best = fabs(A[r][col]); p = r; }
-        if (best < 1e-12) continue;
+    for (int row = 0; row < 5; ++row) {
+        int p = row, col = -1;
+        double best = -1.0;
+#if FPT_NULL_COMPLETE
+        for (int c = 0; c < 9; ++c) {
+            if (is_piv[c]) continue;
+#else
+        for (int c = row > 0 ? piv[row - 1] + 1 : 0; c < 9 && best < 1e-12; ++c) {
+            best = -1.0;
+#endif
+            for (int r = row; r < 5; ++r) if (fabs(A[r][c]) > best) { best = fabs(A[r][c]); p = r; col = c; }
+        }
+        if (!(best >= 1e-12)) return 0;         // degenerate sample
         if (p != row) for (int k = 0; k < 9; ++k) { const double t = A[row][k]; A[row][k] = A[p][k]; A[p][k] = t; }
         const double inv = 1.0 / A[row][col];
         for (int k = 0; k < 9; ++k) A[row][k] *= inv;
@@ -637,9 +738,7 @@ static inline int fivept_solve(const double q1[5][2], const double q2[5][2], dou
         }
         piv[row] = col;
         is_piv[col] = 1;
-        ++row;
     }
-    if (row < 5) return 0;                      // degenerate sample
     double (&EE)[4][9] = w.EE;
     {
         int nb = 0;
@@ -651,6 +750,25 @@ static inline int fivept_solve(const double q1[5][2], const double q2[5][2], dou
             ++nb;
         }
     }
+#if FPT_ORTHO_BASIS
+    for (int i = 0; i < 4; ++i) {               // modified Gram-Schmidt
+        for (int j = 0; j < i; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 9; ++k) d += EE[i][k] * EE[j][k];
+            for (int k = 0; k < 9; ++k) EE[i][k] -= d * EE[j][k];
+        }
+        double n2 = 0.0;
+        for (int k = 0; k < 9; ++k) n2 += EE[i][k] * EE[i][k];
+        const double inv = 1.0 / sqrt(n2);
+        for (int k = 0; k < 9; ++k) EE[i][k] *= inv;
+    }
+#if FPT_BASIS_MIX
+    for (int k = 0; k < 9; ++k) {               // the 4 x 4 Hadamard rotation: still orthonormal, no vector tied to a column any more
+        const double a = EE[0][k], b = EE[1][k], c = EE[2][k], d = EE[3][k];
+        EE[0][k] = 0.5 * ((a - b) + (c - d)); EE[1][k] = 0.5 * ((a + b) - (c + d)); EE[2][k] = 0.5 * ((a - b) - (c - d)); EE[3][k] = 0.5 * ((a + b) + (c + d));
+    }
+#endif
+#endif
     // ---- 2. the ten cubic constraints.  e[k] = linear polynomial x EE0[k] + y EE1[k] + z EE2[k] + EE3[k]
     double e[9][20];
     for (int k = 0; k < 9; ++k) {
@@ -713,23 +831,22 @@ static inline int fivept_solve(const double q1[5][2], const double q2[5][2], dou
     Ax[10 * 6 + 0] = 1.0; Ax[10 * 7 + 1] = 1.0; Ax[10 * 8 + 2] = 1.0; Ax[10 * 9 + 6] = 1.0;
     // ---- 4. eigenvalues
     for (int i = 0; i < 100; ++i) w.hr[i / 10][i % 10] = Ax[i];
-    fpt_hessenberg10_seq(w);
-    fpt_balance10(w);
-    double anorm = 0.0;
-    for (int r = 0; r < 10; ++r) for (int c = (r > 0 ? r - 1 : 0); c < 10; ++c) anorm += fabs(w.hr[r][c]);
-    if (!(anorm > 0.0)) return 0;
-    fpt_aberth10(w, w.zr, w.zi, anorm);
+    if (!fpt_eigenvalues10_seq(w)) return 0;
     // ---- 5. real roots -> (y, z) -> polish on the constraints
     for (int k = 0; k < 10; ++k) {
         w.root[k].valid = 0;
         double x, y, z;
         if (!fpt_root_start(w, k, &x, &y, &z)) continue;
+        FPT_ROOT_HOOK(k, 0, x, y, z);
         for (int it = 0; it < 4; ++it) {
             double mono[20], s[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
             fpt_monomials(x, y, z, mono);
             for (int r = 0; r < 10; ++r) fpt_polish_row(M0[r], mono, s);
             if (fpt_polish_update(s, &x, &y, &z) != 0) break;
         }
+        FPT_ROOT_HOOK(k, 1, x, y, z);
+        for (int it = 0; it < kFptEssentialSteps; ++it) if (fpt_essential_step(w.EE, &x, &y, &z) != 0) break;
+        FPT_ROOT_HOOK(k, 2, x, y, z);
         fpt_root_finish(w, k, x, y, z);
     }
     return fpt_compact(w, E_out);

@@ -2,9 +2,10 @@
 //
 // Same algorithm, same arithmetic per element as the sequential statement in fivept.h (which stays the readable
 // reference and runs on the host in tests/); what changes is where the numbers live and who touches them:
-//   1. null space of the 5 x 9 constraint matrix      lane c = column c, the five rows in registers; the pivot column is
-//                                                      broadcast with v_readlane (lane index uniform), row swaps are
-//                                                      uniform branches -- no LDS, no barrier
+//   1. null space of the 5 x 9 constraint matrix      lane c = column c, the five rows in registers; complete pivoting (each
+//                                                      lane's column maximum, compared over v_readlane), the pivot column
+//                                                      broadcast with v_readlane (lane index uniform), row swaps are uniform
+//                                                      branches; Gram-Schmidt sums over v_readlane -- no LDS, no barrier
 //   2. the ten cubic constraints                       one polynomial per lane, accumulated in REGISTERS (target monomials
 //                                                      are compile-time constants) and stored once; the old form accumulated
 //                                                      in LDS, a read-modify-write chain per term
@@ -46,19 +47,26 @@ __device__ __forceinline__ bool null_space(const double q1[5][2], const double q
         const double v = c3 == 0 ? q1[i][0] : (c3 == 1 ? q1[i][1] : 1.0);
         a[i] = u * v;
     }
-    int col = 0, pivc[5];
+    // complete pivoting: every lane finds the largest entry of its own column among the rows still open, the columns still free
+    // are then compared in ascending order (uniform: every lane sees the same broadcast values) -- the first maximum in
+    // column-major order, as the sequential statement picks it
+    unsigned used = 0u;
+    int pivc[5];
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
-        int p = r;
-        for (;;) {                                               // uniform: every lane sees the same broadcast values
-            if (col >= 9) return false;
-            double best = -1.0;
-            p = r;
+        double mine = -1.0;
+        int mine_row = r;
 #pragma unroll
-            for (int i = r; i < 5; ++i) { const double v = fabs(readlane(a[i], col)); if (v > best) { best = v; p = i; } }
-            if (!(best < 1e-12)) break;
-            ++col;
+        for (int i = r; i < 5; ++i) { const double v = fabs(a[i]); if (v > mine) { mine = v; mine_row = i; } }
+        double best = -1.0;
+        int p = r, col = 0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const double v = readlane(mine, c);
+            const int vr = __builtin_amdgcn_readlane(mine_row, c);
+            if (!((used >> c) & 1u) && v > best) { best = v; p = vr; col = c; }
         }
+        if (!(best >= 1e-12)) return false;
 #pragma unroll
         for (int i = r + 1; i < 5; ++i) if (p == i) { const double t = a[r]; a[r] = a[i]; a[i] = t; }
         const double inv = fpt_rcp(readlane(a[r], col));
@@ -66,11 +74,9 @@ __device__ __forceinline__ bool null_space(const double q1[5][2], const double q
 #pragma unroll
         for (int i = 0; i < 5; ++i) if (i != r) { const double f = readlane(a[i], col); a[i] -= f * a[r]; }
         pivc[r] = col;
-        ++col;
+        used |= 1u << col;
     }
-    unsigned free_cols = 0x1ffu;
-#pragma unroll
-    for (int r = 0; r < 5; ++r) free_cols &= ~(1u << pivc[r]);
+    unsigned free_cols = 0x1ffu & ~used;
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
         const int f = __builtin_ctz(free_cols);                  // free columns in ascending order
@@ -79,6 +85,24 @@ __device__ __forceinline__ bool null_space(const double q1[5][2], const double q
 #pragma unroll
         for (int r = 0; r < 5; ++r) { const double v = readlane(a[r], f); if (lane == pivc[r]) e = -v; }
         ee[nb] = e;
+    }
+    // orthonormal basis: modified Gram-Schmidt, every sum over the nine lanes taken in the sequential statement's order, then
+    // the Hadamard rotation (lanes >= 9 hold zeros throughout)
+    auto sum9 = [](const double v) {
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) acc += readlane(v, c);
+        return acc;
+    };
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < i; ++j) { const double d = sum9(ee[i] * ee[j]); ee[i] -= d * ee[j]; }
+        ee[i] *= fpt_rcp(sqrt(sum9(ee[i] * ee[i])));
+    }
+    {
+        const double a0 = ee[0], b0 = ee[1], c0 = ee[2], d0 = ee[3];
+        ee[0] = 0.5 * ((a0 - b0) + (c0 - d0)); ee[1] = 0.5 * ((a0 + b0) - (c0 + d0)); ee[2] = 0.5 * ((a0 - b0) - (c0 - d0)); ee[3] = 0.5 * ((a0 + b0) + (c0 + d0));
     }
     return true;
 }

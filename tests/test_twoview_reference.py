@@ -1,6 +1,7 @@
-"""The seven-point and four-point solvers against a high-precision reference, on the CPU: the reference against itself, the fixture
-against a recomputation, the host build of coloc_amd/csrc/twoview_min.h against the two rules of DESIGN.md section 11 on every class of
-tests/twoview_cases.py, and cubic_roots alone against mp.polyroots.
+"""The seven-point, four-point and five-point solvers against a high-precision reference, on the CPU: the reference against itself, the
+fixtures against a recomputation, the host builds of coloc_amd/csrc/twoview_min.h and coloc_amd/csrc/fivept.h against the two rules of
+DESIGN.md section 11 on every class of tests/twoview_cases.py, cubic_roots alone against mp.polyroots and the five-point solver's
+eigenvalue stage alone against mp.eig.
 
 The rules (models in conditioned coordinates at unit norm; bound_i = 4096 * max(2^-53 max(w, h), r_ref_i)):
   backward   'F': the model's smallest singular value zeroed at 60 digits, worst point-to-epipolar-line distance of the sample (the smaller
@@ -220,20 +221,39 @@ def test_cubic_table_takes_its_branches():
     assert CUBICS["one_real_R_pos"][2] > 0 > CUBICS["one_real_R_neg"][2]
 
 
-# ---- five points: the reference and the figures, report only ---------------------------------------------------------------------
+# ---- five points ------------------------------------------------------------------------------------------------------------------
+E_CLASSES = cases.classes("E")
+
+
 @pytest.fixture(scope="module")
 def fx_e():
     return cases.load_fixture("E")
 
 
 def test_five_point_fixture_is_the_case_table_and_within_the_size_limit(fx_e):
-    for name in cases.REPORT["E"]:
+    assert sorted(E_CLASSES) == sorted(cases.STORED_E) and not cases.REPORT["E"]
+    for name in cases.STORED_E:
         a, b = cases.class_inputs("E", name, fx_e), cases.class_inputs("E", name)
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]), name
     assert os.path.getsize(cases.FIXTURE_E) <= 74200
 
 
-@pytest.mark.parametrize("name", cases.REPORT["E"])
+def test_five_point_caps_hold_on_the_reference_alone(fx_e):
+    """test_caps_hold_on_the_reference_alone for 'E': no solution out of range in an asserted class, at most 25 % in a hard one.  'E' has no
+    rho and no other excuse: the fixture has none out of range at all, so every one of its 964 solutions is asked for."""
+    total = 0
+    for name in E_CLASSES:
+        refs = cases.class_references(fx_e, "E", name)
+        assert all(len(ss) > 0 for _, _, ss in refs), name
+        sols = [s for _, _, ss in refs for s in ss]
+        out = sum(not s["in_range"] for s in sols)
+        assert out == 0 if name in cases.ASSERTED["E"] else out <= 0.25 * len(sols), name
+        assert out == 0, name                                  # (today's fixture: nothing is excused anywhere)
+        total += len(sols)
+    assert total == 964 and "rho" not in fx_e
+
+
+@pytest.mark.parametrize("name", E_CLASSES)
 def test_five_point_reference_recomputes_and_agrees_with_90_digits(fx_e, name):
     x1, x2, K = cases.class_inputs("E", name, fx_e)
     stored = cases.class_references(fx_e, "E", name)
@@ -250,14 +270,66 @@ def test_five_point_reference_recomputes_and_agrees_with_90_digits(fx_e, name):
             assert max(abs(p - q) for p, q in zip(sa["M"], sb["M"])) <= mpf(10) ** -40
 
 
-@pytest.mark.parametrize("name", cases.REPORT["E"])
-def test_five_point_host_build_keeps_its_structure(fx_e, name):
-    """No rule is asserted (DESIGN.md section 11 has the figures): at most ten slots per sample, each all NaN or wholly finite, and no
-    two returned models matched to one reference solution; every stored solution that is used leads back to a certified one.  Printed:
-    backward error over the class; missed and spurious counts and the worst forward ratio over its first cases.N_REPORT_REF problems."""
+@pytest.mark.parametrize("name", E_CLASSES)
+def test_five_point_host_build_meets_both_rules(fx_e, name):
+    """The two rules of DESIGN.md section 11 on the host build of coloc_amd/csrc/fivept.h, over the whole class, with the asserts of
+    test_host_build_meets_both_rules; and the structure: at most ten slots per sample, each all NaN or wholly finite, no two returned
+    models matched to one reference solution; every stored solution leads back to a certified one.  Completeness is asked of every
+    reference solution, in the hard classes too ('E' has no rho; the fixture has no solution out of range).
+    The solver before the null-space basis was made orthonormal fails noisy, smallbase, forward, nearplanar and far on both rules
+    (forward: 39 of 152 missed, 10 spurious, backward error 1.1e4 x bound) and exact and smallrot on the backward rule (1.2, 1.8 x bound)."""
     import fivept_host
     x1, x2, K = cases.class_inputs("E", name, fx_e)
     fig = cases.evaluate("E", name, fivept_host.class_slots(x1, x2, K), fx_e)
-    print("\nE %s (host, report only): %s" % (name, fig))
-    assert all(r["cert"] <= float(twoview_mp.CERT_TOL) for row in cases.class_table(fx_e, "E", name)[3] for r in row["refs"] or [])
-    assert fig["models"] > 0 and fig["doubled"] == 0
+    print("\nE %s (host): %s" % (name, fig))
+    table = cases.class_table(fx_e, "E", name)[3]
+    assert all(row["refs"] is not None and len(row["refs"]) > 0 for row in table) and fig["refs"] == sum(len(row["refs"]) for row in table)
+    assert all(r["cert"] <= float(twoview_mp.CERT_TOL) and r["in_range"] for row in table for r in row["refs"])
+    assert fig["models"] > 0
+    assert fig["backward_ratio"] <= 1.0
+    assert fig["missed"] == 0 and fig["spurious"] == 0 and fig["doubled"] == 0
+
+
+# ---- the five-point solver's eigenvalue stage alone --------------------------------------------------------------------------------
+# sigma_min(A - x I) / |A|_2 of a computed eigenvalue x: the smallest relative perturbation of A (2-norm) that makes x an exact
+# eigenvalue.  Worst over the real eigenvalues of the fixture's 210 action matrices, measured at 60 digits:
+#   numpy.linalg.eigvals (LAPACK dgeev)                          6.02e-14   (smallbase; 2.35e-14 far, 1.46e-15 nearplanar, <= 8.7e-16 elsewhere)
+#   fpt_hessenberg10_seq + fpt_balance10 + fpt_aberth10          6.43e-17   (exact; 1.3e-17 .. 2.8e-17 elsewhere)
+# The rule allows 8 x LAPACK's worst: a different but sound float64 method may sit a small factor off it.
+# (tools/fivept_attribution.py eig measures both again.)
+EIG_ETA = 8.0 * 6.02e-14
+
+
+def eig_backward_error(A, norm2, x):
+    """sigma_min(A - x I) / |A|_2 at the working precision; A an mp.matrix, x a float."""
+    return mp.svd_r(A - mpf(float(x)) * mp.eye(10), compute_uv=False)[9] / norm2
+
+
+@pytest.mark.parametrize("name", E_CLASSES)
+def test_five_point_eigenvalue_stage_against_mp_eig(fx_e, name):
+    """fpt_hessenberg10_seq + fpt_balance10 + fpt_aberth10 alone on the float64 action matrices the host build forms on the class's 30
+    problems.  Backward: every eigenvalue the solver takes for real (fpt_root_is_real) is an exact eigenvalue of a matrix within
+    EIG_ETA |A|_2 of A.  Complete: every real eigenvalue of mp.eig(A) at 60 digits (|Im| <= 1e-30 (1 + |x|)) is the reference
+    eigenvalue nearest to some returned real one -- whose backward error is then the test, not the distance."""
+    import fivept_host
+    x1, x2, K = cases.class_inputs("E", name, fx_e)
+    worst, n_real = 0.0, 0
+    with mp.workdps(60):
+        for i in range(len(x1)):
+            Ax = fivept_host.workspace(*fivept_host.normalised(x1[i], x2[i], K))["Ax"]
+            assert np.isfinite(Ax).all() and np.abs(Ax).max() > 0
+            got = fivept_host.eig(Ax)
+            assert got is not None
+            mine = [float(z.real) for z in got[0] if not abs(z.imag) > 1e-6 * (1.0 + abs(z.real))]
+            A, norm2 = mp.matrix(Ax.tolist()), mpf(float(np.linalg.norm(Ax, 2)))
+            ref = mp.eig(A, left=False, right=False)
+            real = set(k for k in range(10) if abs(mp.im(ref[k])) <= mpf(10) ** -30 * (1 + abs(ref[k])))
+            n_real += len(real)
+            met = set()
+            for x in mine:
+                eta = float(eig_backward_error(A, norm2, x))
+                worst = max(worst, eta)
+                assert eta <= EIG_ETA, (name, i, x, eta)
+                met.add(min(range(10), key=lambda k: abs(ref[k] - x)))
+            assert real <= met, (name, i, sorted(real - met))
+    print("\nE %s eigenvalue stage: %d real eigenvalues, worst backward error %.3g (allowed %.3g)" % (name, n_real, worst, EIG_ETA))

@@ -17,9 +17,10 @@ relative to depth), smallbase (baseline 1e-3 of the mean depth), neardouble (sam
 'H' asserted: exact, noisy, vga.  'H' hard: collinear (three of the four collinear to 1e-3 of their span), tinyquad (the four within
 10 px of each other), corners (the four within 2 px of the image corners).
 
-The five-point solver ('E', coloc_amd/csrc/fivept.h and fivept_wave.h) has the same reference and the same two figures, report only
-(tests/golden/fivept_reference.npz): exact, noisy, smallbase (1e-3), forward (motion along the optical axis), nearplanar, far (depth 50
-to 60), smallrot (rotation 1e-3 rad); K = [1000 0 640; 0 1000 360; 0 0 1] for both cameras, models in calibrated coordinates.
+The five-point solver ('E', coloc_amd/csrc/fivept.h and fivept_wave.h) has the same reference and the same two rules
+(tests/golden/fivept_reference.npz).  Asserted: exact, noisy, smallrot (rotation 1e-3 rad).  Hard: smallbase (1e-3), forward (motion
+along the optical axis), nearplanar, far (depth 50 to 60).  K = [1000 0 640; 0 1000 360; 0 0 1] for both cameras, models in calibrated
+coordinates.  'E' has no rho: completeness is asked of every in-range solution of every class.
 """
 import os
 
@@ -31,8 +32,9 @@ RHO_CAP = 1e-3
 EPS = 2.0 ** -53
 ASSERTED = {"F": ["exact", "noisy", "vga", "puretrans"], "H": ["exact", "noisy", "vga"]}
 HARD = {"F": ["nearplanar", "smallbase", "neardouble"], "H": ["collinear", "tinyquad", "corners"]}
-REPORT = {"F": [], "H": [], "E": ["exact", "noisy", "smallbase", "forward", "nearplanar", "far", "smallrot"]}
-ASSERTED["E"], HARD["E"] = [], []
+ASSERTED["E"], HARD["E"] = ["exact", "noisy", "smallrot"], ["smallbase", "forward", "nearplanar", "far"]
+REPORT = {"F": [], "H": [], "E": []}
+STORED_E = ["exact", "noisy", "smallbase", "forward", "nearplanar", "far", "smallrot"]      # (the order of FIXTURE_E's classes)
 MODELS = ["F", "H"]                                 # (the models of FIXTURE; 'E' has FIXTURE_E)
 M_OF = {"F": 7, "H": 4, "E": 5}
 SLOTS = {"F": 3, "H": 1, "E": 10}
@@ -48,17 +50,22 @@ def classes(model):
     return ASSERTED[model] + HARD[model] + REPORT[model]
 
 
+def stored_classes(model):
+    """The classes in the order their fixture keeps them."""
+    return STORED_E if model == "E" else classes(model)
+
+
 def all_classes():
     return [(m, c) for m in MODELS for c in classes(m)]
 
 
 def class_offset(model, name):
     """Index of the class's first problem in its fixture's per-problem arrays."""
-    return (classes("E").index(name) if model == "E" else all_classes().index((model, name))) * N_PER_CLASS
+    return (STORED_E.index(name) if model == "E" else all_classes().index((model, name))) * N_PER_CLASS
 
 
 def pool_names(model):
-    return [c for c in classes(model) if (model, c) not in POOL_OF]
+    return [c for c in stored_classes(model) if (model, c) not in POOL_OF]
 
 
 def image_size(name):
@@ -196,7 +203,7 @@ def class_inputs(model, name, fx=None):
     """(x1 (n, m, 2), x2 (n, m, 2), camera) in pixels; from the fixture `fx` when it is given, else rebuilt."""
     if fx is not None:
         p = fx[model + "_pool"][pool_names(model).index(POOL_OF.get((model, name), name))]
-        s = fx[model + "_samples"][classes(model).index(name)].astype(np.int64)
+        s = fx[model + "_samples"][stored_classes(model).index(name)].astype(np.int64)
     else:
         p, s = pool(model, name), samples(model, name).astype(np.int64)
     return np.ascontiguousarray(p[s][..., :2]), np.ascontiguousarray(p[s][..., 2:]), camera(model, name)
@@ -286,7 +293,7 @@ def judge(got, refs, bd, rho, complete_needs_rho):
     bounds = [forward_bound(r["J"], bd) for r in refs]
     diffs = [[np.abs((unit(g, r["hi"]) - r["hi"]) - r["lo"]) for r in refs] for g in got]
     for k, (r, b) in enumerate(zip(refs, bounds)):
-        if not r["in_range"] or (complete_needs_rho and rho < RHO_CAP):
+        if not r["in_range"] or (complete_needs_rho and rho < RHO_CAP):      # ('E' has no rho: class_references gives 1.0)
             continue
         ratios = [float((diffs[j][k] / b).max()) for j in range(len(got))]
         if not ratios or min(ratios) > 1.0:
@@ -303,8 +310,8 @@ def judge(got, refs, bd, rho, complete_needs_rho):
 
 _TABLES = {}
 RECERT_STEPS = {"F": 2, "H": 2, "E": 4}
-N_REPORT_REF = 15          # the tests bring the references of this many problems of a report-only class back (30 ms a solution, five to a
-                           # problem); the generator's report covers whole classes
+N_REPORT_REF = 15          # the tests would bring the references of this many problems of a report-only class back (30 ms a solution,
+                           # five to a problem); no class is report only today
 
 
 def class_table(fx, model, name):

@@ -12,7 +12,7 @@ class; at most 25 % of a hard class's reference solutions out of range or (in ra
 is under the cap by construction: there the condition is on the range alone.  The tool refuses to write otherwise.  It then prints what
 the host build of twoview_min.h scores under the two rules.
 
-The five-point classes ('E', report only) go to tests/golden/fivept_reference.npz in the same layout, their models as float32 (the
+The five-point classes ('E') go to tests/golden/fivept_reference.npz in the same layout, their models as float32 (the
 tests take four Newton steps from them; this tool checks that those land on the certified solution) and without rho.
 
     python tools/make_twoview_reference.py [FH] [E]      # both files by default; about three and ten minutes
@@ -40,11 +40,11 @@ def write(models, path):
     fx = {}
     for model in models:
         fx[model + "_pool"] = np.stack([cases.pool(model, c) for c in cases.pool_names(model)])
-        fx[model + "_samples"] = np.stack([cases.samples(model, c) for c in cases.classes(model)])
+        fx[model + "_samples"] = np.stack([cases.samples(model, c) for c in cases.stored_classes(model)])
     rho, r_ref = [], []
     sol = dict(sol_prob=[], M=[], J=[], in_range=[])
     tables = {}
-    for model, name in [(m, c) for m in models for c in cases.classes(m)]:
+    for model, name in [(m, c) for m in models for c in cases.stored_classes(m)]:
         print("class %s %s" % (model, name))
         x1, x2, wh = cases.class_inputs(model, name)
         size = cases.image_size(name)
